@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- TDVP sweeps/s of the MI355X engine on BASELINE.json's configs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4] [--max-seconds S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4] [--dump-outputs DIR]
+                    [--full [--max-seconds S] [--secondary auto] [--no-cpu-baseline]]
+
+A plain run sets up, runs exactly W warm-up and K timed steps, writes the outputs of the last timed step if
+--dump-outputs is given, and prints the result line (metric, value, unit, ms_per_step, ...).  Everything else the
+benchmark measures -- the roofline / per-phase breakdown from the engine's counters, the CPU baseline, the other
+BASELINE configs as short secondary legs, and the wall budget that cuts the steps to fit -- runs only with --full.
+
+--dump-outputs DIR: after the timed steps, what a caller of the sweep receives -- the MPS -- as DIR/<name>.npy
+(float64): mps_sample (n, 2) = real / imaginary part of a fixed, seeded sample of every site tensor's entries (all of
+a small site, DUMP_SAMPLES_PER_SITE of a large one), mps_sample_index (n, 2) = (site, C-order flat index) of each,
+mps_shapes (L, 3), norm (1,), and on one GPU energy (1,) = <Psi|H|Psi> (computed after the timing).  The inputs are
+seeded, so the same arguments give the same inputs on every run.  Not available with --parallel sites.
 
 One "step" = one half-sweep of one-site TDVP over all L sites of a synthetic
 full-rank MPS under a synthetic Hermitian MPO (SURVEY.md 8d inputs), i.e. L
@@ -11,13 +23,23 @@ _mps_cls.py:482-500, :798-1014).  Sweeps alternate direction (forward, backward,
 ...), two of them are one PyTDSCF time step.  All tensors are generated on /
 resident in HBM before the timed region.
 
-Wall budget.  A C4 sweep takes about a minute, so the requested --steps /
---warmup are an upper bound: after the first warm-up sweep the run knows the
-sweep time and fits `warmup + steps` into --max-seconds (default 400 s, env
-MITDVP_BENCH_BUDGET; the CPU-baseline leg and the start-up are counted).  The
-JSON line reports the sweeps actually run ("steps", "warmup") next to
-"steps_requested" / "warmup_requested"; at least one warm-up and one timed
-sweep always run.
+Exception: a C4 half-sweep takes about 49 s, so in a plain one-GPU C4 run one step
+is one of 8 pieces of a half-sweep (STEPS_PER_HALF_SWEEP): consecutive sites of the
+library's own half-sweep loop (engine.sweep_part), cut so that every piece holds
+1/8 of the modelled H_eff work.  "value" stays sweeps/s: the pieces' shares of a
+half-sweep summed over the timed steps, over the time (config.half_sweeps_timed;
+exactly the half-sweep count when the steps complete whole half-sweeps).  With
+--full a step is a whole half-sweep again.
+
+Wall budget (--full only).  A C4 sweep takes about a minute, so under --full the
+requested --steps / --warmup are an upper bound: after the first warm-up sweep
+the run knows the sweep time and fits `warmup + steps` into --max-seconds
+(default 400 s, env MITDVP_BENCH_BUDGET; the CPU-baseline leg and the start-up
+are counted).  The JSON line reports the sweeps actually run ("steps",
+"warmup") next to "steps_requested" / "warmup_requested"; at least one warm-up
+and one timed sweep always run.  The CPU baseline and the secondary legs are
+bounded by the same clock, so that a --full run ends within about
+--max-seconds + --secondary-seconds + 40 s.
 
 N > 1: either launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE
 in the environment) or plainly as `python bench.py --gpus N`, in which case this
@@ -88,11 +110,18 @@ if CPU_WORKER_FLAG in sys.argv:
     # The CPU-baseline leg runs in a process of its own, pinned BEFORE NumPy / OpenBLAS start their thread pool (threads
     # inherit the affinity of the thread that creates them; the pool of an already running process cannot be re-pinned).
     _pkg, _cpus = one_socket_physical_cores()
+    # a thread limit already set for this job (the CPUs it may really use) caps the pool: more BLAS threads than CPUs
+    # only make the sample crawl
+    _caps = [int(os.environ[_v]) for _v in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS")
+             if os.environ.get(_v, "").strip().isdigit() and int(os.environ[_v]) > 0]
+    if _caps:
+        _cpus = _cpus[:min(_caps)]
     if _cpus:
         os.sched_setaffinity(0, _cpus)
         for _v in ("OPENBLAS_NUM_THREADS", "OMP_NUM_THREADS", "MKL_NUM_THREADS"):
             os.environ[_v] = str(len(_cpus))
     CPU_PLACEMENT = {"pinned": bool(_cpus), "socket": _pkg, "affinity_cpus": len(_cpus),
+                     "thread_limit_from_env": min(_caps) if _caps else None,
                      "note": "one logical CPU per physical core of one socket (os.sched_setaffinity before NumPy / OpenBLAS "
                              "start their threads; OPENBLAS_NUM_THREADS = that count)"}
 
@@ -421,7 +450,79 @@ def energy_at_centre(eng):
     return float(np.vdot(eng.get_site(c), sig).real)
 
 
-def secondary_leg(name, device, gemm_mode, seconds, steps_req, with_cpu, note):
+# A half-sweep of C4 takes about 49 s: in a plain run its step is one of 8 pieces of a half-sweep (~6 s), so that a run
+# of tens of steps fits minutes; every other workload's step is a whole half-sweep.
+STEPS_PER_HALF_SWEEP = {"C4": 8}
+
+
+def half_sweep_pieces(L, d, D, M, parts):
+    """[(sites, share)] of `parts` consecutive pieces of a forward half-sweep: cut where the cumulative modelled H_eff
+    work (flops_heff per site, the MPO's outer bonds 1) crosses k / parts, so the cheap edge sites share a piece with
+    more of the chain; `share` is each piece's part of the half-sweep's modelled work (the shares add up to 1).  A
+    backward half-sweep runs the same pieces mirrored."""
+    from pytdscf_amd.mps import bond_dims
+
+    w = [flops_heff(a, d, b, 1 if p == 0 else M, 1 if p == L - 1 else M) for p, (a, b) in enumerate(bond_dims([d] * L, D))]
+    tot, cum, cuts = sum(w), np.cumsum(w), [0]
+    for k in range(1, parts):
+        t = tot * k / parts
+        c = int(np.searchsorted(cum, t)) + 1  # the piece ends with the site that crosses k / parts ...
+        if c > 1 and t - cum[c - 2] < cum[c - 1] - t:  # ... or just before it, whichever lands nearer
+            c -= 1
+        cuts.append(min(max(c, cuts[-1] + 1), L - (parts - k)))
+    cuts.append(L)
+    return [(b - a, float(sum(w[a:b]) / tot)) for a, b in zip(cuts, cuts[1:])]
+
+
+class PieceSweeper:
+    """Half-sweeps of `eng` in pieces (half_sweep_pieces), alternating direction like the sweeps.  Each piece is one
+    engine.sweep_part call: the next sites of the library's own half-sweep loop (Engine::sweep_part, csrc/engine.hip;
+    sweep() is that loop over all sites).  step() returns the piece's share of a half-sweep."""
+
+    def __init__(self, eng, dt, pieces):
+        self.eng, self.dt, self.pieces = eng, dt, pieces
+        self.forward, self.k = True, 0
+
+    def step(self):
+        n, share = self.pieces[self.k if self.forward else len(self.pieces) - 1 - self.k]
+        left = self.eng.sweep_part(self.dt, self.forward, n)
+        self.k += 1
+        if self.k == len(self.pieces):
+            if left != 0:
+                raise RuntimeError(f"half-sweep in pieces: {left} sites left after the last piece")
+            self.forward, self.k = not self.forward, 0
+        return share
+
+
+DUMP_SAMPLES_PER_SITE = 8192  # 64 sites of C4: 16 MB of samples and indices together
+DUMP_SEED = 20240
+
+
+def dump_outputs(out_dir, eng, nrm, energy=None):
+    """The state the timed sweeps left in `eng`, as float64 .npy files in `out_dir` (module docstring, --dump-outputs).
+    One site tensor at a time is copied to the host (256 MB at C4); which entries are kept depends only on the site
+    shapes and DUMP_SEED.  (Host copies: torch's own HIP runtime is not initialised in a one-GPU run.)"""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    vals, where, shapes = [], [], []
+    for p in range(eng.nsite):
+        c = eng.get_site(p)
+        n = c.size
+        idx = np.arange(n) if n <= DUMP_SAMPLES_PER_SITE else np.sort(rng.choice(n, DUMP_SAMPLES_PER_SITE, replace=False))
+        v = c.reshape(-1)[idx]
+        del c
+        vals.append(np.stack([v.real, v.imag], axis=1))
+        where.append(np.stack([np.full(len(idx), p, dtype=np.float64), idx.astype(np.float64)], axis=1))
+        shapes.append(eng.get_site_shape(p)[:3])
+    arrays = {"mps_sample": np.concatenate(vals), "mps_sample_index": np.concatenate(where),
+              "mps_shapes": np.asarray(shapes, dtype=np.float64), "norm": np.asarray([nrm], dtype=np.float64)}
+    if energy is not None:
+        arrays["energy"] = np.asarray([energy], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def secondary_leg(name, device, gemm_mode, seconds, steps_req, with_cpu, note, cpu_timeout_s=90.0):
     """One short single-GPU run of another BASELINE config after the headline one: the same measurement (warm-up, timed
     sweeps between synchronisations, counters -> roofline / breakdown, the oracle on the host cores), a few seconds of
     sweeps.  Returns the record for the `secondary` key of the JSON line."""
@@ -499,7 +600,7 @@ def secondary_leg(name, device, gemm_mode, seconds, steps_req, with_cpu, note):
             rec["ensemble"] = {"error": f"{type(e).__name__}: {e}"}
     if with_cpu:
         note(f"{name}: timing the CPU baseline (oracle on the host cores)")
-        rec["cpu_baseline"] = cpu_baseline_pinned(L, d, D, M, kh, kk, dt, budget_s=6.0, short=True, timeout_s=90.0)
+        rec["cpu_baseline"] = cpu_baseline_pinned(L, d, D, M, kh, kk, dt, budget_s=6.0, short=True, timeout_s=cpu_timeout_s)
     rec["leg_s"] = time.perf_counter() - t_leg
     return rec
 
@@ -607,18 +708,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=os.environ.get("MITDVP_WORKLOAD", "C4"), choices=sorted(WORKLOADS))
     ap.add_argument("--dt", type=float, default=None, help="time step in a.u. (default per workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (see the module docstring)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline / breakdown, the CPU baseline, the secondary legs and the wall budget")
     ap.add_argument("--max-seconds", type=float, default=float(os.environ.get("MITDVP_BENCH_BUDGET", "400")),
-                    help="wall budget for the whole run; steps / warmup are cut to fit (0 = no limit)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: wall budget for the whole run; steps / warmup are cut to fit (0 = no limit)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baseline")
     ap.add_argument("--secondary", default=os.environ.get("MITDVP_BENCH_SECONDARY", "auto"),
-                    help="other BASELINE configs run as short single-GPU legs after the headline one and reported under "
-                         "the `secondary` key: auto (C2, C3, C5), none, or a comma list")
+                    help="--full: other BASELINE configs run as short single-GPU legs after the headline one and reported "
+                         "under the `secondary` key: auto (C2, C3, C5), none, or a comma list")
     ap.add_argument("--secondary-seconds", type=float, default=float(os.environ.get("MITDVP_BENCH_SECONDARY_BUDGET", "100")),
-                    help="wall budget of all secondary legs together (beside --max-seconds)")
+                    help="--full: wall budget of all secondary legs together (beside --max-seconds)")
     ap.add_argument("--parallel", default=os.environ.get("MITDVP_PARALLEL", "auto"), choices=["auto", "sites", "tp", "replicas"])
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0 or args.gpus < 1:
         ap.error("need --steps >= 1, --warmup >= 0, --gpus >= 1")
+    full = args.full
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -680,6 +786,8 @@ def main():
             mode = "tp"
         else:
             mode = "replicas"
+    if mode == "sites" and args.dump_outputs:
+        sys.exit("bench.py: --dump-outputs needs one GPU or --parallel tp / replicas (the site-sharded state is spread over the ranks)")
     if comm.shared_gpu:  # several processes on one GPU (rehearsals): no persistent kernels, they need every CU
         os.environ.setdefault("MITDVP_SMALL_KERNELS", "0")
     ss = None
@@ -732,18 +840,26 @@ def main():
             note(f"{e}; falling back to independent replicas")
             mode = "replicas"
             eng.init_random([d] * L, D, seed=1 + rank)
-    if eng is not None:
+    # the energy before the run is a --full figure (a plain run waits for the set-up in the sync before the timing)
+    if full and eng is not None:
         e0 = eng.expectation().real  # also builds nothing persistent; forces setup to finish
-    elif ss is not None:
+    elif full and ss is not None:
         e0 = ss.expectation().real  # folded rank by rank on the devices (collective), outside the timed region
 
     # one "unit" of work: a half-sweep; the site-sharded step is two half-sweeps + the junction updates
     unit = 2 if mode == "sites" else 1
     state = {"forward": True}
+    # a plain one-GPU run of a workload with long half-sweeps: a step is a fixed part of a half-sweep (STEPS_PER_HALF_SWEEP)
+    parts = STEPS_PER_HALF_SWEEP.get(args.workload, 1) if (mode == "single" and not full) else 1
+    pieces = half_sweep_pieces(L, d, D, M, parts) if parts > 1 else None
+    piece_sweeper = PieceSweeper(eng, dt, pieces) if parts > 1 else None
+    timed = {"half_sweeps": 0.0}  # with pieces: the half-sweeps the timed steps make up (sum of their shares)
 
     def run_unit():
         if mode == "sites":
             ss.step(dt)
+        elif piece_sweeper is not None:
+            return piece_sweeper.step()
         else:
             eng.sweep(dt, state["forward"])
             state["forward"] = not state["forward"]
@@ -756,38 +872,47 @@ def main():
     note(f"{args.workload} set up on device {comm.gpu} (L={L} d={d} D={D} M={M}), mode {mode}" + (f", <H>={e0:.9f}" if e0 is not None else ""))
 
     barrier = comm.barrier
-    budget = args.max_seconds if args.max_seconds > 0 else float("inf")
-    with_cpu = not args.no_cpu_baseline and world == 1
+    # the wall budget, the CPU baseline and the secondary legs belong to --full; a plain run does what it is asked
+    budget = args.max_seconds if (full and args.max_seconds > 0) else float("inf")
+    with_cpu = full and not args.no_cpu_baseline and world == 1
     reserve = (cpu_baseline_seconds_estimate(L, d, D, M) if with_cpu else 0.0) + 8.0
 
-    # ---- warm-up: at least one unit, which also measures the sweep time ----
+    # ---- warm-up (--full: at least one unit, which also measures the sweep time for the budget) ----
     steps_req = max(unit, (args.steps // unit) * unit)
     warm_done, steps = 0, steps_req
-    warm_target = max(unit, (args.warmup // unit) * unit)
+    warm_target = max(unit if full else 0, (args.warmup // unit) * unit)
+    t_sweep = None
     while warm_done < warm_target:
         t1 = time.perf_counter()
         run_unit()
         sync_norm()
         t_sweep = comm.max_over_ranks(time.perf_counter() - t1) / unit
         warm_done += unit
-        note(f"warm-up sweep {warm_done} done in {t_sweep:.2f}s per sweep")
-        more, steps = plan_sweeps(budget, comm.max_over_ranks(elapsed()), t_sweep, warm_done, warm_target, steps_req, reserve)
-        more, steps = (more // unit) * unit, max(unit, (steps // unit) * unit)
-        warm_target = warm_done + more
-    if steps != args.steps or warm_done != args.warmup:
+        note(f"warm-up step {warm_done} done in {t_sweep:.2f}s per step")
+        if full:
+            more, steps = plan_sweeps(budget, comm.max_over_ranks(elapsed()), t_sweep, warm_done, warm_target, steps_req, reserve)
+            more, steps = (more // unit) * unit, max(unit, (steps // unit) * unit)
+            warm_target = warm_done + more
+    if full and (steps != args.steps or warm_done != args.warmup):
         note(f"wall budget {budget:.0f}s: running {warm_done} warm-up + {steps} timed sweeps "
              f"(requested {args.warmup} + {args.steps})")
     sync_norm()
     meas.counters_reset()
-    profile_in_timed = D >= PROFILE_IN_TIMED_MIN_D  # below: an unprofiled timed region + a profiled repeat
+    # below PROFILE_IN_TIMED_MIN_D (and in a plain run): an unprofiled timed region (+ a profiled repeat under --full)
+    profile_in_timed = full and D >= PROFILE_IN_TIMED_MIN_D
     meas.set_profiling(profile_in_timed)
     barrier()
     t0 = time.perf_counter()
     for i in range(0, steps, unit):
-        run_unit()
+        share = run_unit()
+        if piece_sweeper is not None:
+            timed["half_sweeps"] += share
+        if t_sweep is None and steps > unit:  # no warm-up: the first timed unit tells whether progress notes are due
+            sync_norm()
+            t_sweep = (time.perf_counter() - t0) / unit
         if steps > unit and t_sweep > 5.0:
             sync_norm()
-            note(f"timed sweep {i + unit}/{steps} done")
+            note(f"timed step {i + unit}/{steps} done")
     nrm = sync_norm()
     barrier()
     el_rank = time.perf_counter() - t0
@@ -795,17 +920,60 @@ def main():
         el = comm.max_over_ranks(el_rank)
         value = steps / el
     else:
-        value, el = replica_throughput(comm, float(steps), el_rank)
+        # sweeps/s; with pieces, the half-sweeps the timed pieces make up (exact when they complete whole half-sweeps)
+        value, el = replica_throughput(comm, timed["half_sweeps"] if piece_sweeper is not None else float(steps), el_rank)
     e1 = None
     if profile_in_timed:
         cnt = meas.counters()
     meas.set_profiling(False)
     # norm / energy of the state after exactly the timed sweeps, before the profiled repeat moves it on
-    if ss is not None:  # the sharded state's own norm and energy after the run (collective; not timed)
+    if ss is not None and full:  # the sharded state's own norm and energy after the run (collective; not timed)
         nrm = ss.norm()
         e1 = ss.expectation().real
-    elif mode == "single":  # energy conservation of the run itself, from the blocks the last sweep left around the centre
+    elif mode == "single" and (full or args.dump_outputs):
+        # energy conservation of the run itself, from the blocks the last sweep left around the centre
         e1 = energy_at_centre(eng)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, nrm, e1)
+        note(f"outputs of the last timed step written to {args.dump_outputs}")
+    if not full:
+        if rank == 0:
+            out = {
+                "metric": "tdvp_sweeps_per_sec",
+                "value": value,
+                "unit": "sweeps/s",
+                "n_gpus": args.gpus,
+                "steps": steps,
+                "warmup": warm_done,
+                "ms_per_step": 1e3 * el / steps,
+                "higher_is_better": True,
+                "scaling": "strong" if mode in ("tp", "sites") else "weak",
+                "vs_baseline": None,
+                "dtype": "c128",
+                "data": "synthetic",
+                "config": {
+                    "workload": f"{args.workload}: {desc}",
+                    "L": L, "d": d, "D": D, "M": M, "dt_au": dt, "thresh_sil": 1e-9,
+                    "integrator": integ,
+                    "step": ("one half-sweep (L site exponentials, L-1 QR, L-1 env updates, L-1 bond exponentials)" if parts == 1
+                             else f"one of {parts} pieces of a half-sweep (engine.sweep_part: consecutive local updates of the "
+                                  "library's half-sweep, pieces of equal modelled H_eff work), half-sweeps alternating direction"),
+                    "steps_per_half_sweep": parts,
+                    "half_sweep_pieces": [n for n, _ in pieces] if pieces else None,
+                    "half_sweeps_timed": timed["half_sweeps"] if pieces else float(steps),
+                    "norm_after": nrm,
+                    "parallelism": mode,
+                    "approximate": mode == "sites",
+                },
+                "wall_s": elapsed(),
+            }
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+        if eng is not None:
+            eng.close()
+        if ss is not None:
+            ss.close()
+        comm.close()
+        return
     if not profile_in_timed:
         meas.counters_reset()
         meas.set_profiling(True)
@@ -883,9 +1051,14 @@ def main():
             "roofline": roof,
             "breakdown_ms": brk,
         }
+        # the CPU baseline and the secondary legs run on the same clock as the headline: the whole run ends within about
+        # budget + secondary seconds + 40 s however long the host takes for its sample
+        deadline = (budget + max(0.0, args.secondary_seconds) + 40.0) if mode == "single" and args.secondary != "none" \
+            else budget + 40.0
         if with_cpu:
             note("timing the CPU baseline (oracle on the host cores)")
-            out["cpu_baseline"] = cpu_baseline_pinned(L, d, D, M, kh, kk, dt)
+            out["cpu_baseline"] = cpu_baseline_pinned(L, d, D, M, kh, kk, dt,
+                                                      timeout_s=max(120.0, min(240.0, budget + 40.0 - elapsed())))
         # ---- the other BASELINE configs, driver-observed: short single-GPU legs after the headline run ----
         if mode == "single" and args.secondary != "none":
             names = [w for w in ("C2", "C3", "C5") if w != args.workload] if args.secondary == "auto" else \
@@ -897,10 +1070,17 @@ def main():
             tot_share = sum(share.get(w, 0.3) for w in names) or 1.0
             for w in names:
                 secs = args.secondary_seconds * share.get(w, 0.3) / tot_share
+                left = deadline - elapsed() - 5.0
+                if left < min(secs, 10.0):
+                    out["secondary"][w] = {"error": f"skipped: {left:.0f}s left of the wall budget"}
+                    note(f"secondary leg {w} skipped ({left:.0f}s left)")
+                    continue
+                secs = min(secs, left)
                 note(f"secondary leg {w} ({secs:.0f}s)")
                 try:
                     out["secondary"][w] = secondary_leg(w, comm.gpu, gemm_mode, secs, args.steps if w != "C2" else max(args.steps, 100),
-                                                        not args.no_cpu_baseline, note)
+                                                        not args.no_cpu_baseline, note,
+                                                        cpu_timeout_s=max(20.0, min(90.0, deadline - elapsed() - secs)))
                 except Exception as e:  # noqa: BLE001 -- the headline number stands on its own
                     out["secondary"][w] = {"error": f"{type(e).__name__}: {e}"}
             out["config"]["secondary_summary"] = secondary_summary(out["secondary"])

@@ -124,6 +124,11 @@ int mitdvp_step(mitdvp_engine* h, double dt_au);
 int mitdvp_ensemble_step(mitdvp_engine** hs, int n, double dt_au, int nsteps, int* statuses);
 /* propagate_along_sweep (_mps_cls.py:798-1014), one direction only. */
 int mitdvp_sweep(mitdvp_engine* h, double dt_au, int forward);
+/* The same half-sweep in parts: the next `nsites` local updates of the half-sweep in progress (one is started when none
+ * is), through the code of mitdvp_sweep, which is this call with nsites = nsite.  *left (may be NULL) receives the
+ * sites still to go, 0 when the half-sweep is complete.  While one is in progress only observables, other parts in
+ * the same direction and mitdvp_close are allowed; mitdvp_sweep / mitdvp_step refuse. */
+int mitdvp_sweep_part(mitdvp_engine* h, double dt_au, int forward, int nsites, int* left);
 /* op_sys_sites = None (_mps_cls.py:2311,2371,2417, wavefunction.py:64-65). */
 int mitdvp_invalidate_env(mitdvp_engine* h);
 

@@ -118,6 +118,7 @@ def load() -> C.CDLL:
         "mitdvp_set_shift": (i, [vp, i, d, d]),
         "mitdvp_step": (i, [vp, d]),
         "mitdvp_sweep": (i, [vp, d, i]),
+        "mitdvp_sweep_part": (i, [vp, d, i, i, ip]),
         "mitdvp_invalidate_env": (i, [vp]),
         "mitdvp_set_boundary_env": (i, [vp, i, dp, i, i]),
         "mitdvp_replace_site": (i, [vp, i, dp, i]),

@@ -144,6 +144,12 @@ int mitdvp_set_mpo_core(mitdvp_engine* h, int op_id, int isite, const double* re
 int mitdvp_set_shift(mitdvp_engine* h, int op_id, double re, double im) { ENG_CALL(h, h->e->set_shift(op_id, re, im)); }
 int mitdvp_step(mitdvp_engine* h, double dt) { ENG_CALL(h, h->e->step(dt)); }
 int mitdvp_sweep(mitdvp_engine* h, double dt, int forward) { ENG_CALL(h, h->e->sweep(dt, forward != 0)); }
+int mitdvp_sweep_part(mitdvp_engine* h, double dt, int forward, int nsites, int* left) {
+  ENG_CALL(h, {
+    const int r = h->e->sweep_part(dt, forward != 0, nsites);
+    if (left) *left = r;
+  });
+}
 int mitdvp_ensemble_step(mitdvp_engine** hs, int n, double dt, int nsteps, int* statuses) {
   if (!hs || n < 1 || nsteps < 0) { g_err = "mitdvp_ensemble_step: bad arguments"; return MITDVP_EINVAL; }
   for (int i = 0; i < n; ++i)

@@ -141,6 +141,7 @@ class Engine {
   // hot path
   void step(double dt);
   void sweep(double dt, bool forward);
+  int sweep_part(double dt, bool forward, int nsites);  // sites left in the half-sweep (0: complete)
   void invalidate_env();
 
   // observables
@@ -395,6 +396,11 @@ class Engine {
   void kraus_core(const zc* theta, int m, int d, int K, int n, const KrausOp& op, zc* out);
   void recanonicalize(int lo, int hi, DevBuf& spare);
   void build_left_envs();
+
+  // a half-sweep in progress (sweep_part): the next site, its direction, the spare tensor it works with
+  int sw_next_ = -1;
+  bool sw_fwd_ = true;
+  DevBuf sw_spare_;
 
   // adaptive bond dimension
   bool adaptive_ = false;

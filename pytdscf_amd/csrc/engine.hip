@@ -1209,25 +1209,42 @@ void Engine::local_site_exp(int p, double dt) {
 }
 
 void Engine::sweep(double dt, bool forward) {
-  require_ready();
-  if (L_ == 1) {
-    if (center_ != 0) throw ArgError("no centre site");
-    local_site_exp(0, dt);
-    ss_check();
-    return;
-  }
+  if (sw_next_ >= 0) throw ArgError("sweep: a half-sweep in parts is in progress");
+  sweep_part(dt, forward, L_);
+}
+
+// The half-sweep's loop, resumable: a call runs the next `nsites` sites of the half-sweep in progress (starting one when
+// none is) and returns how many are left; sweep() is one call over all L sites.
+int Engine::sweep_part(double dt, bool forward, int nsites) {
+  if (nsites < 1) throw ArgError("sweep_part: nsites must be >= 1");
   const int begin = forward ? 0 : L_ - 1, end = forward ? L_ - 1 : 0;
-  if (center_ != begin) throw ArgError("sweep must start at the centre (Psi) site");
-  if (forward) build_right_envs();
-  else build_left_envs();
-  const hzc shift = op(0).shift;
-  if (adaptive_) {
-    if (cfg.relax) throw ArgError("adaptive bond dimension is implemented for real-time propagation only");
-    adaptive_prepare();
-    build_superblock_full(forward);
+  if (sw_next_ < 0) {
+    require_ready();
+    if (L_ == 1) {
+      if (center_ != 0) throw ArgError("no centre site");
+      local_site_exp(0, dt);
+      ss_check();
+      return 0;
+    }
+    if (center_ != begin) throw ArgError("sweep must start at the centre (Psi) site");
+    if (forward) build_right_envs();
+    else build_left_envs();
+    if (adaptive_) {
+      if (cfg.relax) throw ArgError("adaptive bond dimension is implemented for real-time propagation only");
+      adaptive_prepare();
+      build_superblock_full(forward);
+    }
+    sw_spare_ = pool_get(V_.n / MAXK);
+    sw_next_ = begin;
+    sw_fwd_ = forward;
+  } else if (forward != sw_fwd_ || center_ != sw_next_) {
+    throw ArgError("sweep_part: the half-sweep in progress runs the other way or its state has moved");
   }
-  DevBuf spare = pool_get(V_.n / MAXK);
-  for (int p = begin; forward ? p <= end : p >= end; p += forward ? 1 : -1) {
+  const hzc shift = op(0).shift;
+  DevBuf& spare = sw_spare_;
+  const int stop = forward ? std::min(end, sw_next_ + nsites - 1) : std::max(end, sw_next_ - nsites + 1);
+  try {
+  for (int p = sw_next_; forward ? p <= stop : p >= stop; p += forward ? 1 : -1) {
     if (adaptive_ && p != end && adaptive_site(p, dt, forward, spare)) continue;
     local_site_exp(p, dt);  // exp_superH_propagation_direct
     if (p == end) break;
@@ -1296,8 +1313,19 @@ void Engine::sweep(double dt, bool forward) {
       center_ = p - 1;
     }
   }
-  pool_put(std::move(spare));
+  } catch (...) {  // a failed local update ends the half-sweep, as it did when the loop was one call
+    sw_next_ = -1;
+    DevBuf drop = std::move(sw_spare_);
+    throw;
+  }
+  if (stop != end) {
+    sw_next_ = stop + (forward ? 1 : -1);
+    return forward ? end - sw_next_ + 1 : sw_next_ - end + 1;
+  }
+  sw_next_ = -1;
+  pool_put(std::move(sw_spare_));
   ss_check();  // the one host synchronisation of a small-bond sweep: errors raised on the device
+  return 0;
 }
 
 void Engine::step(double dt) {

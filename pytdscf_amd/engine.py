@@ -295,6 +295,13 @@ class TDVPEngine:
     def sweep(self, dt_au: float, forward: bool):
         self._ck(self._lib.mitdvp_sweep(self._h, dt_au, int(forward)))
 
+    def sweep_part(self, dt_au: float, forward: bool, nsites: int) -> int:
+        """The next `nsites` local updates of a half-sweep (started when none is in progress) through sweep()'s own
+        code; returns the sites still to go (0: the half-sweep is complete)."""
+        left = C.c_int()
+        self._ck(self._lib.mitdvp_sweep_part(self._h, dt_au, int(forward), int(nsites), C.byref(left)))
+        return left.value
+
     def invalidate_env(self):
         self._ck(self._lib.mitdvp_invalidate_env(self._h))
 

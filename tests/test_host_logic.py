@@ -346,3 +346,69 @@ def test_bench_line_helpers():
     s = bench.secondary_summary({"C3": rec, "C5": {"error": "boom"}})
     assert s["C3"]["value"] == pytest.approx(64.947, rel=1e-4) and s["C3"]["frac"] == pytest.approx(0.5205, rel=1e-3)
     assert s["C3_ensemble"] == {"2": pytest.approx(407.12, rel=1e-4), "4": 566.0} and "error" in s["C5"]
+
+
+def test_bench_dump_outputs_layout(tmp_path):
+    """bench.py --dump-outputs: float64 files, every entry of a small site and a fixed seeded sample of a large one, the
+    same sample on every run (an engine stand-in that hands out the site tensors as the engine's get_site does)."""
+    import bench
+
+    rng = np.random.default_rng(3)
+    shapes = [(1, 4, 8), (8, 4, 3000), (3000, 4, 1)]
+    cores = [rng.standard_normal(s) + 1j * rng.standard_normal(s) for s in shapes]
+
+    class Eng:
+        nsite = len(cores)
+
+        def get_site(self, p):
+            return cores[p].copy()
+
+        def get_site_shape(self, p):
+            return shapes[p] + (0,)
+
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), Eng(), 0.75, -1.5)
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == ["energy.npy", "mps_sample.npy", "mps_sample_index.npy", "mps_shapes.npy", "norm.npy"]
+    a = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(x.dtype == np.float64 for x in a.values())
+    S = bench.DUMP_SAMPLES_PER_SITE
+    assert 96000 > S and a["mps_sample"].shape == (32 + 2 * S, 2) and a["mps_sample_index"].shape == (32 + 2 * S, 2)
+    assert a["mps_shapes"].tolist() == [list(s) for s in shapes] and a["norm"].tolist() == [0.75] and a["energy"].tolist() == [-1.5]
+    for (p, i), (re, im) in zip(a["mps_sample_index"].astype(int), a["mps_sample"]):
+        v = cores[p].reshape(-1)[i]
+        assert (re, im) == (v.real, v.imag)
+    site = a["mps_sample_index"][:, 0]
+    assert (a["mps_sample_index"][site == 0, 1] == np.arange(32)).all()  # a small site: all of it
+    assert len(set(a["mps_sample_index"][site == 1, 1])) == S  # a large one: S distinct entries
+    for n in names:
+        assert (np.load(tmp_path / "b" / n) == a[n[:-4]]).all(), n
+
+
+def test_bench_half_sweep_pieces():
+    """bench.py's pieces of a C4 half-sweep: every site once, shares of the modelled work that add up to one half-sweep
+    and stay near 1/8 each (the cheap edge sites ride with more of the chain), mirrored for the backward direction; the
+    PieceSweeper hands them to sweep_part in that order and alternates the direction after the last one."""
+    import bench
+
+    pieces = bench.half_sweep_pieces(64, 16, 1024, 32, 8)
+    n = [k for k, _ in pieces]
+    sh = [x for _, x in pieces]
+    assert len(pieces) == 8 and sum(n) == 64 and min(n) >= 1 and n == n[::-1]
+    assert abs(sum(sh) - 1) < 1e-12 and max(abs(x - 1 / 8) for x in sh) < 0.02
+
+    class Eng:
+        def __init__(self):
+            self.calls, self.left = [], 64
+
+        def sweep_part(self, dt, forward, nsites):
+            self.calls.append((forward, nsites))
+            self.left -= nsites
+            left, self.left = self.left, (64 if self.left == 0 else self.left)
+            return left
+
+    e = Eng()
+    ps = bench.PieceSweeper(e, 0.5, pieces)
+    got = [ps.step() for _ in range(16)]
+    assert e.calls == [(True, k) for k in n] + [(False, k) for k in n[::-1]]
+    assert got == sh + sh[::-1] and ps.forward and ps.k == 0

@@ -17,7 +17,7 @@ if [ "$which" = all ] || [ "$which" = c2 ]; then
   find /tmp/p_c2w -name "*counter_collection.csv" -exec cp {} $OUT/r02_c2_pmc_write.csv \;
 fi
 if [ "$which" = all ] || [ "$which" = c4 ]; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_c4 -- python3 $REPO/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r02_bench_C4_under_rocprof.json 2> $OUT/c4_bench.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_c4 -- python3 $REPO/bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r02_bench_C4_under_rocprof.json 2> $OUT/c4_bench.err
   find /tmp/p_c4 -name "*kernel_stats.csv" -exec cp {} $OUT/r02_c4_kernel_stats.csv \;
 fi
 ls -la $OUT

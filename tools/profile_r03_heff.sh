@@ -15,10 +15,10 @@ find /tmp/h3 -name "*counter_collection.csv" -exec cp {} $OUT/r03_heff_pmc_util.
 tail -n 1 $OUT/heff_trace.out
 cd $REPO
 for w in C2 C3 C5; do
-  python3 bench.py --workload $w --steps 20 --warmup 5 > $OUT/r03_bench_$w.json 2> $OUT/r03_bench_$w.err
+  python3 bench.py --full --workload $w --steps 20 --warmup 5 > $OUT/r03_bench_$w.json 2> $OUT/r03_bench_$w.err
   tail -c 300 $OUT/r03_bench_$w.json; echo
 done
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_c4 -- python3 $REPO/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r03_bench_C4_under_rocprof.json 2> $OUT/c4_bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_c4 -- python3 $REPO/bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r03_bench_C4_under_rocprof.json 2> $OUT/c4_bench.err
 find /tmp/p_c4 -name "*kernel_stats.csv" -exec cp {} $OUT/r03_c4_kernel_stats.csv \;
 head -5 $OUT/r03_c4_kernel_stats.csv | cut -c1-200

@@ -4,7 +4,7 @@
 set -u
 REPO=$(pwd); OUT=$REPO/gpurun_out/r04prof; mkdir -p $OUT
 for w in C2 C3 C5; do
-  python3 bench.py --workload $w --steps 20 --warmup 5 --secondary none > $OUT/r04_bench_$w.json 2> $OUT/r04_bench_$w.err
+  python3 bench.py --full --workload $w --steps 20 --warmup 5 --secondary none > $OUT/r04_bench_$w.json 2> $OUT/r04_bench_$w.err
   tail -c 200 $OUT/r04_bench_$w.json; echo
 done
 export TMPDIR=/tmp; cd /tmp
@@ -23,6 +23,6 @@ for spec in "C3 128 32 16 8" "C5 512 4 16 6" "C4 1024 16 32 3"; do
   done
 done
 cp $REPO/profiles/r04_heff_traffic_* $OUT/ 2>/dev/null
-MITDVP_BENCH_BUDGET=230 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_c4 -- python3 $REPO/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r04_bench_C4_under_rocprof.json 2> $OUT/c4_bench.err
+MITDVP_BENCH_BUDGET=230 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_c4 -- python3 $REPO/bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r04_bench_C4_under_rocprof.json 2> $OUT/c4_bench.err
 find /tmp/p_c4 -name "*kernel_stats.csv" -exec cp {} $OUT/r04_c4_kernel_stats.csv \;
 head -5 $OUT/r04_c4_kernel_stats.csv | cut -c1-200

@@ -39,7 +39,7 @@ done
 cp $REPO/profiles/r05_* $OUT/ 2>/dev/null
 for w in C3 C5; do
   echo "== kernel stats $w" | tee -a $OUT/progress.txt
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$w -- python3 $REPO/bench.py --workload $w --steps 6 --warmup 2 --secondary none --no-cpu-baseline > $OUT/r05_bench_${w}_under_rocprof.json 2> $OUT/${w}_bench.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$w -- python3 $REPO/bench.py --full --workload $w --steps 6 --warmup 2 --secondary none --no-cpu-baseline > $OUT/r05_bench_${w}_under_rocprof.json 2> $OUT/${w}_bench.err
   find /tmp/p_$w -name "*kernel_stats.csv" -exec cp {} $OUT/r05_$(echo $w | tr A-Z a-z)_kernel_stats.csv \;
 done
 ls $OUT | tee -a $OUT/progress.txt

@@ -26,7 +26,7 @@ cp $REPO/profiles/r05_heff_traffic_*_edge.json $REPO/profiles/r05_heff_mfma_util
 for w in C3 C5 C4; do
   echo "== kernel stats $w $(date +%T)" | tee -a $OUT/progress.txt
   st=6; [ $w = C4 ] && st=2
-  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$w -- python3 $REPO/bench.py --workload $w --steps $st --warmup 1 --secondary none --no-cpu-baseline > $OUT/r05_bench_${w}_under_rocprof_final.json 2> $OUT/${w}_bench.err || { echo "stats $w failed" | tee -a $OUT/progress.txt; exit 1; }
+  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$w -- python3 $REPO/bench.py --full --workload $w --steps $st --warmup 1 --secondary none --no-cpu-baseline > $OUT/r05_bench_${w}_under_rocprof_final.json 2> $OUT/${w}_bench.err || { echo "stats $w failed" | tee -a $OUT/progress.txt; exit 1; }
   find /tmp/p_$w -name "*kernel_stats.csv" -exec cp {} $OUT/r05_$(echo $w | tr A-Z a-z)_kernel_stats_final.csv \;
   if [ $w = C3 ]; then
     f=$(find /tmp/p_$w -name '*kernel_trace.csv' | head -1)

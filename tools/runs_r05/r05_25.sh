@@ -2,7 +2,7 @@
 # the driver's command, then smoke()
 O=gpurun_out/r05drv
 mkdir -p $O
-timeout -k 20 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r05_bench_C4_driver_cmd.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 20 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r05_bench_C4_driver_cmd.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python - <<P
 import json
 r=json.loads(open("$O/r05_bench_C4_driver_cmd.json").read().strip().splitlines()[-1])

@@ -9,7 +9,7 @@ for t in 0 32; do
   echo "tune $t"; sed -n 3,4p $O/tune_$t.txt | cut -c1-120
 done
 for t in 0; do
-  MITDVP_TIMING_ABLATION=1 MITDVP_ZGEMM_TUNE=$t timeout -k 20 300 python bench.py --workload C3 --steps 30 --warmup 3 --no-cpu-baseline --secondary none > $O/c3_$t.json 2> $O/c3_$t.err || { tail -20 $O/c3_$t.err; exit 1; }
+  MITDVP_TIMING_ABLATION=1 MITDVP_ZGEMM_TUNE=$t timeout -k 20 300 python bench.py --full --workload C3 --steps 30 --warmup 3 --no-cpu-baseline --secondary none > $O/c3_$t.json 2> $O/c3_$t.err || { tail -20 $O/c3_$t.err; exit 1; }
   python - <<P
 import json
 r=json.loads(open("$O/c3_$t.json").read().strip().splitlines()[-1])

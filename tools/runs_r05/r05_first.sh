@@ -5,7 +5,7 @@ O=gpurun_out/r05a
 mkdir -p $O
 python -m pytest tests/test_mixedstate_exact.py tests/test_gpu_ensemble.py -m gpu -x -q -s > $O/tests.txt 2>&1 || { tail -30 $O/tests.txt; exit 1; }
 tail -5 $O/tests.txt
-B="python bench.py --no-cpu-baseline --secondary none"
+B="python bench.py --full --no-cpu-baseline --secondary none"
 $B --workload C3 --steps 20 --warmup 2 > $O/c3_base.json 2> $O/c3_base.err
 MITDVP_ZGEMM_BIGTILE=1 $B --workload C3 --steps 20 --warmup 2 > $O/c3_bigtile.json 2> $O/c3_bigtile.err
 MITDVP_EDGE_APPLY=1 $B --workload C3 --steps 20 --warmup 2 > $O/c3_edge.json 2> $O/c3_edge.err

@@ -8,7 +8,7 @@ import sys; sys.path.insert(0,'.')
 from pytdscf_amd.engine import qr_thin
 print(qr_thin(shape=(4096,128), gauge_free=True, reps=2)[2])
 " > $O/qr_trace.txt 2>&1; tail -8 $O/qr_trace.txt
-B="python bench.py --no-cpu-baseline --secondary none"
+B="python bench.py --full --no-cpu-baseline --secondary none"
 echo "== ensemble probe (1024 threads)" | tee -a $O/progress.txt
 timeout -k 10 300 python tools/ensemble_partition_probe.py 2>&1 | tee $O/ens_probe_1024.txt || exit 1
 echo "== ensemble probe (512 threads)" | tee -a $O/progress.txt

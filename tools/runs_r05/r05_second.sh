@@ -3,7 +3,7 @@
 set -o pipefail
 O=gpurun_out/r05b
 mkdir -p $O
-B="python bench.py --no-cpu-baseline --secondary none"
+B="python bench.py --full --no-cpu-baseline --secondary none"
 run() { name=$1; shift; echo "== $name" | tee -a $O/progress.txt; env "$@" timeout -k 10 300 $B --workload ${WL:-C3} --steps ${ST:-20} --warmup 2 > $O/$name.json 2> $O/$name.err || { echo "FAILED $name" | tee -a $O/progress.txt; tail -5 $O/$name.err; return 1; }; }
 run c3_lapack MITDVP_QR_GAUGE_FREE=0 || exit 1
 run c3_gram MITDVP_QR_GAUGE_FREE=1 || exit 1

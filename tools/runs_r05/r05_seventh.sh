@@ -6,7 +6,7 @@ echo "== ensemble tests" | tee -a $O/progress.txt
 timeout -k 10 400 python -m pytest tests/test_gpu_ensemble.py -x -q -s -o faulthandler_timeout=100 > $O/ens_tests.txt 2>&1; rc=$?; tail -30 $O/ens_tests.txt; [ $rc -eq 0 ] || exit 1
 echo "== ensemble probe" | tee -a $O/progress.txt
 timeout -k 10 300 python tools/ensemble_partition_probe.py 2>&1 | tee $O/ens_probe.txt || exit 1
-B="python bench.py --no-cpu-baseline --secondary none"
+B="python bench.py --full --no-cpu-baseline --secondary none"
 timeout -k 10 300 $B --workload C3 --steps 20 --warmup 2 > $O/c3.json 2> $O/c3.err || exit 1
 timeout -k 10 300 $B --workload C2 --steps 100 --warmup 4 > $O/c2.json 2> $O/c2.err || exit 1
 python - <<'P' | tee -a gpurun_out/r05g/progress.txt

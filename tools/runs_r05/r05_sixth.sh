@@ -4,7 +4,7 @@ O=gpurun_out/r05f
 mkdir -p $O
 echo "== edge tests" | tee -a $O/progress.txt
 timeout -k 10 500 python -m pytest tests/test_gpu_edge_apply.py tests/test_gpu_kernels.py -x -q -o faulthandler_timeout=200 > $O/edge_tests.txt 2>&1; rc=$?; tail -8 $O/edge_tests.txt; [ $rc -eq 0 ] || exit 1
-B="python bench.py --no-cpu-baseline --secondary none"
+B="python bench.py --full --no-cpu-baseline --secondary none"
 run() { name=$1; shift; echo "== $name" | tee -a $O/progress.txt; env "$@" timeout -k 10 300 $B --workload ${WL:-C3} --steps ${ST:-20} --warmup 2 > $O/$name.json 2> $O/$name.err || { echo "FAILED $name" | tee -a $O/progress.txt; tail -5 $O/$name.err; return 1; }; }
 run c3_chain MITDVP_EDGE_APPLY=0 || exit 1
 run c3_edge_b4 MITDVP_EDGE_APPLY=1 || exit 1

@@ -11,7 +11,7 @@ from pytdscf_amd.engine import qr_thin
 print(qr_thin(shape=(4096,128), gauge_free=True, reps=2)[2])
 " > $O/qr_trace.txt 2>&1; tail -4 $O/qr_trace.txt
 timeout -k 10 200 python tools/qr_thin_probe.py 2>&1 | tee $O/qr_probe.txt || exit 1
-B="python bench.py --no-cpu-baseline --secondary none"
+B="python bench.py --full --no-cpu-baseline --secondary none"
 timeout -k 10 300 $B --workload C3 --steps 20 --warmup 2 > $O/c3.json 2> $O/c3.err || exit 1
 timeout -k 10 300 $B --workload C5 --steps 4 --warmup 1 > $O/c5.json 2> $O/c5.err || exit 1
 timeout -k 10 300 $B --workload C2 --steps 100 --warmup 4 > $O/c2.json 2> $O/c2.err || exit 1

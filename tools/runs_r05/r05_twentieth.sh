@@ -10,7 +10,7 @@ for t in 0 32; do
 done
 for w in C3 C5; do
   st=30; [ $w = C5 ] && st=4
-  timeout -k 20 300 python bench.py --workload $w --steps $st --warmup 3 --no-cpu-baseline --secondary none > $O/$w.json 2> $O/$w.err || { tail -20 $O/$w.err; exit 1; }
+  timeout -k 20 300 python bench.py --full --workload $w --steps $st --warmup 3 --no-cpu-baseline --secondary none > $O/$w.json 2> $O/$w.err || { tail -20 $O/$w.err; exit 1; }
   python - <<P
 import json
 r=json.loads(open("$O/$w.json").read().strip().splitlines()[-1])
@@ -18,7 +18,7 @@ print("$w", r["value"], r["ms_per_step"], r["roofline"]["frac"])
 P
 done
 for e in 1 0; do
-  MITDVP_EDGE_APPLY=$e timeout -k 20 400 python bench.py --workload C4 --steps 2 --warmup 1 --no-cpu-baseline --secondary none > $O/c4_$e.json 2> $O/c4_$e.err || { tail -20 $O/c4_$e.err; exit 1; }
+  MITDVP_EDGE_APPLY=$e timeout -k 20 400 python bench.py --full --workload C4 --steps 2 --warmup 1 --no-cpu-baseline --secondary none > $O/c4_$e.json 2> $O/c4_$e.err || { tail -20 $O/c4_$e.err; exit 1; }
   python - <<P
 import json
 r=json.loads(open("$O/c4_$e.json").read().strip().splitlines()[-1])
