@@ -638,7 +638,7 @@ int mitdvp_qr_thin(int device, const double* a, int m, int n, int gauge_free, do
     bool used = false;
     auto once = [&] {
       HIP_CHECK(hipMemcpyAsync(A.p(), A0.p(), (size_t)m * n * sizeof(zc), hipMemcpyDeviceToDevice, st));
-      qr_thin(st, A.p(), m, n, Q.p(), R.p(), work.p(), &nl, nullptr, hist, gauge_free != 0, &used);
+      qr_thin(st, A.p(), m, n, Q.p(), R.p(), work.p(), &nl, hist, gauge_free != 0, &used);
     };
     try {
       once();
@@ -680,7 +680,7 @@ int mitdvp_bench_qr(int device, int m, int n, int reps, double* ms_out, long* la
     long nl = 0;
     auto once = [&] {
       HIP_CHECK(hipMemcpyAsync(A.p(), A0.p(), (size_t)m * n * sizeof(zc), hipMemcpyDeviceToDevice, st));
-      qr_householder(st, A.p(), m, n, Q.p(), R.p(), work.p(), &nl, 0, nullptr);
+      qr_householder(st, A.p(), m, n, Q.p(), R.p(), work.p(), &nl);
     };
     once();
     nl = 0;

@@ -5,6 +5,7 @@
 #include <complex>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 
@@ -33,6 +34,39 @@ struct NotConverged : std::runtime_error {
       throw ::mitdvp::HipError(_b);                                                       \
     }                                                                                     \
   } while (0)
+
+// Zero-filled host memory that the device sees coherently: h is the host's pointer, d the device's address of the same
+// bytes.  A kernel publishes a few words through it and the host reads them without a copy; freed with the holder.
+template <class T>
+struct MappedHost {
+  T* h = nullptr;
+  T* d = nullptr;
+  MappedHost() = default;
+  MappedHost(const MappedHost&) = delete;
+  MappedHost& operator=(const MappedHost&) = delete;
+  ~MappedHost() { if (h) (void)hipHostFree(h); }
+  void alloc(size_t bytes) {
+    HIP_CHECK(hipHostMalloc((void**)&h, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(h, 0, bytes);
+    void* dp = nullptr;
+    HIP_CHECK(hipHostGetDevicePointer(&dp, h, 0));
+    d = static_cast<T*>(dp);
+  }
+};
+
+// Waits until the device has published `tag` in the word *w of such memory, then orders the plain loads of what lies
+// behind the word.  Every 65 536 spins the stream is asked: once it is no longer busy (idle, or failed) it is synchronised,
+// which surfaces a failure, and a word that has still not arrived throws HipError(what).  The only host spin in the library.
+template <class T>
+inline void wait_published(hipStream_t st, const volatile T* w, T tag, const char* what) {
+  for (long spins = 0; *w != tag; ++spins) {
+    if ((spins & 0xFFFF) == 0xFFFF && hipStreamQuery(st) != hipErrorNotReady) {
+      HIP_CHECK(hipStreamSynchronize(st));
+      if (*w != tag) throw HipError(what);
+    }
+  }
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+}
 
 __host__ __device__ inline zc zmake(double re, double im) { return make_double2(re, im); }
 __host__ __device__ inline zc zmul(zc a, zc b) {

@@ -199,13 +199,10 @@ class Engine {
   // w2e: the small-site form of the same core (MpoSite::w2el / w2er), nullptr = general path only
   void env_update(const zc* env_in, const zc* T, const zc* w2, zc* env_out, int din, int min_, int d, int dout,
                   int mout, const zc* w2e = nullptr, const MpoSite* sp = nullptr, int sp_side = 0);
-  // x <- exp(scale * Op) x ; returns Krylov dimension used
+  // x <- exp(scale * Op) x ; returns Krylov dimension used.  The Ritz step and the convergence test run on the device
+  // (krylov_dev.h)
   template <class MV>
   int krylov_exp(hzc scale, MV&& matvec, zc* x, long n, int k_prev, long nsize = -1);
-  // the same with the Ritz step and the convergence test on the device (krylov_dev.h): what krylov_exp runs unless
-  // MITDVP_DEVICE_RITZ=0
-  template <class MV>
-  int krylov_exp_dev(hzc scale, MV&& matvec, zc* x, long n, int k_prev, long nsize);
   // x <- lowest eigenvector of Op (improved relaxation); returns Krylov dimension used
   template <class MV>
   int krylov_diag(MV&& matvec, zc* x, long n);
@@ -322,19 +319,14 @@ class Engine {
   // workspaces
   DevBuf X_, Y_, V_, Vdiag_, tmp1_, tmp2_, sig_, sig2_, qrwork_, red_;
   int max_diag_krylov_ = 64;
-  zc* h_red_ = nullptr;  // pinned host mirror of red_ (host-coherent, mapped into the device: h_red_dev_)
-  zc* h_red_dev_ = nullptr;
-  unsigned* h_seq_ = nullptr;      // sequence word the publish kernel bumps and read_partials spins on
-  unsigned* h_seq_dev_ = nullptr;
+  MappedHost<zc> h_red_;        // pinned host mirror of red_
+  MappedHost<unsigned> h_seq_;  // sequence word the publish kernel bumps and read_partials waits on
   unsigned seq_tag_ = 0;
   // device-resident convergence logic of the multi-launch Krylov loop (krylov_dev.h)
-  bool device_ritz_ = true;      // MITDVP_DEVICE_RITZ=0: Ritz step and test on the host (two round trips per checked iteration)
-  bool defer_norm_ = true;       // MITDVP_DEFER_NORM=0: a normalisation launch per Krylov vector (device path only)
   KryDev* kst_ = nullptr;
-  KryPub* h_kpub_ = nullptr;     // host-coherent, mapped into the device: h_kpub_dev_
-  KryPub* h_kpub_dev_ = nullptr;
+  MappedHost<KryPub> h_kpub_;    // the record the device publishes after each checked iteration
   unsigned kry_tag_ = 0;
-  void wait_pub(unsigned tag);   // spins until the record with this tag has been published
+  void wait_pub(unsigned tag);   // waits until the record with this tag has been published
   size_t red_elems_ = 0;
   std::vector<int> kprev_;
 
@@ -380,7 +372,6 @@ class Engine {
   bool chain_keff(SmallChain& c, const zc* L, const zc* R, int d1, int d2, int m, bool exp_mode) const;
   bool chain_env(SmallChain& c, const zc* T, const zc* w2e, int din, int min_, int d, int dout, int mout) const;
   zc* ss_partials(const SmallChain& c);
-  SmallSync* qr_sync();          // exchange state for the persistent QR panel kernel (nullptr: per-column launches)
   QrHistory* qr_hist_ = nullptr; // this engine's memory of the shapes whose fast panels keep failing (qr.h)
   void ss_refresh_plan();
   void ss_check();               // raises what the small-site kernels recorded (not converged / timed out)

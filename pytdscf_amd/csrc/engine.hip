@@ -27,9 +27,7 @@ Engine::Engine(const mitdvp_config& c) : cfg(c), L_(c.nsite) {
   if (const char* e = std::getenv("MITDVP_SMALL_KERNELS")) small_kernels_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_SPARSE_W")) sparse_w_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_TRIM_IDENTITY")) trim_identity_ = std::atoi(e) != 0;
-  if (const char* e = std::getenv("MITDVP_DEVICE_RITZ")) device_ritz_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_EDGE_APPLY")) edge_mode_ = std::atoi(e);
-  if (const char* e = std::getenv("MITDVP_DEFER_NORM")) defer_norm_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_QR_GAUGE_FREE")) qr_gauge_free_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_KEFF_IDENT")) keff_ident_ = std::atoi(e) != 0;
   int ndev = 0;
@@ -63,25 +61,11 @@ Engine::Engine(const mitdvp_config& c) : cfg(c), L_(c.nsite) {
   kprev_.assign(L_, 0);
   red_.reserve(RED_TOTAL);
   red_elems_ = RED_TOTAL;
-  HIP_CHECK(hipHostMalloc((void**)&h_red_, RED_TOTAL * sizeof(zc), hipHostMallocMapped | hipHostMallocCoherent));
-  HIP_CHECK(hipHostMalloc((void**)&h_seq_, 64, hipHostMallocMapped | hipHostMallocCoherent));
-  *h_seq_ = 0;
-  {
-    void* dp = nullptr;
-    HIP_CHECK(hipHostGetDevicePointer(&dp, h_red_, 0));
-    h_red_dev_ = static_cast<zc*>(dp);
-    HIP_CHECK(hipHostGetDevicePointer(&dp, h_seq_, 0));
-    h_seq_dev_ = static_cast<unsigned*>(dp);
-  }
+  h_red_.alloc(RED_TOTAL * sizeof(zc));
+  h_seq_.alloc(64);
   HIP_CHECK(hipMalloc((void**)&kst_, sizeof(KryDev)));
   HIP_CHECK(hipMemsetAsync(kst_, 0, sizeof(KryDev), st_));
-  HIP_CHECK(hipHostMalloc((void**)&h_kpub_, sizeof(KryPub), hipHostMallocMapped | hipHostMallocCoherent));
-  std::memset(h_kpub_, 0, sizeof(KryPub));
-  {
-    void* dp = nullptr;
-    HIP_CHECK(hipHostGetDevicePointer(&dp, h_kpub_, 0));
-    h_kpub_dev_ = static_cast<KryPub*>(dp);
-  }
+  h_kpub_.alloc(sizeof(KryPub));
   // trivial boundary blocks, construct_op_zerosite (_mps_mpo.py:364-419)
   const zc one = make_double2(1.0, 0.0);
   envL_[0].reserve(1); envR_[L_].reserve(1);
@@ -98,9 +82,6 @@ Engine::~Engine() {
   if (rccl_comm_) (void)RcclApi::get().comm_destroy(static_cast<ncclComm_t>(rccl_comm_));
   for (auto& t : pending_) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
   for (auto& e : evpool_) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-  if (h_red_) (void)hipHostFree(h_red_);
-  if (h_seq_) (void)hipHostFree(h_seq_);
-  if (h_kpub_) (void)hipHostFree(h_kpub_);
   if (kst_) (void)hipFree(kst_);
   if (st_) { zgemm_release_stream(st_); (void)hipStreamDestroy(st_); }
 }
@@ -180,7 +161,7 @@ void Engine::counters_reset() {
 // A Krylov iteration's scalars on their way to the host.  hipMemcpyAsync + hipStreamSynchronize costs ~15 us per round
 // trip on this stack; a one-workgroup kernel that copies the values into the (host-coherent, device-mapped) pinned buffer
 // and then bumps a sequence word the host spins on costs ~7 us (tools/probes/sync_latency.hip).  Local exponentials of the
-// mid-size regime wait for three or four such round trips each.  MITDVP_SPIN_SYNC=0: the copy + synchronise form.
+// mid-size regime wait for three or four such round trips each.  Reads of more than 16384 elements keep the copy + synchronise form.
 __global__ __launch_bounds__(256) void k_publish(const zc* __restrict__ src, zc* __restrict__ dst, size_t count,
                                                  volatile unsigned* seq, unsigned tag) {
   for (size_t e = threadIdx.x; e < count; e += 256) dst[e] = src[e];
@@ -191,35 +172,19 @@ __global__ __launch_bounds__(256) void k_publish(const zc* __restrict__ src, zc*
 
 void Engine::read_partials(size_t off, size_t count) {
   cnt_.n_host_waits += 1;
-  static const bool spin = !(std::getenv("MITDVP_SPIN_SYNC") && std::atoi(std::getenv("MITDVP_SPIN_SYNC")) == 0);
-  if (spin && h_seq_ && count <= 16384) {
+  if (count <= 16384) {
     const unsigned tag = ++seq_tag_;
-    hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, st_, red_.p + off, h_red_dev_ + off, count, h_seq_dev_, tag);
+    hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, st_, red_.p + off, h_red_.d + off, count, h_seq_.d, tag);
     HIP_CHECK(hipGetLastError());
-    volatile unsigned* w = h_seq_;
-    for (long spins = 0; *w != tag; ++spins) {
-      if ((spins & 0xFFFF) == 0xFFFF && hipStreamQuery(st_) != hipErrorNotReady) {
-        // the stream is idle (or failed) and the word never arrived: surface the error / fall through after a sync
-        HIP_CHECK(hipStreamSynchronize(st_));
-        if (*w != tag) throw HipError("read_partials: the publish kernel did not deliver");
-      }
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);  // the values behind the word are read with plain loads
+    wait_published(st_, h_seq_.h, tag, "read_partials: the publish kernel did not deliver");
     return;
   }
-  HIP_CHECK(hipMemcpyAsync(h_red_ + off, red_.p + off, count * sizeof(zc), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipMemcpyAsync(h_red_.h + off, red_.p + off, count * sizeof(zc), hipMemcpyDeviceToHost, st_));
   HIP_CHECK(hipStreamSynchronize(st_));
 }
 
 void Engine::wait_pub(unsigned tag) {
-  volatile unsigned* w = &h_kpub_->seq;
-  for (long spins = 0; *w != tag; ++spins) {
-    if ((spins & 0xFFFF) == 0xFFFF && hipStreamQuery(st_) != hipErrorNotReady) {
-      HIP_CHECK(hipStreamSynchronize(st_));
-      if (*w != tag) throw HipError("wait_pub: the Krylov record was not published");
-    }
-  }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  wait_published(st_, &h_kpub_.h->seq, tag, "wait_pub: the Krylov record was not published");
 }
 
 // ---------------------------------------------------------------------------
@@ -730,7 +695,7 @@ void Engine::choose_apply_forms(const zc* Lb, const MpoSite& w, const zc* Rb, in
   static_assert(sizeof(IdentRecord) == 128 * 8 + 128 * 16 && sizeof(IdentRecord) <= 4 * NPART * sizeof(zc), "layout of the identity-check record");
   // (the record comes back through the pinned mirror of the reduction area -- read_partials: ~10 us; a copy into pageable
   // host memory followed by a stream synchronisation measured ~120 us of idle GPU per site, 9 % of a C3 sweep)
-  const IdentRecord& h = *reinterpret_cast<const IdentRecord*>(h_red_ + RED_MISC);
+  const IdentRecord& h = *reinterpret_cast<const IdentRecord*>(h_red_.h + RED_MISC);
   // The identity states of a site do not change from sweep to sweep (they follow from the MPO's structure and the
   // canonical form): first only the blocks that were identity multiples last time are looked at (3 of 16 at C5); all of
   // them again when one of those has stopped being one, or when there is no previous answer.
@@ -850,7 +815,7 @@ void Engine::keff_prepare(const zc* L, const zc* R, int d1, int d2, int m) {
   double* dev = reinterpret_cast<double*>(red_.p + RED_MISC);
   zc* lam_dev = red_.p + RED_MISC + 64;
   struct IdentRecord { double dev[128]; hzc lam[128]; };
-  const IdentRecord& h = *reinterpret_cast<const IdentRecord*>(h_red_ + RED_MISC);
+  const IdentRecord& h = *reinterpret_cast<const IdentRecord*>(h_red_.h + RED_MISC);
   HIP_CHECK(hipMemsetAsync(dev, 0, 128 * sizeof(double), st_));
   ident_deviation_multi(st_, L, m, (long)d1, (long)m * d1, d1, dev, lam_dev, ~0ull, false);
   ident_deviation_multi(st_, R, m, (long)d2, (long)m * d2, d2, dev + 64, lam_dev + 64, ~0ull, false);
@@ -991,7 +956,7 @@ void Engine::gauge_qr_left(const zc* psi, int dl, int d, int dr, zc* A_out, zc* 
   HIP_CHECK(hipMemcpyAsync(tmp1_.p, psi, n * sizeof(zc), hipMemcpyDeviceToDevice, st_));
   timer_begin(3);
   long nl = 0;
-  qr_thin(st_, tmp1_.p, dl * d, dr, A_out, sigma_out, qrwork_.p, &nl, qr_sync(), qr_hist_, qr_gauge_free_);
+  qr_thin(st_, tmp1_.p, dl * d, dr, A_out, sigma_out, qrwork_.p, &nl, qr_hist_, qr_gauge_free_);
   timer_end();
   cnt_.n_launch += nl;
   cnt_.n_qr += 1;
@@ -1003,7 +968,7 @@ void Engine::gauge_qr_right(const zc* psi, int dl, int d, int dr, zc* B_out, zc*
   timer_begin(3);
   long nl = 0;
   transpose_rev3(st_, psi, tmp1_.p, dl, d, dr);  // (dr, d, dl)
-  qr_thin(st_, tmp1_.p, dr * d, dl, Bt_out, sig2_.p, qrwork_.p, &nl, qr_sync(), qr_hist_, qr_gauge_free_);
+  qr_thin(st_, tmp1_.p, dr * d, dl, Bt_out, sig2_.p, qrwork_.p, &nl, qr_hist_, qr_gauge_free_);
   transpose_batched(st_, sig2_.p, sigma_out, dl, dl, dl, dl, 1, 0, 0);  // sigma = R^T
   if (B_out) transpose_rev3(st_, Bt_out, B_out, dr, d, dl);             // (dl, d, dr)
   timer_end();
@@ -1098,7 +1063,7 @@ void Engine::canonicalize(double scale) {
       vec_scale_inv_norm(st_, sig_.p, (long)dl * dl, nrm, 1e-300);
       if (scale <= 0.0) {
         read_partials(RED_MISC, NPART / 2);
-        const double* hp = reinterpret_cast<const double*>(h_red_ + RED_MISC);
+        const double* hp = reinterpret_cast<const double*>(h_red_.h + RED_MISC);
         double t = 0;
         for (int i = 0; i < NPART; ++i) t += hp[i];
         if (t > 0) log_scale += 0.5 * std::log(t);
@@ -1115,7 +1080,7 @@ void Engine::canonicalize(double scale) {
   const long n0 = (long)dl_[0] * dd_[0] * dr_[0];
   vec_sumsq(st_, site_[0].p, n0, reinterpret_cast<double*>(red_.p + RED_MISC));
   read_partials(RED_MISC, NPART / 2);
-  const double* hp = reinterpret_cast<const double*>(h_red_ + RED_MISC);
+  const double* hp = reinterpret_cast<const double*>(h_red_.h + RED_MISC);
   double s = 0;
   for (int i = 0; i < NPART; ++i) s += hp[i];
   if (s == 0.0) throw ArgError("canonicalize: zero state");
@@ -1181,7 +1146,7 @@ bool Engine::left_block_is_identity(const zc* L, int dl, int m) {
 // is not checked
 void Engine::identity_blocks(const zc* L, int dl, int ml, const zc* R, int dr, int mr, bool* left, bool* right) {
   double* dev = reinterpret_cast<double*>(red_.p + RED_MISC);
-  const double* h = reinterpret_cast<const double*>(h_red_ + RED_MISC);
+  const double* h = reinterpret_cast<const double*>(h_red_.h + RED_MISC);
   if (L) ident_deviation(st_, L, (long)ml * dl, dl, dev);
   if (R) ident_deviation(st_, R + (size_t)(mr - 1) * dr, (long)mr * dr, dr, dev + 1);
   if (L || R) read_partials(RED_MISC, 1);
@@ -1254,7 +1219,7 @@ int Engine::sweep_part(double dt, bool forward, int nsites) {
       // Psi2Asigma: site[p] (destroyed) -> A in spare, sigma in sig_
       timer_begin(3);
       long nl = 0;
-      qr_thin(st_, site_[p].p, dl * d, dr, spare.p, sig_.p, qrwork_.p, &nl, qr_sync(), qr_hist_, qr_gauge_free_);
+      qr_thin(st_, site_[p].p, dl * d, dr, spare.p, sig_.p, qrwork_.p, &nl, qr_hist_, qr_gauge_free_);
       timer_end();
       cnt_.n_launch += nl; cnt_.n_qr += 1;
       cnt_.qr_flops += 4.0 * (4.0 * (double)dl * d * dr * dr - 4.0 * (double)dr * dr * dr / 3.0);

@@ -6,192 +6,8 @@
 namespace mitdvp {
 
 // ---------------------------------------------------------------------------
-// local propagator: x <- exp(scale*Op) x
-// ---------------------------------------------------------------------------
-template <class MV>
-int Engine::krylov_exp(hzc scale, MV&& matvec, zc* x, long n, int k_prev, long nsize) {
-  // nsize: element count of the UNPADDED input tensor (adaptive rank: x is zero-padded to
-  // the output shape but _iter_info still counts psi_states, _integrator.py:178-186, :524)
-  if (nsize <= 0) nsize = n;
-  if (device_ritz_) return krylov_exp_dev(scale, matvec, x, n, k_prev, nsize);
-  const int ndim = (int)std::min<long>(nsize, cfg.max_krylov);
-  const int n_warm = (int)std::min<long>(nsize, std::min(std::max(0, k_prev - 2), 15));
-  const bool lanczos = cfg.integrator == MITDVP_LANCZOS;
-  const bool cn = cfg.conserve_norm != 0;
-  zc* V = V_.p;
-  const long ldv = n;
-  zc* alpha_p = red_.p + RED_ALPHA;
-  double* nrm_p = reinterpret_cast<double*>(red_.p + RED_NRM);
-  zc* h_p = red_.p + RED_H;
-  double* misc_d = reinterpret_cast<double*>(red_.p + RED_MISC);
-
-  // _normalize (_integrator.py:189-203)
-  double beta0 = 1.0;
-  HIP_CHECK(hipMemcpyAsync(V, x, n * sizeof(zc), hipMemcpyDeviceToDevice, st_));
-  if (!cn) {
-    vec_sumsq(st_, x, n, misc_d);
-    read_partials(RED_MISC, NPART / 2);
-    const double* hp = reinterpret_cast<const double*>(h_red_ + RED_MISC);
-    double s = 0;
-    for (int i = 0; i < NPART; ++i) s += hp[i];
-    beta0 = std::sqrt(s);
-    if (beta0 == 0.0) throw ArgError("Initial psi has zero norm.");
-    vec_scale(st_, V, n, make_double2(1.0 / beta0, 0.0));
-  }
-
-  std::vector<hzc> alpha;            // Lanczos diagonal
-  std::vector<double> beta;          // norms of the new vectors
-  std::vector<hzc> hess((size_t)(ndim + 1) * ndim, hzc(0, 0));  // Arnoldi Hessenberg (row-major, ld = ndim)
-  std::vector<hzc> coef_prev;
-  int next_unread = 0;
-
-  auto sum_z = [&](size_t off) {
-    double re = 0, im = 0;
-    for (int i = 0; i < NPART; ++i) { re += h_red_[off + i].x; im += h_red_[off + i].y; }
-    return hzc(re, im);
-  };
-  auto sum_d = [&](size_t off_zc, int row) {
-    const double* p = reinterpret_cast<const double*>(h_red_ + off_zc) + (size_t)row * NPART;
-    double s = 0;
-    for (int i = 0; i < NPART; ++i) s += p[i];
-    return s;
-  };
-
-  auto finalize = [&](const std::vector<hzc>& coef, int k) {
-    Coefs c{};
-    for (int j = 0; j < k; ++j) {
-      const hzc v = cn ? coef[j] : coef[j] * beta0;  // _rescale, :206-213
-      c.c[j] = make_double2(v.real(), v.imag());
-    }
-    if (cn) {
-      vec_lincomb(st_, x, V, ldv, k, c, n, misc_d);
-      read_partials(RED_MISC, NPART / 2);
-      const double* hp = reinterpret_cast<const double*>(h_red_ + RED_MISC);
-      double s = 0;
-      for (int i = 0; i < NPART; ++i) s += hp[i];
-      vec_scale(st_, x, n, make_double2(1.0 / std::sqrt(s), 0.0));
-    } else {
-      vec_lincomb(st_, x, V, ldv, k, c, n, nullptr);
-    }
-    cnt_.n_launch += 2;
-  };
-
-  for (int l = 0; l < ndim; ++l) {
-    zc* vl = V + (size_t)l * ldv;
-    zc* vn = V + (size_t)(l + 1) * ldv;
-    matvec(vl, vn);
-    timer_begin(4);
-    if (lanczos && n <= SMALL_VEC_N && small_kernels_) {
-      // small-bond regime: dot, update, norm and normalisation in one single-workgroup launch
-      vec_lanczos_step_small(st_, vn, cfg.lanczos_variant == 0 ? V : vl, vl, l > 0 ? V + (size_t)(l - 1) * ldv : nullptr, n,
-                             alpha_p + (size_t)l * NPART, l > 0 ? nrm_p + (size_t)(l - 1) * NPART : nullptr,
-                             nrm_p + (size_t)l * NPART, KRYLOV_EPS);
-      cnt_.n_launch += 1;
-    } else {
-      if (lanczos) {
-        // alpha_l = <v0 | H v_l> (reference, :556) or <v_l | H v_l> (orthodox)
-        vec_dot(st_, cfg.lanczos_variant == 0 ? V : vl, vn, n, true, alpha_p + (size_t)l * NPART);
-        vec_lanczos_update(st_, vn, vl, l > 0 ? V + (size_t)(l - 1) * ldv : nullptr, n, alpha_p + (size_t)l * NPART,
-                           l > 0 ? nrm_p + (size_t)(l - 1) * NPART : nullptr, nrm_p + (size_t)l * NPART);
-      } else {
-        vec_multi_dot(st_, V, ldv, l + 1, vn, n, h_p + (size_t)l * MAXK * NPART);
-        vec_arnoldi_update(st_, vn, V, ldv, l + 1, n, h_p + (size_t)l * MAXK * NPART, nrm_p + (size_t)l * NPART);
-      }
-      vec_scale_inv_norm(st_, vn, n, nrm_p + (size_t)l * NPART, KRYLOV_EPS);
-      cnt_.n_launch += 3;
-    }
-    timer_end();
-
-    const bool last_possible = (l + 1 == nsize);
-    if (l < n_warm && !last_possible && l + 1 < ndim) continue;  // warm-up: no host sync (:578-579)
-
-    // ---- bring the scalars of iterations [next_unread, l] to the host -------
-    if (lanczos) {
-      read_partials(RED_ALPHA + (size_t)next_unread * NPART, (size_t)(l + 1 - next_unread) * NPART);
-    } else {
-      read_partials(RED_H + (size_t)next_unread * MAXK * NPART, (size_t)(l + 1 - next_unread) * MAXK * NPART);
-    }
-    read_partials(RED_NRM, (size_t)MAXK * NPART / 2 + 1);
-    int ld = l;
-    bool exhausted = false;
-    for (int q = next_unread; q <= l; ++q) {
-      const double b = std::sqrt(sum_d(RED_NRM, q));
-      if ((int)beta.size() <= q) beta.resize(q + 1);
-      beta[q] = b;
-      if (lanczos) {
-        if ((int)alpha.size() <= q) alpha.resize(q + 1);
-        alpha[q] = sum_z(RED_ALPHA + (size_t)q * NPART);
-      } else {
-        for (int j = 0; j <= q; ++j) hess[(size_t)j * ndim + q] = sum_z(RED_H + ((size_t)q * MAXK + j) * NPART);
-        if (b > KRYLOV_EPS && q + 1 < ndim + 1) hess[(size_t)(q + 1) * ndim + q] = b;
-      }
-      if (b < KRYLOV_EPS || q + 1 == nsize) {  // Krylov space exhausted (:569, :392)
-        ld = q;
-        exhausted = true;
-        break;
-      }
-    }
-    next_unread = l + 1;
-    if (ld < n_warm && !exhausted) continue;
-
-    // ---- Ritz propagation in the Krylov space (:581-637, :397-409) ---------
-    const int k = ld + 1;
-    std::vector<hzc> coef(k);
-    if (ld == 0) {
-      coef[0] = std::exp(scale * (lanczos ? alpha[0] : hess[0]));
-    } else if (lanczos) {
-      bool real_alpha = true;
-      for (int q = 0; q < k; ++q)
-        if (std::fabs(alpha[q].imag()) > 1e-10) real_alpha = false;
-      if (real_alpha) {
-        std::vector<double> a(k), b(k);
-        for (int q = 0; q < k; ++q) { a[q] = alpha[q].real(); b[q] = beta[q]; }
-        coef = expm_tridiag_e0(a, b, k, scale);
-      } else {
-        std::vector<hzc> T((size_t)k * k, hzc(0, 0));
-        for (int q = 0; q < k; ++q) {
-          T[(size_t)q * k + q] = scale * alpha[q];
-          if (q + 1 < k) T[(size_t)q * k + q + 1] = T[(size_t)(q + 1) * k + q] = scale * beta[q];
-        }
-        coef = expm_col0(T, k);
-      }
-    } else {
-      std::vector<hzc> Hk((size_t)k * k);
-      for (int i = 0; i < k; ++i)
-        for (int j = 0; j < k; ++j) Hk[(size_t)i * k + j] = scale * hess[(size_t)i * ndim + j];
-      coef = expm_col0(Hk, k);
-    }
-
-    if (exhausted) {
-      finalize(coef, k);
-      return k;
-    }
-    if (!coef_prev.empty()) {
-      // || psi_k - psi_{k-1} ||  (:644-652) without materialising either vector
-      Coefs dc{};
-      for (int j = 0; j < k; ++j) {
-        const hzc dlt = coef[j] - (j < (int)coef_prev.size() ? coef_prev[j] : hzc(0, 0));
-        dc.c[j] = make_double2(dlt.real(), dlt.imag());
-      }
-      vec_lincomb(st_, nullptr, V, ldv, k, dc, n, misc_d);
-      cnt_.n_launch += 1;
-      read_partials(RED_MISC, NPART / 2);
-      const double* hp = reinterpret_cast<const double*>(h_red_ + RED_MISC);
-      double s = 0;
-      for (int i = 0; i < NPART; ++i) s += hp[i];
-      if (std::sqrt(s) < cfg.thresh) {
-        finalize(coef, k);
-        return k;
-      }
-    }
-    coef_prev = coef;
-  }
-  throw NotConverged(std::string(lanczos ? "Short Iterative Lanczos" : "Short Iterative Arnoldi") +
-                     " is not converged in " + std::to_string(ndim) + " basis. Try shorter time interval.");
-}
-
-// ---------------------------------------------------------------------------
-// The same local propagator with the Ritz step and the convergence test on the device (krylov_dev.h).  Which iterations
+// local propagator: x <- exp(scale*Op) x, with the Ritz step and the convergence test on the device (krylov_dev.h;
+// small_linalg.h keeps their host twins, which the tests pin the device forms against).  Which iterations
 // are inspected is the reference's rule (_iter_info, _integrator.py:178-186; :578-579) and depends on k_prev only, so the
 // host queues the inspections without looking at any result; convergence needs two consecutive Ritz vectors (:638-651),
 // i.e. cannot come before iteration n_warm + 1 unless the Krylov space is exhausted: that is the first record the host
@@ -199,7 +15,10 @@ int Engine::krylov_exp(hzc scale, MV&& matvec, zc* x, long n, int k_prev, long n
 // host read; every further iteration one more.
 // ---------------------------------------------------------------------------
 template <class MV>
-int Engine::krylov_exp_dev(hzc scale, MV&& matvec, zc* x, long n, int k_prev, long nsize) {
+int Engine::krylov_exp(hzc scale, MV&& matvec, zc* x, long n, int k_prev, long nsize) {
+  // nsize: element count of the UNPADDED input tensor (adaptive rank: x is zero-padded to
+  // the output shape but _iter_info still counts psi_states, _integrator.py:178-186, :524)
+  if (nsize <= 0) nsize = n;
   const int ndim = (int)std::min<long>(nsize, cfg.max_krylov);
   const int n_warm = (int)std::min<long>(nsize, std::min(std::max(0, k_prev - 2), 15));
   const bool lanczos = cfg.integrator == MITDVP_LANCZOS;
@@ -224,7 +43,8 @@ int Engine::krylov_exp_dev(hzc scale, MV&& matvec, zc* x, long n, int k_prev, lo
   int q0 = 0;
   // deferred normalisation (Lanczos, vectors too long for the one-workgroup step kernel): the basis stays unnormalised
   // and every consumer applies 1 / beta on the fly -- one launch and one pass over the vector less per iteration
-  const bool deferred = defer_norm_ && lanczos && !(n <= SMALL_VEC_N && small_kernels_);
+  const bool small_step = lanczos && n <= SMALL_VEC_N && small_kernels_;
+  const bool deferred = lanczos && !small_step;
   for (int l = 0; l < ndim; ++l) {
     zc* vl = V + (size_t)l * ldv;
     zc* vn = V + (size_t)(l + 1) * ldv;
@@ -235,20 +55,14 @@ int Engine::krylov_exp_dev(hzc scale, MV&& matvec, zc* x, long n, int k_prev, lo
       vec_lanczos_update_deferred(st_, vn, vl, l > 0 ? V + (size_t)(l - 1) * ldv : nullptr, n, alpha_p + (size_t)l * NPART, nrm_p, l,
                                   cfg.lanczos_variant != 0, KRYLOV_EPS, nrm_p + (size_t)l * NPART);
       cnt_.n_launch += 2;
-    } else if (lanczos && n <= SMALL_VEC_N && small_kernels_) {
+    } else if (small_step) {
       vec_lanczos_step_small(st_, vn, cfg.lanczos_variant == 0 ? V : vl, vl, l > 0 ? V + (size_t)(l - 1) * ldv : nullptr, n,
                              alpha_p + (size_t)l * NPART, l > 0 ? nrm_p + (size_t)(l - 1) * NPART : nullptr,
                              nrm_p + (size_t)l * NPART, KRYLOV_EPS);
       cnt_.n_launch += 1;
-    } else {
-      if (lanczos) {
-        vec_dot(st_, cfg.lanczos_variant == 0 ? V : vl, vn, n, true, alpha_p + (size_t)l * NPART);
-        vec_lanczos_update(st_, vn, vl, l > 0 ? V + (size_t)(l - 1) * ldv : nullptr, n, alpha_p + (size_t)l * NPART,
-                           l > 0 ? nrm_p + (size_t)(l - 1) * NPART : nullptr, nrm_p + (size_t)l * NPART);
-      } else {
-        vec_multi_dot(st_, V, ldv, l + 1, vn, n, h_p + (size_t)l * MAXK * NPART);
-        vec_arnoldi_update(st_, vn, V, ldv, l + 1, n, h_p + (size_t)l * MAXK * NPART, nrm_p + (size_t)l * NPART);
-      }
+    } else {  // Arnoldi
+      vec_multi_dot(st_, V, ldv, l + 1, vn, n, h_p + (size_t)l * MAXK * NPART);
+      vec_arnoldi_update(st_, vn, V, ldv, l + 1, n, h_p + (size_t)l * MAXK * NPART, nrm_p + (size_t)l * NPART);
       vec_scale_inv_norm(st_, vn, n, nrm_p + (size_t)l * NPART, KRYLOV_EPS);
       cnt_.n_launch += 3;
     }
@@ -270,7 +84,7 @@ int Engine::krylov_exp_dev(hzc scale, MV&& matvec, zc* x, long n, int k_prev, lo
     a.orthodox = cfg.lanczos_variant != 0 ? 1 : 0;
     kry_ritz(st_, a);
     const unsigned tag = ++kry_tag_;
-    kry_diff(st_, kst_, V, ldv, n, cfg.thresh, h_kpub_dev_, tag);
+    kry_diff(st_, kst_, V, ldv, n, cfg.thresh, h_kpub_.d, tag);
     cnt_.n_launch += 2;
     timer_end();
     first = false;
@@ -278,13 +92,13 @@ int Engine::krylov_exp_dev(hzc scale, MV&& matvec, zc* x, long n, int k_prev, lo
     if (l < l_sync) continue;
     wait_pub(tag);
     cnt_.n_host_waits += 1;
-    if (h_kpub_->state == KRY_RUNNING) continue;
-    const int k = h_kpub_->k;
-    const double beta0 = h_kpub_->beta0;
+    if (h_kpub_.h->state == KRY_RUNNING) continue;
+    const int k = h_kpub_.h->k;
+    const double beta0 = h_kpub_.h->beta0;
     if (!cn && !(beta0 > 0.0)) throw ArgError("Initial psi has zero norm.");
     Coefs c{};
     for (int j = 0; j < k; ++j) {
-      const zc v = h_kpub_->coef[j];
+      const zc v = h_kpub_.h->coef[j];
       c.c[j] = cn ? v : make_double2(v.x * beta0, v.y * beta0);  // _rescale, :206-213
     }
     if (cn) {
@@ -351,8 +165,8 @@ int Engine::krylov_diag(MV&& matvec, zc* x, long n) {
     read_partials(RED_ALPHA + (size_t)slot * NPART, NPART);
     read_partials(RED_NRM, (size_t)MAXK * NPART / 2 + 1);
     double a = 0, b2 = 0;
-    for (int q = 0; q < NPART; ++q) a += h_red_[RED_ALPHA + (size_t)slot * NPART + q].x;
-    const double* np_ = reinterpret_cast<const double*>(h_red_ + RED_NRM) + (size_t)slot * NPART;
+    for (int q = 0; q < NPART; ++q) a += h_red_.h[RED_ALPHA + (size_t)slot * NPART + q].x;
+    const double* np_ = reinterpret_cast<const double*>(h_red_.h + RED_NRM) + (size_t)slot * NPART;
     for (int q = 0; q < NPART; ++q) b2 += np_[q];
     alpha.push_back(a);
     beta.push_back(std::sqrt(b2));

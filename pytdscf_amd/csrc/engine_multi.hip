@@ -159,7 +159,7 @@ void Engine::ms_canonicalize(int s, double scale) {
   const long n0 = (long)m.dl[s][0] * m.d[0] * m.dr[s][0];
   vec_sumsq(st_, m.site[s][0].p, n0, reinterpret_cast<double*>(red_.p + RED_MISC));
   read_partials(RED_MISC, NPART / 2);
-  const double* hp = reinterpret_cast<const double*>(h_red_ + RED_MISC);
+  const double* hp = reinterpret_cast<const double*>(h_red_.h + RED_MISC);
   double t = 0;
   for (int i = 0; i < NPART; ++i) t += hp[i];
   if (t == 0.0) throw ArgError("ms_canonicalize: zero state");
@@ -361,7 +361,7 @@ void Engine::ms_sweep(double dt, bool forward) {
       if (forward) {
         timer_begin(3);
         long nl = 0;
-        qr_thin(st_, m.site[s][p].p, dl * d, dr, m.spare.p, m.sigstack.p + so[s], qrwork_.p, &nl, qr_sync(), qr_hist_, qr_gauge_free_);
+        qr_thin(st_, m.site[s][p].p, dl * d, dr, m.spare.p, m.sigstack.p + so[s], qrwork_.p, &nl, qr_hist_, qr_gauge_free_);
         timer_end();
         cnt_.n_launch += nl; cnt_.n_qr += 1;
         cnt_.qr_flops += 4.0 * (4.0 * (double)dl * d * dr * dr - 4.0 * (double)dr * dr * dr / 3.0);
@@ -553,7 +553,7 @@ double Engine::ms_operate(int op_id, int maxstep, double conv_tol, int* iters_ou
       const long e = (long)m.dl[s][p] * m.d[p] * m.dr[s][p];
       vec_sumsq(st_, m.site[s][p].p, e, reinterpret_cast<double*>(red_.p + RED_MISC));
       read_partials(RED_MISC, NPART / 2);
-      const double* hp = reinterpret_cast<const double*>(h_red_ + RED_MISC);
+      const double* hp = reinterpret_cast<const double*>(h_red_.h + RED_MISC);
       for (int k = 0; k < NPART; ++k) s2 += hp[k];
     }
     nrm = std::sqrt(s2);
@@ -665,7 +665,7 @@ void Engine::ms_pops(double* out) {
     const long n0 = (long)m.dl[s][0] * m.d[0] * m.dr[s][0];
     vec_sumsq(st_, m.site[s][0].p, n0, reinterpret_cast<double*>(red_.p + RED_MISC));
     read_partials(RED_MISC, NPART / 2);
-    const double* hp = reinterpret_cast<const double*>(h_red_ + RED_MISC);
+    const double* hp = reinterpret_cast<const double*>(h_red_.h + RED_MISC);
     double t = 0;
     for (int i = 0; i < NPART; ++i) t += hp[i];
     out[s] = t;
@@ -685,7 +685,7 @@ hzc Engine::ms_expect(int op_id) {
     vec_dot(st_, m.site[i][0].p, y, n0, true, red_.p + RED_MISC);
     read_partials(RED_MISC, NPART);
     double re = 0, im = 0;
-    for (int k = 0; k < NPART; ++k) { re += h_red_[RED_MISC + k].x; im += h_red_[RED_MISC + k].y; }
+    for (int k = 0; k < NPART; ++k) { re += h_red_.h[RED_MISC + k].x; im += h_red_.h[RED_MISC + k].y; }
     return hzc(re, im);
   };
   hzc tot(0, 0);

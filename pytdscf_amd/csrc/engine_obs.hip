@@ -14,7 +14,7 @@ double Engine::norm() {
   const long n = (long)dl_[center_] * dd_[center_] * dr_[center_];
   vec_sumsq(st_, site_[center_].p, n, reinterpret_cast<double*>(red_.p + RED_MISC));
   read_partials(RED_MISC, NPART / 2);
-  const double* hp = reinterpret_cast<const double*>(h_red_ + RED_MISC);
+  const double* hp = reinterpret_cast<const double*>(h_red_.h + RED_MISC);
   double s = 0;
   for (int i = 0; i < NPART; ++i) s += hp[i];
   return std::sqrt(s);
@@ -55,7 +55,7 @@ hzc Engine::expect(int op_id) {
   vec_dot(st_, site_[0].p, tmp2_.p, n0, true, red_.p + RED_MISC);
   read_partials(RED_MISC, NPART);
   double re = 0, im = 0;
-  for (int i = 0; i < NPART; ++i) { re += h_red_[RED_MISC + i].x; im += h_red_[RED_MISC + i].y; }
+  for (int i = 0; i < NPART; ++i) { re += h_red_.h[RED_MISC + i].x; im += h_red_.h[RED_MISC + i].y; }
   pool_put(std::move(ra));
   pool_put(std::move(rb));
   return hzc(re, im);

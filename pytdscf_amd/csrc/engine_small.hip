@@ -16,7 +16,7 @@
 
 namespace mitdvp {
 
-// Compute-unit ranges claimed by CU-masked engines, per device.  Persistent grids (k_small_site, k_qr_panel) need all
+// Compute-unit ranges claimed by CU-masked engines, per device.  Persistent grids (k_small_site) need all
 // their workgroups resident at once: two masked engines whose ranges overlap, or a masked engine beside a full-device one,
 // could each hold compute units the other's waiting workgroups need.  Overlapping claims are refused, and while any range
 // is claimed on a device the full-device engines there run the multi-launch kernels (small_ok()).
@@ -95,13 +95,6 @@ zc* Engine::ss_partials(const SmallChain& c) {
   small_sync_alloc(ss_, L_, st_);
   ss_dirty_ = true;
   return ss_part_.p;
-}
-
-SmallSync* Engine::qr_sync() {
-  if (!small_kernels_ || n_cu_ <= 0) return nullptr;
-  small_sync_alloc(ss_, L_, st_);
-  ss_dirty_ = true;
-  return &ss_;
 }
 
 // which sites run their local exponentials in one launch; device <-> host Krylov memories are

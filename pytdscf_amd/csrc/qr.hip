@@ -17,11 +17,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <map>
-#include <mutex>
 #include <type_traits>
 
-#include "grid_exchange.h"
-#include "small_site.h"
 #include "vecops.h"
 
 namespace mitdvp {
@@ -511,12 +508,10 @@ void qr_small_fast_launch(hipStream_t st, const zc* A, int m, int n, zc* Q, zc* 
 static int qr_small_launch(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc* work, bool fast, bool gauge_free) {
   if (n > 32 || m > 320) return 0;
   const int rpt = (m + 15) / 16;
-  // MITDVP_QR_SMALL_FAST=0: the per-column Householder kernel only (A/B runs)
-  static const bool sf_on = !(std::getenv("MITDVP_QR_SMALL_FAST") && std::atoi(std::getenv("MITDVP_QR_SMALL_FAST")) == 0);
   // work: [0, 1024) W of the Householder kernel, [1024, 1024 + 32 m) the first round's Q, then the verdict word
   const int* run_if = nullptr;
   zc* q_in_kernel = nullptr;
-  if (fast && sf_on && Q) {
+  if (fast && Q) {
     int* fail = reinterpret_cast<int*>(work + 1024 + (size_t)32 * m);
     qr_small_fast_launch(st, A, m, n, Q, R, work + 1024, fail, gauge_free);
     run_if = fail;
@@ -551,142 +546,6 @@ static int qr_small_launch(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc
 }
 
 // ---------------------------------------------------------------------------
-// Panel factorisation in ONE persistent launch (any m up to 64 x 256 rows below the panel's first row).
-//
-// The per-column launches above cost a kernel boundary each (~6 us begin-to-begin on this GPU whatever the
-// kernel does).  Here a workgroup keeps 256 rows of the panel in registers for all 32 column steps; per step
-// the workgroups exchange their 32 partial column products through grid_exchange.h (one store -> load round
-// trip, ~3 us) and read the current row from a small double-buffered agent-scope buffer.  The products with
-// the FINISHED columns (c < j) travel along and give V^H V, hence zlarft's T (T^-1 = striu(V^H V) +
-// diag(1 / tau)) without the Gram GEMM; the unit-lower-trapezoid copy of the panel that the trailing
-// GEMMs take is written by the same kernel.  One launch replaces 33 + 4.
-// ---------------------------------------------------------------------------
-struct QrPanelArgs {
-  zc* A; long lda; int m, j0, j1;
-  zc* Vp;      // (m - j0) x nbp, unit lower trapezoid
-  zc* T;       // nbp x nbp
-  zc* tau;     // tau + j0
-  zc* rowbuf;  // [2][32] agent-scope row exchange
-  unsigned long long* gran; unsigned* abort_w; unsigned* err_w; unsigned epoch0;
-};
-
-template <int RPT>
-__global__ __launch_bounds__(512) void k_qr_panel(QrPanelArgs g) {
-  constexpr int NRG = 16, NW = 8, RB = NRG * RPT;
-  __shared__ zc part[NW][32];
-  __shared__ zc rowj[32];
-  __shared__ zc xc[2][RB];
-  __shared__ zc Gs[32][33];
-  __shared__ zc Tt[32][33];
-  __shared__ zc taus[32];
-  __shared__ double pay[64], red[64];
-  extern __shared__ __attribute__((aligned(16))) char dyn[];  // exchange scratch: G * 64 doubles
-  double* val = reinterpret_cast<double*>(dyn);
-  const int tid = threadIdx.x, c = tid & 31, rg = tid >> 5, w = tid >> 6, lane = tid & 63;
-  const int nbp = g.j1 - g.j0, m = g.m;
-  const int r0 = g.j0 + blockIdx.x * RB;
-  GxSync sy{g.gran, g.abort_w, (int)gridDim.x, (int)blockIdx.x, g.epoch0};
-  zc a[RPT];
-#pragma unroll
-  for (int q = 0; q < RPT; ++q) {
-    const int i = r0 + rg + NRG * q;
-    a[q] = (i < m && c < nbp) ? g.A[(long)i * g.lda + g.j0 + c] : make_double2(0.0, 0.0);
-  }
-  for (int e = tid; e < 32 * 33; e += 512) (&Gs[0][0])[e] = make_double2(0.0, 0.0);
-  auto stage_col = [&](int jj, int buf) {
-    if (c == jj) {
-#pragma unroll
-      for (int q = 0; q < RPT; ++q) xc[buf][rg + NRG * q] = a[q];
-    }
-  };
-  // partial products of column jj with every column over this workgroup's rows below row j0 + jj;
-  // the owner of that row exports it
-  auto publish = [&](int jj, int buf) {
-    const int jrow = g.j0 + jj;
-    double sr = 0.0, si = 0.0;
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-      const int i = r0 + rg + NRG * q;
-      const zc x = xc[buf][rg + NRG * q];
-      if (i > jrow && i < m && c < nbp) {
-        sr += x.x * a[q].x + x.y * a[q].y;
-        si += x.x * a[q].y - x.y * a[q].x;
-      }
-      if (i == jrow) gx_stz(g.rowbuf + (size_t)buf * 32 + c, a[q]);
-    }
-    sr += __shfl_xor(sr, 32, 64);
-    si += __shfl_xor(si, 32, 64);
-    if (lane < 32) part[w][c] = make_double2(sr, si);
-    __syncthreads();
-    if (tid < 64) {
-      const int cc = tid >> 1;
-      double t = 0.0;
-#pragma unroll
-      for (int u = 0; u < NW; ++u) t += (tid & 1) ? part[u][cc].y : part[u][cc].x;
-      pay[tid] = t;
-    }
-    __syncthreads();
-  };
-  stage_col(0, 0);
-  __syncthreads();
-  publish(0, 0);
-  for (int jj = 0; jj < nbp; ++jj) {
-    const int buf = jj & 1, jrow = g.j0 + jj;
-    if (!gx_exchange<512>(sy, pay, 64, red, val)) {
-      if (blockIdx.x == 0 && tid == 0) atomicMax(g.err_w, 2u);
-      return;
-    }
-    if (tid < 32) rowj[tid] = gx_ldz(g.rowbuf + (size_t)buf * 32 + tid);
-    __syncthreads();
-    const zc yj = make_double2(red[2 * jj], red[2 * jj + 1]), yc = make_double2(red[2 * c], red[2 * c + 1]);
-    const House h = zlarfg(rowj[jj], yj.x);
-    zc f = make_double2(0.0, 0.0);
-    const bool active = c > jj && c < nbp;
-    if (active) f = zmul(zconj(h.tau), zadd(zmul(zconj(h.scale), yc), rowj[c]));
-    if (rg == 0 && c < jj) Gs[c][jj] = zadd(zconj(rowj[c]), zmul(h.scale, zconj(yc)));
-    if (tid == 0) taus[jj] = h.tau;
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-      const int i = r0 + rg + NRG * q;
-      if (i >= jrow && i < m) {
-        const zc v = (i == jrow) ? make_double2(1.0, 0.0) : zmul(xc[buf][rg + NRG * q], h.scale);
-        if (active) a[q] = zsub(a[q], zmul(v, f));
-        else if (c == jj) a[q] = (i == jrow) ? make_double2(h.beta, 0.0) : v;
-      }
-    }
-    if (jj + 1 < nbp) {
-      stage_col(jj + 1, buf ^ 1);
-      __syncthreads();
-      publish(jj + 1, buf ^ 1);
-    }
-  }
-  // the factored panel, its unit lower trapezoid, tau
-#pragma unroll
-  for (int q = 0; q < RPT; ++q) {
-    const int i = r0 + rg + NRG * q;
-    if (i < m && c < nbp) {
-      g.A[(long)i * g.lda + g.j0 + c] = a[q];
-      const int ic = i - g.j0;
-      g.Vp[(long)ic * nbp + c] = (ic == c) ? make_double2(1.0, 0.0) : (ic > c ? a[q] : make_double2(0.0, 0.0));
-    }
-  }
-  if (blockIdx.x != 0) return;
-  __syncthreads();
-  if (tid < nbp) g.tau[tid] = taus[tid];
-  // T = S^-1, S = striu(V^H V) + diag(1 / tau): column r by back substitution, the columns side by side
-  if (rg == 0 && c < nbp) {
-    for (int t = nbp - 1; t >= 0; --t) {
-      zc acc = make_double2(t == c ? 1.0 : 0.0, 0.0);
-      for (int sI = t + 1; sI <= c; ++sI) acc = zsub(acc, zmul(Gs[t][sI], Tt[sI][c]));
-      const zc tt = taus[t];
-      const zc v = (t > c || (tt.x == 0.0 && tt.y == 0.0)) ? make_double2(0.0, 0.0) : zmul(tt, acc);
-      Tt[t][c] = v;
-      g.T[(long)t * nbp + c] = v;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
 // rows per workgroup in the panel kernels: enough workgroups to spread a column
 // step over the chip, few enough that summing their partials stays cheap
 // (measured: 32 rows per workgroup win up to the C4 shape 16384 x 1024 -- 61 vs 66 ms for the seven QRs of a
@@ -708,16 +567,18 @@ void qr_set_fast(int on) { g_qr_fast = on ? 1 : 0; }
 int qr_get_fast() { return qr_fast_enabled() ? 1 : 0; }
 // shapes whose panels keep failing the conditioning checks (rank-deficient / strongly graded tensors) skip the fast
 // attempt for a while: 2, 4, ... 64 factorisations after each consecutive failure
-struct QrBackoff { int fails = 0, skip = 0; };
+struct QrBackoff {
+  int fails = 0, skip = 0;
+  void passed() { fails = 0; }
+  void failed() { fails = std::min(fails + 1, 6); skip = 1 << fails; }
+};
 // ... and where a factorisation's verdict reaches the host: one word of host-coherent mapped memory the device writes
 // behind a sequence number, the host spins on it (~7 us; hipMemcpyAsync + hipStreamSynchronize cost 15-50 us per QR
 // on this stack, tools/probes/sync_latency.hip)
 struct QrHistory {
   std::map<long, QrBackoff> by_shape;
-  int* h_word = nullptr;       // [0] flag, [1] sequence number
-  int* d_word = nullptr;
+  MappedHost<int> word;        // [0] flag, [1] sequence number
   int tag = 0;
-  ~QrHistory() { if (h_word) (void)hipHostFree(h_word); }
 };
 QrHistory* qr_history_new() { return new QrHistory(); }
 void qr_history_free(QrHistory* h) { delete h; }
@@ -729,30 +590,18 @@ __global__ void k_qr_publish_flag(const int* __restrict__ flag, int* __restrict_
 }
 // the host-coherent word a factorisation's verdict travels through: [0] flag, [1] sequence number
 static void qr_pub_ensure(QrHistory* hist) {
-  if (hist->h_word) return;
-  HIP_CHECK(hipHostMalloc((void**)&hist->h_word, 64, hipHostMallocMapped | hipHostMallocCoherent));
-  hist->h_word[0] = hist->h_word[1] = 0;
-  void* dp = nullptr;
-  HIP_CHECK(hipHostGetDevicePointer(&dp, hist->h_word, 0));
-  hist->d_word = static_cast<int*>(dp);
+  if (!hist->word.h) hist->word.alloc(64);
 }
 static int qr_pub_wait(hipStream_t st, QrHistory* hist, int tag) {
-  volatile int* w = hist->h_word;
-  for (long spins = 0; w[1] != tag; ++spins) {
-    if ((spins & 0xFFFF) == 0xFFFF && hipStreamQuery(st) != hipErrorNotReady) {
-      HIP_CHECK(hipStreamSynchronize(st));
-      if (w[1] != tag) throw HipError("qr: the verdict of the fast panels was not published");
-    }
-  }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  return w[0];
+  wait_published(st, hist->word.h + 1, tag, "qr: the verdict of the fast panels was not published");
+  return hist->word.h[0];
 }
 // the sticky failure flag of the fast panels, read on the host
 static int qr_read_flag(hipStream_t st, const int* dev_flag, QrHistory* hist) {
   if (hist) {
     qr_pub_ensure(hist);
     const int tag = ++hist->tag;
-    hipLaunchKernelGGL(k_qr_publish_flag, dim3(1), dim3(1), 0, st, dev_flag, hist->d_word, tag);
+    hipLaunchKernelGGL(k_qr_publish_flag, dim3(1), dim3(1), 0, st, dev_flag, hist->word.d, tag);
     HIP_CHECK(hipGetLastError());
     return qr_pub_wait(st, hist, tag);
   }
@@ -781,22 +630,20 @@ static size_t qr_work_elems_house(int m, int n, int next) {
   return e;
 }
 
-static void qr_impl(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc* work, long* nlaunch, int next, SmallSync* sy, bool fast,
-                    QrHistory* hist, bool gauge_free = false);
+static void qr_impl(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc* work, long* nlaunch, int next, bool fast, QrHistory* hist,
+                    bool gauge_free = false);
 
-void qr_householder(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc* work, long* nlaunch, int next, SmallSync* sy,
-                    QrHistory* hist) {
-  qr_impl(st, A, m, n, Q, R, work, nlaunch, next, sy, qr_fast_enabled(), hist);
+void qr_householder(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc* work, long* nlaunch, int next, QrHistory* hist) {
+  qr_impl(st, A, m, n, Q, R, work, nlaunch, next, qr_fast_enabled(), hist);
 }
 
-void qr_thin(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc* work, long* nlaunch, SmallSync* sy, QrHistory* hist,
-             bool gauge_free, bool* used_gauge_free) {
+void qr_thin(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc* work, long* nlaunch, QrHistory* hist, bool gauge_free,
+             bool* used_gauge_free) {
   if (used_gauge_free) *used_gauge_free = false;
-  static const bool gram_on = !(std::getenv("MITDVP_QR_GRAM") && std::atoi(std::getenv("MITDVP_QR_GRAM")) == 0);
   static const bool small_on = !(std::getenv("MITDVP_SMALL_KERNELS") && std::atoi(std::getenv("MITDVP_SMALL_KERNELS")) == 0);
   // matrices of up to 320 x 32 keep the one-workgroup kernel (one launch, no host wait); narrower than 16 columns there
   // is nothing to gain over one panel
-  bool gram = gauge_free && gram_on && m >= n && n >= 16 && !(small_on && m <= 320 && n <= 32);
+  bool gram = gauge_free && m >= n && n >= 16 && !(small_on && m <= 320 && n <= 32);
   const long gkey = -((long)m * 100003L + n);  // the gauge-free path's own back-off entry
   if (gram && hist) {
     QrBackoff& bo = hist->by_shape[gkey];
@@ -808,7 +655,7 @@ void qr_thin(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc* work, long* 
     if (hist) {  // the factorisation's last Cholesky kernel publishes the verdict itself
       qr_pub_ensure(hist);
       const int tag = ++hist->tag;
-      const int nl = qr_gram(st, A, m, n, Q, R, gw, hist->d_word, tag);
+      const int nl = qr_gram(st, A, m, n, Q, R, gw, hist->word.d, tag);
       if (nlaunch) *nlaunch += nl;
       bad = qr_pub_wait(st, hist, tag);
     } else {
@@ -817,50 +664,27 @@ void qr_thin(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc* work, long* 
       bad = qr_read_flag(st, qr_gram_flag(gw, m, n), nullptr);
     }
     if (!bad) {
-      if (hist) hist->by_shape[gkey].fails = 0;
+      if (hist) hist->by_shape[gkey].passed();
       if (used_gauge_free) *used_gauge_free = true;
       return;
     }
-    if (hist) {  // rank-deficient / strongly graded: the Householder panels from now on, asked again after 2, 4, .. 64 calls
-      QrBackoff& bo = hist->by_shape[gkey];
-      bo.fails = std::min(bo.fails + 1, 6);
-      bo.skip = 1 << bo.fails;
-    }
+    // rank-deficient / strongly graded: the Householder panels from now on, asked again after 2, 4, .. 64 calls
+    if (hist) hist->by_shape[gkey].failed();
   }
   // The one-workgroup kernel of the small regime (m <= 320, n <= 32) keeps LAPACK's signs by default: its sign chain is
   // 9.4 of 66 us (C2 +2 %), and the small-size parity tests of the adaptive sweep, gates, several states and `operate`
   // compare tensors element by element with the reference's fixtures.  MITDVP_QR_SMALL_GAUGE_FREE=1 drops the chain too.
   const char* sf_env = std::getenv("MITDVP_QR_SMALL_GAUGE_FREE");  // (read per call: a handful of times per sweep)
   const bool small_free = sf_env && std::atoi(sf_env) != 0;
-  qr_impl(st, A, m, n, Q, R, work, nlaunch, 0, sy, qr_fast_enabled(), hist, gauge_free && small_free);
+  qr_impl(st, A, m, n, Q, R, work, nlaunch, 0, qr_fast_enabled(), hist, gauge_free && small_free);
 }
 
-static void qr_impl(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc* work, long* nlaunch, int next, SmallSync* sy, bool fast,
-                    QrHistory* hist, bool gauge_free) {
+static void qr_impl(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc* work, long* nlaunch, int next, bool fast, QrHistory* hist,
+                    bool gauge_free) {
   if (m < n) throw ArgError("qr: m < n (bond dimension larger than the row space) is not supported");
   if (next < 0 || n + next > m) throw ArgError("qr: more orthogonal-complement columns requested than exist");
   if (n <= 0) return;
   static const bool small_on = !(std::getenv("MITDVP_SMALL_KERNELS") && std::atoi(std::getenv("MITDVP_SMALL_KERNELS")) == 0);
-  // opt-in (MITDVP_QR_PANEL=1): measured SLOWER than the per-column launches it replaces -- C5 (2048 x 512): 578 ms
-  // of QR per sweep against 510 ms, C3 (4096 x 128): 4.6 against 3.8 ms, at 64 / 128 rows per workgroup; a kernel
-  // boundary (~1.5 us + the kernel's own ~3 us) is a cheaper grid-wide barrier on this GPU than an exchange of
-  // 64 doubles per workgroup through agent-scope memory (profiles/r02_qr_panel_ab.json).  It cuts the launches of a
-  // C5 sweep from 92 628 to 25 288, which is what it is kept for (launch-rate-limited hosts, graphs).
-  static const bool panel_on = small_on && std::getenv("MITDVP_QR_PANEL") && std::atoi(std::getenv("MITDVP_QR_PANEL")) != 0;
-  if (panel_on && sy) {  // the panel kernel's exchange scratch is dynamic LDS on top of ~48 KB static: lift the 64 KB default
-    static std::mutex mu;
-    static bool attr_done[64] = {};
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_qr_panel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_qr_panel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_qr_panel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_qr_panel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      if (dev >= 0 && dev < 64) attr_done[dev] = true;
-    }
-  }
   if (next == 0 && small_on) {  // factorisation in one launch (matrix in registers), Q in a second
     const int nls = qr_small_launch(st, A, m, n, Q, R, work, fast, gauge_free);
     if (nls) {
@@ -928,30 +752,8 @@ static void qr_impl(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc* work,
     };
     zc* Tp = T + (size_t)ip * QR_NB * QR_NB;
     if (fast) Vp = vpanel(ip);
-    // rows per workgroup: as few as the 64-workgroup exchange allows -- the column update of a step is spread
-    // over (rows / rb) compute units, and that, not the exchange, is what a step waits for when rb is large
-    int rb = 32;
-    const int gcap = (sy && sy->max_grid > 0) ? std::min(GX_MAXG, sy->max_grid) : GX_MAXG;
-    while ((mp + rb - 1) / rb > gcap && rb < 256) rb *= 2;
-    if (const char* e = std::getenv("MITDVP_QR_RB")) rb = std::max(32, std::min(256, std::atoi(e)));
-    const int gpan = (mp + rb - 1) / rb;
     if (fast) {
       nl += qr_fast_panel(st, A, lda, m, j0, nbp, Vp, Tp, tau, fws, fflag);
-    } else if (panel_on && sy && sy->slots && gpan <= gcap) {
-      // one persistent launch: column steps, T and the unit-lower copy of the panel
-      sy->launches += 1;
-      if ((sy->launches & 0xFFFFFu) == 0u) sy->launches += 1;  // tag 0 is the cleared state
-      QrPanelArgs pa{A, lda, m, j0, j1, Vp, Tp, tau + j0, rowb[0],
-                     reinterpret_cast<unsigned long long*>(sy->slots), sy->words + 2, sy->words + 3,
-                     (sy->launches & 0xFFFFFu) << 12};
-      const size_t dyn = (size_t)gpan * 64 * sizeof(double);
-      PersistentLaunch chain(st, gpan, sy->partitioned);
-      if (rb == 32) hipLaunchKernelGGL(k_qr_panel<2>, dim3(gpan), dim3(512), dyn, st, pa);
-      else if (rb == 64) hipLaunchKernelGGL(k_qr_panel<4>, dim3(gpan), dim3(512), dyn, st, pa);
-      else if (rb == 128) hipLaunchKernelGGL(k_qr_panel<8>, dim3(gpan), dim3(512), dyn, st, pa);
-      else hipLaunchKernelGGL(k_qr_panel<16>, dim3(gpan), dim3(512), dyn, st, pa);
-      ++nl;
-      HIP_CHECK(hipGetLastError());
     } else {
       if (rows == 32) panel(std::integral_constant<int, 32>{});
       else if (rows == 128) panel(std::integral_constant<int, 128>{});
@@ -992,16 +794,12 @@ static void qr_impl(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc* work,
     if (!fast) return false;
     const int bad = qr_read_flag(st, fflag, hist);
     if (!bad) {
-      if (hist) hist->by_shape[bkey].fails = 0;
+      if (hist) hist->by_shape[bkey].passed();
       return false;
     }
-    if (hist) {
-      QrBackoff& bo = hist->by_shape[bkey];
-      bo.fails = std::min(bo.fails + 1, 6);
-      bo.skip = 1 << bo.fails;
-    }
+    if (hist) hist->by_shape[bkey].failed();
     HIP_CHECK(hipMemcpyAsync(A, backup, (size_t)m * n * sizeof(zc), hipMemcpyDeviceToDevice, st));
-    qr_impl(st, A, m, n, Q, R, work, nlaunch, next, sy, false, nullptr);
+    qr_impl(st, A, m, n, Q, R, work, nlaunch, next, false, nullptr);
     return true;
   };
   // R
@@ -1017,9 +815,8 @@ static void qr_impl(hipStream_t st, zc* A, int m, int n, zc* Q, zc* R, zc* work,
   // right half (Schreiber & Van Loan) -- built by doubling (log2(panels) levels of two batched GEMMs on blocks of
   // G = V^H V), after which Q = E - V (T (V[:n+next, :])^H) is three large GEMMs instead of three small ones per panel
   // applied in reverse order (zungqr): 15 launches instead of 3 per panel + split-K combines, ~0.15 against ~0.55 ms at
-  // 2048 x 512.  Panel counts that are not a power of two keep the reverse loop.  MITDVP_QR_GLOBALT=0: off.
-  static const bool globalt_on = !(std::getenv("MITDVP_QR_GLOBALT") && std::atoi(std::getenv("MITDVP_QR_GLOBALT")) == 0);
-  if (fast && globalt_on && n % QR_NB == 0 && npan >= 2 && (npan & (npan - 1)) == 0) {
+  // 2048 x 512.  Panel counts that are not a power of two keep the reverse loop.
+  if (fast && n % QR_NB == 0 && npan >= 2 && (npan & (npan - 1)) == 0) {
     zc* Vf = backup + qr_fast_work_elems(m, n);
     zc* Gm = Vf + (size_t)m * n;
     zc* Tb = Gm + (size_t)n * n;

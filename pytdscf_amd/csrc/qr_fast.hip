@@ -43,39 +43,6 @@ __device__ __forceinline__ zc cdiv(zc a, zc b) {
 }
 }  // namespace
 
-// partial Gram matrices of a tall panel: part[blk][i][j] = sum_{rows of blk} conj(P[r][i]) P[r][j]
-// (P = mp x nb, leading dimension ld; the rows of a workgroup are summed in a fixed order: deterministic)
-__global__ __launch_bounds__(256) void k_fq_gram(const zc* __restrict__ P, long ld, int mp, int nb, zc* __restrict__ part,
-                                                 int rows_per_blk) {
-  __shared__ zc tile[32][NB + 1];
-  const int t = threadIdx.x, ti = t >> 4, tj = t & 15;
-  const long r0 = (long)blockIdx.x * rows_per_blk;
-  const int nr = (int)min((long)rows_per_blk, mp - r0);
-  zc acc[2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};
-  for (int base = 0; base < nr; base += 32) {
-    const int rows = min(32, nr - base);
-    __syncthreads();
-    for (int e = t; e < 32 * NB; e += 256) {
-      const int r = e >> 5, c = e & 31;
-      tile[r][c] = (r < rows && c < nb) ? P[(r0 + base + r) * ld + c] : make_double2(0.0, 0.0);
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int k = 0; k < 32; ++k) {
-      const zc a0 = tile[k][ti], a1 = tile[k][ti + 16], b0 = tile[k][tj], b1 = tile[k][tj + 16];
-      acc[0][0] = cadd(acc[0][0], cmulc(a0, b0));
-      acc[0][1] = cadd(acc[0][1], cmulc(a0, b1));
-      acc[1][0] = cadd(acc[1][0], cmulc(a1, b0));
-      acc[1][1] = cadd(acc[1][1], cmulc(a1, b1));
-    }
-  }
-  zc* o = part + (size_t)blockIdx.x * NB * NB;
-  o[ti * NB + tj] = acc[0][0];
-  o[ti * NB + tj + 16] = acc[0][1];
-  o[(ti + 16) * NB + tj] = acc[1][0];
-  o[(ti + 16) * NB + tj + 16] = acc[1][1];
-}
-
 // G = sum of the partials; G = R^H R (upper Cholesky factor, real positive diagonal); Rinv = R^-1.
 // second != 0: additionally Rtot = R * Rprev (the panel's triangular factor after both rounds), else Rtot = R.
 // One workgroup, FQ_NQ matrix elements per thread.  The 32 pivots are a chain of rank-1 updates in LDS
@@ -365,11 +332,6 @@ __global__ __launch_bounds__(1024 / FQ_NQ) void k_fq_reconstruct(const zc* __res
   }
 }
 
-static int fq_rows_per_blk(int m) {  // at most 128 workgroups (= partial Gram matrices), at least 32 rows each
-  int r = (m + 127) / 128;
-  r = (r + 31) / 32 * 32;
-  return r < 32 ? 32 : r;
-}
 // (Round 4, measured and dropped -- profiles/r04_qr_chain_ab.txt: fewer, larger Gram workgroups (sqrt(0.22 m) partials
 // instead of m / 32) take 13 us off the first-round Cholesky kernel, whose one workgroup streams the partials, and put
 // 12 us onto the two Gram launches, whose plain-FMA tiles cost ~5 us per 32 rows; the same chain kernels with 512
@@ -810,9 +772,10 @@ __global__ __launch_bounds__(SF_T) void k_qr_small_fast(const zc* __restrict__ A
   if (tid == 0) *fail = 0;
   stamp(9);
 }
-// Partial Gram matrices of a tall panel on the matrix cores: workgroup b takes rows_per_blk rows (eight waves = four row
+// Partial Gram matrices of a tall panel on the matrix cores, part[blk][i][j] = sum_{rows of blk} conj(P[r][i]) P[r][j]
+// (P = mp x nb, leading dimension ld; a fixed summation order: deterministic): workgroup b takes rows_per_blk rows (eight waves = four row
 // quarters x two halves of the six streams, as in the small kernel) and writes ONE 32 x 32 partial, Hermitian, zero beyond nb.
-// 128 rows cost about what k_fq_gram's plain-FMA tiles need for 32, so a 4096-row panel leaves 32 partials for the one
+// 128 rows cost about what the plain-FMA tiles of the kernel it replaced needed for 32, so a 4096-row panel leaves 32 partials for the one
 // workgroup of the Cholesky kernel to stream instead of 128 (27 of that kernel's 38 us were that stream).
 __global__ __launch_bounds__(SF_T) void k_fq_gram_mfma(const zc* __restrict__ P, long ld, int mp, int nb, zc* __restrict__ part,
                                                        int rows_per_blk, int cd_mode) {
@@ -835,12 +798,7 @@ __global__ __launch_bounds__(SF_T) void k_fq_gram_mfma(const zc* __restrict__ P,
 }
 }  // namespace
 
-// MITDVP_QR_GRAM_MFMA=0: the plain-FMA Gram kernel with 32 rows per workgroup (A/B runs)
-static bool fq_gram_mfma_on() {
-  static const bool on = !(std::getenv("MITDVP_QR_GRAM_MFMA") && std::atoi(std::getenv("MITDVP_QR_GRAM_MFMA")) == 0);
-  return on;
-}
-static int fq_rows_per_blk_mfma(int m) {  // 128 rows per workgroup (MITDVP_QR_GRAM_ROWS; QR ms per 6 sweeps at 64 / 128 / 256 / 512 rows: C3 12.1 / 11.6 / 11.9 / 12.9, C5 1565 / 1557 / 1602 / 1758; 13.2 / 1648 with k_fq_gram), at most 128 workgroups
+static int fq_rows_per_blk_mfma(int m) {  // 128 rows per workgroup (MITDVP_QR_GRAM_ROWS; QR ms per 6 sweeps at 64 / 128 / 256 / 512 rows: C3 12.1 / 11.6 / 11.9 / 12.9, C5 1565 / 1557 / 1602 / 1758; 13.2 / 1648 with the plain-FMA kernel it replaced, 32 rows per workgroup), at most 128 workgroups
   static const int rows_env = [] { const char* e = std::getenv("MITDVP_QR_GRAM_ROWS"); return e ? std::max(32, std::atoi(e) / 4 * 4) : 128; }();
   int r = rows_env;
   if ((m + r - 1) / r > 128) r = ((m + 127) / 128 + 3) / 4 * 4;
@@ -848,13 +806,8 @@ static int fq_rows_per_blk_mfma(int m) {  // 128 rows per workgroup (MITDVP_QR_G
 }
 // number of partials written
 static int fq_gram_launch(hipStream_t st, const zc* P, long ld, int mp, int nb, zc* part) {
-  if (fq_gram_mfma_on()) {
-    const int rpb = fq_rows_per_blk_mfma(mp), nblk = (mp + rpb - 1) / rpb;
-    hipLaunchKernelGGL(k_fq_gram_mfma, dim3(nblk), dim3(SF_T), 0, st, P, ld, mp, nb, part, rpb, zgemm_cd_mode(st));
-    return nblk;
-  }
-  const int rpb = fq_rows_per_blk(mp), nblk = (mp + rpb - 1) / rpb;
-  hipLaunchKernelGGL(k_fq_gram, dim3(nblk), dim3(256), 0, st, P, ld, mp, nb, part, rpb);
+  const int rpb = fq_rows_per_blk_mfma(mp), nblk = (mp + rpb - 1) / rpb;
+  hipLaunchKernelGGL(k_fq_gram_mfma, dim3(nblk), dim3(SF_T), 0, st, P, ld, mp, nb, part, rpb, zgemm_cd_mode(st));
   return nblk;
 }
 

@@ -1113,10 +1113,9 @@ bool small_chain_plan(SmallChain& c, bool exp_mode, int n_cu) {
   // Still not placed: one slab per workgroup wants more workgroups, or more LDS per workgroup (wide chunks), than the
   // slice offers.  Several slabs per workgroup (round 5): narrow chunks keep B / R / X / Y small, the grid is
   // ceil(na / spw) * nsc <= gmax.  Fewest slabs per workgroup first, then the most chunks that fit; A resident if it fits.
-  static const bool multi_on = !(std::getenv("MITDVP_SS_MULTISLAB") && std::atoi(std::getenv("MITDVP_SS_MULTISLAB")) == 0);
   // (only for slices of at most 64 compute units -- four or more replicas: on larger grids a chain that does not fit with
   // one slab per workgroup is better served by the general multi-launch kernels, which is what it got before)
-  if (!multi_on || n_cu > 64) return false;
+  if (n_cu > 64) return false;
   for (int spw = 2; spw <= 64 && spw <= 2 * c.na; spw *= 2) {
     const int ngrp = (c.na + spw - 1) / spw;
     if (ngrp > gmax) continue;
@@ -1140,7 +1139,7 @@ bool small_chain_plan(SmallChain& c, bool exp_mode, int n_cu) {
 }
 
 // ---- persistent launches of several engines on one GPU ---------------------------------------------------------
-// k_small_site / k_qr_panel exchange data BETWEEN their workgroups inside one launch, so all workgroups of a launch
+// k_small_site exchanges data BETWEEN its workgroups inside one launch, so all workgroups of a launch
 // must be resident together.  Two such grids from two engines (an ensemble of trajectories on one GPU, host threads)
 // could each get part of the chip and wait for the rest of themselves until the 2 s timeout.  Per device, process
 // wide, while more than one engine uses the family: every persistent launch is entered in a list with an event and
