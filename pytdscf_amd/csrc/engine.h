@@ -188,7 +188,7 @@ class Engine {
   // edge-structured MPO core between canonical environments: sigma = sum_t W[0,:,:,t] (psi R_t^T) + sum_{c>=1} W[c,:,:,mr-1] (L_c psi),
   // each a GEMM whose 64 x 64 tiles are contracted with W in the epilogue (zgemm_reduce): X / Y never exist
   void heff_apply_edge(const zc* L, const MpoSite& w, const zc* R, const zc* psi, zc* out, int dl, int d, int dr);
-  // which forms the H_eff applies of the site between these blocks take (sets trim_l_, trim_r_, edge_; one host
+  // which forms the H_eff applies of the site between these blocks take (sets trim_l_, trim_r_, edge_, fold_l_, fold_r_; one host
   // synchronisation for the numerical identity checks); the caller resets them when the local solve is over
   void choose_apply_forms(const zc* Lb, const MpoSite& w, const zc* Rb, int dl, int d, int dr);
   void keff_apply_rect(const zc* L, const zc* R, const zc* sig, zc* out, int dlo, int dli, int dro, int dri, int m);
@@ -293,6 +293,10 @@ class Engine {
   bool trim_identity_ = true;  // MITDVP_TRIM_IDENTITY=0 switches the shortcut off
   bool edge_ = false;          // the current local exponential's applies take heff_apply_edge
   int edge_mode_ = -1;         // MITDVP_EDGE_APPLY: 0 never, 1 wherever valid, -1 (default) the size rule of choose_apply_forms
+  // the folded variant of the edge form, per side: the reduced core contracted into the environment block once per
+  // local solve (choose_apply_forms, operators in Y_ / X_), the side's apply one plain GEMM (heff_apply_edge)
+  bool fold_r_ = false, fold_l_ = false;
+  int fold_mode_ = -1;         // MITDVP_FOLD_APPLY: 0 never, 1 wherever the edge form is valid, -1 (default) the rule of choose_apply_forms
   bool right_block_is_identity(const zc* R, int dr, int m);
   void identity_blocks(const zc* L, int dl, int ml, const zc* R, int dr, int mr, bool* left, bool* right);
   int L_;

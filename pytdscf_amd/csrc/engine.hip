@@ -28,6 +28,7 @@ Engine::Engine(const mitdvp_config& c) : cfg(c), L_(c.nsite) {
   if (const char* e = std::getenv("MITDVP_SPARSE_W")) sparse_w_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_TRIM_IDENTITY")) trim_identity_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_EDGE_APPLY")) edge_mode_ = std::atoi(e);
+  if (const char* e = std::getenv("MITDVP_FOLD_APPLY")) fold_mode_ = std::atoi(e);
   if (const char* e = std::getenv("MITDVP_QR_GAUGE_FREE")) qr_gauge_free_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_KEFF_IDENT")) keff_ident_ = std::atoi(e) != 0;
   int ndev = 0;
@@ -615,11 +616,27 @@ void Engine::heff_apply_rect(const zc* L, const MpoSite& w, const zc* R, const z
 // Both are GEMMs of the size of stages S1 / S3 whose 64 x 64 tiles hold whole (j, t) / (c, j) groups and are contracted
 // with the d x (d M) reduced core in the epilogue (zgemm_reduce): the M-fold intermediates X and Y of the three-stage
 // chain ("must be tiled / fused") are never written.  psiT = psi with its last two indices swapped.
+//
+// The folded variant (fold_r_ / fold_l_, per side, chosen and built by choose_apply_forms): the M-fold product of a side
+// is not needed when its MPO bond is wider than d.  With the reduced core contracted into the block once per local solve,
+//   GR[(i,r)][(j,s)] = sum_t wr[i,j,t] R[r,t,s]   (in Y_),      GL[(a,i)][(b,j)] = sum_c wl[i,c,j] L[a,c,b]   (in X_),
+// the side is one plain GEMM, sigma[a][(i,r)] = psi[a][(j,s)] GR^T resp. sigma[(a,i)][r] += GL psi[(b,j)][r]: mr / d
+// resp. ml / d times fewer products, no transpose, no epilogue.
 void Engine::heff_apply_edge(const zc* L, const MpoSite& w, const zc* R, const zc* psi, zc* out, int dl, int d, int dr) {
   const int ml = w.ml, mr = w.mr;
   bool first = true;
   double exe = 0.0;
-  if (w.edge_has_r) {  // R side: rows (a, j), columns (r, t)
+  if (w.edge_has_r && fold_r_) {
+    timer_begin(12);
+    ZgemmDesc g = zgemm_desc(psi, Y_.p, out, dl, d * dr, d * dr);
+    g.transB = 1; g.ldb = (long)d * dr;
+    zgemm(st_, g);
+    timer_end();
+    first = false;
+    cnt_.n_launch += 1;
+    exe += 8.0 * (double)dl * d * dr * d * dr;
+    cnt_.heff_stage_flops[2] += 8.0 * (double)dl * d * dr * d * dr;
+  } else if (w.edge_has_r) {  // R side: rows (a, j), columns (r, t)
     timer_begin(12);
     ZgemmDesc g = zgemm_desc(psi, R, out, dl * d, dr * mr, dr);
     g.transB = 1; g.ldb = dr;
@@ -633,7 +650,17 @@ void Engine::heff_apply_edge(const zc* L, const MpoSite& w, const zc* R, const z
     exe += 8.0 * ((double)dl * d * dr * mr * dr + (double)dl * dr * d * d * mr);
     cnt_.heff_stage_flops[2] += 8.0 * ((double)dl * d * dr * mr * dr + (double)dl * dr * d * d * mr);
   }
-  if (w.edge_has_l) {
+  if (w.edge_has_l && fold_l_) {
+    timer_begin(10);
+    ZgemmDesc g = zgemm_desc(X_.p, psi, out, dl * d, dr, dl * d);
+    if (!first) g.beta = make_double2(1.0, 0.0);
+    zgemm(st_, g);
+    timer_end();
+    first = false;
+    cnt_.n_launch += 1;
+    exe += 8.0 * (double)dl * d * dl * d * dr;
+    cnt_.heff_stage_flops[0] += 8.0 * (double)dl * d * dl * d * dr;
+  } else if (w.edge_has_l) {
     timer_begin(11);
     transpose_batched(st_, psi, X_.p, d, dr, dr, d, dl, (long)d * dr, (long)d * dr);  // psiT[b][s][j]
     timer_end();
@@ -662,17 +689,27 @@ void Engine::heff_apply_edge(const zc* L, const MpoSite& w, const zc* R, const z
 // blocks L[:, 0, :] and R[:, mr-1, :] (checked from D = 256 on, where one check per site buys 1 / M of stages S1 / S3 in
 // every apply); the edge form needs the identity states of both bonds (all blocks checked: two launches, one copy).
 void Engine::choose_apply_forms(const zc* Lb, const MpoSite& w, const zc* Rb, int dl, int d, int dr) {
-  trim_l_ = trim_r_ = edge_ = false;
+  trim_l_ = trim_r_ = edge_ = fold_l_ = fold_r_ = false;
   int a0, a1;
   const bool sharded = shard_range(dl, a0, a1);
   const int ml = w.ml, mr = w.mr;
+  // The folded variant of a side (heff_apply_edge), should the core turn out edge-structured.  The rule: a side's GEMM
+  // shrinks by m / d, so it is folded when its MPO bond is wider than d; building the operator is d^2 m D^2 products and
+  // one write of (d D)^2 elements per local solve, against (m - d) d D^3 products saved in every apply (measured:
+  // profiles/fold_apply_ab.txt).  The operators live in the chain form's workspaces, which the edge form leaves idle and
+  // nothing else writes during a local solve (Y_: GR; X_: GL, or psiT of an unfolded L side): (d D)^2 <= D M d D whenever
+  // d <= M, so a side whose operator does not fit is not folded and no memory is ever allocated for one.
+  const bool can_fold_r = fold_mode_ != 0 && !sharded && (fold_mode_ > 0 || mr > d) && (size_t)d * dr * d * dr <= Y_.n;
+  const bool can_fold_l = fold_mode_ != 0 && !sharded && (fold_mode_ > 0 || ml > d) && (size_t)dl * d * dl * d <= X_.n;
+  // (a folded side has no reducing epilogue: its group shapes need not be among those zgemm_reduce is built for)
   const bool edge_cand = edge_mode_ != 0 && trim_identity_ && !w.whost.empty() && !sharded && dl >= 32 && dr >= 32 &&
-                         zgemm_reduce_ok(d, mr, d) && zgemm_reduce_ok(ml, d, d) && (long)d * dr < (1L << 20) &&
+                         (can_fold_r || zgemm_reduce_ok(d, mr, d)) && (can_fold_l || zgemm_reduce_ok(ml, d, d)) && (long)d * dr < (1L << 20) &&
                          // the size rule: the epilogue streams the d x (d M) reduced core once per tile -- cheap beside a
                          // tile's K loop only while d M is small (measured: profiles/r04_edge_apply_ab.txt)
                          // round 5: with the 4 x 4 x 4 epilogue (no padded products at d M = 512) the form also wins where the
                          // W stage is a large share of the chain, i.e. at short bonds: C3 (D = 128) heff -9 %, C4 (D = 1024) +2 %
-                         (edge_mode_ > 0 || ((long)d * std::max(ml, mr) <= 64 && (long)dl * dr <= 512L * 512L) ||
+                         // (both sides folded: no epilogue at all, two plain GEMMs m / d times smaller than the chain's outer stages)
+                         (edge_mode_ > 0 || (can_fold_r && can_fold_l) || ((long)d * std::max(ml, mr) <= 64 && (long)dl * dr <= 512L * 512L) ||
                           // (later in round 5: with the cores in fragment order and the unguarded epilogue the form is level with
                           // the chain at C4 too -- 0.02064 against 0.02058 sweeps/s, H_eff frac 0.899 against 0.875, a ninth of the
                           // chain's intermediate traffic -- so shapes that run that variant take it at any bond)
@@ -762,6 +799,15 @@ void Engine::choose_apply_forms(const zc* Lb, const MpoSite& w, const zc* Rb, in
     w.edge_has_l = has_l; w.edge_has_r = has_r; w.edge_valid = true;
   }
   edge_ = true;
+  fold_r_ = w.edge_has_r && can_fold_r;
+  fold_l_ = w.edge_has_l && can_fold_l;
+  if (fold_r_ || fold_l_) {  // once per local solve, on the stream, no synchronisation
+    timer_begin(11);
+    if (fold_r_) fold_env_core(st_, Rb, w.w_edge_r.p, Y_.p, dr, mr, d, (long)d * mr, mr, 1, (long)dr * d * dr, (long)d * dr, dr, 1);
+    if (fold_l_) fold_env_core(st_, Lb, w.w_edge_l.p, X_.p, dl, ml, d, (long)ml * d, 1, d, (long)dl * d, (long)d * dl * d, 1, d);
+    timer_end();
+    cnt_.n_launch += (fold_r_ ? 1 : 0) + (fold_l_ ? 1 : 0);
+  }
 }
 
 void Engine::heff_apply(const zc* L, const MpoSite& w, const zc* R, const zc* psi, zc* out, int dl, int d, int dr,

@@ -47,6 +47,11 @@ void ident_deviation(hipStream_t st, const zc* blk, long ld, int n, double* out_
 // mask: bit c set = block c is looked at (the others' outputs are meaningless)
 void ident_deviation_multi(hipStream_t st, const zc* base, int nblk, long blk_stride, long ld, int n, double* out_dev,
                            zc* lam_dev, unsigned long long mask = ~0ull, bool clear = true);
+// An environment block env (n, m, n) with a reduced MPO core folded in (the folded variant of the edge form,
+// Engine::heff_apply_edge): G[i * gi + p * gp + j * gj + q * gq] = sum_c w[i * wi + j * wj + c * wm] * env[p][c][q],
+// i, j < d, m <= 64.  The caller's strides must address d * d * n * n distinct elements of G.
+void fold_env_core(hipStream_t st, const zc* env, const zc* w, zc* G, int n, int m, int d, long wi, long wj, long wm, long gi,
+                   long gp, long gj, long gq);
 void copy2d(hipStream_t st, zc* dst, long ldd, const zc* src, long lds, long rows, int cols, int zero_to, zc a,
             bool accumulate);
 // Block lists of the K_eff apply with identity states skipped (Engine::keff_prepare): up to 64 blocks, scalars by value.

@@ -896,4 +896,63 @@ void ident_deviation(hipStream_t st, const zc* blk, long ld, int n, double* out_
   HIP_CHECK(hipGetLastError());
 }
 
+// An environment block with a reduced MPO core folded in (fold_env_core): one workgroup per (p, 64 values of q).  The
+// slab env[p][:][q0..q0+63] sits in LDS (m x 64 elements, m <= 64); lane = q, a wave takes (i, four values of j) at a
+// time: one LDS read feeds four products, the core elements are the same for the whole wave (scalar loads), and a core
+// element group of zeros (most of a finite-state-machine core) is skipped.  Stores are 16 bytes per lane, contiguous over
+// the wave where q is the fast output index (gq = 1) and four consecutive elements per lane where j is (gj = 1).
+__device__ __forceinline__ double readlane_f64(double v, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+__global__ __launch_bounds__(256) void k_fold_env_core(const zc* __restrict__ env, const zc* __restrict__ w, zc* __restrict__ G,
+                                                       int n, int m, int d, long wi, long wj, long wm, long gi, long gp,
+                                                       long gj, long gq) {
+  extern __shared__ __attribute__((aligned(16))) char fold_raw[];
+  zc* es = reinterpret_cast<zc*>(fold_raw);
+  const int p = blockIdx.y, q0 = blockIdx.x * 64;
+  for (int e = threadIdx.x; e < m * 64; e += 256) {
+    const int c = e >> 6, q = q0 + (e & 63);
+    es[e] = q < n ? env[((long)p * m + c) * n + q] : make_double2(0.0, 0.0);
+  }
+  __syncthreads();
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int q = q0 + lane;
+  const int njb = (d + 3) / 4;
+  for (int item = wave; item < d * njb; item += 4) {
+    const int i = item / njb, j0 = (item % njb) * 4;
+    // lane c holds the core elements of bond state c (one vector load per j); the loop reads them back lane by lane
+    // into scalar registers, so the test for a group of zeros and the products' first factors are wave-uniform
+    zc fv[4];
+    for (int u = 0; u < 4; ++u)
+      fv[u] = lane < m ? w[i * wi + min(j0 + u, d - 1) * wj + lane * wm] : make_double2(0.0, 0.0);
+    zc acc[4] = {};
+    for (int c = 0; c < m; ++c) {
+      zc f[4];
+      bool any = false;
+      for (int u = 0; u < 4; ++u) {
+        f[u] = make_double2(readlane_f64(fv[u].x, c), readlane_f64(fv[u].y, c));
+        any = any || f[u].x != 0.0 || f[u].y != 0.0;
+      }
+      if (!any) continue;
+      const zc e = es[c * 64 + lane];
+      for (int u = 0; u < 4; ++u) {  // four fused multiply-adds per product (the kernel is bound by the vector FP64 rate)
+        acc[u].x = fma(-f[u].y, e.y, fma(f[u].x, e.x, acc[u].x));
+        acc[u].y = fma(f[u].y, e.x, fma(f[u].x, e.y, acc[u].y));
+      }
+    }
+    if (q < n)
+      for (int u = 0; u < 4; ++u)
+        if (j0 + u < d) G[i * gi + p * gp + (j0 + u) * gj + q * gq] = acc[u];
+  }
+}
+// G[i * gi + p * gp + j * gj + q * gq] = sum_c w[i * wi + j * wj + c * wm] * env[p][c][q]   (env: n x m x n, i, j < d)
+void fold_env_core(hipStream_t st, const zc* env, const zc* w, zc* G, int n, int m, int d, long wi, long wj, long wm, long gi,
+                   long gp, long gj, long gq) {
+  if (n < 1 || d < 1) return;
+  if (m < 1 || m > 64 || n > 65535) throw ArgError("fold_env_core: MPO bond in [1, 64] and bond dimension <= 65535");
+  hipLaunchKernelGGL(k_fold_env_core, dim3((n + 63) / 64, n), dim3(256), (size_t)m * 64 * sizeof(zc), st, env, w, G, n, m, d,
+                     wi, wj, wm, gi, gp, gj, gq);
+  HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace mitdvp
