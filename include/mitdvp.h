@@ -441,6 +441,8 @@ typedef struct {
   double heff_stage_flops[3]; /* 8-flop-per-complex-MAC count of what the three stages EXECUTE (trimmed identity blocks,
                                  skipped zero blocks and tile padding of the W stage accounted; the 3M product's 6 / 8 is
                                  applied by the reader): with heff_stage_ms the roofline of each stage's kernel */
+  double n_env_fold;       /* environment updates that took the structured form (Gram matrix of the site tensor + folded
+                              operator of the general MPO-bond states) instead of the M-fold chain */
 } mitdvp_counters;
 int mitdvp_counters_get(mitdvp_engine* h, mitdvp_counters* out);
 int mitdvp_counters_reset(mitdvp_engine* h);

@@ -93,6 +93,17 @@ struct MpoSite {
   mutable DevBuf w_edge_l, w_edge_r;
   mutable DevBuf w_edge_lf, w_edge_rf;  // the same cores in the epilogue's fragment order (zgemm_reduce_pack_core)
   mutable bool edge_lf_ok = false, edge_rf_ok = false;
+  // Structured environment update (Engine::env_update_fold), per direction (0: -> consumes L with its identity set S,
+  // 1: <- consumes R with E; "in" = the MPO bond of the consumed block, "out" = the other one).  Built beside the edge
+  // cores and valid with them (edge_valid):
+  //   ws[i][j][out]        = sum_{in in the identity set} (multiple of in) W[in, i, j, out]   (all out states)
+  //   wg[k][i][in][j]      = W[in, i, j, t0[k]] for in NOT in the identity set, else 0        (unweighted)
+  // t0 = the out states fed by a general in state (one "all applied" state per summand of a finite-state-machine MPO).
+  struct EnvFold {
+    std::vector<int> t0;
+    DevBuf ws, wg;
+  };
+  mutable EnvFold envf[2];
   DevBuf wtr;  // Liouville trace operator: O2[f][(a,c,d)] = O[a,d,c,f], n = sqrt(site dim)
   int ntr = 0, mltr = 0, mrtr = 0;
   int dtr = 0;  // physical entries per (a, f) of wtr: n*n, or the size of the site's subspace when it was set
@@ -197,6 +208,10 @@ class Engine {
   // generic environment update: env_in (din, min, din), T (din, d, dout),
   // W2 ((d*mout) x (min*d)) -> env_out (dout, mout, dout)
   // w2e: the small-site form of the same core (MpoSite::w2el / w2er), nullptr = general path only
+  // the structured form of the update (Gram matrix of the site tensor + folded operator of the general states)
+  bool env_fold_ok(const zc* env_in, int din, int min_, int d, int dout, int mout, const MpoSite* sp, int sp_side);
+  void env_update_fold(const zc* env_in, const zc* T, zc* env_out, int din, int min_, int d, int dout, int mout,
+                       const MpoSite::EnvFold& f);
   void env_update(const zc* env_in, const zc* T, const zc* w2, zc* env_out, int din, int min_, int d, int dout,
                   int mout, const zc* w2e = nullptr, const MpoSite* sp = nullptr, int sp_side = 0);
   // x <- exp(scale * Op) x ; returns Krylov dimension used.  The Ritz step and the convergence test run on the device
@@ -297,6 +312,11 @@ class Engine {
   // local solve (choose_apply_forms, operators in Y_ / X_), the side's apply one plain GEMM (heff_apply_edge)
   bool fold_r_ = false, fold_l_ = false;
   int fold_mode_ = -1;         // MITDVP_FOLD_APPLY: 0 never, 1 wherever the edge form is valid, -1 (default) the rule of choose_apply_forms
+  // MITDVP_FOLD_ENV: the structured environment update (env_update_fold): 0 never, 1 wherever it is valid, -1 (default) the
+  // rule of env_fold_ok.  The identity sets it relies on are those the last choose_apply_forms found for exactly these
+  // blocks of this site (env_chk_; one update may use them, any update clears them)
+  int fold_env_mode_ = -1;
+  struct EnvChecked { const MpoSite* w = nullptr; const zc* blk[2] = {nullptr, nullptr}; int n[2] = {0, 0}; } env_chk_;
   bool right_block_is_identity(const zc* R, int dr, int m);
   void identity_blocks(const zc* L, int dl, int ml, const zc* R, int dr, int mr, bool* left, bool* right);
   int L_;

@@ -29,6 +29,7 @@ Engine::Engine(const mitdvp_config& c) : cfg(c), L_(c.nsite) {
   if (const char* e = std::getenv("MITDVP_TRIM_IDENTITY")) trim_identity_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_EDGE_APPLY")) edge_mode_ = std::atoi(e);
   if (const char* e = std::getenv("MITDVP_FOLD_APPLY")) fold_mode_ = std::atoi(e);
+  if (const char* e = std::getenv("MITDVP_FOLD_ENV")) fold_env_mode_ = std::atoi(e);
   if (const char* e = std::getenv("MITDVP_QR_GAUGE_FREE")) qr_gauge_free_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_KEFF_IDENT")) keff_ident_ = std::atoi(e) != 0;
   int ndev = 0;
@@ -690,6 +691,7 @@ void Engine::heff_apply_edge(const zc* L, const MpoSite& w, const zc* R, const z
 // every apply); the edge form needs the identity states of both bonds (all blocks checked: two launches, one copy).
 void Engine::choose_apply_forms(const zc* Lb, const MpoSite& w, const zc* Rb, int dl, int d, int dr) {
   trim_l_ = trim_r_ = edge_ = fold_l_ = fold_r_ = false;
+  env_chk_ = EnvChecked{};
   int a0, a1;
   const bool sharded = shard_range(dl, a0, a1);
   const int ml = w.ml, mr = w.mr;
@@ -794,11 +796,49 @@ void Engine::choose_apply_forms(const zc* Lb, const MpoSite& w, const zc* Rb, in
     w.w_edge_rf.reserve(wr.size());
     w.edge_lf_ok = zgemm_reduce_pack_core(st_, w.w_edge_l.p, (long)ml * d, d, ml * d, w.w_edge_lf.p);
     w.edge_rf_ok = zgemm_reduce_pack_core(st_, w.w_edge_r.p, (long)d * mr, d, d * mr, w.w_edge_rf.p);
+    // the cores of the structured environment update (env_update_fold), both directions: the blocks out of an identity
+    // state summed with its multiple (all out states), and, per out state a general state feeds, those blocks unweighted
+    for (int side = 0; side < 2; ++side) {
+      const int mi = side == 0 ? ml : mr, mo = side == 0 ? mr : ml;
+      const unsigned long long I = side == 0 ? S : E;
+      const std::vector<hzc>& wt = side == 0 ? lam : mu;
+      auto blk = [&](int in, int out) { return side == 0 ? (size_t)in * mr + out : (size_t)out * mr + in; };
+      auto Wel = [&](int in, int i, int j, int out) {
+        return side == 0 ? W[(((size_t)in * d + i) * d + j) * mr + out] : W[(((size_t)out * d + i) * d + j) * mr + in];
+      };
+      MpoSite::EnvFold& f = w.envf[side];
+      f.t0.clear();
+      for (int out = 0; out < mo; ++out)
+        for (int in = 0; in < mi; ++in)
+          if (!((I >> in) & 1ull) && w.nzblk[blk(in, out)]) { f.t0.push_back(out); break; }
+      std::vector<hzc> ws((size_t)d * d * mo, hzc(0, 0)), wg(std::max<size_t>(f.t0.size(), 1) * d * mi * d, hzc(0, 0));
+      for (int in = 0; in < mi; ++in) {
+        if (!((I >> in) & 1ull)) continue;
+        for (int out = 0; out < mo; ++out) {
+          if (!w.nzblk[blk(in, out)]) continue;
+          for (int i = 0; i < d; ++i)
+            for (int j = 0; j < d; ++j) ws[((size_t)i * d + j) * mo + out] += wt[in] * Wel(in, i, j, out);
+        }
+      }
+      for (size_t k = 0; k < f.t0.size(); ++k)
+        for (int in = 0; in < mi; ++in) {
+          if (((I >> in) & 1ull) || !w.nzblk[blk(in, f.t0[k])]) continue;
+          for (int i = 0; i < d; ++i)
+            for (int j = 0; j < d; ++j) wg[((k * d + i) * mi + in) * d + j] = Wel(in, i, j, f.t0[k]);
+        }
+      f.ws.reserve(ws.size());
+      f.wg.reserve(wg.size());
+      HIP_CHECK(hipMemcpyAsync(f.ws.p, ws.data(), ws.size() * sizeof(zc), hipMemcpyHostToDevice, st_));
+      HIP_CHECK(hipMemcpyAsync(f.wg.p, wg.data(), wg.size() * sizeof(zc), hipMemcpyHostToDevice, st_));
+      HIP_CHECK(hipStreamSynchronize(st_));  // the host vectors go out of scope
+    }
     HIP_CHECK(hipStreamSynchronize(st_));
     w.edge_s = S; w.edge_e = E; w.edge_lam = lam; w.edge_mu = mu;
     w.edge_has_l = has_l; w.edge_has_r = has_r; w.edge_valid = true;
   }
   edge_ = true;
+  // S / E describe exactly these two blocks of this site: the next environment update may rely on them (env_fold_ok)
+  env_chk_.w = &w; env_chk_.blk[0] = Lb; env_chk_.blk[1] = Rb; env_chk_.n[0] = dl; env_chk_.n[1] = dr;
   fold_r_ = w.edge_has_r && can_fold_r;
   fold_l_ = w.edge_has_l && can_fold_l;
   if (fold_r_ || fold_l_) {  // once per local solve, on the stream, no synchronisation
@@ -978,6 +1018,63 @@ void Engine::env_update_rect(const zc* env_in, const zc* Tk, const zc* Tb, const
                            (double)nm * dbo * dko * mout * d);
 }
 
+// The structured update.  With I the states of the consumed block's MPO bond whose blocks env_in[:, c, :] are multiples
+// lam_c of the identity (found by choose_apply_forms for this very block), the sum over c splits:
+//   c in I:      env_in drops out.  G[(i,a')][(j,r)] = sum_a conj(T[a,i,a']) T[a,j,r]  (the site tensor's Gram matrix, one
+//                GEMM of d^2 D^3 products) and env_out[a',t,r] = sum_{i,j} ws[i,j,t] G[(i,a')][(j,r)] for every t
+//                (gram_env_core: d^2 M D^2 products);
+//   c not in I:  only the few out states t0 a general state feeds (one per summand of a finite-state-machine MPO).  With
+//                GL_t0[(a,i)][(b,j)] = sum_{c not in I} W[c,i,j,t0] env_in[a,c,b]  (fold_env_core),
+//                env_out[:, t0, :] += T^H (GL_t0 T): d^2 D^3 + d D^3 products.
+// (1 + |t0|) d^2 D^3 + |t0| d D^3 products against the chain's 2 M d D^3.  The Gram matrix and then GL_t0 T live in Y_,
+// GL_t0 in X_: the chain's own workspaces, (d D)^2 <= D M d D whenever d <= M; nothing is allocated.
+bool Engine::env_fold_ok(const zc* env_in, int din, int min_, int d, int dout, int mout, const MpoSite* sp, int sp_side) {
+  const EnvChecked chk = env_chk_;
+  env_chk_ = EnvChecked{};  // whatever this update does, the sets have had their one use
+  int a0, a1;
+  if (fold_env_mode_ == 0 || !sp || adaptive_ || shard_range(din, a0, a1)) return false;
+  if (chk.w != sp || chk.blk[sp_side] != env_in || chk.n[sp_side] != din || !sp->edge_valid || sp->d != d) return false;
+  if (min_ != (sp_side == 0 ? sp->ml : sp->mr) || mout != (sp_side == 0 ? sp->mr : sp->ml)) return false;
+  if (min_ > 64 || mout > 64 || d > 64 || din > 65535 || dout > 65535) return false;  // the two kernels' ranges
+  const MpoSite::EnvFold& f = sp->envf[sp_side];
+  const double nt = (double)f.t0.size();
+  if ((size_t)d * dout * d * dout > Y_.n || (size_t)din * d * dout > Y_.n || (nt > 0 && (size_t)din * d * din * d > X_.n)) return false;
+  if (fold_env_mode_ > 0) return true;
+  // the rule: the consumed side's MPO bond wider than d (as for the folded apply), and at most three quarters of the
+  // chain's products left (one general out state always passes; a direct sum with several is taken while it pays)
+  const double fresh = (double)d * d * dout * dout * din + nt * ((double)d * d * din * din * dout + (double)d * din * dout * dout);
+  const double chain = (double)min_ * d * din * din * dout + (double)mout * d * din * dout * dout;
+  return min_ > d && 4.0 * fresh <= 3.0 * chain;
+}
+
+void Engine::env_update_fold(const zc* env_in, const zc* T, zc* env_out, int din, int min_, int d, int dout, int mout,
+                             const MpoSite::EnvFold& f) {
+  timer_begin(1);
+  {  // G[(i,a')][(j,r)] = conj(T)[a][(i,a')] T[a][(j,r)]
+    ZgemmDesc g = zgemm_desc(T, T, Y_.p, d * dout, d * dout, din);
+    g.transA = 1; g.conjA = 1; g.lda = (long)d * dout;
+    zgemm(st_, g);
+  }
+  gram_env_core(st_, Y_.p, f.ws.p, env_out, dout, mout, d);
+  for (size_t k = 0; k < f.t0.size(); ++k) {
+    // GL[(a,i)][(b,j)] (in X_), Z[(a,i)][r] = GL T[(b,j)][r] (in Y_: the Gram matrix has been consumed), block t0 += T^H Z
+    fold_env_core(st_, env_in, f.wg.p + k * (size_t)d * min_ * d, X_.p, din, min_, d, (long)min_ * d, 1, d, (long)din * d,
+                  (long)d * din * d, 1, d);
+    ZgemmDesc g = zgemm_desc(X_.p, T, Y_.p, din * d, dout, din * d);
+    zgemm(st_, g);
+    ZgemmDesc h = zgemm_desc(T, Y_.p, env_out + (size_t)f.t0[k] * dout, dout, dout, din * d);
+    h.transA = 1; h.conjA = 1; h.lda = dout; h.ldc = (long)mout * dout; h.beta = make_double2(1.0, 0.0);
+    zgemm(st_, h);
+  }
+  timer_end();
+  cnt_.n_launch += 2 + 3 * (long long)f.t0.size();
+  cnt_.n_env += 1;
+  cnt_.n_env_fold += 1;
+  // (algorithmic count, as heff_flops: the chain's)
+  cnt_.env_flops += 8.0 * ((double)din * din * min_ * d * dout + (double)din * dout * min_ * mout * d * d +
+                           (double)din * dout * dout * mout * d);
+}
+
 void Engine::env_update(const zc* env_in, const zc* T, const zc* w2, zc* env_out, int din, int min_, int d, int dout,
                         int mout, const zc* w2e, const MpoSite* sp, int sp_side) {
   SmallChain sc;
@@ -989,6 +1086,11 @@ void Engine::env_update(const zc* env_in, const zc* T, const zc* w2, zc* env_out
     cnt_.n_env += 1;
     cnt_.env_flops += 8.0 * ((double)din * din * min_ * d * dout + (double)din * dout * min_ * mout * d * d +
                              (double)din * dout * dout * mout * d);
+    env_chk_ = EnvChecked{};
+    return;
+  }
+  if (env_fold_ok(env_in, din, min_, d, dout, mout, sp, sp_side)) {
+    env_update_fold(env_in, T, env_out, din, min_, d, dout, mout, sp->envf[sp_side]);
     return;
   }
   env_update_rect(env_in, T, T, w2, env_out, din, din, min_, d, dout, dout, mout, sp, sp_side);

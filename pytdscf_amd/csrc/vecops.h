@@ -52,6 +52,10 @@ void ident_deviation_multi(hipStream_t st, const zc* base, int nblk, long blk_st
 // i, j < d, m <= 64.  The caller's strides must address d * d * n * n distinct elements of G.
 void fold_env_core(hipStream_t st, const zc* env, const zc* w, zc* G, int n, int m, int d, long wi, long wj, long wm, long gi,
                    long gp, long gj, long gq);
+// The Gram matrix G ((d n) x (d n), rows (i, p), columns (j, q)) of a site tensor contracted with a reduced core
+// (the structured environment update, Engine::env_update_fold): out[p][t][q] = sum_{i, j} ws[(i * d + j) * m + t] *
+// G[(i, p)][(j, q)], all m <= 64 blocks of the (n, m, n) block, which is overwritten.
+void gram_env_core(hipStream_t st, const zc* G, const zc* ws, zc* out, int n, int m, int d);
 void copy2d(hipStream_t st, zc* dst, long ldd, const zc* src, long lds, long rows, int cols, int zero_to, zc a,
             bool accumulate);
 // Block lists of the K_eff apply with identity states skipped (Engine::keff_prepare): up to 64 blocks, scalars by value.

@@ -955,4 +955,72 @@ void fold_env_core(hipStream_t st, const zc* env, const zc* w, zc* G, int n, int
   HIP_CHECK(hipGetLastError());
 }
 
+// The site's Gram matrix contracted with a reduced MPO core (gram_env_core; the structured environment update,
+// Engine::env_update_fold): one workgroup per (p, 64 values of q), lane = q.  For one i at a time the slab
+// G[(i, p)][(j, q0..q0+63)], all j, sits in LDS (d x 64 elements); wave v owns the output blocks t = v, v + 4, ... (TU of
+// them at most) and walks j: lane t holds the core element ws[i][j][t] (one vector load per (i, j)), read back into
+// scalar registers, so a zero element -- and a (i, j) with nothing but zeros for this wave's blocks, which then does not
+// read the slab at all -- is skipped wave-uniformly.  Sums run over i, then j, in that order whatever the launch: deterministic.
+// Stores are 16 bytes per lane, contiguous over the wave.
+template <int TU>
+__global__ __launch_bounds__(256) void k_gram_env_core(const zc* __restrict__ G, const zc* __restrict__ ws, zc* __restrict__ out,
+                                                       int n, int m, int d) {
+  extern __shared__ __attribute__((aligned(16))) char gram_raw[];
+  zc* es = reinterpret_cast<zc*>(gram_raw);
+  const int p = blockIdx.y, q0 = blockIdx.x * 64;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int q = q0 + lane;
+  const long ldg = (long)d * n;
+  constexpr int UC = TU < 8 ? TU : 8;
+  zc acc[TU] = {};
+  for (int i = 0; i < d; ++i) {
+    __syncthreads();  // the previous slab has been read by every wave
+    for (int e = threadIdx.x; e < d * 64; e += 256) {
+      const int j = e >> 6, qq = q0 + (e & 63);
+      es[e] = qq < n ? G[((long)i * n + p) * ldg + (long)j * n + qq] : make_double2(0.0, 0.0);
+    }
+    __syncthreads();
+    for (int j = 0; j < d; ++j) {
+      const zc fv = lane < m ? ws[((long)i * d + j) * m + lane] : make_double2(0.0, 0.0);
+#pragma unroll
+      for (int u0 = 0; u0 < TU; u0 += UC) {  // UC blocks at a time: their core elements fit the scalar registers
+        zc f[UC];
+        bool any = false;
+#pragma unroll
+        for (int u = 0; u < UC; ++u) {
+          const int t = min(wave + 4 * (u0 + u), 63);  // (t >= m reads a lane that holds zero)
+          f[u] = make_double2(readlane_f64(fv.x, t), readlane_f64(fv.y, t));
+          any = any || f[u].x != 0.0 || f[u].y != 0.0;
+        }
+        if (!any) continue;
+        const zc e = es[j * 64 + lane];
+#pragma unroll
+        for (int u = 0; u < UC; ++u) {
+          if (f[u].x == 0.0 && f[u].y == 0.0) continue;
+          acc[u0 + u].x = fma(-f[u].y, e.y, fma(f[u].x, e.x, acc[u0 + u].x));
+          acc[u0 + u].y = fma(f[u].y, e.x, fma(f[u].x, e.y, acc[u0 + u].y));
+        }
+      }
+    }
+  }
+  if (q < n) {
+#pragma unroll
+    for (int u = 0; u < TU; ++u) {
+      const int t = wave + 4 * u;
+      if (t < m) out[((long)p * m + t) * n + q] = acc[u];
+    }
+  }
+}
+// out[p][t][q] = sum_{i, j} ws[(i * d + j) * m + t] * G[(i, p)][(j, q)]   (G: (d n) x (d n) row-major; out: n x m x n)
+void gram_env_core(hipStream_t st, const zc* G, const zc* ws, zc* out, int n, int m, int d) {
+  if (n < 1 || d < 1) return;
+  if (m < 1 || m > 64 || n > 65535 || d > 64) throw ArgError("gram_env_core: MPO bond in [1, 64], d <= 64 and bond dimension <= 65535");
+  const dim3 grid((n + 63) / 64, n), block(256);
+  const size_t lds = (size_t)d * 64 * sizeof(zc);
+  if (m <= 16) hipLaunchKernelGGL(k_gram_env_core<4>, grid, block, lds, st, G, ws, out, n, m, d);
+  else if (m <= 32) hipLaunchKernelGGL(k_gram_env_core<8>, grid, block, lds, st, G, ws, out, n, m, d);
+  else hipLaunchKernelGGL(k_gram_env_core<16>, grid, block, lds, st, G, ws, out, n, m, d);
+  HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace mitdvp
