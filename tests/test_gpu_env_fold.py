@@ -13,70 +13,21 @@ split_center builds next is compared.  Tolerance: 1e-12 relative in the max norm
 tests/test_gpu_fold_apply.py (complex128, the same summation lengths in another order).
 """
 
-import os
-
 import numpy as np
 import pytest
 
+from helpers.fold_seam import TOL, engine_under
+from helpers.fold_seam import rel as _rel
+from helpers.fold_seam import solve_update_check as _solve_update_check
+from helpers.fold_seam import split as _split
+from helpers.fold_seam import to_site as _to_site
+
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-12
-
-
-def _rel(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
 
 
 def _engine(L, fold_env="1", **kw):
-    """an engine with MITDVP_FOLD_ENV set while it is created (None: unset) and without the one-launch small-bond kernels,
-    which would take the shortest of these shapes before any form is chosen"""
-    from pytdscf_amd import TDVPEngine
-
-    want = {"MITDVP_FOLD_ENV": fold_env, "MITDVP_SMALL_KERNELS": "0"}
-    old = {k: os.environ.get(k) for k in want}
-    for k, v in want.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = v
-    try:
-        return TDVPEngine(L, **kw)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _to_site(eng, c):
-    eng.build_envs(1)
-    for _ in range(c):
-        eng.split_center(True)
-        eng.absorb_bond(True)
-    assert eng.counters()["n_env_fold"] == 0  # no check ran before any of these updates
-
-
-def _split(orc, eng, mpo, c, forward):
-    """split the centre c and return (block the library built, the oracle's update of the same inputs)"""
-    if forward:
-        env_in = eng.get_env(0, c)
-        eng.split_center(True)
-        return eng.get_env(0, c + 1), orc.env_update_left(env_in, eng.get_site(c), mpo[c])
-    env_in = eng.get_env(1, c + 1)
-    eng.split_center(False)
-    return eng.get_env(1, c), orc.env_update_right(env_in, eng.get_site(c), mpo[c])
-
-
-def _solve_update_check(orc, eng, mpo, c, forward, want_fold, dt=0.1):
-    n0 = eng.counters()["n_env_fold"]
-    eng.site_exp(dt)  # the local solve: its check of the two blocks is what the update may rely on
-    got, ref = _split(orc, eng, mpo, c, forward)
-    took = eng.counters()["n_env_fold"] - n0
-    r = _rel(got, ref)
-    print(f"site {c} {'->' if forward else '<-'} block {got.shape}: structured {took:.0f}, rel err {r:.3e}")
-    assert took == want_fold
-    assert r < TOL
+    """an engine with MITDVP_FOLD_ENV set while it is created (None: unset)"""
+    return engine_under(L, {"MITDVP_FOLD_ENV": fold_env}, **kw)
 
 
 @pytest.mark.parametrize("forward", [True, False])

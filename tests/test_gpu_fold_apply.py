@@ -11,69 +11,20 @@ Tolerance: 1e-12 relative in the max norm over the whole output, as tests/test_g
 summation lengths: the fold changes the order of the sums, not their number of terms).
 """
 
-import os
-
 import numpy as np
 import pytest
 
+from helpers.fold_seam import EDGE, FOLD_L, FOLD_R, engine_under
+from helpers.fold_seam import check_center as _check_center
+from helpers.fold_seam import crandn as _crandn
+from helpers.fold_seam import to_site as _to_site
+
 pytestmark = pytest.mark.gpu
-
-EDGE, FOLD_R, FOLD_L = 0x10, 0x20, 0x40
-
-
-def _crandn(rng, *s):
-    a = rng.standard_normal(s + (2,))
-    return a.view(np.complex128).reshape(s)
-
-
-def _rel(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
 
 
 def _engine(L, fold="1", edge="1", **kw):
-    """an engine with MITDVP_FOLD_APPLY / MITDVP_EDGE_APPLY set while it is created (None: the variable unset), and
-    without the one-launch small-bond kernels, which would take the shortest of these shapes before any form is chosen"""
-    from pytdscf_amd import TDVPEngine
-
-    want = {"MITDVP_FOLD_APPLY": fold, "MITDVP_EDGE_APPLY": edge, "MITDVP_SMALL_KERNELS": "0"}
-    old = {k: os.environ.get(k) for k in want}
-    for k, v in want.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = v
-    try:
-        return TDVPEngine(L, **kw)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _to_site(eng, c):
-    eng.build_envs(1)
-    for _ in range(c):
-        eng.split_center(True)
-        eng.absorb_bond(True)
-
-
-def _check_center(orc, eng, mpo, c, rng, want_flags, tol=1e-12):
-    got, flags = eng.heff_apply_center()
-    assert flags & 0x70 == want_flags, hex(flags)
-    if flags & EDGE:
-        assert flags & 7 == 0, hex(flags)
-    Lb, Rb, psi = eng.get_env(0, c), eng.get_env(1, c + 1), eng.get_site(c)
-    r = _rel(got, orc.heff_apply(Lb, mpo[c], Rb, psi))
-    print(f"site {c} shape {psi.shape} flags {flags:#x}: rel err {r:.3e}")
-    assert r < tol
-    x = _crandn(rng, *psi.shape)  # a second vector through the same operators
-    got, flags2 = eng.heff_apply_center(x)
-    assert flags2 & 0x70 == flags & 0x70, hex(flags2)
-    r = _rel(got, orc.heff_apply(Lb, mpo[c], Rb, x))
-    print(f"site {c} random vector: rel err {r:.3e}")
-    assert r < tol
+    """an engine with MITDVP_FOLD_APPLY / MITDVP_EDGE_APPLY set while it is created (None: the variable unset)"""
+    return engine_under(L, {"MITDVP_FOLD_APPLY": fold, "MITDVP_EDGE_APPLY": edge}, **kw)
 
 
 @pytest.mark.parametrize("mode", ["3m", "4m"])
