@@ -122,6 +122,33 @@ int mitdvp_step(mitdvp_engine* h, double dt_au);
  * mitdvp_config): their launches then overlap on the chip without any admission control.  Returns the first non-zero
  * status (that engine's mitdvp_last_error holds the message); statuses[i] (may be NULL) receives each engine's own. */
 int mitdvp_ensemble_step(mitdvp_engine** hs, int n, double dt_au, int nsteps, int* statuses);
+
+/* Batched trajectories: any number of replicas of one chain shape stepped by ONE kernel launch per half-sweep for the whole
+ * batch (k_batch_sweep: one workgroup owns one replica, the replica index is the workgroup index; no host threads, no
+ * compute-unit ranges, no limit of 16).  Replicas are ordinary engine handles -- each owns its tensors and its own MPO, so
+ * per-replica Hamiltonians work -- which the batch borrows; it owns the pointer tables, status words and scratch only, and
+ * must be destroyed before the engines.  mitdvp_batch_create returns MITDVP_EINVAL (message: mitdvp_last_error(NULL)) and
+ * leaves every engine untouched unless: all handles are distinct and on one device, none is confined to a compute-unit
+ * range (cu_count == 0), each is a single electronic state, none is adaptive, a segment or bond-sharded, relax is 0 or 1,
+ * no gates or Kraus maps are set, site and MPO shapes are identical across the replicas at every site, integrator,
+ * lanczos_variant, conserve_norm, thresh, max_krylov and relax are identical, and the shapes are inside the kernel's
+ * envelope: dl*d*dr <= 8192 per site (d = 4, D = 32 is 4096), MPO bonds <= 16, bonds <= 64, dl*d >= dr and d*dr >= dl; the
+ * message names the offending site and the limit.  The same checks run again at every step: engines may be used on their
+ * own (setters, propagate, observables) between batch calls.
+ *   mitdvp_batch_step : nsteps time steps (forward and backward half-sweep each) of every replica; all engines must have
+ *                       their centre at site 0, as for mitdvp_step.  Two launches per time step, whatever n and nsite.
+ *   mitdvp_batch_sweep: one half-sweep.
+ * Afterwards every engine is an ordinary consistent engine (centre, gauges, environment cache, Krylov memories, counters;
+ * n_launch counts the batch's launches once, on replica 0).  statuses[i] (may be NULL) receives replica i's own status; the
+ * call returns the first non-zero one.  A replica that fails (MITDVP_ENOTCONV: its local exponential did not converge in
+ * max_krylov vectors) stops working, the others finish; its message is in mitdvp_last_error(hs[i]), and its state was left
+ * in the middle of a half-sweep: the caller must set its tensors again (set_site / init_random + canonicalize) before
+ * using it further. */
+typedef struct mitdvp_batch mitdvp_batch;
+int mitdvp_batch_create(mitdvp_engine** hs, int n, mitdvp_batch** out);
+int mitdvp_batch_step(mitdvp_batch* b, double dt_au, int nsteps, int* statuses);
+int mitdvp_batch_sweep(mitdvp_batch* b, double dt_au, int forward, int* statuses);
+void mitdvp_batch_destroy(mitdvp_batch* b);
 /* propagate_along_sweep (_mps_cls.py:798-1014), one direction only. */
 int mitdvp_sweep(mitdvp_engine* h, double dt_au, int forward);
 /* The same half-sweep in parts: the next `nsites` local updates of the half-sweep in progress (one is started when none

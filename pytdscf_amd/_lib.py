@@ -216,6 +216,10 @@ def load() -> C.CDLL:
         "mitdvp_set_small_kernels": (i, [vp, i]),
         "mitdvp_ensemble_step": (i, [C.POINTER(vp), i, d, i, ip]),
         "mitdvp_device_cu_count": (i, [i, ip]),
+        "mitdvp_batch_create": (i, [C.POINTER(vp), i, C.POINTER(vp)]),
+        "mitdvp_batch_step": (i, [vp, d, i, ip]),
+        "mitdvp_batch_sweep": (i, [vp, d, i, ip]),
+        "mitdvp_batch_destroy": (None, [vp]),
         "mitdvp_cu_mask_probe": (i, [i, C.POINTER(C.c_uint), i, i, C.c_size_t, i, ip]),
     }
     for name, (res, args) in sig.items():

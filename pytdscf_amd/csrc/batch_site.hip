@@ -1,0 +1,649 @@
+// batch_site.hip -- batched trajectories: k_batch_sweep, ONE workgroup per replica, a whole half-sweep per launch.
+//
+// At trajectory shapes (d = 2..4, D <= 32, M <= 16) a local problem is a few tens of kilobytes, so one workgroup can own
+// one replica completely: the replica index is blockIdx.x, nothing is exchanged between workgroups, and therefore there is
+// no spin wait, no residency requirement, no compute-unit mask and no admission control -- the hardware schedules the B
+// workgroups as compute units free up, for any B.  For p = begin .. end the workgroup runs what Engine::sweep_part runs
+// with a launch per item:
+//   1. exp(scale * H_eff) on the centre tensor        (three-stage chain of small_site.h, stages as workgroup GEMMs)
+//   2. the gauge move Psi -> A sigma / sigma B         (Householder thin QR inside the workgroup; the gauge is free)
+//   3. the environment update L[p + 1] / R[p]          (operand roles of Engine::chain_env)
+//   4. exp(scale * K_eff) on sigma                     (Engine::chain_keff)
+//   5. the absorb Psi(p + 1) = sigma B / Psi(p - 1) = A sigma
+// The scalar logic of a local exponential (Lanczos alpha variants, Arnoldi, _iter_info warm-up, conserve_norm rescale,
+// exhausted Krylov space, the projected exponential, the |psi_k - psi_{k-1}| test) is small_exp_dev.h: the same functions
+// k_small_site calls.
+//
+// What is resident where:
+//   * LDS, 56 544 bytes static per workgroup: the two operand tiles of the running product (16 x 32 complex each, rows
+//     padded to 33; aliased with the 6 k x k matrices of the projected exponential, which never run at the same time), the
+//     Krylov scalars (alpha, beta, 1 / beta, Hessenberg matrix, Ritz coefficients), the Householder scalars of a gauge
+//     move and the reduction partials.  LDS would allow two workgroups per compute unit; the register file does not (256
+//     VGPRs x 8 waves = 2 waves per SIMD): ONE workgroup, i.e. one replica, is resident per compute unit, 256 at a time.
+//   * global memory, per replica, L2-resident at these sizes: the tensors and blocks of the engine, and a scratch area with
+//     sigma, a spare tensor, the QR work matrix, the M-fold intermediates X and Y of an apply and the Krylov basis.
+//     Everything in it is written and re-read by the SAME workgroup only and ordered by workgroup-scope barriers
+//     (__syncthreads: release / acquire fences at workgroup scope around s_barrier).  No device-scope atomic, no flag.
+// Every loop is bounded: the Krylov loop by max_krylov, the projected exponential by its fixed caps, the rest by the shapes.
+//
+// Arithmetic: complex128 FMA products out of LDS tiles; every reduction is a wave tree followed by a fixed order over the
+// waves, and every element of every intermediate is computed by the same thread in the same order whatever the grid: a
+// replica's result depends neither on B nor on the compute unit it ran on.
+//
+// Resources: see the figures next to k_batch_sweep below.
+#include "batch_site.h"
+#include "small_exp_dev.h"
+
+#include <algorithm>
+
+#include "../../include/mitdvp.h"
+
+namespace mitdvp {
+namespace {
+
+constexpr int BT_TM = 32, BT_TN = 32, BT_TK = 16;  // output tile and K step of the workgroup product
+constexpr int BT_LD = 33;                          // padded leading dimension of the LDS tiles (bank spread)
+static_assert(SS_THREADS == 512, "k_batch_sweep: a 32 x 32 tile is two outputs per thread of 512");
+static_assert(2 * BT_TK * BT_LD <= 6 * MAXK * MAXK, "the tiles alias the projected exponential's scratch");
+
+struct BtSh {  // pointers into the workgroup's LDS
+  zc* mats;      // [6 * MAXK * MAXK]  projected exponential; the product tiles alias it
+  double* wsh;   // [SS_WAVES * SS_PAYMAX]
+  double* red;   // [8]
+  zc *alpha, *coef, *cprev, *hess;
+  double *beta, *invb;
+  int* ctl;
+  zc *udiag, *rdiag;  // [BATCH_MAX_BOND] Householder: diagonal entry of u_j, diagonal of R
+  double* gam;        // [BATCH_MAX_BOND] 2 / (u_j^H u_j), 0: no reflection
+};
+
+// element-wise sums of NV values per thread over the workgroup -> sh.red[0 .. NV), the same bits in every thread
+template <int NV>
+__device__ __forceinline__ void wg_reduce(const double (&v)[NV], const BtSh& sh) {
+  static_assert(NV <= 8, "red holds 8 values");
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+#pragma unroll
+  for (int q = 0; q < NV; ++q) {
+    const double r = wave_sum64(v[q]);
+    if (lane == 0) sh.wsh[q * SS_WAVES + w] = r;
+  }
+  __syncthreads();
+  if (tid < NV) sh.red[tid] = wtree(sh.wsh + tid * SS_WAVES);
+  __syncthreads();
+}
+
+// C(m, n) = sum_k a(m, k) b(k, n) by the whole workgroup: fa / fb fetch an operand element (global memory, any layout),
+// fc stores a result.  32 x 32 output tiles, thread t owns column t % 32 of rows t / 32 and t / 32 + 16; K in steps of 16
+// through two LDS tiles.  AK / BK: k is the fast index of the operand in memory (the tile is fetched k-fastest then).
+// The k order of every output is fixed; ends with a barrier (the results are visible to the workgroup).
+template <bool AK, bool BK, class FA, class FB, class FC>
+__device__ __forceinline__ void wg_gemm(int M, int N, int K, zc* tiles, FA&& fa, FB&& fb, FC&& fc) {
+  zc* As = tiles;                   // [BT_TK][BT_LD]: As[kk][mm]
+  zc* Bs = tiles + BT_TK * BT_LD;   // [BT_TK][BT_LD]: Bs[kk][nn]
+  const int tid = threadIdx.x;
+  const int tn = tid & 31, tm = tid >> 5;
+  const int a_kk = AK ? (tid & 15) : (tid >> 5), a_mm = AK ? (tid >> 4) : (tid & 31);
+  const int b_kk = BK ? (tid & 15) : (tid >> 5), b_nn = BK ? (tid >> 4) : (tid & 31);
+  for (int m0 = 0; m0 < M; m0 += BT_TM)
+    for (int n0 = 0; n0 < N; n0 += BT_TN) {
+      double c0r = 0.0, c0i = 0.0, c1r = 0.0, c1i = 0.0;
+      for (int k0 = 0; k0 < K; k0 += BT_TK) {
+        zc za = make_double2(0.0, 0.0), zb = za;
+        if (m0 + a_mm < M && k0 + a_kk < K) za = fa(m0 + a_mm, k0 + a_kk);
+        if (n0 + b_nn < N && k0 + b_kk < K) zb = fb(k0 + b_kk, n0 + b_nn);
+        As[a_kk * BT_LD + a_mm] = za;
+        Bs[b_kk * BT_LD + b_nn] = zb;
+        __syncthreads();
+#pragma unroll 4
+        for (int kk = 0; kk < BT_TK; ++kk) {
+          const zc a0 = As[kk * BT_LD + tm], a1 = As[kk * BT_LD + tm + 16], b = Bs[kk * BT_LD + tn];
+          c0r = fma(a0.x, b.x, c0r); c0r = fma(-a0.y, b.y, c0r);
+          c0i = fma(a0.x, b.y, c0i); c0i = fma(a0.y, b.x, c0i);
+          c1r = fma(a1.x, b.x, c1r); c1r = fma(-a1.y, b.y, c1r);
+          c1i = fma(a1.x, b.y, c1i); c1i = fma(a1.y, b.x, c1i);
+        }
+        __syncthreads();
+      }
+      if (n0 + tn < N) {
+        if (m0 + tm < M) fc(m0 + tm, n0 + tn, make_double2(c0r, c0i));
+        if (m0 + tm + 16 < M) fc(m0 + tm + 16, n0 + tn, make_double2(c1r, c1i));
+      }
+    }
+  __syncthreads();
+}
+
+// out[a,i,r] = sum L[a,c,b] W[c,i,j,t] R[r,t,s] (scl * v)[b,j,s]   (small_site.h stages 1-3; Engine::chain_heff)
+__device__ __noinline__ void bt_heff(const BatchShape& s, const zc* Lb, const zc* W2, const zc* Rb, const zc* v, double scl, zc* X,
+                        zc* Y, zc* out, zc* tiles) {
+  const int dl = s.dl, d = s.d, dr = s.dr, ml = s.ml, mr = s.mr;
+  const int ddr = d * dr;
+  // X[(a,c)][(j,s)] = sum_b L[(a,c)][b] v[b][(j,s)]
+  wg_gemm<true, false>(dl * ml, ddr, dl, tiles,
+      [&](int m, int k) { return Lb[(long)m * dl + k]; },
+      [&](int k, int n) { const zc z = v[(long)k * ddr + n]; return make_double2(z.x * scl, z.y * scl); },
+      [&](int m, int n, zc z) { X[(long)m * ddr + n] = z; });
+  // Y[a][(i,t)][s] = sum_(c,j) W2[(i,t)][(c,j)] X[a][(c,j)][s]
+  const int kw = ml * d, mw = d * mr;
+  wg_gemm<true, false>(mw, dl * dr, kw, tiles,
+      [&](int m, int k) { return W2[(long)m * kw + k]; },
+      [&](int k, int n) { const int a = n / dr, ss = n - a * dr; return X[((long)a * kw + k) * dr + ss]; },
+      [&](int m, int n, zc z) { const int a = n / dr, ss = n - a * dr; Y[((long)a * mw + m) * dr + ss] = z; });
+  // out[(a,i)][r] = sum_(t,s) Y[(a,i)][(t,s)] R[r][(t,s)]
+  const int kr = mr * dr;
+  wg_gemm<true, true>(dl * d, dr, kr, tiles,
+      [&](int m, int k) { return Y[(long)m * kr + k]; },
+      [&](int k, int n) { return Rb[(long)n * kr + k]; },
+      [&](int m, int n, zc z) { out[(long)m * dr + n] = z; });
+}
+
+// out[a,r] = sum L[a,c,b] (scl * sigma)[b,s] R[r,c,s]   (Engine::chain_keff; no W stage)
+__device__ __noinline__ void bt_keff(int dim, int m, const zc* Lb, const zc* Rb, const zc* v, double scl, zc* X, zc* out, zc* tiles) {
+  wg_gemm<true, false>(dim * m, dim, dim, tiles,
+      [&](int mm, int k) { return Lb[(long)mm * dim + k]; },
+      [&](int k, int n) { const zc z = v[(long)k * dim + n]; return make_double2(z.x * scl, z.y * scl); },
+      [&](int mm, int n, zc z) { X[(long)mm * dim + n] = z; });
+  const int kr = m * dim;
+  wg_gemm<true, true>(dim, dim, kr, tiles,
+      [&](int mm, int k) { return X[(long)mm * kr + k]; },
+      [&](int k, int n) { return Rb[(long)n * kr + k]; },
+      [&](int mm, int n, zc z) { out[(long)mm * dim + n] = z; });
+}
+
+// env'[a,q,r] = sum conj(T)(b,c,a) env[b,p,s] W2e[(q,t)][(c,p)] T(s,t,r)   (Engine::chain_env), T(in, phys, out) =
+// T[in * sTi + phys * sTd + out * sTo]: the site tensor itself (->) or its mirror image (<-) without a copy.
+// env (din, min, din) -> env' (dout, mout, dout).
+__device__ __noinline__ void bt_env(const zc* env, const zc* T, long sTi, long sTd, long sTo, const zc* W2e, int din, int min_, int d,
+                       int dout, int mout, zc* X, zc* Y, zc* out, zc* tiles) {
+  const int nx = min_ * din;
+  // X[(c,a)][(p,s)] = sum_b conj(T(b,c,a)) env[b][(p,s)]
+  wg_gemm<false, false>(d * dout, nx, din, tiles,
+      [&](int m, int k) { const int c = m / dout, a = m - c * dout; const zc z = T[k * sTi + c * sTd + a * sTo]; return make_double2(z.x, -z.y); },
+      [&](int k, int n) { return env[(long)k * nx + n]; },
+      [&](int m, int n, zc z) { X[(long)m * nx + n] = z; });
+  // Y[a][(q,t)][s] = sum_(c,p) W2e[(q,t)][(c,p)] X[c][a][p][s]
+  const int kw = d * min_, mw = mout * d;
+  wg_gemm<true, false>(mw, dout * din, kw, tiles,
+      [&](int m, int k) { return W2e[(long)m * kw + k]; },
+      [&](int k, int n) {
+        const int c = k / min_, p = k - c * min_, a = n / din, ss = n - a * din;
+        return X[(((long)c * dout + a) * min_ + p) * din + ss];
+      },
+      [&](int m, int n, zc z) { const int a = n / din, ss = n - a * din; Y[((long)a * mw + m) * din + ss] = z; });
+  // out[(a,q)][r] = sum_(t,s) Y[(a,q)][(t,s)] T(s,t,r)
+  const int kr = d * din;
+  wg_gemm<true, false>(dout * mout, dout, kr, tiles,
+      [&](int m, int k) { return Y[(long)m * kr + k]; },
+      [&](int k, int n) { const int t = k / din, ss = k - t * din; return T[ss * sTi + t * sTd + n * sTo]; },
+      [&](int m, int n, zc z) { out[(long)m * dout + n] = z; });
+}
+
+// dst = A (M x K) . B (K x N), all row-major, by way of tmp (dst may be A or B): the absorb of a sweep
+__device__ __noinline__ void bt_matmul(const zc* A, const zc* B, zc* tmp, zc* dst, int M, int N, int K, zc* tiles) {
+  wg_gemm<true, false>(M, N, K, tiles,
+      [&](int m, int k) { return A[(long)m * K + k]; },
+      [&](int k, int n) { return B[(long)k * N + n]; },
+      [&](int m, int n, zc z) { tmp[(long)m * N + n] = z; });
+  for (long e = threadIdx.x; e < (long)M * N; e += SS_THREADS) dst[e] = tmp[e];
+  __syncthreads();
+}
+
+// Thin QR of the m x n matrix a(i, j) = src[i * si + j * sj] (m >= n): Q(i, j) -> qdst[i * si + j * sj] (qdst may be src),
+// R(i, j) -> rdst[i * ri + j * rj].  Householder reflections H_j = 1 - gam u u^H with u = x + phase(x_j) |x| e_j, so
+// R_jj = -phase |x|: no sign convention on diag(R) (the gauge of the sweep is free, qr_thin(..., gauge_free)); a zero
+// column gives H_j = 1, so Q is an isometry for rank-deficient input as well.  Wk is the (m x n, row-major) work matrix.
+// Element (i, c) belongs to lane i % 64 of wave c % 8 from the first copy to the last store: besides the column of the
+// current reflector, published by one barrier per column, a thread reads only what it wrote itself.
+__device__ __noinline__ void bt_qr(const zc* src, zc* qdst, long si, long sj, zc* rdst, long ri, long rj, int m, int n, zc* Wk,
+                      const BtSh& sh) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (int c = w; c < n; c += SS_WAVES)
+    for (int i = lane; i < m; i += 64) Wk[(long)i * n + c] = src[i * si + c * sj];
+  for (int j = 0; j < n; ++j) {
+    if (w == j % SS_WAVES) {  // the owner wave of column j: its norm below the diagonal, the reflector's scalars
+      double s = 0.0;
+      zc ajj = make_double2(0.0, 0.0);
+      for (int i = lane; i < m; i += 64)
+        if (i >= j) {
+          const zc z = Wk[(long)i * n + j];
+          s += z.x * z.x + z.y * z.y;
+          if (i == j) ajj = z;
+        }
+      s = __shfl(wave_sum64(s), 0, 64);
+      ajj.x = __shfl(ajj.x, j & 63, 64);
+      ajj.y = __shfl(ajj.y, j & 63, 64);
+      const double nx = sqrt(s), aa = sqrt(ajj.x * ajj.x + ajj.y * ajj.y);
+      zc ph = make_double2(1.0, 0.0);
+      if (aa > 0.0) ph = make_double2(ajj.x / aa, ajj.y / aa);
+      if (lane == 0) {
+        if (nx > 1e-150) {
+          sh.udiag[j] = make_double2(ajj.x + ph.x * nx, ajj.y + ph.y * nx);
+          sh.gam[j] = 1.0 / (nx * (nx + aa));
+          sh.rdiag[j] = make_double2(-ph.x * nx, -ph.y * nx);
+        } else {
+          sh.udiag[j] = ajj;
+          sh.gam[j] = 0.0;
+          sh.rdiag[j] = ajj;
+        }
+      }
+    }
+    __syncthreads();
+    const double gam = sh.gam[j];
+    if (gam == 0.0) continue;
+    const zc ud = sh.udiag[j];
+    int c = j + 1 + ((w - (j + 1)) % SS_WAVES + SS_WAVES) % SS_WAVES;  // first column right of j that this wave owns
+    for (; c < n; c += SS_WAVES) {
+      double dr_ = 0.0, di_ = 0.0;
+      for (int i = lane; i < m; i += 64)
+        if (i >= j) {
+          const zc u = i == j ? ud : Wk[(long)i * n + j];
+          const zc x = Wk[(long)i * n + c];
+          dr_ += u.x * x.x + u.y * x.y;  // conj(u) x
+          di_ += u.x * x.y - u.y * x.x;
+        }
+      dr_ = __shfl(wave_sum64(dr_), 0, 64) * gam;
+      di_ = __shfl(wave_sum64(di_), 0, 64) * gam;
+      for (int i = lane; i < m; i += 64)
+        if (i >= j) {
+          const zc u = i == j ? ud : Wk[(long)i * n + j];
+          zc x = Wk[(long)i * n + c];
+          x.x -= u.x * dr_ - u.y * di_;
+          x.y -= u.x * di_ + u.y * dr_;
+          Wk[(long)i * n + c] = x;
+        }
+    }
+  }
+  __syncthreads();
+  // Q e_c = H_0 ... H_c e_c (H_j e_c = e_c for j > c), column c in place in qdst
+  for (int c = w; c < n; c += SS_WAVES) {
+    for (int i = lane; i < m; i += 64) qdst[i * si + c * sj] = make_double2(i == c ? 1.0 : 0.0, 0.0);
+    for (int j = c; j >= 0; --j) {
+      const double gam = sh.gam[j];
+      if (gam == 0.0) continue;
+      const zc ud = sh.udiag[j];
+      double dr_ = 0.0, di_ = 0.0;
+      for (int i = lane; i < m; i += 64)
+        if (i >= j) {
+          const zc u = i == j ? ud : Wk[(long)i * n + j];
+          const zc x = qdst[i * si + c * sj];
+          dr_ += u.x * x.x + u.y * x.y;
+          di_ += u.x * x.y - u.y * x.x;
+        }
+      dr_ = __shfl(wave_sum64(dr_), 0, 64) * gam;
+      di_ = __shfl(wave_sum64(di_), 0, 64) * gam;
+      for (int i = lane; i < m; i += 64)
+        if (i >= j) {
+          const zc u = i == j ? ud : Wk[(long)i * n + j];
+          zc x = qdst[i * si + c * sj];
+          x.x -= u.x * dr_ - u.y * di_;
+          x.y -= u.x * di_ + u.y * dr_;
+          qdst[i * si + c * sj] = x;
+        }
+    }
+  }
+  for (int t = tid; t < n * n; t += SS_THREADS) {
+    const int i = t / n, c = t - i * n;
+    zc z = make_double2(0.0, 0.0);
+    if (c > i) z = Wk[(long)i * n + c];
+    else if (c == i) z = sh.rdiag[i];
+    rdst[i * ri + c * rj] = z;
+  }
+  __syncthreads();
+}
+
+// the operator of a local exponential: H_eff of a site (W2 != nullptr) or K_eff of a bond (dim x dim, MPO bond m)
+struct BtOp {
+  BatchShape s;
+  const zc *Lb, *W2, *Rb;
+  int dim, m;
+  zc *X, *Y, *tiles;
+};
+__device__ __forceinline__ void bt_apply(const BtOp& o, const zc* vin, double scl, zc* out) {
+  if (o.W2) bt_heff(o.s, o.Lb, o.W2, o.Rb, vin, scl, o.X, o.Y, out, o.tiles);
+  else bt_keff(o.dim, o.m, o.Lb, o.Rb, vin, scl, o.X, out, o.tiles);
+}
+// x <- exp(scale * Op) x for the operator op (bt_apply: out = Op (scl * vin), ends with a barrier):
+// short_iterative_lanczos / _arnoldi as k_small_site's EXP mode runs them, with one workgroup owning the whole vector.
+// The basis is kept unnormalised (u_j, factors 1 / beta_j applied on the fly) in U[j * N ...), j >= 1; slot 0 of U holds
+// the new vector until its norm is known (conserve_norm).  Element e belongs to thread e % 512 throughout.
+__device__ __noinline__ int bt_exp(const BtOp& op, zc* x, zc* U, long N, int* kprev_p, zc scale, zc shift, const SmallExp& ex,
+                                   const BtSh& sh, long long* stats, int stat_slot, long long flops_per_apply) {
+  const int tid = threadIdx.x;
+  const bool lanczos = ex.integrator == MITDVP_LANCZOS;
+  const bool cn = ex.conserve_norm != 0;
+  const bool add_shift = shift.x != 0.0 || shift.y != 0.0;
+  const long nsize = N;
+  const int ndim = (int)min((long)ex.max_krylov, nsize);
+  const int k_prev = __hip_atomic_load(kprev_p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  const int n_warm = ss_n_warm(k_prev, nsize);
+  zc* alpha = sh.alpha; zc* coef = sh.coef; zc* cprev = sh.cprev; zc* hess = sh.hess;
+  double* beta = sh.beta; double* invb = sh.invb; int* ctl = sh.ctl;
+
+  auto basis = [&](int j, long e) -> zc {
+    zc z = j == 0 ? x[e] : U[(size_t)j * N + e];
+    const double f = invb[j];
+    z.x *= f; z.y *= f;
+    return z;
+  };
+  auto account = [&](int k, int napply) {
+    if (tid == 0) {
+      __hip_atomic_store(kprev_p, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      stats[stat_slot] += napply;
+      stats[2 + stat_slot] += (long long)napply * flops_per_apply;
+    }
+  };
+
+  // ---- _normalize (_integrator.py:189-203) ---------------------------------------------
+  double beta0 = 1.0;
+  if (!cn) {
+    double s[1] = {0.0};
+    for (long e = tid; e < N; e += SS_THREADS) { const zc z = x[e]; s[0] += z.x * z.x + z.y * z.y; }
+    wg_reduce(s, sh);
+    beta0 = sqrt(sh.red[0]);
+    if (beta0 == 0.0) return SS_EZERO;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    invb[0] = 1.0 / beta0;
+    ctl[3] = 0;  // next_unread
+  }
+  __syncthreads();
+
+  bool have_prev = false;
+  int prev_len = 0;
+  int napply = 0;
+  for (int l = 0; l < ndim; ++l) {
+    zc* un = U + (size_t)(l + 1) * N;
+    bt_apply(op, l == 0 ? x : U + (size_t)l * N, invb[l], un);
+    napply += 1;
+    if (add_shift)  // (Op + shift) v_l: the projections below see the scalar term too
+      for (long e = tid; e < N; e += SS_THREADS) {
+        zc v = un[e];
+        const zc vl = basis(l, e);
+        v.x += shift.x * vl.x - shift.y * vl.y;
+        v.y += shift.x * vl.y + shift.y * vl.x;
+        un[e] = v;
+      }
+    // ---- projections <v_j | Op v_l>: Lanczos one (j = 0 reference, j = l orthodox), Arnoldi j = 0 .. l ----
+    const int jlo = lanczos ? (ex.variant == 0 ? 0 : l) : 0;
+    const int jhi = lanczos ? jlo : l;
+    const int nd = jhi - jlo + 1;
+    for (int j0 = 0; j0 < nd; j0 += 4) {
+      double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      for (long e = tid; e < N; e += SS_THREADS) {
+        const zc v = un[e];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j0 + j < nd) {
+            const zc b = basis(jlo + j0 + j, e);  // conj(b) * v
+            acc[2 * j] += b.x * v.x + b.y * v.y;
+            acc[2 * j + 1] += b.x * v.y - b.y * v.x;
+          }
+      }
+      wg_reduce(acc, sh);
+      if (tid == 0)
+        for (int j = 0; j < 4 && j0 + j < nd; ++j) {
+          const zc z = make_double2(sh.red[2 * j], sh.red[2 * j + 1]);
+          if (lanczos) alpha[l] = z;
+          else hess[(j0 + j) * MAXK + l] = z;
+        }
+      __syncthreads();
+    }
+    // ---- orthogonalise, norm (_integrator.py:556-562; _orth_step_np :247-260) ---------------------
+    {
+      double s[1] = {0.0};
+      const double bprev = l > 0 ? beta[l - 1] : 0.0;
+      for (long e = tid; e < N; e += SS_THREADS) {
+        const zc vl = basis(l, e);
+        zc u = un[e];
+        if (lanczos) {
+          const zc al = alpha[l];
+          u.x -= al.x * vl.x - al.y * vl.y;
+          u.y -= al.x * vl.y + al.y * vl.x;
+          if (l > 0) {
+            const zc vm = basis(l - 1, e);
+            u.x -= bprev * vm.x;
+            u.y -= bprev * vm.y;
+          }
+        } else {
+          for (int j = 0; j <= l; ++j) {
+            const zc h = hess[j * MAXK + l];
+            const zc vj = j == l ? vl : basis(j, e);
+            u.x -= h.x * vj.x - h.y * vj.y;
+            u.y -= h.x * vj.y + h.y * vj.x;
+          }
+        }
+        un[e] = u;
+        s[0] += u.x * u.x + u.y * u.y;
+      }
+      wg_reduce(s, sh);
+    }
+    if (tid == 0) ss_decide(l, nsize, ndim, n_warm, lanczos, sh.red[0], beta, invb, hess, ctl);
+    __syncthreads();
+    int act = ctl[1];
+    const int k = ctl[2];
+    if (act == 0) continue;
+
+    // ---- coef = exp(scale * T_k) e_0 ------------------------------------------------------------
+    if (!ss_try_tridiag(lanczos, k, alpha, beta, scale, coef)) {
+      zc* Tm = sh.mats;
+      zc* M2 = Tm + MAXK * MAXK;
+      zc* M3 = M2 + MAXK * MAXK;
+      zc* M4 = M3 + MAXK * MAXK;
+      zc* Pm = M4 + MAXK * MAXK;
+      zc* Qm = Pm + MAXK * MAXK;
+      ss_fill_T(Tm, k, lanczos, alpha, beta, hess, scale);
+      ss_expm_col0(Tm, M2, M3, M4, Pm, Qm, k, coef, sh.wsh);
+    }
+    if (act == 1) {
+      if (have_prev) {  // || psi_k - psi_{k-1} ||  (:644-652)
+        double s[1] = {0.0};
+        for (long e = tid; e < N; e += SS_THREADS) {
+          double re = 0.0, im = 0.0;
+          for (int j = 0; j < k; ++j) {
+            zc dd = coef[j];
+            if (j < prev_len) { dd.x -= cprev[j].x; dd.y -= cprev[j].y; }
+            const zc vj = basis(j, e);
+            re += dd.x * vj.x - dd.y * vj.y;
+            im += dd.x * vj.y + dd.y * vj.x;
+          }
+          s[0] += re * re + im * im;
+        }
+        wg_reduce(s, sh);
+        if (sqrt(sh.red[0]) < ex.thresh) act = 2;
+      }
+      if (act == 1) {
+        __syncthreads();
+        if (tid < k) cprev[tid] = coef[tid];
+        __syncthreads();
+        have_prev = true;
+        prev_len = k;
+        continue;
+      }
+    }
+    // ---- act == 2: psi = sum_j c_j v_j, renormalised or rescaled (_rescale, :206-213) ------------
+    {
+      const double cs_ = cn ? 1.0 : beta0;
+      double s[1] = {0.0};
+      for (long e = tid; e < N; e += SS_THREADS) {
+        double re = 0.0, im = 0.0;
+        for (int j = 0; j < k; ++j) {
+          const zc dd = make_double2(coef[j].x * cs_, coef[j].y * cs_);
+          const zc vj = basis(j, e);
+          re += dd.x * vj.x - dd.y * vj.y;
+          im += dd.x * vj.y + dd.y * vj.x;
+        }
+        if (cn) U[e] = make_double2(re, im);
+        else x[e] = make_double2(re, im);
+        s[0] += re * re + im * im;
+      }
+      if (cn) {
+        wg_reduce(s, sh);
+        const double inv = 1.0 / sqrt(sh.red[0]);
+        for (long e = tid; e < N; e += SS_THREADS) {  // the same thread wrote U[e] above
+          zc z = U[e];
+          z.x *= inv; z.y *= inv;
+          x[e] = z;
+        }
+      }
+      account(k, napply);
+      __syncthreads();
+      return SS_OK;
+    }
+  }
+  account(ndim, napply);  // "... is not converged in N basis. Try shorter time interval." (:430, :653)
+  __syncthreads();
+  return SS_ENOTCONV;
+}
+
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 256 VGPRs, occupancy 2 waves
+// per SIMD (one workgroup per compute unit), 56 544 bytes of LDS, and 816 bytes of private memory per lane: the kernel
+// body SPILLS 93 vector and 31 scalar registers around the calls of its stage functions (a few times per site of the
+// sweep), and the argument blocks those functions take by reference live there too.  The stages are separate
+// (non-inlined) device functions because inlined into one body the spills sat inside the product loops (119 VGPRs, 928
+// bytes); the product functions bt_heff / bt_keff / bt_env / bt_matmul themselves use 178-196 VGPRs and no private
+// memory, bt_exp 254 VGPRs and 16 bytes.  This misses the "no spills" aim; what it costs is measured, not guessed:
+// profiles/batch_probe.txt and DESIGN.md section 7.3.
+__global__ __launch_bounds__(SS_THREADS) void k_batch_sweep(BatchArgs g) {
+  __shared__ __attribute__((aligned(16))) zc s_mats[6 * MAXK * MAXK];
+  __shared__ zc s_z[3 * MAXK + (MAXK + 1) * MAXK + 2 * BATCH_MAX_BOND];
+  __shared__ double s_d[SS_WAVES * SS_PAYMAX + 8 + 2 * MAXK + 1 + BATCH_MAX_BOND];
+  __shared__ int s_ctl[4];
+  BtSh sh;
+  sh.mats = s_mats;
+  sh.alpha = s_z; sh.coef = sh.alpha + MAXK; sh.cprev = sh.coef + MAXK; sh.hess = sh.cprev + MAXK;
+  sh.udiag = sh.hess + (MAXK + 1) * MAXK; sh.rdiag = sh.udiag + BATCH_MAX_BOND;
+  sh.wsh = s_d; sh.red = sh.wsh + SS_WAVES * SS_PAYMAX; sh.beta = sh.red + 8; sh.invb = sh.beta + MAXK;
+  sh.gam = sh.invb + MAXK + 1;
+  sh.ctl = s_ctl;
+
+  const int r = blockIdx.x, tid = threadIdx.x, L = g.L;
+  if (g.status[r] != SS_OK) return;  // a replica that failed in an earlier launch of the call does no more work
+  void* const* tab = g.ptrs + (size_t)r * g.ptr_stride;
+  zc* const* site = reinterpret_cast<zc* const*>(tab);
+  zc* const* envL = reinterpret_cast<zc* const*>(tab + L);
+  zc* const* envR = reinterpret_cast<zc* const*>(tab + 2 * L + 1);
+  const zc* const* w2l = reinterpret_cast<const zc* const*>(tab + 3 * L + 2);
+  const zc* const* w2el = reinterpret_cast<const zc* const*>(tab + 4 * L + 2);
+  const zc* const* w2er = reinterpret_cast<const zc* const*>(tab + 5 * L + 2);
+  zc* scr = reinterpret_cast<zc*>(tab[6 * L + 2]);
+  zc* sig = scr + g.plan.o_sig;
+  zc* spare = scr + g.plan.o_spare;
+  zc* work = scr + g.plan.o_work;
+  zc* X = scr + g.plan.o_x;
+  zc* Y = scr + g.plan.o_y;
+  zc* U = scr + g.plan.o_u;
+  int* kprev = g.kprev + (size_t)r * L;
+  long long* stats = g.stats + (size_t)r * 4;
+  const zc shift = g.shift[r];
+  const zc sc_site = make_double2(g.site_re, g.site_im), sc_bond = make_double2(g.bond_re, g.bond_im);
+  const bool fwd = g.forward != 0;
+  zc* tiles = sh.mats;
+
+  int rc = SS_OK;
+  for (int step = 0; step < L; ++step) {
+    const int p = fwd ? step : L - 1 - step;
+    const BatchShape s = g.shp[p];
+    const int dl = s.dl, d = s.d, dr = s.dr;
+    const long N = (long)dl * d * dr;
+    {  // 1. exp(scale * H_eff) on the centre tensor
+      const zc* Lb = envL[p];
+      const zc* Rb = envR[p + 1];
+      const zc* W2 = w2l[p];
+      const long long fl = (long long)(8.0 * ((double)dl * dl * s.ml * d * dr + (double)dl * dr * s.ml * s.mr * d * d +
+                                              (double)dl * dr * dr * s.mr * d));
+      const BtOp op{s, Lb, W2, Rb, 0, 0, X, Y, tiles};
+      rc = bt_exp(op, site[p], U, N, kprev + p, sc_site, shift, g.e, sh, stats, 0, fl);
+    }
+    if (rc != SS_OK || step == L - 1) break;
+    if (fwd) {
+      // 2. Psi2Asigma: A in place of Psi, sigma (dr x dr)
+      bt_qr(site[p], site[p], dr, 1, sig, dr, 1, dl * d, dr, work, sh);
+      // 3. L[p + 1]
+      bt_env(envL[p], site[p], (long)d * dr, dr, 1, w2el[p], dl, s.ml, d, dr, s.mr, X, Y, envL[p + 1], tiles);
+      // 4. exp(scale * K_eff) on sigma
+      const zc* Lb = envL[p + 1];
+      const zc* Rb = envR[p + 1];
+      const int m = s.mr;
+      const BtOp op{s, Lb, nullptr, Rb, dr, m, X, Y, tiles};
+      rc = bt_exp(op, sig, U, (long)dr * dr, kprev + p, sc_bond, shift, g.e, sh, stats, 1, (long long)(16.0 * (double)m * dr * dr * dr));
+      if (rc != SS_OK) break;
+      // 5. Psi(p + 1) = sigma . B(p + 1)
+      const BatchShape q = g.shp[p + 1];
+      const int nn = q.d * q.dr;
+      zc* nxt = site[p + 1];
+      bt_matmul(sig, nxt, spare, nxt, dr, nn, dr, tiles);
+    } else {
+      // 2. Psi2sigmaB: Psi^T = Q R  ->  B = Q^T in place of Psi, sigma = R^T (dl x dl)
+      const int mq = d * dr;
+      bt_qr(site[p], site[p], 1, mq, sig, 1, dl, mq, dl, work, sh);
+      // 3. R[p] from the mirror image of B (dr, d, dl), read in place
+      bt_env(envR[p + 1], site[p], 1, dr, (long)d * dr, w2er[p], dr, s.mr, d, dl, s.ml, X, Y, envR[p], tiles);
+      // 4. exp(scale * K_eff) on sigma
+      const zc* Lb = envL[p];
+      const zc* Rb = envR[p];
+      const int m = s.ml;
+      const BtOp op{s, Lb, nullptr, Rb, dl, m, X, Y, tiles};
+      rc = bt_exp(op, sig, U, (long)dl * dl, kprev + p, sc_bond, shift, g.e, sh, stats, 1, (long long)(16.0 * (double)m * dl * dl * dl));
+      if (rc != SS_OK) break;
+      // 5. Psi(p - 1) = A(p - 1) . sigma
+      const BatchShape q = g.shp[p - 1];
+      const int mm_ = q.dl * q.d;
+      zc* prv = site[p - 1];
+      bt_matmul(prv, sig, spare, prv, mm_, dl, dl, tiles);
+    }
+  }
+  if (rc != SS_OK && tid == 0) g.status[r] = rc;
+}
+
+}  // namespace
+
+bool batch_plan(const BatchShape* shp, int L, BatchPlan& plan, std::string& why) {
+  plan = BatchPlan{};
+  for (int p = 0; p < L; ++p) {
+    const BatchShape& s = shp[p];
+    const long n = (long)s.dl * s.d * s.dr;
+    const std::string at = "batch: site " + std::to_string(p) + " (" + std::to_string(s.dl) + ", " + std::to_string(s.d) + ", " +
+                           std::to_string(s.dr) + "), MPO bonds (" + std::to_string(s.ml) + ", " + std::to_string(s.mr) + "): ";
+    if (s.dl < 1 || s.d < 1 || s.dr < 1 || s.ml < 1 || s.mr < 1) { why = at + "bad shape"; return false; }
+    if (n > BATCH_MAX_SITE) {
+      why = at + "the site tensor has " + std::to_string(n) + " elements, the batched kernel takes at most " + std::to_string(BATCH_MAX_SITE);
+      return false;
+    }
+    if (s.ml > BATCH_MAX_MPO || s.mr > BATCH_MAX_MPO) {
+      why = at + "the batched kernel takes MPO bonds of at most " + std::to_string(BATCH_MAX_MPO);
+      return false;
+    }
+    if (s.dl > BATCH_MAX_BOND || s.dr > BATCH_MAX_BOND) {
+      why = at + "the batched kernel takes bonds of at most " + std::to_string(BATCH_MAX_BOND);
+      return false;
+    }
+    if ((p + 1 < L && (long)s.dl * s.d < s.dr) || (p > 0 && (long)s.d * s.dr < s.dl)) {
+      why = at + "a bond is wider than the row space it is split from (the gauge move needs dl * d >= dr and d * dr >= dl)";
+      return false;
+    }
+    const long mm = std::max(s.ml, s.mr), dd = std::max(s.dl, s.dr);
+    plan.max_site = std::max(plan.max_site, n);
+    plan.max_bond = std::max(plan.max_bond, dd * dd);
+    // X / Y of an H_eff apply (ml N, mr N), of a K_eff apply (m D^2) and of an environment update (d D^2 m each)
+    plan.nx = std::max(plan.nx, std::max(mm * n, mm * dd * dd));
+    plan.ny = std::max(plan.ny, mm * n);
+  }
+  size_t o = 0;
+  plan.o_sig = o; o += (size_t)plan.max_bond;
+  plan.o_spare = o; o += (size_t)plan.max_site;
+  plan.o_work = o; o += (size_t)plan.max_site;
+  plan.o_x = o; o += (size_t)plan.nx;
+  plan.o_y = o; o += (size_t)plan.ny;
+  plan.o_u = o; o += (size_t)MAXK * (size_t)std::max(plan.max_site, plan.max_bond);
+  plan.total = o;
+  return true;
+}
+
+void batch_sweep_launch(hipStream_t st, const BatchArgs& a, int nrep) {
+  if (nrep < 1 || a.L < 1) throw ArgError("batch: nothing to launch");
+  if (a.e.max_krylov < 1 || a.e.max_krylov > MAXK - 1) throw ArgError("batch: max_krylov must be in [1, 20]");
+  hipLaunchKernelGGL(k_batch_sweep, dim3(nrep), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace mitdvp

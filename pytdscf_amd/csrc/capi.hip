@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "engine_batch.h"
 #include "engine_internal.h"
 #include "engine_krylov.inc"
 
@@ -186,6 +187,52 @@ int mitdvp_ensemble_step(mitdvp_engine** hs, int n, double dt, int nsteps, int* 
   }
   return first;
 }
+// ---- batched trajectories (engine_batch.hip, batch_site.hip) ----
+namespace {
+int batch_finish(mitdvp_batch* b, const std::vector<int>& st, int* statuses) {
+  int first = MITDVP_OK;
+  for (size_t i = 0; i < st.size(); ++i) {
+    int rc = MITDVP_OK;
+    if (st[i] != mitdvp::SS_OK) {
+      rc = st[i] == mitdvp::SS_ENOTCONV ? MITDVP_ENOTCONV : MITDVP_EINVAL;
+      b->hs[i]->err = b->b->status_message(st[i]);
+      if (first == MITDVP_OK) first = rc;
+    }
+    if (statuses) statuses[i] = rc;
+  }
+  return first;
+}
+}  // namespace
+int mitdvp_batch_create(mitdvp_engine** hs, int n, mitdvp_batch** out) {
+  if (!hs || !out || n < 1) { g_err = "mitdvp_batch_create: bad arguments"; return MITDVP_EINVAL; }
+  *out = nullptr;
+  for (int i = 0; i < n; ++i)
+    if (!hs[i] || !hs[i]->e) { g_err = "mitdvp_batch_create: null engine"; return MITDVP_EINVAL; }
+  auto* b = new mitdvp_batch();
+  const int rc = guard(nullptr, [&] {
+    std::vector<mitdvp::Engine*> es;
+    for (int i = 0; i < n; ++i) { es.push_back(hs[i]->e.get()); b->hs.push_back(hs[i]); }
+    b->b.reset(new mitdvp::Batch(es));
+  });
+  if (rc != MITDVP_OK) { delete b; return rc; }
+  *out = b;
+  return MITDVP_OK;
+}
+int mitdvp_batch_step(mitdvp_batch* b, double dt_au, int nsteps, int* statuses) {
+  if (!b || !b->b) { g_err = "null handle"; return MITDVP_EINVAL; }
+  std::vector<int> st((size_t)b->b->size(), 0);
+  const int rc = guard(nullptr, [&] { b->b->step(dt_au, nsteps, st.data()); });
+  if (rc != MITDVP_OK) return rc;
+  return batch_finish(b, st, statuses);
+}
+int mitdvp_batch_sweep(mitdvp_batch* b, double dt_au, int forward, int* statuses) {
+  if (!b || !b->b) { g_err = "null handle"; return MITDVP_EINVAL; }
+  std::vector<int> st((size_t)b->b->size(), 0);
+  const int rc = guard(nullptr, [&] { b->b->sweep(dt_au, forward != 0, st.data()); });
+  if (rc != MITDVP_OK) return rc;
+  return batch_finish(b, st, statuses);
+}
+void mitdvp_batch_destroy(mitdvp_batch* b) { delete b; }
 int mitdvp_invalidate_env(mitdvp_engine* h) { ENG_CALL(h, h->e->invalidate_env()); }
 int mitdvp_replace_site(mitdvp_engine* h, int isite, const double* reim, int gauge) {
   ENG_CALL(h, { NEED(reim); h->e->replace_site(isite, reim, gauge); });

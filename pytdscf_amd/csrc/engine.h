@@ -127,6 +127,7 @@ struct PhaseTimer {
 };
 
 class SiteShard;
+class Batch;
 // compute-unit ranges of CU-masked engines (engine_small.hip): overlapping claims throw ArgError
 void cu_range_claim(int device, int first, int count);
 void cu_range_release(int device, int first, int count);
@@ -134,6 +135,7 @@ int cu_ranges_claimed(int device);
 
 class Engine {
   friend class SiteShard;  // shard.hip: the junction update works on the tensors and blocks of two engines in place
+  friend class Batch;      // engine_batch.hip: borrows engines, steps their chains with one launch per half-sweep
 
  public:
   explicit Engine(const mitdvp_config& cfg);

@@ -1,0 +1,307 @@
+// engine_batch.hip -- batched trajectories on the host side: a Batch borrows B ordinary engines (each owns its tensors and
+// its own MPO), owns the pointer tables, the status words and the per-replica scratch of k_batch_sweep (batch_site.hip),
+// and steps all replicas with ONE launch per half-sweep.  No host threads, no compute-unit masks, no persistent-launch
+// admission: the kernel's workgroups never wait for each other.  Host waits of a call: ONE stream synchronisation, behind
+// the copy of the status words at its end (plain hipStreamSynchronize: the library's wait helper, wait_published, spins on
+// a mapped word, which this path has none of); besides it only what the engines' own preparation does on first use
+// (right-environment build, workspace growth) and one synchronisation when the scratch area has to grow.
+#include "engine_batch.h"
+#include "capi_internal.h"
+
+#include <algorithm>
+#include <cstring>
+
+mitdvp_batch::mitdvp_batch() = default;
+mitdvp_batch::~mitdvp_batch() = default;
+
+namespace mitdvp {
+
+namespace {
+template <class T>
+void dev_alloc(T*& p, size_t n) {
+  HIP_CHECK(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)));
+}
+}  // namespace
+
+std::vector<BatchShape> Batch::shapes_of(Engine& e) {
+  std::vector<BatchShape> s((size_t)e.L_);
+  auto it = e.ops_.find(0);
+  for (int p = 0; p < e.L_; ++p) {
+    if (!e.site_[p].p) throw ArgError("batch: a replica has no tensor at site " + std::to_string(p));
+    if (it == e.ops_.end() || !it->second.sites[p].set) throw ArgError("batch: a replica has no MPO core at site " + std::to_string(p));
+    const MpoSite& w = it->second.sites[p];
+    if (w.d != e.dd_[p]) throw ArgError("MPO physical dimension differs from the site tensor's");
+    s[p] = BatchShape{e.dl_[p], e.dd_[p], e.dr_[p], w.ml, w.mr};
+  }
+  return s;
+}
+
+// everything mitdvp_batch_create promises to check; touches no engine state
+void Batch::validate() {
+  const int n = (int)eng_.size();
+  Engine& e0 = *eng_[0];
+  for (int i = 0; i < n; ++i) {
+    Engine& e = *eng_[i];
+    const std::string who = "batch: replica " + std::to_string(i) + " ";
+    for (int k = 0; k < i; ++k)
+      if (eng_[k] == eng_[i]) throw ArgError("batch: the same engine is listed twice");
+    if (e.cfg.device != e0.cfg.device) throw ArgError(who + "is on another device");
+    if (e.cfg.cu_count != 0) throw ArgError(who + "is confined to a compute-unit range (cu_count != 0): the batched kernel runs on the whole device");
+    if (e.ms_) throw ArgError(who + "has several electronic states");
+    if (e.adaptive_) throw ArgError(who + "has an adaptive bond dimension");
+    if (e.segment_) throw ArgError(who + "is a segment of a site-sharded chain");
+    if (e.nranks_ != 1) throw ArgError(who + "is bond-sharded over several GPUs");
+    if (e.cfg.relax != 0 && e.cfg.relax != 1) throw ArgError(who + "uses improved relaxation (relax must be 0 or 1)");
+    if (!e.gates_.empty() || !e.kraus_.empty()) throw ArgError(who + "has gates or Kraus maps set");
+    if (e.sw_next_ >= 0) throw ArgError(who + "has a half-sweep in parts in progress");
+    if (e.L_ != e0.L_) throw ArgError(who + "has another number of sites");
+    if (e.cfg.integrator != e0.cfg.integrator || e.cfg.lanczos_variant != e0.cfg.lanczos_variant ||
+        e.cfg.conserve_norm != e0.cfg.conserve_norm || e.cfg.thresh != e0.cfg.thresh || e.cfg.max_krylov != e0.cfg.max_krylov ||
+        e.cfg.relax != e0.cfg.relax)
+      throw ArgError(who + "differs from replica 0 in integrator, lanczos_variant, conserve_norm, thresh, max_krylov or relax");
+  }
+  if (e0.cfg.max_krylov < 1 || e0.cfg.max_krylov > MAXK - 1) throw ArgError("batch: max_krylov must be in [1, 20]");
+  std::vector<BatchShape> s0 = shapes_of(e0);
+  for (int i = 1; i < n; ++i) {
+    std::vector<BatchShape> s = shapes_of(*eng_[i]);
+    for (int p = 0; p < e0.L_; ++p) {
+      if (s[p].dl != s0[p].dl || s[p].d != s0[p].d || s[p].dr != s0[p].dr)
+        throw ArgError("batch: replica " + std::to_string(i) + " differs from replica 0 in the shape of site " + std::to_string(p));
+      if (s[p].ml != s0[p].ml || s[p].mr != s0[p].mr)
+        throw ArgError("batch: replica " + std::to_string(i) + " differs from replica 0 in the MPO bonds of site " + std::to_string(p));
+    }
+  }
+  for (int p = 0; p + 1 < e0.L_; ++p)
+    if (s0[p].dr != s0[p + 1].dl) throw ArgError("bond dimension mismatch between neighbouring sites");
+  for (int p = 0; p + 1 < e0.L_; ++p)  // the kernel writes block p + 1 with mr[p]; the buffer is sized with ml[p + 1]
+    if (s0[p].mr != s0[p + 1].ml)
+      throw ArgError("batch: MPO bond mismatch between sites " + std::to_string(p) + " and " + std::to_string(p + 1));
+  if (s0[0].ml != 1 || s0[e0.L_ - 1].mr != 1) throw ArgError("batch: the outer MPO bonds must be 1");
+  if (s0[0].dl != 1 || s0[e0.L_ - 1].dr != 1) throw ArgError("open boundary bonds must be 1");
+  BatchPlan pl;
+  std::string why;
+  if (!batch_plan(s0.data(), e0.L_, pl, why)) throw ArgError(why);
+  if (s0.size() != shp_.size() || std::memcmp(s0.data(), shp_.data(), s0.size() * sizeof(BatchShape)) != 0) {
+    shp_ = s0;
+    shapes_dirty_ = true;
+  }
+  plan_ = pl;
+}
+
+Batch::Batch(const std::vector<Engine*>& engines) : eng_(engines) {
+  if (eng_.empty()) throw ArgError("batch: no replicas");
+  for (Engine* e : eng_)
+    if (!e) throw ArgError("batch: null engine");
+  validate();
+  device_ = eng_[0]->cfg.device;
+  L_ = eng_[0]->L_;
+  HIP_CHECK(hipSetDevice(device_));
+  HIP_CHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
+  const size_t n = eng_.size();
+  ev_.assign(n, nullptr);
+  for (size_t i = 0; i < n; ++i) HIP_CHECK(hipEventCreateWithFlags(&ev_[i], hipEventDisableTiming));
+  dev_alloc(d_ptrs_, n * ptrs_per_replica());
+  dev_alloc(d_shp_, (size_t)L_);
+  dev_alloc(d_shift_, n);
+  dev_alloc(d_kprev_, n * L_);
+  dev_alloc(d_status_, n);
+  dev_alloc(d_stats_, n * 4);
+}
+
+Batch::~Batch() {
+  (void)hipSetDevice(device_);
+  if (st_) (void)hipStreamSynchronize(st_);
+  for (hipEvent_t e : ev_)
+    if (e) (void)hipEventDestroy(e);
+  if (d_ptrs_) (void)hipFree(d_ptrs_);
+  if (d_shp_) (void)hipFree(d_shp_);
+  if (d_shift_) (void)hipFree(d_shift_);
+  if (d_kprev_) (void)hipFree(d_kprev_);
+  if (d_status_) (void)hipFree(d_status_);
+  if (d_stats_) (void)hipFree(d_stats_);
+  if (d_scratch_) (void)hipFree(d_scratch_);
+  if (st_) (void)hipStreamDestroy(st_);
+}
+
+// Brings every engine to the state a half-sweep in direction `forward` starts from, makes the block buffers of every
+// bond exist, and rebuilds the device tables when a shape or a buffer moved since the last call.
+void Batch::prepare(bool forward) {
+  const size_t n = eng_.size();
+  const int begin = forward ? 0 : L_ - 1;
+  // what depends on the engines' state is checked for ALL of them before any of them is touched
+  for (size_t i = 0; i < n; ++i) {
+    const Engine& e = *eng_[i];
+    const std::string who = "batch: replica " + std::to_string(i) + ": ";
+    if (e.center_ != begin) throw ArgError(who + "sweep must start at the centre (Psi) site");
+    for (int p = 0; p < L_; ++p) {
+      const int want = p < begin ? MITDVP_GAUGE_A : (p == begin ? MITDVP_GAUGE_PSI : MITDVP_GAUGE_B);
+      if (e.gauge_[p] != want) throw ArgError(who + "the chain is not canonical around the centre site");
+    }
+  }
+  for (size_t i = 0; i < n; ++i) {
+    Engine& e = *eng_[i];
+    e.require_ready();
+    e.ss_check();
+    if (L_ > 1) {
+      if (forward) e.build_right_envs();
+      else e.build_left_envs();
+    }
+    for (int b = 1; b < L_; ++b) {  // bond b is left of site b: blocks (dl[b], ml[b], dl[b])
+      const size_t need = (size_t)shp_[b].dl * shp_[b].ml * shp_[b].dl;
+      if (!e.envL_[b].p || e.envL_[b].n < need) { e.pool_put(std::move(e.envL_[b])); e.envL_[b] = e.pool_get(need); e.envL_ok_[b] = 0; }
+      if (!e.envR_[b].p || e.envR_[b].n < need) { e.pool_put(std::move(e.envR_[b])); e.envR_[b] = e.pool_get(need); e.envR_ok_[b] = 0; }
+    }
+    e.ss_pull_kprev();
+  }
+  // scratch (grows only when the shapes or the number of replicas grew: the one other synchronisation)
+  const size_t per = (plan_.total + 15) / 16 * 16;
+  if (per * n > scratch_elems_) {
+    HIP_CHECK(hipStreamSynchronize(st_));
+    if (d_scratch_) (void)hipFree(d_scratch_);
+    d_scratch_ = nullptr;
+    dev_alloc(d_scratch_, per * n);
+    scratch_elems_ = per * n;
+  }
+  // tables: [site L][envL L+1][envR L+1][w2l L][w2el L][w2er L][scratch 1] per replica
+  const size_t ppr = ptrs_per_replica();
+  std::vector<void*> h(n * ppr);
+  std::vector<zc> shift(n);
+  std::vector<int> kp(n * L_);
+  for (size_t i = 0; i < n; ++i) {
+    Engine& e = *eng_[i];
+    void** q = h.data() + i * ppr;
+    const Operator& o = e.ops_.find(0)->second;
+    for (int p = 0; p < L_; ++p) q[p] = e.site_[p].p;
+    for (int b = 0; b <= L_; ++b) { q[L_ + b] = e.envL_[b].p; q[2 * L_ + 1 + b] = e.envR_[b].p; }
+    for (int p = 0; p < L_; ++p) {
+      q[3 * L_ + 2 + p] = o.sites[p].w2l.p;
+      q[4 * L_ + 2 + p] = o.sites[p].w2el.p;
+      q[5 * L_ + 2 + p] = o.sites[p].w2er.p;
+    }
+    q[6 * L_ + 2] = d_scratch_ + i * per;
+    shift[i] = make_double2(o.shift.real(), o.shift.imag());
+    for (int p = 0; p < L_; ++p) kp[i * L_ + p] = e.kprev_[p];
+  }
+  if (h != h_ptrs_) {
+    h_ptrs_ = h;
+    HIP_CHECK(hipMemcpyAsync(d_ptrs_, h_ptrs_.data(), h_ptrs_.size() * sizeof(void*), hipMemcpyHostToDevice, st_));
+  }
+  if (shapes_dirty_) {
+    HIP_CHECK(hipMemcpyAsync(d_shp_, shp_.data(), shp_.size() * sizeof(BatchShape), hipMemcpyHostToDevice, st_));
+    shapes_dirty_ = false;
+  }
+  h_shift_ = shift;
+  h_kprev_ = kp;
+  HIP_CHECK(hipMemcpyAsync(d_shift_, h_shift_.data(), n * sizeof(zc), hipMemcpyHostToDevice, st_));
+  HIP_CHECK(hipMemcpyAsync(d_kprev_, h_kprev_.data(), h_kprev_.size() * sizeof(int), hipMemcpyHostToDevice, st_));
+  HIP_CHECK(hipMemsetAsync(d_status_, 0, n * sizeof(int), st_));
+  HIP_CHECK(hipMemsetAsync(d_stats_, 0, n * 4 * sizeof(long long), st_));
+  // what the engines have queued on their own streams comes first
+  for (size_t i = 0; i < n; ++i) {
+    HIP_CHECK(hipEventRecord(ev_[i], eng_[i]->st_));
+    HIP_CHECK(hipStreamWaitEvent(st_, ev_[i], 0));
+  }
+}
+
+void Batch::launch(double dt, bool forward) {
+  const size_t n = eng_.size();
+  Engine& e0 = *eng_[0];
+  BatchArgs a{};
+  a.L = L_;
+  a.forward = forward ? 1 : 0;
+  a.shp = d_shp_;
+  a.ptrs = d_ptrs_;
+  a.ptr_stride = (int)ptrs_per_replica();
+  a.shift = d_shift_;
+  a.kprev = d_kprev_;
+  a.status = d_status_;
+  a.stats = d_stats_;
+  a.plan = plan_;
+  a.e = SmallExp{};
+  a.e.integrator = e0.cfg.integrator; a.e.variant = e0.cfg.lanczos_variant; a.e.conserve_norm = e0.cfg.conserve_norm;
+  a.e.max_krylov = e0.cfg.max_krylov; a.e.thresh = e0.cfg.thresh;
+  const hzc ss = e0.scale_site(dt), sb = e0.scale_bond(dt);
+  a.site_re = ss.real(); a.site_im = ss.imag(); a.bond_re = sb.real(); a.bond_im = sb.imag();
+  batch_sweep_launch(st_, a, (int)n);
+  n_launch_ += 1;
+}
+
+// after the launches of a call: statuses, Krylov memories, counters, and the engines' own bookkeeping
+void Batch::finish(bool ends_forward, int half_sweeps, int* statuses) {
+  const size_t n = eng_.size();
+  std::vector<int> st(n), kp(n * L_);
+  std::vector<long long> stats(n * 4);
+  HIP_CHECK(hipMemcpyAsync(st.data(), d_status_, n * sizeof(int), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipMemcpyAsync(kp.data(), d_kprev_, kp.size() * sizeof(int), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipMemcpyAsync(stats.data(), d_stats_, stats.size() * sizeof(long long), hipMemcpyDeviceToHost, st_));
+  for (size_t i = 0; i < n; ++i) {  // the device copy of an engine's own one-launch exponentials, on the batch's stream
+    Engine& e = *eng_[i];
+    if (e.ss_.kprev && !e.exp_small_.empty())
+      HIP_CHECK(hipMemcpyAsync(e.ss_.kprev, d_kprev_ + i * L_, (size_t)L_ * sizeof(int), hipMemcpyDeviceToDevice, st_));
+  }
+  HIP_CHECK(hipStreamSynchronize(st_));  // the one host wait of the call
+  for (size_t i = 0; i < n; ++i) {
+    Engine& e = *eng_[i];
+    for (int p = 0; p < L_; ++p) e.kprev_[p] = kp[i * L_ + p];
+    e.cnt_.n_heff += stats[i * 4 + 0];
+    e.cnt_.n_keff += stats[i * 4 + 1];
+    e.cnt_.heff_flops += (double)stats[i * 4 + 2];
+    e.cnt_.keff_flops += (double)stats[i * 4 + 3];
+    if (st[i] == SS_OK) {  // a replica that stopped part-way did less: only what the device counted is added for it
+      e.cnt_.n_exp_site += (long long)half_sweeps * L_;
+      e.cnt_.n_exp_bond += (long long)half_sweeps * (L_ - 1);
+      e.cnt_.n_qr += (long long)half_sweeps * (L_ - 1);
+      e.cnt_.n_env += (long long)half_sweeps * (L_ - 1);
+    }
+    if (i == 0) e.cnt_.n_launch += half_sweeps;  // the batch's launches are counted once
+    const int centre = ends_forward ? L_ - 1 : 0;
+    for (int p = 0; p < L_; ++p) e.gauge_[p] = p < centre ? MITDVP_GAUGE_A : (p == centre ? MITDVP_GAUGE_PSI : MITDVP_GAUGE_B);
+    e.center_ = centre;
+    for (int b = 1; b < L_; ++b) {
+      e.envL_ok_[b] = ends_forward ? 1 : 0;
+      e.envR_ok_[b] = ends_forward ? 0 : 1;
+    }
+    e.env_chk_ = Engine::EnvChecked{};
+    if (st[i] != SS_OK) {  // the replica stopped in the middle of a half-sweep: its chain must be set up again
+      for (int b = 1; b < L_; ++b) { e.envL_ok_[b] = 0; e.envR_ok_[b] = 0; }
+      for (int p = 0; p < L_; ++p) e.gauge_[p] = MITDVP_GAUGE_C;
+      e.center_ = -1;
+    }
+    if (statuses) statuses[i] = st[i];
+  }
+}
+
+void Batch::step(double dt, int nsteps, int* statuses) {
+  if (nsteps < 0) throw ArgError("batch: nsteps must be >= 0");
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  if (nsteps == 0) {
+    for (size_t i = 0; statuses && i < eng_.size(); ++i) statuses[i] = SS_OK;
+    return;
+  }
+  prepare(true);
+  for (int s = 0; s < nsteps; ++s) {
+    launch(dt, true);
+    launch(dt, false);
+  }
+  finish(false, nsteps * 2, statuses);
+}
+
+void Batch::sweep(double dt, bool forward, int* statuses) {
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  prepare(forward);
+  launch(dt, forward);
+  finish(L_ > 1 ? forward : false, 1, statuses);
+}
+
+std::string Batch::status_message(int code) const {
+  const Engine& e0 = *eng_[0];
+  if (code == SS_ENOTCONV)
+    return std::string(e0.cfg.integrator == MITDVP_LANCZOS ? "Short Iterative Lanczos" : "Short Iterative Arnoldi") +
+           " is not converged in " + std::to_string(e0.cfg.max_krylov) + " basis. Try shorter time interval.";
+  if (code == SS_EZERO) return "Initial psi has zero norm.";
+  return "batch: unknown status " + std::to_string(code);
+}
+
+}  // namespace mitdvp

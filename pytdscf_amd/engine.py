@@ -756,6 +756,111 @@ class TDVPEnsemble:
         self.engines = []
 
 
+class TDVPBatch:
+    """B independent trajectories (replicas) of one chain shape on ONE GPU, any B: one kernel launch per half-sweep for the
+    whole batch (``mitdvp_batch_step`` / ``k_batch_sweep``: one workgroup owns one replica, the replica index is the
+    workgroup index).  Unlike ``TDVPEnsemble`` there are no compute-unit ranges, no host threads and no limit of 16
+    replicas; the replicas are ordinary full-device engines (``engines``), usable on their own between batch calls, and
+    ``from_engines`` takes engines that each carry their own MPO.  Shapes must be inside the kernel's envelope
+    (dl*d*dr <= 8192 per site, MPO bonds <= 16) and equal across replicas, as must the integrator settings.
+
+    ``propagate`` raises the first failing replica's error (a replica that does not converge stops, the others finish)
+    and leaves every replica's status code in ``statuses``.
+    """
+
+    def __init__(self, n_replicas: int, nsite: int, *, device: int = 0, **engine_kw):
+        if n_replicas < 1:
+            raise ValueError("n_replicas must be >= 1")
+        if "cu_range" in engine_kw:
+            raise ValueError("TDVPBatch replicas run on the whole device: no cu_range")
+        self.engines = []
+        self._own = True
+        self._b = None
+        self._key = None
+        self.statuses = []
+        self._lib = _lib.load()
+        try:
+            for _ in range(n_replicas):
+                self.engines.append(TDVPEngine(nsite, device=device, **engine_kw))
+        except Exception:
+            self.close()
+            raise
+
+    @classmethod
+    def from_engines(cls, engines):
+        """A batch over existing engines (each with its own MPO and state); ``close`` leaves them open."""
+        engines = list(engines)
+        if not engines:
+            raise ValueError("n_replicas must be >= 1")
+        self = cls.__new__(cls)
+        self.engines = engines
+        self._own = False
+        self._b = None
+        self._key = None
+        self.statuses = []
+        self._lib = _lib.load()
+        return self
+
+    def __len__(self):
+        return len(self.engines)
+
+    def __getitem__(self, i):
+        return self.engines[i]
+
+    def set_mpo(self, cores, op_id: int = 0):
+        for e in self.engines:
+            e.set_mpo(cores, op_id)
+
+    def _handle(self):
+        # created at the first step (the engines get their tensors and MPOs after construction) and again when the list
+        # of engines changed; the library validates the replicas at creation and at every step
+        key = tuple(e._h.value if hasattr(e._h, "value") else e._h for e in self.engines)
+        if self._b is None or key != self._key:
+            self._drop()
+            n = len(self.engines)
+            hs = (C.c_void_p * n)(*[e._h for e in self.engines])
+            b = C.c_void_p()
+            _lib.check(self._lib.mitdvp_batch_create(hs, n, C.byref(b)))
+            self._b, self._key = b, key
+        return self._b
+
+    def _run(self, call):
+        n = len(self.engines)
+        st = (C.c_int * n)()
+        rc = call(self._handle(), st)
+        self.statuses = list(st)
+        if rc != 0:
+            bad = next((i for i in range(n) if st[i] != 0), None)
+            if bad is None:
+                _lib.check(rc)  # the call itself was refused
+            _lib.check(st[bad], self.engines[bad]._h)
+
+    def propagate(self, dt_au: float, nsteps: int = 1):
+        """``nsteps`` time steps of every replica: two launches per time step for the whole batch."""
+        self._run(lambda b, st: self._lib.mitdvp_batch_step(b, float(dt_au), int(nsteps), st))
+
+    def sweep(self, dt_au: float, forward: bool):
+        self._run(lambda b, st: self._lib.mitdvp_batch_sweep(b, float(dt_au), int(bool(forward)), st))
+
+    def _drop(self):
+        if getattr(self, "_b", None) is not None:
+            self._lib.mitdvp_batch_destroy(self._b)
+            self._b = None
+
+    def close(self):
+        self._drop()
+        if self._own:
+            for e in self.engines:
+                e.close()
+        self.engines = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def device_cu_count(device: int = 0) -> int:
     """compute units of the device (256 on MI355X)"""
     n = C.c_int()
