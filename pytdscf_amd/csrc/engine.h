@@ -55,6 +55,14 @@ struct DevBuf {
   }
 };
 
+// The forms the H_eff applies of ONE local solve take: made by Engine::choose_apply_forms, held on that solve's stack,
+// handed to each of its applies.  trim_l / trim_r: the FIRST MPO-bond block of the left / the last one of the right
+// environment is the identity (the sites on that side are canonical and the MPO passes "nothing applied yet" through;
+// the reference short-circuits such blocks as well, _mps_mpo.py:510-523) and stage S1 / S3 skips it; edge: the applies
+// take heff_apply_edge, fold_l / fold_r: with that side folded.  The default is the plain three-stage chain, which is
+// what every apply outside such a solve gets.
+struct ApplyPlan { bool trim_l = false, trim_r = false, edge = false, fold_l = false, fold_r = false; };
+
 struct MpoSite {
   int ml = 0, d = 0, mr = 0;
   DevBuf w2l;  // W2L[(i,t)][(c,j)] = W[c,i,j,t]   (d*mr) x (ml*d)
@@ -80,30 +88,34 @@ struct MpoSite {
   // (a canonical chain under a finite-state-machine MPO, or a direct sum of such: the "nothing applied yet" / "all
   // applied" states; a sign or weight of a summand may ride on them), and every non-zero (c, t) block of W in a row of S
   // or a column of E, the apply is two products with a reducing epilogue and no intermediate in memory.  The reduced
-  // cores depend on (S, E, lam, mu), found numerically per site, and are cached:
-  //   w_edge_r[i][(j, t)] = sum_{c in S} lam_c W[c, i, j, t]
-  //   w_edge_l[i][(c, j)] = sum_{t in E} mu_t W[c, i, j, t] for c not in S, else 0
+  // cores depend on (S, E, lam, mu), found numerically per site, and are cached (EdgeCache):
+  //   w_r[i][(j, t)] = sum_{c in S} lam_c W[c, i, j, t]
+  //   w_l[i][(c, j)] = sum_{t in E} mu_t W[c, i, j, t] for c not in S, else 0
   std::vector<hzc> whost;           // the core as uploaded (ml, d, d, mr); empty when a bond exceeds 64 states
   std::vector<char> nzblk;          // [c * mr + t]: block (c, t) holds a non-zero
-  mutable bool edge_valid = false;  // w_edge_l / w_edge_r correspond to (edge_s, edge_e)
-  mutable unsigned long long edge_s = 0, edge_e = 0;
-  mutable std::vector<hzc> edge_lam, edge_mu;
-  mutable bool edge_has_l = false, edge_has_r = false;
-  mutable int edge_skip = 0;        // local solves for which the (failed) structure check is not repeated
-  mutable DevBuf w_edge_l, w_edge_r;
-  mutable DevBuf w_edge_lf, w_edge_rf;  // the same cores in the epilogue's fragment order (zgemm_reduce_pack_core)
-  mutable bool edge_lf_ok = false, edge_rf_ok = false;
   // Structured environment update (Engine::env_update_fold), per direction (0: -> consumes L with its identity set S,
   // 1: <- consumes R with E; "in" = the MPO bond of the consumed block, "out" = the other one).  Built beside the edge
-  // cores and valid with them (edge_valid):
+  // cores and valid with them (EdgeCache::valid):
   //   ws[i][j][out]        = sum_{in in the identity set} (multiple of in) W[in, i, j, out]   (all out states)
   //   wg[k][i][in][j]      = W[in, i, j, t0[k]] for in NOT in the identity set, else 0        (unweighted)
   // t0 = the out states fed by a general in state (one "all applied" state per summand of a finite-state-machine MPO).
-  struct EnvFold {
-    std::vector<int> t0;
-    DevBuf ws, wg;
+  struct EnvFold { std::vector<int> t0; DevBuf ws, wg; };
+  // what the local solves find out about the site and keep from sweep to sweep: written through the const core
+  struct EdgeCache {
+    bool valid = false;  // the cores below correspond to (s, e, lam, mu)
+    unsigned long long s = 0, e = 0;
+    std::vector<hzc> lam, mu;
+    bool has_l = false, has_r = false;
+    int skip = 0;        // local solves for which the (failed) structure check is not repeated
+    DevBuf w_l, w_r;
+    DevBuf w_lf, w_rf;   // the same cores in the epilogue's fragment order (zgemm_reduce_pack_core)
+    bool lf_ok = false, rf_ok = false;
+    EnvFold envf[2];
+    // the cores of w for these identity sets and multiples, on the host, uploaded; nothing to do when they are the cached ones
+    void rebuild(hipStream_t st, const MpoSite& w, unsigned long long S, unsigned long long E, const std::vector<hzc>& lam,
+                 const std::vector<hzc>& mu);
   };
-  mutable EnvFold envf[2];
+  mutable EdgeCache edge;
   DevBuf wtr;  // Liouville trace operator: O2[f][(a,c,d)] = O[a,d,c,f], n = sqrt(site dim)
   int ntr = 0, mltr = 0, mrtr = 0;
   int dtr = 0;  // physical entries per (a, f) of wtr: n*n, or the size of the site's subspace when it was set
@@ -136,6 +148,7 @@ int cu_ranges_claimed(int device);
 class Engine {
   friend class SiteShard;  // shard.hip: the junction update works on the tensors and blocks of two engines in place
   friend class Batch;      // engine_batch.hip: borrows engines, steps their chains with one launch per half-sweep
+  struct KeffCompact;      // the compact form of a bond solve's K_eff applies (below)
 
  public:
   explicit Engine(const mitdvp_config& cfg);
@@ -193,17 +206,21 @@ class Engine {
 
   // ---- building blocks (also used by the unit-level C entry points) -------
   void heff_apply(const zc* L, const MpoSite& w, const zc* R, const zc* psi, zc* out, int dl, int d, int dr,
-                  hzc shift);
-  void keff_apply(const zc* L, const zc* R, const zc* sig, zc* out, int d1, int d2, int m, hzc shift);
-  // rectangular blocks (bra bond != ket bond), no shift term: the adaptive-rank applies
+                  hzc shift, const ApplyPlan& plan = {});
+  // kc: the compact form keff_prepare made for exactly these blocks, nullptr = the plain path
+  void keff_apply(const zc* L, const zc* R, const zc* sig, zc* out, int d1, int d2, int m, hzc shift,
+                  const KeffCompact* kc = nullptr);
+  // rectangular blocks (bra bond != ket bond), no shift term: the adaptive-rank applies (of the plan: trim_l / trim_r)
   void heff_apply_rect(const zc* L, const MpoSite& w, const zc* R, const zc* psi, zc* out, int dlo, int dli, int d,
-                       int dro, int dri);
+                       int dro, int dri, const ApplyPlan& plan = {});
   // edge-structured MPO core between canonical environments: sigma = sum_t W[0,:,:,t] (psi R_t^T) + sum_{c>=1} W[c,:,:,mr-1] (L_c psi),
-  // each a GEMM whose 64 x 64 tiles are contracted with W in the epilogue (zgemm_reduce): X / Y never exist
-  void heff_apply_edge(const zc* L, const MpoSite& w, const zc* R, const zc* psi, zc* out, int dl, int d, int dr);
-  // which forms the H_eff applies of the site between these blocks take (sets trim_l_, trim_r_, edge_, fold_l_, fold_r_; one host
-  // synchronisation for the numerical identity checks); the caller resets them when the local solve is over
-  void choose_apply_forms(const zc* Lb, const MpoSite& w, const zc* Rb, int dl, int d, int dr);
+  // each a GEMM whose 64 x 64 tiles are contracted with W in the epilogue (zgemm_reduce): X / Y never exist; a side the
+  // plan folds (fold_l / fold_r) is one plain GEMM with the operator choose_apply_forms left in X_ / Y_
+  void heff_apply_edge(const zc* L, const MpoSite& w, const zc* R, const zc* psi, zc* out, int dl, int d, int dr,
+                       const ApplyPlan& plan);
+  // which forms the H_eff applies of the site between these blocks take (one host synchronisation for the numerical
+  // identity checks; builds the folded operators): valid for the local solve that asked, while the blocks stay as they are
+  ApplyPlan choose_apply_forms(const zc* Lb, const MpoSite& w, const zc* Rb, int dl, int d, int dr);
   void keff_apply_rect(const zc* L, const zc* R, const zc* sig, zc* out, int dlo, int dli, int dro, int dri, int m);
   void env_update_rect(const zc* env_in, const zc* Tk, const zc* Tb, const zc* w2, zc* env_out, int dbi, int dki,
                        int min_, int d, int dbo, int dko, int mout, const MpoSite* sp = nullptr, int sp_side = 0);
@@ -298,28 +315,26 @@ class Engine {
     int dev = -1, first = 0, count = 0;
     ~CuClaim() { if (dev >= 0) cu_range_release(dev, first, count); }
   } cu_claim_;
-  // H_eff applies of the current local exponential: the last MPO-bond block of the right environment is the identity
-  // (sites right of the centre are right-canonical and the MPO passes "nothing applied yet" through: the reference
-  // short-circuits such blocks as well, _mps_mpo.py:510-523) -- verified numerically per site, see local_site_exp
-  bool trim_r_ = false;
-  bool trim_l_ = false;  // the same for the FIRST MPO-bond block of the left environment (stage S1: rows (a, c = 0) of X = psi)
-  bool left_block_is_identity(const zc* L, int dl, int m);
   // gauge moves of the sweep without LAPACK's sign convention on diag(R) (qr_thin; MITDVP_QR_GAUGE_FREE=0: always the
   // Householder panels).  The unit-level entry point mitdvp_gauge_trf keeps the convention.
   bool qr_gauge_free_ = true;
   bool trim_identity_ = true;  // MITDVP_TRIM_IDENTITY=0 switches the shortcut off
-  bool edge_ = false;          // the current local exponential's applies take heff_apply_edge
   int edge_mode_ = -1;         // MITDVP_EDGE_APPLY: 0 never, 1 wherever valid, -1 (default) the size rule of choose_apply_forms
-  // the folded variant of the edge form, per side: the reduced core contracted into the environment block once per
-  // local solve (choose_apply_forms, operators in Y_ / X_), the side's apply one plain GEMM (heff_apply_edge)
-  bool fold_r_ = false, fold_l_ = false;
+  // the folded variant of the edge form, per side (ApplyPlan::fold_r / fold_l): the reduced core contracted into the
+  // environment block once per local solve (choose_apply_forms, operators in Y_ / X_), the side's apply one plain GEMM
   int fold_mode_ = -1;         // MITDVP_FOLD_APPLY: 0 never, 1 wherever the edge form is valid, -1 (default) the rule of choose_apply_forms
   // MITDVP_FOLD_ENV: the structured environment update (env_update_fold): 0 never, 1 wherever it is valid, -1 (default) the
   // rule of env_fold_ok.  The identity sets it relies on are those the last choose_apply_forms found for exactly these
-  // blocks of this site (env_chk_; one update may use them, any update clears them)
+  // blocks of this site: env_chk_, set there and nowhere else.  It outlives the call (in segment mode site_exp and
+  // split_center are separate library calls), but one update may use it and any update takes it away
   int fold_env_mode_ = -1;
   struct EnvChecked { const MpoSite* w = nullptr; const zc* blk[2] = {nullptr, nullptr}; int n[2] = {0, 0}; } env_chk_;
-  bool right_block_is_identity(const zc* R, int dr, int m);
+  EnvChecked take_env_checked() { const EnvChecked c = env_chk_; env_chk_ = EnvChecked{}; return c; }
+  // One look at the MPO-bond states of the two blocks around a site or bond (identity_sets): per state its deviation from
+  // a multiple of the identity and that multiple, [0, 64) the left block's states, [64, 128) the right block's
+  struct IdentRecord { double dev[128]; hzc lam[128]; };
+  static_assert(sizeof(IdentRecord) == 128 * 8 + 128 * 16 && sizeof(IdentRecord) <= 4 * NPART * sizeof(zc), "layout of the identity-check record");
+  const IdentRecord& identity_sets(const zc* L, int ml, int dl, unsigned long long ms, const zc* R, int mr, int dr, unsigned long long me);
   void identity_blocks(const zc* L, int dl, int ml, const zc* R, int dr, int mr, bool* left, bool* right);
   int L_;
   hipStream_t st_ = nullptr;
@@ -370,17 +385,17 @@ class Engine {
   //            + (sum_{c in S n E} lam_c mu_c) sigma:
   // the first GEMM runs over the blocks not in S, the second over those not in E (compact copies of the kept blocks, made
   // once per exponential), the rest are scaled copies.  The reference skips such blocks outright (_mps_mpo.py:489-523).
+  // keff_prepare hands it to the bond solve that asked (nullptr: not worth it); a member so that Lc / Rc keep their allocations.
   struct KeffCompact {
-    bool on = false;
+    int m = 0;                           // MPO bond of the blocks it was made from
     int n1 = 0, nE = 0, nG = 0, nS = 0;  // X row layout per slab: [E \ S | general | S \ E]; n1 = nE + nG rows come from GEMM 1
     BlockList fillS{}, accE{};           // scaled copies lam_c sigma -> X; mu_c X_c -> out
     zc both = make_double2(0.0, 0.0);
     DevBuf Lc, Rc;
   } kc_;
-  int kc_m_ = 0;               // MPO bond of the blocks kc_ was made from
   bool keff_ident_ = true;     // MITDVP_KEFF_IDENT=0: off (A/B testing)
-  void keff_prepare(const zc* L, const zc* R, int d1, int d2, int m);
-  void keff_apply_compact(const zc* sig, zc* out, int d1, int d2, hzc shift);
+  const KeffCompact* keff_prepare(const zc* L, const zc* R, int d1, int d2, int m);
+  void keff_apply_compact(const KeffCompact& k, const zc* sig, zc* out, int d1, int d2, hzc shift);
   bool sparse_w_ = true;       // MITDVP_SPARSE_W=0: always the dense W stage (A/B testing)
   // the W stage of an apply / environment update: dense GEMM, or row ranges of dense / list kernels (returns the
   // executed share of the dense flop count)

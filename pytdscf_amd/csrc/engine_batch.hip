@@ -261,7 +261,7 @@ void Batch::finish(bool ends_forward, int half_sweeps, int* statuses) {
       e.envL_ok_[b] = ends_forward ? 1 : 0;
       e.envR_ok_[b] = ends_forward ? 0 : 1;
     }
-    e.env_chk_ = Engine::EnvChecked{};
+    (void)e.take_env_checked();  // the blocks its sets described are gone
     if (st[i] != SS_OK) {  // the replica stopped in the middle of a half-sweep: its chain must be set up again
       for (int b = 1; b < L_; ++b) { e.envL_ok_[b] = 0; e.envR_ok_[b] = 0; }
       for (int p = 0; p < L_; ++p) e.gauge_[p] = MITDVP_GAUGE_C;

@@ -13,7 +13,6 @@
 
 namespace mitdvp {
 
-
 constexpr double KRYLOV_EPS = 1e-12;  // _integrator.py:22
 
 // layout of the reduction scratch (units: zc)

@@ -112,16 +112,15 @@ void Engine::heff_apply_center(const double* in, double* out, int* flags) {
   DevBuf x = pool_get(n), y = pool_get(n);
   if (in) copy_in(x.p, in, n);
   else HIP_CHECK(hipMemcpyAsync(x.p, site_[p].p, n * sizeof(zc), hipMemcpyDeviceToDevice, st_));
-  choose_apply_forms(Lb, w, Rb, dl, d, dr);
-  struct Reset { bool& f; bool& g; bool& e; ~Reset() { f = false; g = false; e = false; } } reset{trim_r_, trim_l_, edge_};
+  const ApplyPlan plan = choose_apply_forms(Lb, w, Rb, dl, d, dr);
   SmallChain sc;
   const bool small = small_ok() && chain_heff(sc, Lb, w, Rb, dl, d, dr, false);
-  const bool edge = edge_ && !small;
+  const bool edge = plan.edge && !small;
   const bool sparse = !small && !edge && sparse_w_ && dr >= 64 && w.kl_l.p && w.sp_frac_l <= 0.6;
   if (flags)
-    *flags = (trim_l_ && !small && !edge ? 1 : 0) | (trim_r_ && !small && !edge ? 2 : 0) | (sparse ? 4 : 0) | (small ? 8 : 0) |
-             (edge ? 16 : 0) | (edge && fold_r_ ? 0x20 : 0) | (edge && fold_l_ ? 0x40 : 0);
-  heff_apply(Lb, w, Rb, x.p, y.p, dl, d, dr, op(0).shift);
+    *flags = (plan.trim_l && !small && !edge ? 1 : 0) | (plan.trim_r && !small && !edge ? 2 : 0) | (sparse ? 4 : 0) | (small ? 8 : 0) |
+             (edge ? 16 : 0) | (edge && plan.fold_r ? 0x20 : 0) | (edge && plan.fold_l ? 0x40 : 0);
+  heff_apply(Lb, w, Rb, x.p, y.p, dl, d, dr, op(0).shift, plan);
   copy_out(out, y.p, n);
   pool_put(std::move(x)); pool_put(std::move(y));
 }
