@@ -509,13 +509,13 @@ void Engine::env_update_rect(const zc* env_in, const zc* Tk, const zc* Tb, const
 
 // The structured update.  With I the states of the consumed block's MPO bond whose blocks env_in[:, c, :] are multiples
 // lam_c of the identity (found by choose_apply_forms for this very block), the sum over c splits:
-//   c in I:      env_in drops out.  G[(i,a')][(j,r)] = sum_a conj(T[a,i,a']) T[a,j,r]  (the site tensor's Gram matrix, one
-//                GEMM of d^2 D^3 products) and env_out[a',t,r] = sum_{i,j} ws[i,j,t] G[(i,a')][(j,r)] for every t
+//   c in I:      env_in drops out.  G[(i,a')][(j,r)] = sum_a conj(T[a,i,a']) T[a,j,r]  (the site tensor's Gram matrix, Hermitian:
+//                its upper block half by block rows, d (d + 1) / 2 D^3 products, the lower half mirrored) and env_out[a',t,r] = sum_{i,j} ws[i,j,t] G[(i,a')][(j,r)] for every t
 //                (gram_env_core: d^2 M D^2 products);
 //   c not in I:  only the few out states t0 a general state feeds (one per summand of a finite-state-machine MPO).  With
 //                GL_t0[(a,i)][(b,j)] = sum_{c not in I} W[c,i,j,t0] env_in[a,c,b]  (fold_env_core),
 //                env_out[:, t0, :] += T^H (GL_t0 T): d^2 D^3 + d D^3 products.
-// (1 + |t0|) d^2 D^3 + |t0| d D^3 products against the chain's 2 M d D^3.  The Gram matrix and then GL_t0 T live in Y_,
+// (d (d + 1) / 2 + |t0| d^2) D^3 + |t0| d D^3 products against the chain's 2 M d D^3.  The Gram matrix and then GL_t0 T live in Y_,
 // GL_t0 in X_: the chain's own workspaces, (d D)^2 <= D M d D whenever d <= M; nothing is allocated.
 bool Engine::env_fold_ok(const zc* env_in, int din, int min_, int d, int dout, int mout, const MpoSite* sp, int sp_side) {
   const EnvChecked chk = take_env_checked();  // whatever this update does, the sets have had their one use
@@ -538,11 +538,17 @@ bool Engine::env_fold_ok(const zc* env_in, int din, int min_, int d, int dout, i
 void Engine::env_update_fold(const zc* env_in, const zc* T, zc* env_out, int din, int min_, int d, int dout, int mout,
                              const MpoSite::EnvFold& f) {
   timer_begin(1);
-  {  // G[(i,a')][(j,r)] = conj(T)[a][(i,a')] T[a][(j,r)]
-    ZgemmDesc g = zgemm_desc(T, T, Y_.p, d * dout, d * dout, din);
-    g.transA = 1; g.conjA = 1; g.lda = (long)d * dout;
+  // G[(i,a')][(j,r)] = conj(T)[a][(i,a')] T[a][(j,r)] is Hermitian: block row i of the product is formed from its diagonal
+  // block on (j >= i: d (d + 1) / 2 of the d^2 blocks, the diagonal ones whole), the blocks below the diagonal are the
+  // conjugate transposes of those above (gram_mirror_lower: one read and one write of that half)
+  const long ldg = (long)d * dout;
+  for (int i = 0; i < d; ++i) {
+    ZgemmDesc g = zgemm_desc(T + (size_t)i * dout, T + (size_t)i * dout, Y_.p + (size_t)i * dout * ldg + (size_t)i * dout, dout,
+                             (d - i) * dout, din);
+    g.transA = 1; g.conjA = 1; g.lda = ldg; g.ldb = ldg; g.ldc = ldg;
     zgemm(st_, g);
   }
+  gram_mirror_lower(st_, Y_.p, dout, d);
   gram_env_core(st_, Y_.p, f.ws.p, env_out, dout, mout, d);
   for (size_t k = 0; k < f.t0.size(); ++k) {
     // GL[(a,i)][(b,j)] (in X_), Z[(a,i)][r] = GL T[(b,j)][r] (in Y_: the Gram matrix has been consumed), block t0 += T^H Z
@@ -555,7 +561,7 @@ void Engine::env_update_fold(const zc* env_in, const zc* T, zc* env_out, int din
     zgemm(st_, h);
   }
   timer_end();
-  cnt_.n_launch += 2 + 3 * (long long)f.t0.size();
+  cnt_.n_launch += d + (d > 1 ? 1 : 0) + 1 + 3 * (long long)f.t0.size();
   cnt_.n_env += 1;
   cnt_.n_env_fold += 1;
   // (algorithmic count, as heff_flops: the chain's)

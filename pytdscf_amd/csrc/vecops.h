@@ -56,6 +56,9 @@ void fold_env_core(hipStream_t st, const zc* env, const zc* w, zc* G, int n, int
 // (the structured environment update, Engine::env_update_fold): out[p][t][q] = sum_{i, j} ws[(i * d + j) * m + t] *
 // G[(i, p)][(j, q)], all m <= 64 blocks of the (n, m, n) block, which is overwritten.
 void gram_env_core(hipStream_t st, const zc* G, const zc* ws, zc* out, int n, int m, int d);
+// The lower block half of that Gram matrix from its upper one, in place: blocks (i, j), i > j, become the conjugate
+// transposes of the blocks (j, i) (n x n each); blocks i <= j are only read.  d <= 64.
+void gram_mirror_lower(hipStream_t st, zc* G, int n, int d);
 void copy2d(hipStream_t st, zc* dst, long ldd, const zc* src, long lds, long rows, int cols, int zero_to, zc a,
             bool accumulate);
 // Block lists of the K_eff apply with identity states skipped (Engine::keff_prepare): up to 64 blocks, scalars by value.

@@ -1011,6 +1011,41 @@ __global__ __launch_bounds__(256) void k_gram_env_core(const zc* __restrict__ G,
     }
   }
 }
+// The lower block half of a Hermitian (d n) x (d n) matrix from its upper one (gram_mirror_lower): G[(i,p)][(j,q)] =
+// conj(G[(j,q)][(i,p)]) for the block pairs i > j; diagonal blocks are left as they are.  One workgroup per 32 x 32 tile of
+// a block pair: the source tile's rows are read 512 B contiguous per half-wave, turned through LDS (33 elements per
+// row: the column read walks the banks) and stored 512 B contiguous per half-wave.  Reads blocks i < j only, writes
+// blocks i > j only: no element is both read and written, whatever the order of the workgroups.
+__global__ __launch_bounds__(256) void k_gram_mirror_lower(zc* G, int n, int d) {
+  __shared__ zc tile[32][33];
+  int i = 1, j = blockIdx.z;  // pair index -> (i, j), j < i < d: pairs ordered (1,0), (2,0), (2,1), ...
+  while (j >= i) { j -= i; ++i; }
+  const long ldg = (long)d * n;
+  const int q0 = blockIdx.x * 32, p0 = blockIdx.y * 32;  // the destination tile: rows p0.., columns q0.. of block (i, j)
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const zc* src = G + ((long)j * n) * ldg + (long)i * n;  // block (j, i): rows q, columns p
+  zc* dst = G + ((long)i * n) * ldg + (long)j * n;
+  for (int r = ty; r < 32; r += 8) {
+    const int q = q0 + r, p = p0 + tx;
+    if (q < n && p < n) tile[r][tx] = src[(long)q * ldg + p];
+  }
+  __syncthreads();
+  for (int r = ty; r < 32; r += 8) {
+    const int p = p0 + r, q = q0 + tx;
+    if (p < n && q < n) {
+      const zc v = tile[tx][r];
+      dst[(long)p * ldg + q] = make_double2(v.x, -v.y);
+    }
+  }
+}
+void gram_mirror_lower(hipStream_t st, zc* G, int n, int d) {
+  if (n < 1 || d < 2) return;
+  if (n > 65535 || d > 64) throw ArgError("gram_mirror_lower: d <= 64 and bond dimension <= 65535");
+  const int nt = (n + 31) / 32;
+  hipLaunchKernelGGL(k_gram_mirror_lower, dim3(nt, nt, d * (d - 1) / 2), dim3(256), 0, st, G, n, d);
+  HIP_CHECK(hipGetLastError());
+}
+
 // out[p][t][q] = sum_{i, j} ws[(i * d + j) * m + t] * G[(i, p)][(j, q)]   (G: (d n) x (d n) row-major; out: n x m x n)
 void gram_env_core(hipStream_t st, const zc* G, const zc* ws, zc* out, int n, int m, int d) {
   if (n < 1 || d < 1) return;
