@@ -149,6 +149,38 @@ int mitdvp_batch_create(mitdvp_engine** hs, int n, mitdvp_batch** out);
 int mitdvp_batch_step(mitdvp_batch* b, double dt_au, int nsteps, int* statuses);
 int mitdvp_batch_sweep(mitdvp_batch* b, double dt_au, int forward, int* statuses);
 void mitdvp_batch_destroy(mitdvp_batch* b);
+/* Observables of a batch without a walk over its engines (k_batch_observe: one workgroup per replica, ONE launch observes
+ * every replica; k_batch_mean: ONE launch forms the ensemble means on the device, replica after replica in index order).
+ * `what` is a non-empty set of MITDVP_OBS_* bits; MITDVP_OBS_RDM goes with a strictly ascending list `sites` of nsites
+ * sites (one-site reduced densities, d x d, row = ket, column = bra, not symmetrised, as mitdvp_site_rdm), and only with
+ * it.  All replicas must have their centre at site 0 with the chain canonical around it (the state mitdvp_batch_step
+ * leaves); for MITDVP_OBS_ENERGY (operator 0, as mitdvp_expect) the right environment blocks are built once with the
+ * engines' own launches when no step has built them yet.  weights: n doubles or NULL (1 / n each).
+ * Every pointer of `out` may be NULL.  Per replica, record-major ([record][replica]...): norm (the root, as mitdvp_norm),
+ * autocorr[..][2], energy[..][2], rdm[..][nrdm][2] with nrdm = the sum of d_p * d_p over the listed sites, in list order.
+ * Means over the replicas ([record]...): mean_norm2 (the mean of the SQUARED norms), mean_autocorr, mean_energy, mean_rdm.
+ * counts (may be NULL) receives {records, replicas, nrdm}; with out == NULL the call only validates what does not depend
+ * on the engines' state and returns the counts, like mitdvp_reduced_density.
+ *   mitdvp_batch_observe: one observation of the current state: two launches, one host wait.
+ *   mitdvp_batch_run    : nsteps time steps as mitdvp_batch_step, recording the state before step 0 and after every
+ *                         `every`-th step (nsteps must be a multiple of every; nsteps / every + 1 records).  The records
+ *                         stay on the device until the end: the call has the one host wait of mitdvp_batch_step, and
+ *                         2 nsteps + records + 1 launches, whatever n and nsites.  Asking for the means only is the cheap
+ *                         form.  A replica that fails to converge behaves as in mitdvp_batch_step; its records from then
+ *                         on are zeros, the call returns its status, and the MEANS of such a call are not usable.
+ * A refused request (MITDVP_EINVAL, message: mitdvp_last_error(NULL)) leaves every engine untouched. */
+#define MITDVP_OBS_NORM 1
+#define MITDVP_OBS_AUTOCORR 2
+#define MITDVP_OBS_ENERGY 4
+#define MITDVP_OBS_RDM 8
+typedef struct mitdvp_batch_out {
+  double *norm, *autocorr, *energy, *rdm;
+  double *mean_norm2, *mean_autocorr, *mean_energy, *mean_rdm;
+} mitdvp_batch_out;
+int mitdvp_batch_observe(mitdvp_batch* b, const int* sites, int nsites, int what, const double* weights,
+                         const mitdvp_batch_out* out, size_t counts[3]);
+int mitdvp_batch_run(mitdvp_batch* b, double dt_au, int nsteps, int every, const int* sites, int nsites, int what,
+                     const double* weights, const mitdvp_batch_out* out, size_t counts[3], int* statuses);
 /* propagate_along_sweep (_mps_cls.py:798-1014), one direction only. */
 int mitdvp_sweep(mitdvp_engine* h, double dt_au, int forward);
 /* The same half-sweep in parts: the next `nsites` local updates of the half-sweep in progress (one is started when none

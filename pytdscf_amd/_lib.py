@@ -76,6 +76,15 @@ class Counters(C.Structure):
         return d
 
 
+class BatchOut(C.Structure):
+    """mitdvp_batch_out: host destinations of a batch's observables, NULL = not wanted"""
+
+    _fields_ = [(k, C.POINTER(C.c_double)) for k in
+                ("norm", "autocorr", "energy", "rdm", "mean_norm2", "mean_autocorr", "mean_energy", "mean_rdm")]
+
+
+OBS_NORM, OBS_AUTOCORR, OBS_ENERGY, OBS_RDM = 1, 2, 4, 8
+
 COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t)
 P2P_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t)  # mitdvp_p2p_fn
 
@@ -220,6 +229,8 @@ def load() -> C.CDLL:
         "mitdvp_batch_step": (i, [vp, d, i, ip]),
         "mitdvp_batch_sweep": (i, [vp, d, i, ip]),
         "mitdvp_batch_destroy": (None, [vp]),
+        "mitdvp_batch_observe": (i, [vp, ip, i, i, dp, C.POINTER(BatchOut), C.POINTER(C.c_size_t)]),
+        "mitdvp_batch_run": (i, [vp, d, i, i, ip, i, i, dp, C.POINTER(BatchOut), C.POINTER(C.c_size_t), ip]),
         "mitdvp_cu_mask_probe": (i, [i, C.POINTER(C.c_uint), i, i, C.c_size_t, i, ip]),
     }
     for name, (res, args) in sig.items():

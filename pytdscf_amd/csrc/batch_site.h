@@ -54,4 +54,39 @@ struct BatchArgs {
 // one launch: grid = nrep workgroups, a half-sweep of every replica
 void batch_sweep_launch(hipStream_t st, const BatchArgs& a, int nrep);
 
+// ---- batched observables (k_batch_observe, k_batch_mean) ----
+// what is wanted of an observation: the values of MITDVP_OBS_* (include/mitdvp.h)
+enum { BOBS_NORM = 1, BOBS_AUTOCORR = 2, BOBS_ENERGY = 4, BOBS_RDM = 8, BOBS_ALL = 15 };
+// One replica's record, in doubles: [0] norm^2, [1] 0, [2, 3] autocorrelation, [4, 5] energy, then the site RDMs of the
+// listed sites in list order, d_p * d_p complex numbers each (row = ket, column = bra).  What was not asked is 0.
+constexpr int BOBS_HEAD = 6;
+constexpr long BATCH_OBS_MAX_RDM = 65536;  // complex elements of all observed RDMs of one replica together
+
+// The observation's own carve of a replica's scratch area, offsets in complex elements from the START OF THE CARVE (the
+// carve lies behind the sweep's, BatchPlan::total, which it leaves as it is): the transfer matrix T and its successor
+// (max_bond each), U = T C (max_site), and X, Y, H C of the energy's H_eff apply (nx, ny, max_site).
+struct BatchObsPlan {
+  size_t o_t = 0, o_t2 = 0, o_u = 0, o_x = 0, o_y = 0, o_h = 0, total = 0;
+};
+void batch_observe_plan(const BatchPlan& plan, BatchObsPlan& obs);
+
+struct BatchObsArgs {
+  int L, what, nsites;
+  const BatchShape* shp;    // [L], device
+  void* const* ptrs;        // the pointer table of BatchArgs
+  int ptr_stride;
+  const zc* shift;          // [B]
+  const int* status;        // [B]: a replica whose word is set does no work, its record is zeros
+  const int* sites;         // [nsites], device, strictly ascending
+  size_t carve;             // offset of the observation's carve in a replica's scratch area, complex elements
+  BatchObsPlan plan;
+  double* rec;              // [B][rec_len]: this observation's records
+  long rec_len;             // BOBS_HEAD + 2 * sum d_p^2
+};
+// one launch: grid = nrep workgroups, one record per replica.  Precondition: centre at site 0, sites 1 .. L-1 in gauge B,
+// and for BOBS_ENERGY valid right blocks.
+void batch_observe_launch(hipStream_t st, const BatchObsArgs& a, int nrep);
+// one launch: mean[q][e] = sum_r w[r] rec[q][r][e], r in index order, one thread per (q, e)
+void batch_mean_launch(hipStream_t st, const double* rec, const double* w, double* mean, int nrep, long rec_len, long nrec);
+
 }  // namespace mitdvp

@@ -1,4 +1,5 @@
 // batch_site.hip -- batched trajectories: k_batch_sweep, ONE workgroup per replica, a whole half-sweep per launch.
+// (Further down: k_batch_observe / k_batch_mean, the observables of every replica and their ensemble means, one launch each.)
 //
 // At trajectory shapes (d = 2..4, D <= 32, M <= 16) a local problem is a few tens of kilobytes, so one workgroup can own
 // one replica completely: the replica index is blockIdx.x, nothing is exchanged between workgroups, and therefore there is
@@ -595,6 +596,168 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_sweep(BatchArgs g) {
   if (rc != SS_OK && tid == 0) g.status[r] = rc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Batched observables: k_batch_observe, ONE workgroup per replica as above, one record per replica and launch
+// (BatchObsArgs in batch_site.h has the record's layout).  The state is the one a batch step leaves: centre at site 0,
+// sites 1 .. L-1 right-canonical.
+//   norm^2           sum of squares of the centre tensor                                     (Engine::norm)
+//   site RDMs        one left-to-right pass of the transfer matrix T (dl x dl, starts as 1) up to the last listed site:
+//                    U = T^T C; at a listed site rho[j][j'] = sum_{a',s} U[a'][j][s] conj(C[a'][j'][s]); then
+//                    T'[s][s'] = sum_{a',j} U[a'][j][s] conj(C[a'][j][s'])                    (Engine::site_rdm)
+//   autocorrelation  the same pass without the conjugate over all L sites: U = T C, T' = C^T U (Engine::autocorr)
+//   energy           <C | H_eff C> + shift <C | C> with bt_heff at site 0                     (Engine::expect)
+// What is resident where: LDS holds the two operand tiles of wg_gemm and the reduction partials (17 472 bytes); T, its
+// successor, U and the X / Y / H C of the H_eff apply live in the observation's own carve of the replica's scratch area
+// (global memory, L2-resident), written and re-read by this workgroup only and ordered by workgroup barriers.  The T / U
+// products are wg_gemm; the d x d output of a site RDM is NOT (its K = dl dr is up to 4096 and d^2 may be 4): there K
+// is split over all 512 threads, four outputs at a time, and wg_reduce finishes in its fixed order.  Every element has
+// one owner thread and every sum one order: a record depends neither on B nor on the compute unit.  No atomics.
+__device__ __noinline__ void bo_rdm(const zc* U, const zc* C, int dl, int d, int dr, double* out, const BtSh& sh) {
+  const int tid = threadIdx.x, K = dl * dr, nout = d * d;
+  for (int e0 = 0; e0 < nout; e0 += 4) {
+    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = tid; k < K; k += SS_THREADS) {
+      const int a = k / dr, s = k - a * dr;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (e0 + q < nout) {
+          const int e = e0 + q, j = e / d, jp = e - j * d;
+          const zc u = U[((long)a * d + j) * dr + s], c = C[((long)a * d + jp) * dr + s];
+          acc[2 * q] += u.x * c.x + u.y * c.y;  // u conj(c)
+          acc[2 * q + 1] += u.y * c.x - u.x * c.y;
+        }
+    }
+    wg_reduce(acc, sh);
+    if (tid < 8 && 2 * e0 + tid < 2 * nout) out[2 * e0 + tid] = sh.red[tid];
+  }
+  __syncthreads();
+}
+
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 194 VGPRs -- those of bt_heff, the
+// non-inlined product function shared with k_batch_sweep -- so occupancy 2 waves per SIMD (one workgroup per compute
+// unit); no vector or scalar register spills; 128 bytes of private memory per lane (the argument blocks of the calls of
+// bo_rdm and bt_heff); 17 472 bytes of LDS.  The aim of 128 VGPRs (two workgroups per compute unit) is missed; the aim of
+// no spills inside the product loops is met.  k_batch_mean: 13 VGPRs, no LDS, no private memory.
+__global__ __launch_bounds__(SS_THREADS) void k_batch_observe(BatchObsArgs g) {
+  __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
+  __shared__ double s_d[SS_WAVES * 8 + 8];
+  BtSh sh{};
+  sh.mats = s_tiles;
+  sh.wsh = s_d;
+  sh.red = s_d + SS_WAVES * 8;
+  zc* tiles = s_tiles;
+
+  const int r = blockIdx.x, tid = threadIdx.x, L = g.L;
+  double* rec = g.rec + (size_t)r * g.rec_len;
+  for (long e = tid; e < g.rec_len; e += SS_THREADS) rec[e] = 0.0;
+  __syncthreads();
+  if (g.status[r] != SS_OK) return;  // a replica that failed: zeros
+  void* const* tab = g.ptrs + (size_t)r * g.ptr_stride;
+  const zc* const* site = reinterpret_cast<const zc* const*>(tab);
+  const zc* const* envL = reinterpret_cast<const zc* const*>(tab + L);
+  const zc* const* envR = reinterpret_cast<const zc* const*>(tab + 2 * L + 1);
+  const zc* const* w2l = reinterpret_cast<const zc* const*>(tab + 3 * L + 2);
+  zc* scr = reinterpret_cast<zc*>(tab[6 * L + 2]) + g.carve;
+  zc* T = scr + g.plan.o_t;
+  zc* T2 = scr + g.plan.o_t2;
+  zc* U = scr + g.plan.o_u;
+
+  const BatchShape s0 = g.shp[0];
+  const long N0 = (long)s0.dl * s0.d * s0.dr;
+  double n2 = 0.0;
+  if (g.what & (BOBS_NORM | BOBS_ENERGY)) {
+    const zc* C = site[0];
+    double s[1] = {0.0};
+    for (long e = tid; e < N0; e += SS_THREADS) { const zc z = C[e]; s[0] += z.x * z.x + z.y * z.y; }
+    wg_reduce(s, sh);
+    n2 = sh.red[0];
+    if ((g.what & BOBS_NORM) && tid == 0) rec[0] = n2;
+  }
+
+  if (g.what & BOBS_RDM) {
+    if (tid == 0) T[0] = make_double2(1.0, 0.0);
+    __syncthreads();
+    const int last = g.sites[g.nsites - 1];
+    int k = 0;
+    long off = BOBS_HEAD;
+    for (int p = 0; p <= last; ++p) {
+      const BatchShape s = g.shp[p];
+      const int dl = s.dl, d = s.d, dr = s.dr, ddr = d * dr;
+      const zc* C = site[p];
+      // U[a'][(j,s)] = sum_a T[a][a'] C[a][(j,s)]
+      wg_gemm<false, false>(dl, ddr, dl, tiles,
+          [&](int m, int kk) { return T[(long)kk * dl + m]; },
+          [&](int kk, int n) { return C[(long)kk * ddr + n]; },
+          [&](int m, int n, zc z) { U[(long)m * ddr + n] = z; });
+      if (g.sites[k] == p) {
+        bo_rdm(U, C, dl, d, dr, rec + off, sh);
+        off += 2L * d * d;
+        ++k;
+      }
+      if (p < last) {
+        // T'[s][s'] = sum_(a',j) U[(a',j)][s] conj(C[(a',j)][s'])
+        wg_gemm<false, false>(dr, dr, dl * d, tiles,
+            [&](int m, int kk) { return U[(long)kk * dr + m]; },
+            [&](int kk, int n) { const zc z = C[(long)kk * dr + n]; return make_double2(z.x, -z.y); },
+            [&](int m, int n, zc z) { T2[(long)m * dr + n] = z; });
+        zc* t = T; T = T2; T2 = t;
+      }
+    }
+  }
+
+  if (g.what & BOBS_AUTOCORR) {
+    if (tid == 0) T[0] = make_double2(1.0, 0.0);
+    __syncthreads();
+    for (int p = 0; p < L; ++p) {
+      const BatchShape s = g.shp[p];
+      const int dl = s.dl, d = s.d, dr = s.dr, ddr = d * dr;
+      const zc* C = site[p];
+      // U[m][(j,s)] = sum_n T[m][n] C[n][(j,s)]
+      wg_gemm<true, false>(dl, ddr, dl, tiles,
+          [&](int m, int kk) { return T[(long)m * dl + kk]; },
+          [&](int kk, int n) { return C[(long)kk * ddr + n]; },
+          [&](int m, int n, zc z) { U[(long)m * ddr + n] = z; });
+      // T'[i][j] = sum_(m,s) C[(m,s)][i] U[(m,s)][j]
+      wg_gemm<false, false>(dr, dr, dl * d, tiles,
+          [&](int m, int kk) { return C[(long)kk * dr + m]; },
+          [&](int kk, int n) { return U[(long)kk * dr + n]; },
+          [&](int m, int n, zc z) { T2[(long)m * dr + n] = z; });
+      zc* t = T; T = T2; T2 = t;
+    }
+    if (tid == 0) { const zc z = T[0]; rec[2] = z.x; rec[3] = z.y; }
+    __syncthreads();
+  }
+
+  if (g.what & BOBS_ENERGY) {
+    zc* H = scr + g.plan.o_h;
+    const zc* C = site[0];
+    bt_heff(s0, envL[0], w2l[0], envR[1], C, 1.0, scr + g.plan.o_x, scr + g.plan.o_y, H, tiles);
+    double acc[2] = {0.0, 0.0};
+    for (long e = tid; e < N0; e += SS_THREADS) {
+      const zc c = C[e], h = H[e];
+      acc[0] += c.x * h.x + c.y * h.y;  // conj(c) h
+      acc[1] += c.x * h.y - c.y * h.x;
+    }
+    wg_reduce(acc, sh);
+    if (tid == 0) {
+      const zc sft = g.shift[r];
+      rec[4] = sh.red[0] + sft.x * n2;
+      rec[5] = sh.red[1] + sft.y * n2;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_batch_mean(const double* __restrict__ rec, const double* __restrict__ w,
+                                                    double* __restrict__ mean, int nrep, long rec_len, long nrec) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= nrec * rec_len) return;
+  const long q = idx / rec_len, e = idx - q * rec_len;
+  const double* src = rec + (size_t)q * nrep * rec_len + e;
+  double acc = 0.0;
+  for (int r = 0; r < nrep; ++r) acc += w[r] * src[(size_t)r * rec_len];  // index order: deterministic by construction
+  mean[idx] = acc;
+}
+
 }  // namespace
 
 bool batch_plan(const BatchShape* shp, int L, BatchPlan& plan, std::string& why) {
@@ -643,6 +806,31 @@ void batch_sweep_launch(hipStream_t st, const BatchArgs& a, int nrep) {
   if (nrep < 1 || a.L < 1) throw ArgError("batch: nothing to launch");
   if (a.e.max_krylov < 1 || a.e.max_krylov > MAXK - 1) throw ArgError("batch: max_krylov must be in [1, 20]");
   hipLaunchKernelGGL(k_batch_sweep, dim3(nrep), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
+
+void batch_observe_plan(const BatchPlan& plan, BatchObsPlan& obs) {
+  size_t o = 0;
+  obs.o_t = o; o += (size_t)plan.max_bond;
+  obs.o_t2 = o; o += (size_t)plan.max_bond;
+  obs.o_u = o; o += (size_t)plan.max_site;
+  obs.o_x = o; o += (size_t)plan.nx;
+  obs.o_y = o; o += (size_t)plan.ny;
+  obs.o_h = o; o += (size_t)plan.max_site;
+  obs.total = o;
+}
+
+void batch_observe_launch(hipStream_t st, const BatchObsArgs& a, int nrep) {
+  if (nrep < 1 || a.L < 1) throw ArgError("batch: nothing to launch");
+  if (!(a.what & BOBS_ALL) || ((a.what & BOBS_RDM) != 0) != (a.nsites > 0)) throw ArgError("batch: nothing to observe");
+  hipLaunchKernelGGL(k_batch_observe, dim3(nrep), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
+
+void batch_mean_launch(hipStream_t st, const double* rec, const double* w, double* mean, int nrep, long rec_len, long nrec) {
+  const long total = nrec * rec_len;
+  if (nrep < 1 || total < 1) throw ArgError("batch: nothing to average");
+  hipLaunchKernelGGL(k_batch_mean, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, rec, w, mean, nrep, rec_len, nrec);
   HIP_CHECK(hipGetLastError());
 }
 

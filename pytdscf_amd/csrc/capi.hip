@@ -232,6 +232,29 @@ int mitdvp_batch_sweep(mitdvp_batch* b, double dt_au, int forward, int* statuses
   if (rc != MITDVP_OK) return rc;
   return batch_finish(b, st, statuses);
 }
+int mitdvp_batch_run(mitdvp_batch* b, double dt_au, int nsteps, int every, const int* sites, int nsites, int what,
+                     const double* weights, const mitdvp_batch_out* out, size_t counts[3], int* statuses) {
+  if (!b || !b->b) { g_err = "null handle"; return MITDVP_EINVAL; }
+  std::vector<int> st((size_t)b->b->size(), 0);
+  const int rc = guard(nullptr, [&] {
+    if (nsteps < 0 || every < 1 || nsteps % every != 0)
+      throw mitdvp::ArgError("batch: nsteps must be >= 0 and a multiple of every >= 1");
+    HIP_CHECK(hipSetDevice(b->b->device()));
+    const long nrdm = b->b->observe_sizes(sites, nsites, what);
+    if (counts) { counts[0] = (size_t)(nsteps / every + 1); counts[1] = (size_t)b->b->size(); counts[2] = (size_t)nrdm; }
+    if (!out) return;  // size query
+    mitdvp::Batch::ObsOut o;
+    o.norm = out->norm; o.autocorr = out->autocorr; o.energy = out->energy; o.rdm = out->rdm;
+    o.mean_norm2 = out->mean_norm2; o.mean_autocorr = out->mean_autocorr; o.mean_energy = out->mean_energy; o.mean_rdm = out->mean_rdm;
+    b->b->run(dt_au, nsteps, every, sites, nsites, what, weights, o, st.data());
+  });
+  if (rc != MITDVP_OK) return rc;
+  return batch_finish(b, st, statuses);
+}
+int mitdvp_batch_observe(mitdvp_batch* b, const int* sites, int nsites, int what, const double* weights,
+                         const mitdvp_batch_out* out, size_t counts[3]) {
+  return mitdvp_batch_run(b, 0.0, 0, 1, sites, nsites, what, weights, out, counts, nullptr);
+}
 void mitdvp_batch_destroy(mitdvp_batch* b) { delete b; }
 int mitdvp_invalidate_env(mitdvp_engine* h) { ENG_CALL(h, h->e->invalidate_env()); }
 int mitdvp_replace_site(mitdvp_engine* h, int isite, const double* reim, int gauge) {

@@ -20,6 +20,20 @@ class Batch {
 
   void step(double dt, int nsteps, int* statuses);        // statuses[i]: SS_OK / SS_ENOTCONV / SS_EZERO of replica i
   void sweep(double dt, bool forward, int* statuses);
+
+  // Host destinations of the observables, every one may be null; nrec records on the leading axis (mitdvp_batch_out).
+  struct ObsOut {
+    double *norm = nullptr, *autocorr = nullptr, *energy = nullptr, *rdm = nullptr;  // [nrec][B], [nrec][B][2], .., [nrec][B][nrdm][2]
+    double *mean_norm2 = nullptr, *mean_autocorr = nullptr, *mean_energy = nullptr, *mean_rdm = nullptr;
+  };
+  // validates the request (ArgError otherwise, every engine untouched): what non-empty, the RDM bit and the site list go
+  // together, sites in range and strictly ascending; returns sum d_p^2 over the listed sites
+  long observe_sizes(const int* sites, int nsites, int what);
+  // records the state before step 0 and after every `every`-th of nsteps steps (nsteps = 0: one observation of the
+  // current state): one k_batch_observe launch per record, ONE k_batch_mean launch for all of them, records on the device
+  // until the end, one host wait.  weights: B doubles or null (1 / B).
+  void run(double dt, int nsteps, int every, const int* sites, int nsites, int what, const double* weights, const ObsOut& out,
+           int* statuses);
   std::string status_message(int code) const;
   int size() const { return (int)eng_.size(); }
   int device() const { return device_; }
@@ -48,11 +62,24 @@ class Batch {
   std::vector<int> h_kprev_;
   long long n_launch_ = 0;
 
+  // observables: the carve behind the sweep's in a replica's scratch area, and the device buffers of a recorded run
+  BatchObsPlan obs_plan_;
+  size_t carve_ = 0;            // offset of the observation's carve, complex elements
+  double* d_rec_ = nullptr;     // [nrec][B][rec_len]
+  double* d_mean_ = nullptr;    // [nrec][rec_len]
+  double* d_w_ = nullptr;       // [B]
+  int* d_sites_ = nullptr;      // [L]
+  size_t rec_elems_ = 0, mean_elems_ = 0;
+  std::vector<double> h_w_, h_rec_, h_mean_;
+  std::vector<int> h_sites_;
+
   static std::vector<BatchShape> shapes_of(Engine& e);
   void validate();
-  void prepare(bool forward);
+  void prepare(bool forward, bool build_envs = true);
   void launch(double dt, bool forward);
-  void finish(bool ends_forward, int half_sweeps, int* statuses);
+  void launch_observe(int what, int nsites, long record, long rec_len);
+  void finish(bool ends_forward, int half_sweeps, int* statuses, int other_launches = 0);
+  void finish_observe(int launches, int* statuses);
 };
 
 }  // namespace mitdvp

@@ -9,6 +9,7 @@
 #include "capi_internal.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 mitdvp_batch::mitdvp_batch() = default;
@@ -86,6 +87,8 @@ void Batch::validate() {
     shapes_dirty_ = true;
   }
   plan_ = pl;
+  batch_observe_plan(plan_, obs_plan_);
+  carve_ = (plan_.total + 15) / 16 * 16;
 }
 
 Batch::Batch(const std::vector<Engine*>& engines) : eng_(engines) {
@@ -106,6 +109,8 @@ Batch::Batch(const std::vector<Engine*>& engines) : eng_(engines) {
   dev_alloc(d_kprev_, n * L_);
   dev_alloc(d_status_, n);
   dev_alloc(d_stats_, n * 4);
+  dev_alloc(d_w_, n);
+  dev_alloc(d_sites_, (size_t)L_);
 }
 
 Batch::~Batch() {
@@ -120,12 +125,16 @@ Batch::~Batch() {
   if (d_status_) (void)hipFree(d_status_);
   if (d_stats_) (void)hipFree(d_stats_);
   if (d_scratch_) (void)hipFree(d_scratch_);
+  if (d_rec_) (void)hipFree(d_rec_);
+  if (d_mean_) (void)hipFree(d_mean_);
+  if (d_w_) (void)hipFree(d_w_);
+  if (d_sites_) (void)hipFree(d_sites_);
   if (st_) (void)hipStreamDestroy(st_);
 }
 
 // Brings every engine to the state a half-sweep in direction `forward` starts from, makes the block buffers of every
 // bond exist, and rebuilds the device tables when a shape or a buffer moved since the last call.
-void Batch::prepare(bool forward) {
+void Batch::prepare(bool forward, bool build_envs) {
   const size_t n = eng_.size();
   const int begin = forward ? 0 : L_ - 1;
   // what depends on the engines' state is checked for ALL of them before any of them is touched
@@ -142,7 +151,7 @@ void Batch::prepare(bool forward) {
     Engine& e = *eng_[i];
     e.require_ready();
     e.ss_check();
-    if (L_ > 1) {
+    if (L_ > 1 && build_envs) {
       if (forward) e.build_right_envs();
       else e.build_left_envs();
     }
@@ -154,7 +163,7 @@ void Batch::prepare(bool forward) {
     e.ss_pull_kprev();
   }
   // scratch (grows only when the shapes or the number of replicas grew: the one other synchronisation)
-  const size_t per = (plan_.total + 15) / 16 * 16;
+  const size_t per = carve_ + (obs_plan_.total + 15) / 16 * 16;  // the sweep's carve, then the observation's
   if (per * n > scratch_elems_) {
     HIP_CHECK(hipStreamSynchronize(st_));
     if (d_scratch_) (void)hipFree(d_scratch_);
@@ -227,7 +236,7 @@ void Batch::launch(double dt, bool forward) {
 }
 
 // after the launches of a call: statuses, Krylov memories, counters, and the engines' own bookkeeping
-void Batch::finish(bool ends_forward, int half_sweeps, int* statuses) {
+void Batch::finish(bool ends_forward, int half_sweeps, int* statuses, int other_launches) {
   const size_t n = eng_.size();
   std::vector<int> st(n), kp(n * L_);
   std::vector<long long> stats(n * 4);
@@ -253,7 +262,7 @@ void Batch::finish(bool ends_forward, int half_sweeps, int* statuses) {
       e.cnt_.n_qr += (long long)half_sweeps * (L_ - 1);
       e.cnt_.n_env += (long long)half_sweeps * (L_ - 1);
     }
-    if (i == 0) e.cnt_.n_launch += half_sweeps;  // the batch's launches are counted once
+    if (i == 0) e.cnt_.n_launch += half_sweeps + other_launches;  // the batch's launches are counted once
     const int centre = ends_forward ? L_ - 1 : 0;
     for (int p = 0; p < L_; ++p) e.gauge_[p] = p < centre ? MITDVP_GAUGE_A : (p == centre ? MITDVP_GAUGE_PSI : MITDVP_GAUGE_B);
     e.center_ = centre;
@@ -293,6 +302,117 @@ void Batch::sweep(double dt, bool forward, int* statuses) {
   prepare(forward);
   launch(dt, forward);
   finish(L_ > 1 ? forward : false, 1, statuses);
+}
+
+// ---- observables (k_batch_observe, k_batch_mean) ----
+long Batch::observe_sizes(const int* sites, int nsites, int what) {
+  validate();
+  if (!(what & BOBS_ALL) || (what & ~BOBS_ALL)) throw ArgError("batch: nothing to observe (what must be a non-empty set of MITDVP_OBS_* bits)");
+  if (nsites < 0 || (nsites > 0 && !sites)) throw ArgError("batch: bad list of observed sites");
+  if (((what & BOBS_RDM) != 0) != (nsites > 0)) throw ArgError("batch: MITDVP_OBS_RDM and a non-empty list of sites go together");
+  long nrdm = 0;
+  for (int k = 0; k < nsites; ++k) {
+    if (sites[k] < 0 || sites[k] >= L_) throw ArgError("batch: observed site " + std::to_string(sites[k]) + " is out of range");
+    if (k > 0 && sites[k] <= sites[k - 1]) throw ArgError("batch: the observed sites must be strictly ascending");
+    nrdm += (long)shp_[sites[k]].d * shp_[sites[k]].d;
+    if (nrdm > BATCH_OBS_MAX_RDM)
+      throw ArgError("batch: the observed site RDMs have more than " + std::to_string(BATCH_OBS_MAX_RDM) + " elements per replica");
+  }
+  return nrdm;
+}
+
+void Batch::launch_observe(int what, int nsites, long record, long rec_len) {
+  BatchObsArgs a{};
+  a.L = L_;
+  a.what = what;
+  a.nsites = nsites;
+  a.shp = d_shp_;
+  a.ptrs = d_ptrs_;
+  a.ptr_stride = (int)ptrs_per_replica();
+  a.shift = d_shift_;
+  a.status = d_status_;
+  a.sites = d_sites_;
+  a.carve = carve_;
+  a.plan = obs_plan_;
+  a.rec = d_rec_ + (size_t)record * eng_.size() * rec_len;
+  a.rec_len = rec_len;
+  batch_observe_launch(st_, a, (int)eng_.size());
+  n_launch_ += 1;
+}
+
+// the end of a call that only observed: the one host wait; the engines keep their bookkeeping as it is
+void Batch::finish_observe(int launches, int* statuses) {
+  HIP_CHECK(hipStreamSynchronize(st_));
+  eng_[0]->cnt_.n_launch += launches;
+  for (size_t i = 0; statuses && i < eng_.size(); ++i) statuses[i] = SS_OK;
+}
+
+void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, int what, const double* weights, const ObsOut& out,
+                int* statuses) {
+  if (nsteps < 0) throw ArgError("batch: nsteps must be >= 0");
+  if (every < 1) throw ArgError("batch: every must be >= 1");
+  if (nsteps % every != 0) throw ArgError("batch: nsteps must be a multiple of every");
+  HIP_CHECK(hipSetDevice(device_));
+  const long nrdm = observe_sizes(sites, nsites, what);
+  const size_t n = eng_.size();
+  const long nrec = nsteps / every + 1, rec_len = BOBS_HEAD + 2 * nrdm;
+  prepare(true, nsteps > 0 || (what & BOBS_ENERGY));
+  // buffers of the records and their means (grow only), the site list and the weights
+  const size_t need_rec = (size_t)nrec * n * rec_len, need_mean = (size_t)nrec * rec_len;
+  if (need_rec > rec_elems_ || need_mean > mean_elems_) {
+    HIP_CHECK(hipStreamSynchronize(st_));
+    if (need_rec > rec_elems_) {
+      if (d_rec_) (void)hipFree(d_rec_);
+      d_rec_ = nullptr;
+      dev_alloc(d_rec_, need_rec);
+      rec_elems_ = need_rec;
+    }
+    if (need_mean > mean_elems_) {
+      if (d_mean_) (void)hipFree(d_mean_);
+      d_mean_ = nullptr;
+      dev_alloc(d_mean_, need_mean);
+      mean_elems_ = need_mean;
+    }
+  }
+  h_sites_.assign(sites, sites + nsites);
+  h_w_.assign(n, 1.0 / (double)n);
+  if (weights) h_w_.assign(weights, weights + n);
+  if (nsites) HIP_CHECK(hipMemcpyAsync(d_sites_, h_sites_.data(), (size_t)nsites * sizeof(int), hipMemcpyHostToDevice, st_));
+  HIP_CHECK(hipMemcpyAsync(d_w_, h_w_.data(), n * sizeof(double), hipMemcpyHostToDevice, st_));
+
+  launch_observe(what, nsites, 0, rec_len);
+  for (int s = 0; s < nsteps; ++s) {
+    launch(dt, true);
+    launch(dt, false);
+    if ((s + 1) % every == 0) launch_observe(what, nsites, (s + 1) / every, rec_len);
+  }
+  batch_mean_launch(st_, d_rec_, d_w_, d_mean_, (int)n, rec_len, nrec);
+  n_launch_ += 1;
+  const bool per_replica = out.norm || out.autocorr || out.energy || out.rdm;
+  h_mean_.resize(need_mean);
+  HIP_CHECK(hipMemcpyAsync(h_mean_.data(), d_mean_, need_mean * sizeof(double), hipMemcpyDeviceToHost, st_));
+  if (per_replica) {
+    h_rec_.resize(need_rec);
+    HIP_CHECK(hipMemcpyAsync(h_rec_.data(), d_rec_, need_rec * sizeof(double), hipMemcpyDeviceToHost, st_));
+  }
+  if (nsteps > 0) finish(false, nsteps * 2, statuses, (int)nrec + 1);
+  else finish_observe((int)nrec + 1, statuses);
+
+  for (long q = 0; q < nrec; ++q) {
+    const double* m = h_mean_.data() + (size_t)q * rec_len;
+    if (out.mean_norm2) out.mean_norm2[q] = m[0];
+    if (out.mean_autocorr) { out.mean_autocorr[2 * q] = m[2]; out.mean_autocorr[2 * q + 1] = m[3]; }
+    if (out.mean_energy) { out.mean_energy[2 * q] = m[4]; out.mean_energy[2 * q + 1] = m[5]; }
+    if (out.mean_rdm && nrdm) std::memcpy(out.mean_rdm + (size_t)q * 2 * nrdm, m + BOBS_HEAD, (size_t)2 * nrdm * sizeof(double));
+    for (size_t i = 0; per_replica && i < n; ++i) {
+      const double* r = h_rec_.data() + ((size_t)q * n + i) * rec_len;
+      const size_t at = (size_t)q * n + i;
+      if (out.norm) out.norm[at] = std::sqrt(r[0]);
+      if (out.autocorr) { out.autocorr[2 * at] = r[2]; out.autocorr[2 * at + 1] = r[3]; }
+      if (out.energy) { out.energy[2 * at] = r[4]; out.energy[2 * at + 1] = r[5]; }
+      if (out.rdm && nrdm) std::memcpy(out.rdm + at * 2 * nrdm, r + BOBS_HEAD, (size_t)2 * nrdm * sizeof(double));
+    }
+  }
 }
 
 std::string Batch::status_message(int code) const {

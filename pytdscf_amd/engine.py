@@ -778,6 +778,7 @@ class TDVPBatch:
         self._b = None
         self._key = None
         self.statuses = []
+        self.records = {}
         self._lib = _lib.load()
         try:
             for _ in range(n_replicas):
@@ -798,6 +799,7 @@ class TDVPBatch:
         self._b = None
         self._key = None
         self.statuses = []
+        self.records = {}
         self._lib = _lib.load()
         return self
 
@@ -835,9 +837,89 @@ class TDVPBatch:
                 _lib.check(rc)  # the call itself was refused
             _lib.check(st[bad], self.engines[bad]._h)
 
-    def propagate(self, dt_au: float, nsteps: int = 1):
-        """``nsteps`` time steps of every replica: two launches per time step for the whole batch."""
-        self._run(lambda b, st: self._lib.mitdvp_batch_step(b, float(dt_au), int(nsteps), st))
+    def propagate(self, dt_au: float, nsteps: int = 1, observe: dict | None = None, every: int = 1):
+        """``nsteps`` time steps of every replica: two launches per time step for the whole batch.
+
+        ``observe=None``: nothing else, returns ``None``.  ``observe=dict(...)`` with the arguments of ``observe``: a
+        recorded run (``mitdvp_batch_run``) -- the state before step 0 and after every ``every``-th step is observed on
+        the device, one launch per record, and everything comes back at the end of the call; returns what ``observe``
+        returns with a leading record axis of ``nsteps // every + 1``."""
+        if observe is None:
+            self._run(lambda b, st: self._lib.mitdvp_batch_step(b, float(dt_au), int(nsteps), st))
+            return None
+        return self._observed(float(dt_au), int(nsteps), int(every), **observe)
+
+    def observe(self, sites=(), norm: bool = True, autocorr: bool = False, energy: bool = False, weights=None,
+                per_replica: bool = True):
+        """The current state of every replica observed by ONE launch, the ensemble means formed by a second one
+        (``mitdvp_batch_observe``); all replicas must have their centre at site 0.  ``sites``: strictly ascending sites
+        whose one-site reduced densities are wanted.  Returns a dict of NumPy arrays: ``mean_norm2`` (the mean of the
+        SQUARED norms), ``mean_autocorr``, ``mean_energy``, ``mean_rdm`` (a list of (d, d) arrays, one per site) and, with
+        ``per_replica``, ``norm`` (B,), ``autocorr`` (B,), ``energy`` (B,), ``rdm`` (a list of (B, d, d) arrays) -- only
+        what was asked.  ``weights``: B numbers, default 1 / B each."""
+        rec = self._observed(0.0, 0, 1, sites=sites, norm=norm, autocorr=autocorr, energy=energy, weights=weights,
+                             per_replica=per_replica)
+        return {k: ([x[0] for x in v] if isinstance(v, list) else v[0]) for k, v in rec.items()}
+
+    def _observed(self, dt_au, nsteps, every, sites=(), norm=True, autocorr=False, energy=False, weights=None, per_replica=True):
+        n = len(self.engines)
+        sites = [int(p) for p in sites]
+        what = ((_lib.OBS_NORM if norm else 0) | (_lib.OBS_AUTOCORR if autocorr else 0) | (_lib.OBS_ENERGY if energy else 0)
+                | (_lib.OBS_RDM if sites else 0))
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+            if w.shape != (n,):
+                raise ValueError(f"weights must be {n} numbers, one per replica (got shape {w.shape})")
+        b = self._handle()
+        sarr = (C.c_int * max(len(sites), 1))(*sites)
+        cnt = (C.c_size_t * 3)()
+        wp = None if w is None else _dp(w)
+        _lib.check(self._lib.mitdvp_batch_run(b, dt_au, nsteps, every, sarr, len(sites), what, wp, None, cnt, None))
+        nrec, _, nrdm = int(cnt[0]), int(cnt[1]), int(cnt[2])
+        out = _lib.BatchOut()
+        keep = {}
+
+        def want(name, shape, dtype):
+            keep[name] = np.zeros(shape, dtype=dtype)
+            setattr(out, name, _dp(keep[name]))
+
+        if norm:
+            want("mean_norm2", (nrec,), np.float64)
+        if autocorr:
+            want("mean_autocorr", (nrec,), np.complex128)
+        if energy:
+            want("mean_energy", (nrec,), np.complex128)
+        if sites:
+            want("mean_rdm", (nrec, nrdm), np.complex128)
+        if per_replica:
+            if norm:
+                want("norm", (nrec, n), np.float64)
+            if autocorr:
+                want("autocorr", (nrec, n), np.complex128)
+            if energy:
+                want("energy", (nrec, n), np.complex128)
+            if sites:
+                want("rdm", (nrec, n, nrdm), np.complex128)
+        try:
+            self._run(lambda bb, st: self._lib.mitdvp_batch_run(bb, dt_au, nsteps, every, sarr, len(sites), what, wp,
+                                                                C.byref(out), cnt, st))
+        finally:
+            self.records = self._split(keep, sites)  # a replica that did not converge raises; what was recorded stays readable here
+        return self.records
+
+    def _split(self, keep, sites):
+        """the flat RDM axis cut into one (.., d, d) array per observed site"""
+        res = dict(keep)
+        dims = [self.engines[0].get_site_shape(p)[1] for p in sites]
+        for name in ("mean_rdm", "rdm"):
+            if name in res:
+                flat, parts, at = res[name], [], 0
+                for d in dims:
+                    parts.append(flat[..., at:at + d * d].reshape(flat.shape[:-1] + (d, d)))
+                    at += d * d
+                res[name] = parts
+        return res
 
     def sweep(self, dt_au: float, forward: bool):
         self._run(lambda b, st: self._lib.mitdvp_batch_sweep(b, float(dt_au), int(bool(forward)), st))
