@@ -181,6 +181,36 @@ int mitdvp_batch_observe(mitdvp_batch* b, const int* sites, int nsites, int what
                          const mitdvp_batch_out* out, size_t counts[3]);
 int mitdvp_batch_run(mitdvp_batch* b, double dt_au, int nsteps, int every, const int* sites, int nsites, int what,
                      const double* weights, const mitdvp_batch_out* out, size_t counts[3], int* statuses);
+/* One-site channels of a batch, applied between the two half-sweeps of every time step -- the slot of the reference's
+ * one_gate_to_apply (_mps_cls.py:489-492) -- by ONE more launch per step for the whole batch (k_batch_channel: one workgroup
+ * per replica walks the centre from site L-1 down to the lowest site with a channel, applying each site's channel to the
+ * centre tensor, and back up, rebuilding the left blocks).  While at least one channel is set a time step of
+ * mitdvp_batch_step / mitdvp_batch_run is three launches; with none set nothing changes.
+ *   mitdvp_batch_set_channel: `ops_reim` holds nops matrices d x d (row-major [k][out][in], interleaved re / im) for `site`;
+ *       NULL removes the site's channel.  MITDVP_CHANNEL_GATE (nops == 1): C[a,i,s] = sum_j U[i,j] C[a,j,s], as is -- U need
+ *       not be unitary.  MITDVP_CHANNEL_JUMP (2 <= nops <= 16): a Kraus channel {B_k} unravelled into quantum jumps: with
+ *       the centre at the site, w_k = |B_k C|^2, W = sum_k w_k in index order, one uniform u in [0, 1), the smallest k
+ *       whose running sum exceeds u W (if rounding leaves none, the last k with w_k > 0), and C <- B_k C sqrt(|C|^2 / w_k):
+ *       the norm before the jump is kept.  W == 0 stops that replica only (MITDVP_EINVAL in its status, "zero norm" in
+ *       its message; its tensors must be set again, as after MITDVP_ENOTCONV).  MITDVP_EINVAL (message:
+ *       mitdvp_last_error(NULL), nothing changed, every engine untouched) when the site is out of range, d is not the
+ *       site's physical dimension, nops is out of range for the kind, or the replicas run in imaginary time (relax == 1);
+ *       the message names the site and the limit.  mitdvp_batch_sweep (a single half-sweep) refuses while a channel is set.
+ *   mitdvp_batch_set_seed: the generator is counter-based, no state is stored: with mix(z) = { z ^= z >> 30;
+ *       z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31 } on 64-bit unsigned integers,
+ *       key = mix(mix(mix(seed ^ trajectory_id) + step) + site) and u = (key >> 11) * 2^-53, where step counts the batch's
+ *       completed time steps since this call (or creation: seed 0) -- the batch's count, advanced by every
+ *       mitdvp_batch_step / mitdvp_batch_run whether or not a channel is set and whatever the replicas' statuses are; it
+ *       does not say how far a replica that failed got.  trajectory_ids: n numbers, NULL = 0 .. n-1; a
+ *       replica's draws depend on its id only, not on n or its place in the batch.  Resets the step counter and the jump
+ *       counters.
+ *   mitdvp_batch_jump_counts: counts[n][nsite][16] (long long), how often operator k of a site's jump channel was picked
+ *       since the last mitdvp_batch_set_seed; sites without a jump channel are zeros.  One host wait. */
+#define MITDVP_CHANNEL_GATE 1
+#define MITDVP_CHANNEL_JUMP 2
+int mitdvp_batch_set_channel(mitdvp_batch* b, int site, int kind, const double* ops_reim, int nops, int d);
+int mitdvp_batch_set_seed(mitdvp_batch* b, unsigned long long seed, const unsigned long long* trajectory_ids);
+int mitdvp_batch_jump_counts(mitdvp_batch* b, long long* counts);
 /* propagate_along_sweep (_mps_cls.py:798-1014), one direction only. */
 int mitdvp_sweep(mitdvp_engine* h, double dt_au, int forward);
 /* The same half-sweep in parts: the next `nsites` local updates of the half-sweep in progress (one is started when none

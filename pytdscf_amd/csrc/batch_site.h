@@ -54,6 +54,31 @@ struct BatchArgs {
 // one launch: grid = nrep workgroups, a half-sweep of every replica
 void batch_sweep_launch(hipStream_t st, const BatchArgs& a, int nrep);
 
+// ---- one-site channels between the half-sweeps (k_batch_channel) ----
+constexpr int BATCH_MAX_JUMP = 16;  // operators of one jump channel
+enum { BCH_NONE = 0, BCH_GATE = 1, BCH_JUMP = 2 };  // the values of MITDVP_CHANNEL_* (include/mitdvp.h)
+struct BatchChanSite {
+  int kind, nops;   // BCH_*; 1 for a gate, 2 .. BATCH_MAX_JUMP for a jump channel
+  long long off;    // first operator in BatchChanArgs::ops, complex elements; nops matrices d x d, row-major, follow
+};
+struct BatchChanArgs {
+  int L, lo;                  // lo: the lowest site that carries a channel
+  const BatchShape* shp;      // [L], device
+  void* const* ptrs;          // the pointer table of BatchArgs
+  int ptr_stride;
+  int* status;                // [B]; W == 0 at a jump sets SS_EZERO on that replica
+  BatchPlan plan;
+  const BatchChanSite* chan;  // [L], device
+  const zc* ops;              // device, the operators of all channels
+  unsigned long long seed;
+  long long step;             // completed time steps of the batch since the seed was set
+  const unsigned long long* ids;  // [B] trajectory ids
+  long long* counts;          // [B][L][BATCH_MAX_JUMP]: how often operator k of site p was picked
+};
+// one launch: grid = nrep workgroups.  Precondition: centre at site L - 1, sites 0 .. L-2 in gauge A with valid left
+// blocks (the state a forward half-sweep leaves); the same state is left, with the channels applied.
+void batch_channel_launch(hipStream_t st, const BatchChanArgs& a, int nrep);
+
 // ---- batched observables (k_batch_observe, k_batch_mean) ----
 // what is wanted of an observation: the values of MITDVP_OBS_* (include/mitdvp.h)
 enum { BOBS_NORM = 1, BOBS_AUTOCORR = 2, BOBS_ENERGY = 4, BOBS_RDM = 8, BOBS_ALL = 15 };

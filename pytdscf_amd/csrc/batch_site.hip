@@ -1,5 +1,6 @@
 // batch_site.hip -- batched trajectories: k_batch_sweep, ONE workgroup per replica, a whole half-sweep per launch.
-// (Further down: k_batch_observe / k_batch_mean, the observables of every replica and their ensemble means, one launch each.)
+// (Further down: k_batch_observe / k_batch_mean, the observables of every replica and their ensemble means, one launch each;
+// k_batch_channel, one-site gates and quantum-jump channels between the two half-sweeps of a time step, one launch.)
 //
 // At trajectory shapes (d = 2..4, D <= 32, M <= 16) a local problem is a few tens of kilobytes, so one workgroup can own
 // one replica completely: the replica index is blockIdx.x, nothing is exchanged between workgroups, and therefore there is
@@ -758,6 +759,170 @@ __global__ __launch_bounds__(256) void k_batch_mean(const double* __restrict__ r
   mean[idx] = acc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// One-site channels between the two half-sweeps of a time step: k_batch_channel, ONE workgroup per replica as above, one
+// launch per time step (the slot of Engine::step's gates: forward half-sweep, maps with the centre at L-1, backward
+// half-sweep).  Precondition: the state a forward half-sweep leaves (centre at L-1, sites 0 .. L-2 in gauge A).
+//   downward walk  p = L-1 .. lo (the lowest site with a channel): the site's channel acts on the CENTRE tensor; then, for
+//                  p > lo, Psi -> sigma B (bt_qr in the backward sweep's roles) and Psi(p-1) = A(p-1) sigma.  No
+//                  environment work: the backward half-sweep rebuilds every right block itself.
+//   upward walk    p = lo .. L-2: Psi -> A sigma, L[p+1] by bt_env in the forward sweep's roles, Psi(p+1) = sigma B(p+1):
+//                  the centre is back at L-1 and every left block is valid.
+// A gate is C[a,i,s] = sum_j U[i,j] C[a,j,s], as is.  A jump channel {B_k} picks ONE k per visit: w_k = |B_k C|^2 (the
+// centre tensor carries the whole norm, so these are the branch weights of the state), W = sum_k w_k in index order, u
+// from the counter generator below, the smallest k whose running sum exceeds u W (if rounding leaves none: the last k
+// with w_k > 0), C <- B_k C sqrt(|C|^2 / w_k).  W == 0 is SS_EZERO for that replica.  The Krylov memories are not touched.
+// What is resident where: LDS holds the two operand tiles of wg_gemm, the Householder scalars of a gauge move, the
+// reduction partials and the K + 1 weights (20 168 bytes); the operators are read from the batch's device array
+// (L2-resident, a few hundred bytes a site); sigma, the spare tensor, the QR work matrix and X / Y of the environment
+// update are the sweep's carve of the replica's scratch area.  Every element has one owner thread and every sum one order.
+__device__ __forceinline__ unsigned long long bc_mix(unsigned long long z) {
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ULL;
+  z ^= z >> 27; z *= 0x94D049BB133111EBULL;
+  z ^= z >> 31;
+  return z;
+}
+// u in [0, 1): a function of (seed, trajectory, step, site) only -- no generator state anywhere
+__device__ __forceinline__ double bc_uniform(unsigned long long seed, unsigned long long traj, unsigned long long step, unsigned long long site) {
+  const unsigned long long key = bc_mix(bc_mix(bc_mix(seed ^ traj) + step) + site);
+  return (double)(key >> 11) * 0x1.0p-53;
+}
+
+// C[a,i,s] <- scl * sum_j Bm[i][j] C[a,j,s] by way of tmp; element e belongs to thread e % 512 in both passes
+__device__ __noinline__ void bc_apply(const zc* Bm, double scl, zc* C, zc* tmp, int dl, int d, int dr) {
+  const int ddr = d * dr;
+  const long N = (long)dl * ddr;
+  for (long e = threadIdx.x; e < N; e += SS_THREADS) {
+    const int a = (int)(e / ddr), rem = (int)(e - (long)a * ddr), i = rem / dr, s = rem - i * dr;
+    const zc* col = C + (long)a * ddr + s;
+    const zc* row = Bm + (long)i * d;
+    double re = 0.0, im = 0.0;
+    for (int j = 0; j < d; ++j) {
+      const zc b = row[j], c = col[(long)j * dr];
+      re = fma(b.x, c.x, re); re = fma(-b.y, c.y, re);
+      im = fma(b.x, c.y, im); im = fma(b.y, c.x, im);
+    }
+    tmp[e] = make_double2(re * scl, im * scl);
+  }
+  __syncthreads();
+  for (long e = threadIdx.x; e < N; e += SS_THREADS) C[e] = tmp[e];
+  __syncthreads();
+}
+
+// wk[k] = |B_k C|^2 for k < K, wk[BATCH_MAX_JUMP] = |C|^2: the same bits in every thread after the closing barrier.
+// Only the norms are kept: B_k C of the picked k is formed a second time by bc_apply (d multiply-adds per element, at
+// d <= 16 cheaper than a K-fold copy of the centre tensor in the scratch area).
+__device__ __noinline__ void bc_weights(const zc* ops, int K, const zc* C, int dl, int d, int dr, double* wk, const BtSh& sh) {
+  const int tid = threadIdx.x, ddr = d * dr;
+  const long N = (long)dl * ddr;
+  for (int k0 = 0; k0 < K; k0 += 4) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (long e = tid; e < N; e += SS_THREADS) {
+      const int a = (int)(e / ddr), rem = (int)(e - (long)a * ddr), i = rem / dr, s = rem - i * dr;
+      const zc* col = C + (long)a * ddr + s;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (k0 + q < K) {
+          const zc* row = ops + ((long)(k0 + q) * d + i) * d;
+          double re = 0.0, im = 0.0;
+          for (int j = 0; j < d; ++j) {
+            const zc b = row[j], c = col[(long)j * dr];
+            re = fma(b.x, c.x, re); re = fma(-b.y, c.y, re);
+            im = fma(b.x, c.y, im); im = fma(b.y, c.x, im);
+          }
+          acc[q] += re * re + im * im;
+        }
+    }
+    wg_reduce(acc, sh);
+    if (tid < 4 && k0 + tid < K) wk[k0 + tid] = sh.red[tid];
+  }
+  double s[1] = {0.0};
+  for (long e = tid; e < N; e += SS_THREADS) { const zc z = C[e]; s[0] += z.x * z.x + z.y * z.y; }
+  wg_reduce(s, sh);
+  if (tid == 0) wk[BATCH_MAX_JUMP] = sh.red[0];
+  __syncthreads();
+}
+
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 200 VGPRs -- those of the
+// non-inlined bt_env / bt_matmul shared with k_batch_sweep -- so occupancy 2 waves per SIMD (one workgroup per compute
+// unit); no vector or scalar register spills; 160 bytes of private memory per lane (the argument blocks of the calls);
+// 20 168 bytes of LDS.
+__global__ __launch_bounds__(SS_THREADS) void k_batch_channel(BatchChanArgs g) {
+  __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
+  __shared__ zc s_z[2 * BATCH_MAX_BOND];
+  __shared__ double s_d[SS_WAVES * 8 + 8 + BATCH_MAX_BOND + BATCH_MAX_JUMP + 1];
+  BtSh sh{};
+  sh.mats = s_tiles;
+  sh.udiag = s_z; sh.rdiag = s_z + BATCH_MAX_BOND;
+  sh.wsh = s_d; sh.red = sh.wsh + SS_WAVES * 8; sh.gam = sh.red + 8;
+  double* wk = sh.gam + BATCH_MAX_BOND;  // [BATCH_MAX_JUMP + 1]
+  zc* tiles = s_tiles;
+
+  const int r = blockIdx.x, tid = threadIdx.x, L = g.L;
+  if (g.status[r] != SS_OK) return;  // a replica that failed in an earlier launch of the call does no more work
+  void* const* tab = g.ptrs + (size_t)r * g.ptr_stride;
+  zc* const* site = reinterpret_cast<zc* const*>(tab);
+  zc* const* envL = reinterpret_cast<zc* const*>(tab + L);
+  const zc* const* w2el = reinterpret_cast<const zc* const*>(tab + 4 * L + 2);
+  zc* scr = reinterpret_cast<zc*>(tab[6 * L + 2]);
+  zc* sig = scr + g.plan.o_sig;
+  zc* spare = scr + g.plan.o_spare;
+  zc* work = scr + g.plan.o_work;
+  zc* X = scr + g.plan.o_x;
+  zc* Y = scr + g.plan.o_y;
+  const int lo = g.lo;
+
+  int rc = SS_OK;
+  for (int p = L - 1; p >= lo; --p) {
+    const BatchShape s = g.shp[p];
+    const int dl = s.dl, d = s.d, dr = s.dr;
+    const BatchChanSite ch = g.chan[p];
+    const zc* ops = g.ops + ch.off;
+    if (ch.kind == BCH_GATE) {
+      bc_apply(ops, 1.0, site[p], spare, dl, d, dr);
+    } else if (ch.kind == BCH_JUMP) {
+      const int K = ch.nops;
+      bc_weights(ops, K, site[p], dl, d, dr, wk, sh);
+      double W = 0.0;
+      for (int k = 0; k < K; ++k) W += wk[k];
+      if (!(W > 0.0)) { rc = SS_EZERO; break; }
+      const double u = bc_uniform(g.seed, g.ids[r], (unsigned long long)g.step, (unsigned long long)p);
+      const double thr = u * W;
+      int pick = -1, lastpos = 0;
+      double run = 0.0;
+      for (int k = 0; k < K; ++k) {
+        run += wk[k];
+        if (wk[k] > 0.0) lastpos = k;
+        if (pick < 0 && run > thr) pick = k;
+      }
+      if (pick < 0) pick = lastpos;
+      const double scl = sqrt(wk[BATCH_MAX_JUMP] / wk[pick]);
+      bc_apply(ops + (long)pick * d * d, scl, site[p], spare, dl, d, dr);  // its barriers order the reads of wk above
+      if (tid == 0) g.counts[((size_t)r * L + p) * BATCH_MAX_JUMP + pick] += 1;
+    }
+    if (p > lo) {
+      // Psi2sigmaB and Psi(p - 1) = A(p - 1) . sigma, as the backward sweep
+      const int mq = d * dr;
+      bt_qr(site[p], site[p], 1, mq, sig, 1, dl, mq, dl, work, sh);
+      const BatchShape q = g.shp[p - 1];
+      zc* prv = site[p - 1];
+      bt_matmul(prv, sig, spare, prv, q.dl * q.d, dl, dl, tiles);
+    }
+  }
+  if (rc == SS_OK)
+    for (int p = lo; p < L - 1; ++p) {
+      const BatchShape s = g.shp[p];
+      const int dl = s.dl, d = s.d, dr = s.dr;
+      // Psi2Asigma, L[p + 1], Psi(p + 1) = sigma . B(p + 1), as the forward sweep
+      bt_qr(site[p], site[p], dr, 1, sig, dr, 1, dl * d, dr, work, sh);
+      bt_env(envL[p], site[p], (long)d * dr, dr, 1, w2el[p], dl, s.ml, d, dr, s.mr, X, Y, envL[p + 1], tiles);
+      const BatchShape q = g.shp[p + 1];
+      zc* nxt = site[p + 1];
+      bt_matmul(sig, nxt, spare, nxt, dr, q.d * q.dr, dr, tiles);
+    }
+  if (rc != SS_OK && tid == 0) g.status[r] = rc;
+}
+
 }  // namespace
 
 bool batch_plan(const BatchShape* shp, int L, BatchPlan& plan, std::string& why) {
@@ -806,6 +971,13 @@ void batch_sweep_launch(hipStream_t st, const BatchArgs& a, int nrep) {
   if (nrep < 1 || a.L < 1) throw ArgError("batch: nothing to launch");
   if (a.e.max_krylov < 1 || a.e.max_krylov > MAXK - 1) throw ArgError("batch: max_krylov must be in [1, 20]");
   hipLaunchKernelGGL(k_batch_sweep, dim3(nrep), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
+
+void batch_channel_launch(hipStream_t st, const BatchChanArgs& a, int nrep) {
+  if (nrep < 1 || a.L < 1) throw ArgError("batch: nothing to launch");
+  if (a.lo < 0 || a.lo >= a.L) throw ArgError("batch: no channel is set");
+  hipLaunchKernelGGL(k_batch_channel, dim3(nrep), dim3(SS_THREADS), 0, st, a);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -255,6 +255,18 @@ int mitdvp_batch_observe(mitdvp_batch* b, const int* sites, int nsites, int what
                          const mitdvp_batch_out* out, size_t counts[3]) {
   return mitdvp_batch_run(b, 0.0, 0, 1, sites, nsites, what, weights, out, counts, nullptr);
 }
+int mitdvp_batch_set_channel(mitdvp_batch* b, int site, int kind, const double* ops_reim, int nops, int d) {
+  if (!b || !b->b) { g_err = "null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->set_channel(site, kind, ops_reim, nops, d); });
+}
+int mitdvp_batch_set_seed(mitdvp_batch* b, unsigned long long seed, const unsigned long long* trajectory_ids) {
+  if (!b || !b->b) { g_err = "null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->set_seed(seed, trajectory_ids); });
+}
+int mitdvp_batch_jump_counts(mitdvp_batch* b, long long* counts) {
+  if (!b || !b->b) { g_err = "null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->jump_counts(counts); });
+}
 void mitdvp_batch_destroy(mitdvp_batch* b) { delete b; }
 int mitdvp_invalidate_env(mitdvp_engine* h) { ENG_CALL(h, h->e->invalidate_env()); }
 int mitdvp_replace_site(mitdvp_engine* h, int isite, const double* reim, int gauge) {

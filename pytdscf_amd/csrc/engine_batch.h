@@ -1,4 +1,5 @@
 // engine_batch.h -- batched trajectories (engine_batch.hip): B borrowed engines stepped by one launch per half-sweep.
+// One-site gates and quantum-jump channels set on the batch act between the two half-sweeps of a time step: one more launch.
 #pragma once
 #include <string>
 #include <vector>
@@ -19,7 +20,17 @@ class Batch {
   Batch& operator=(const Batch&) = delete;
 
   void step(double dt, int nsteps, int* statuses);        // statuses[i]: SS_OK / SS_ENOTCONV / SS_EZERO of replica i
-  void sweep(double dt, bool forward, int* statuses);
+  void sweep(double dt, bool forward, int* statuses);  // refused while a channel is set
+
+  // One-site channels applied between the two half-sweeps of every time step (k_batch_channel, one more launch per step
+  // while at least one is set).  kind: BCH_GATE (nops == 1) or BCH_JUMP (2 <= nops <= BATCH_MAX_JUMP); ops_reim: nops
+  // matrices d x d, row-major, interleaved re / im; null removes the site's channel.  ArgError (nothing changed) when the
+  // site is out of range, d is not the site's physical dimension, nops is out of range or the replicas run in imaginary time.
+  void set_channel(int site, int kind, const double* ops_reim, int nops, int d);
+  // seed and trajectory ids (null: 0 .. B-1) of the jump generator; resets the step counter and the jump counters
+  void set_seed(unsigned long long seed, const unsigned long long* ids);
+  void jump_counts(long long* counts);  // [B][L][BATCH_MAX_JUMP], zeros where no jump channel acted
+  bool has_channels() const { return chan_lo_ >= 0; }
 
   // Host destinations of the observables, every one may be null; nrec records on the leading axis (mitdvp_batch_out).
   struct ObsOut {
@@ -73,12 +84,36 @@ class Batch {
   std::vector<double> h_w_, h_rec_, h_mean_;
   std::vector<int> h_sites_;
 
+  // channels: the table and the operators (host copies and their device images), the generator's seed, ids and step
+  // counter, the jump counters
+  std::vector<BatchChanSite> chan_;        // [L]
+  std::vector<std::vector<zc>> chan_ops_;  // [L] operators of a site's channel
+  int chan_lo_ = -1;                       // lowest site with a channel, -1: none
+  bool chan_dirty_ = false;
+  std::vector<BatchChanSite> h_chan_;
+  std::vector<zc> h_ops_;
+  BatchChanSite* d_chan_ = nullptr;
+  zc* d_ops_ = nullptr;
+  size_t ops_elems_ = 0;
+  unsigned long long seed_ = 0;
+  // The BATCH's count of time steps launched since the seed was set, the `step` of the generator: it advances by nsteps
+  // in every step / run call, with or without channels and whatever the replicas' statuses are -- it says nothing about
+  // how far a replica that failed got (its status word does, and it draws nothing more).
+  long long steps_done_ = 0;
+  std::vector<unsigned long long> h_ids_;
+  unsigned long long* d_ids_ = nullptr;
+  long long* d_counts_ = nullptr;
+
   static std::vector<BatchShape> shapes_of(Engine& e);
+  void check_channels() const;
+  void upload_channels();
+  void launch_channel(long long step);
+  void reset_generator(unsigned long long seed, const unsigned long long* ids);  // set_seed without its wait for the stream
   void validate();
   void prepare(bool forward, bool build_envs = true);
   void launch(double dt, bool forward);
   void launch_observe(int what, int nsites, long record, long rec_len);
-  void finish(bool ends_forward, int half_sweeps, int* statuses, int other_launches = 0);
+  void finish(bool ends_forward, int half_sweeps, int* statuses, int other_launches = 0, int channel_passes = 0);
   void finish_observe(int launches, int* statuses);
 };
 

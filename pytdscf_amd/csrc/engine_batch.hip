@@ -1,6 +1,8 @@
 // engine_batch.hip -- batched trajectories on the host side: a Batch borrows B ordinary engines (each owns its tensors and
 // its own MPO), owns the pointer tables, the status words and the per-replica scratch of k_batch_sweep (batch_site.hip),
-// and steps all replicas with ONE launch per half-sweep.  No host threads, no compute-unit masks, no persistent-launch
+// and steps all replicas with ONE launch per half-sweep (and, while one-site channels are set on the batch -- gates,
+// quantum-jump channels: the table, the operators, the generator's seed / ids / step counter and the jump counters are the
+// batch's -- ONE launch of k_batch_channel between the two half-sweeps of a time step).  No host threads, no compute-unit masks, no persistent-launch
 // admission: the kernel's workgroups never wait for each other.  Host waits of a call: ONE stream synchronisation, behind
 // the copy of the status words at its end (plain hipStreamSynchronize: the library's wait helper, wait_published, spins on
 // a mapped word, which this path has none of); besides it only what the engines' own preparation does on first use
@@ -111,6 +113,12 @@ Batch::Batch(const std::vector<Engine*>& engines) : eng_(engines) {
   dev_alloc(d_stats_, n * 4);
   dev_alloc(d_w_, n);
   dev_alloc(d_sites_, (size_t)L_);
+  dev_alloc(d_chan_, (size_t)L_);
+  dev_alloc(d_ids_, n);
+  dev_alloc(d_counts_, n * L_ * BATCH_MAX_JUMP);
+  chan_.assign((size_t)L_, BatchChanSite{BCH_NONE, 0, 0});
+  chan_ops_.assign((size_t)L_, {});
+  reset_generator(0, nullptr);  // nothing is queued on the new stream: no wait; a batch without channels pays two small async operations
 }
 
 Batch::~Batch() {
@@ -129,6 +137,10 @@ Batch::~Batch() {
   if (d_mean_) (void)hipFree(d_mean_);
   if (d_w_) (void)hipFree(d_w_);
   if (d_sites_) (void)hipFree(d_sites_);
+  if (d_chan_) (void)hipFree(d_chan_);
+  if (d_ops_) (void)hipFree(d_ops_);
+  if (d_ids_) (void)hipFree(d_ids_);
+  if (d_counts_) (void)hipFree(d_counts_);
   if (st_) (void)hipStreamDestroy(st_);
 }
 
@@ -236,7 +248,7 @@ void Batch::launch(double dt, bool forward) {
 }
 
 // after the launches of a call: statuses, Krylov memories, counters, and the engines' own bookkeeping
-void Batch::finish(bool ends_forward, int half_sweeps, int* statuses, int other_launches) {
+void Batch::finish(bool ends_forward, int half_sweeps, int* statuses, int other_launches, int channel_passes) {
   const size_t n = eng_.size();
   std::vector<int> st(n), kp(n * L_);
   std::vector<long long> stats(n * 4);
@@ -261,8 +273,12 @@ void Batch::finish(bool ends_forward, int half_sweeps, int* statuses, int other_
       e.cnt_.n_exp_bond += (long long)half_sweeps * (L_ - 1);
       e.cnt_.n_qr += (long long)half_sweeps * (L_ - 1);
       e.cnt_.n_env += (long long)half_sweeps * (L_ - 1);
+      if (channel_passes) {  // a channel pass: two gauge moves and one left block per site above the lowest channel
+        e.cnt_.n_qr += (long long)channel_passes * 2 * (L_ - 1 - chan_lo_);
+        e.cnt_.n_env += (long long)channel_passes * (L_ - 1 - chan_lo_);
+      }
     }
-    if (i == 0) e.cnt_.n_launch += half_sweeps + other_launches;  // the batch's launches are counted once
+    if (i == 0) e.cnt_.n_launch += half_sweeps + other_launches + channel_passes;  // the batch's launches are counted once
     const int centre = ends_forward ? L_ - 1 : 0;
     for (int p = 0; p < L_; ++p) e.gauge_[p] = p < centre ? MITDVP_GAUGE_A : (p == centre ? MITDVP_GAUGE_PSI : MITDVP_GAUGE_B);
     e.center_ = centre;
@@ -288,20 +304,130 @@ void Batch::step(double dt, int nsteps, int* statuses) {
     for (size_t i = 0; statuses && i < eng_.size(); ++i) statuses[i] = SS_OK;
     return;
   }
+  check_channels();
   prepare(true);
+  const bool chan = has_channels();  // without a channel: the two launches per step of before, nothing else
+  if (chan) upload_channels();
   for (int s = 0; s < nsteps; ++s) {
     launch(dt, true);
+    if (chan) launch_channel(steps_done_ + s);
     launch(dt, false);
   }
-  finish(false, nsteps * 2, statuses);
+  steps_done_ += nsteps;
+  finish(false, nsteps * 2, statuses, 0, chan ? nsteps : 0);
 }
 
 void Batch::sweep(double dt, bool forward, int* statuses) {
   HIP_CHECK(hipSetDevice(device_));
   validate();
+  if (has_channels())
+    throw ArgError("batch: a single half-sweep is refused while channels are set (site " + std::to_string(chan_lo_) +
+                   " carries one): they act between the two half-sweeps of a time step");
   prepare(forward);
   launch(dt, forward);
   finish(L_ > 1 ? forward : false, 1, statuses);
+}
+
+// ---- one-site channels between the half-sweeps (k_batch_channel) ----
+void Batch::set_channel(int site, int kind, const double* ops_reim, int nops, int d) {
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  if (site < 0 || site >= L_) throw ArgError("batch: channel site " + std::to_string(site) + " is out of range (the chain has " + std::to_string(L_) + " sites)");
+  const std::string at = "batch: channel on site " + std::to_string(site) + ": ";
+  if (ops_reim) {
+    if (kind != BCH_GATE && kind != BCH_JUMP) throw ArgError(at + "kind must be MITDVP_CHANNEL_GATE or MITDVP_CHANNEL_JUMP");
+    if (kind == BCH_GATE && nops != 1) throw ArgError(at + "a gate is one matrix (got " + std::to_string(nops) + ")");
+    if (kind == BCH_JUMP && (nops < 2 || nops > BATCH_MAX_JUMP))
+      throw ArgError(at + "a jump channel has 2 to " + std::to_string(BATCH_MAX_JUMP) + " operators (got " + std::to_string(nops) + ")");
+    if (d != shp_[site].d)
+      throw ArgError(at + "the operators are " + std::to_string(d) + " x " + std::to_string(d) + ", the site's physical dimension is " +
+                     std::to_string(shp_[site].d));
+    if (eng_[0]->cfg.relax != 0) throw ArgError(at + "channels do not go with imaginary time (relax must be 0)");
+    const size_t ne = (size_t)nops * d * d;
+    std::vector<zc> ops(ne);
+    for (size_t e = 0; e < ne; ++e) ops[e] = make_double2(ops_reim[2 * e], ops_reim[2 * e + 1]);
+    chan_ops_[site] = std::move(ops);
+    chan_[site] = BatchChanSite{kind, nops, 0};
+  } else {
+    chan_ops_[site].clear();
+    chan_[site] = BatchChanSite{BCH_NONE, 0, 0};
+  }
+  chan_lo_ = -1;
+  for (int p = L_ - 1; p >= 0; --p)
+    if (chan_[p].kind != BCH_NONE) chan_lo_ = p;
+  chan_dirty_ = true;
+}
+
+// what may have changed on the engines since the channels were set (validate() has just refreshed shp_)
+void Batch::check_channels() const {
+  if (!has_channels()) return;
+  if (eng_[0]->cfg.relax != 0) throw ArgError("batch: channels do not go with imaginary time (relax must be 0)");
+  for (int p = 0; p < L_; ++p)
+    if (chan_[p].kind != BCH_NONE && chan_ops_[p].size() != (size_t)chan_[p].nops * shp_[p].d * shp_[p].d)
+      throw ArgError("batch: channel on site " + std::to_string(p) + ": the operators no longer match the site's physical dimension " +
+                     std::to_string(shp_[p].d));
+}
+
+void Batch::upload_channels() {
+  if (!chan_dirty_) return;
+  h_chan_ = chan_;
+  h_ops_.clear();
+  for (int p = 0; p < L_; ++p) {
+    h_chan_[p].off = (long long)h_ops_.size();
+    h_ops_.insert(h_ops_.end(), chan_ops_[p].begin(), chan_ops_[p].end());
+  }
+  if (h_ops_.size() > ops_elems_) {
+    HIP_CHECK(hipStreamSynchronize(st_));
+    if (d_ops_) (void)hipFree(d_ops_);
+    d_ops_ = nullptr;
+    dev_alloc(d_ops_, h_ops_.size());
+    ops_elems_ = h_ops_.size();
+  }
+  HIP_CHECK(hipMemcpyAsync(d_chan_, h_chan_.data(), h_chan_.size() * sizeof(BatchChanSite), hipMemcpyHostToDevice, st_));
+  if (!h_ops_.empty()) HIP_CHECK(hipMemcpyAsync(d_ops_, h_ops_.data(), h_ops_.size() * sizeof(zc), hipMemcpyHostToDevice, st_));
+  chan_dirty_ = false;
+}
+
+void Batch::launch_channel(long long step) {
+  BatchChanArgs a{};
+  a.L = L_;
+  a.lo = chan_lo_;
+  a.shp = d_shp_;
+  a.ptrs = d_ptrs_;
+  a.ptr_stride = (int)ptrs_per_replica();
+  a.status = d_status_;
+  a.plan = plan_;
+  a.chan = d_chan_;
+  a.ops = d_ops_;
+  a.seed = seed_;
+  a.step = step;
+  a.ids = d_ids_;
+  a.counts = d_counts_;
+  batch_channel_launch(st_, a, (int)eng_.size());
+  n_launch_ += 1;
+}
+
+void Batch::set_seed(unsigned long long seed, const unsigned long long* ids) {
+  HIP_CHECK(hipSetDevice(device_));
+  HIP_CHECK(hipStreamSynchronize(st_));  // h_ids_ may still be the source of an earlier copy
+  reset_generator(seed, ids);
+}
+
+void Batch::reset_generator(unsigned long long seed, const unsigned long long* ids) {
+  const size_t n = eng_.size();
+  seed_ = seed;
+  steps_done_ = 0;
+  h_ids_.resize(n);
+  for (size_t i = 0; i < n; ++i) h_ids_[i] = ids ? ids[i] : (unsigned long long)i;
+  HIP_CHECK(hipMemcpyAsync(d_ids_, h_ids_.data(), n * sizeof(unsigned long long), hipMemcpyHostToDevice, st_));
+  HIP_CHECK(hipMemsetAsync(d_counts_, 0, n * L_ * BATCH_MAX_JUMP * sizeof(long long), st_));
+}
+
+void Batch::jump_counts(long long* counts) {
+  if (!counts) throw ArgError("batch: null destination for the jump counters");
+  HIP_CHECK(hipSetDevice(device_));
+  HIP_CHECK(hipMemcpyAsync(counts, d_counts_, eng_.size() * L_ * BATCH_MAX_JUMP * sizeof(long long), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipStreamSynchronize(st_));
 }
 
 // ---- observables (k_batch_observe, k_batch_mean) ----
@@ -356,7 +482,10 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   const long nrdm = observe_sizes(sites, nsites, what);
   const size_t n = eng_.size();
   const long nrec = nsteps / every + 1, rec_len = BOBS_HEAD + 2 * nrdm;
+  const bool chan = has_channels() && nsteps > 0;
+  if (chan) check_channels();
   prepare(true, nsteps > 0 || (what & BOBS_ENERGY));
+  if (chan) upload_channels();
   // buffers of the records and their means (grow only), the site list and the weights
   const size_t need_rec = (size_t)nrec * n * rec_len, need_mean = (size_t)nrec * rec_len;
   if (need_rec > rec_elems_ || need_mean > mean_elems_) {
@@ -383,6 +512,7 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   launch_observe(what, nsites, 0, rec_len);
   for (int s = 0; s < nsteps; ++s) {
     launch(dt, true);
+    if (chan) launch_channel(steps_done_ + s);
     launch(dt, false);
     if ((s + 1) % every == 0) launch_observe(what, nsites, (s + 1) / every, rec_len);
   }
@@ -395,7 +525,8 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
     h_rec_.resize(need_rec);
     HIP_CHECK(hipMemcpyAsync(h_rec_.data(), d_rec_, need_rec * sizeof(double), hipMemcpyDeviceToHost, st_));
   }
-  if (nsteps > 0) finish(false, nsteps * 2, statuses, (int)nrec + 1);
+  steps_done_ += nsteps;
+  if (nsteps > 0) finish(false, nsteps * 2, statuses, (int)nrec + 1, chan ? nsteps : 0);
   else finish_observe((int)nrec + 1, statuses);
 
   for (long q = 0; q < nrec; ++q) {
@@ -420,7 +551,8 @@ std::string Batch::status_message(int code) const {
   if (code == SS_ENOTCONV)
     return std::string(e0.cfg.integrator == MITDVP_LANCZOS ? "Short Iterative Lanczos" : "Short Iterative Arnoldi") +
            " is not converged in " + std::to_string(e0.cfg.max_krylov) + " basis. Try shorter time interval.";
-  if (code == SS_EZERO) return "Initial psi has zero norm.";
+  if (code == SS_EZERO)
+    return has_channels() ? "Initial psi has zero norm, or every operator of a jump channel gave it zero weight." : "Initial psi has zero norm.";
   return "batch: unknown status " + std::to_string(code);
 }
 

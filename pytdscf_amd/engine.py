@@ -779,6 +779,8 @@ class TDVPBatch:
         self._key = None
         self.statuses = []
         self.records = {}
+        self._channels = {}
+        self._seed = None
         self._lib = _lib.load()
         try:
             for _ in range(n_replicas):
@@ -800,6 +802,8 @@ class TDVPBatch:
         self._key = None
         self.statuses = []
         self.records = {}
+        self._channels = {}
+        self._seed = None
         self._lib = _lib.load()
         return self
 
@@ -824,7 +828,112 @@ class TDVPBatch:
             b = C.c_void_p()
             _lib.check(self._lib.mitdvp_batch_create(hs, n, C.byref(b)))
             self._b, self._key = b, key
+            try:  # a handle made anew (the list of engines changed) gets the channels again and counts steps from 0
+                for site, (kind, ops) in self._channels.items():
+                    self._push_channel(site, kind, ops)
+                if self._seed is not None:
+                    seed, ids = self._seed
+                    if ids is not None and len(ids) != n:  # the library reads one id per replica
+                        raise ValueError(f"the batch has {n} replicas now, trajectory_ids were given for {len(ids)}: "
+                                         "call set_jumps again")
+                    self._push_seed(seed, ids)
+            except Exception:
+                self._drop()
+                raise
         return self._b
+
+    # ---- one-site channels between the two half-sweeps of a time step (mitdvp_batch_set_channel) ----
+    def _push_channel(self, site, kind, ops):
+        if ops is None:
+            _lib.check(self._lib.mitdvp_batch_set_channel(self._b, int(site), 0, None, 0, 0))
+        else:
+            _lib.check(self._lib.mitdvp_batch_set_channel(self._b, int(site), kind, _dp(ops), ops.shape[0], ops.shape[1]))
+
+    def _push_seed(self, seed, ids):
+        arr = None if ids is None else (C.c_uint64 * len(ids))(*ids)
+        _lib.check(self._lib.mitdvp_batch_set_seed(self._b, C.c_uint64(seed), arr))
+
+    def _set_channels(self, kind, table):
+        """``table``: {site: operators (K, d, d) or None}.  The library validates; a refused table changes nothing."""
+        new = {}
+        for site, ops in dict(table).items():
+            if ops is not None:
+                ops = _c128(ops)
+                if kind == _lib.CHANNEL_GATE and ops.ndim == 1:  # a diagonal gate, as TDVPEngine.set_gates takes it
+                    ops = np.diag(ops)
+                if kind == _lib.CHANNEL_GATE and ops.ndim == 2:
+                    ops = ops[None]
+                if ops.ndim != 3 or ops.shape[1] != ops.shape[2]:
+                    raise ValueError(f"site {site}: the operators must be square matrices, (K, d, d); got shape {ops.shape}")
+                ops = np.ascontiguousarray(ops)
+            new[int(site)] = (kind, ops)
+        self._handle()
+        done = []
+        try:
+            for site, (k, ops) in new.items():
+                self._push_channel(site, k, ops)
+                done.append(site)
+        except Exception:
+            for site in done:  # back to what was set before
+                self._push_channel(site, *self._channels.get(site, (0, None)))
+            raise
+        for site, (k, ops) in new.items():
+            if ops is None:
+                self._channels.pop(site, None)
+            else:
+                self._channels[site] = (k, ops)
+
+    def set_gates(self, gates: dict):
+        """``{site: U (d, d) or a length-d diagonal}``: one-site gates applied to every replica between the two half-sweeps of each time step
+        (the reference's ``one_gate_to_apply``), as they are -- ``U`` need not be unitary.  ``{site: None}`` removes a
+        site's channel.  One more launch per time step while any channel is set.  The replicas must have their tensors
+        and MPOs already (the library checks the physical dimensions)."""
+        self._set_channels(_lib.CHANNEL_GATE, gates)
+
+    def set_jumps(self, jumps: dict, seed: int = 0, trajectory_ids=None):
+        """``{site: B (K, d, d)}``, 2 <= K <= 16: a Kraus channel per site unravelled into quantum jumps -- at every time
+        step each replica picks ONE operator k with probability |B_k psi|^2 / sum_k |B_k psi|^2 and keeps its norm.  The
+        uniforms are ``trajectories.jump_uniform(seed, trajectory_id, step, site)``; ``trajectory_ids`` (default
+        0 .. B-1) name the replicas, so a chunked ensemble draws what one big batch draws.  Sets the seed: the step
+        counter and ``jump_counts()`` start again from zero.  ``{site: None}`` removes a site's channel.
+
+        The step counter and the jump counters live in the library's batch object.  That object is made anew when the
+        list ``engines`` is changed between calls (an engine replaced, added or taken out); the channels and the seed
+        are then set again on the new one, so the step counter and the jump counters start again from zero in the
+        middle of an ensemble, and ``trajectory_ids`` given for another number of replicas raise ``ValueError`` until
+        ``set_jumps`` is called again."""
+        n = len(self.engines)
+        ids = None
+        if trajectory_ids is not None:
+            ids = [int(t) for t in trajectory_ids]
+            if len(ids) != n or any(not 0 <= t < 2**64 for t in ids):
+                raise ValueError(f"trajectory_ids must be {n} integers in [0, 2^64), one per replica")
+        seed = int(seed)
+        if not 0 <= seed < 2**64:
+            raise ValueError("seed must be in [0, 2^64)")
+        stale, made = self._seed, self._b
+        self._seed = (seed, ids)  # a batch object made anew inside this call gets these ids, not the ones of before
+        try:
+            self._set_channels(_lib.CHANNEL_JUMP, jumps)
+            self._push_seed(seed, ids)
+        except Exception:
+            self._seed = stale
+            if self._b is not made:  # made anew with the seed that was refused: the next call makes it again
+                self._drop()
+            raise
+
+    def jump_counts(self):
+        """(B, L, 16) integers: how often operator k of site p's jump channel was picked by replica r since the seed
+        was set; zeros where no jump channel acts.  They start again from zero with every ``set_jumps`` and when the
+        list ``engines`` was changed since the last call (see ``set_jumps``)."""
+        n, nsite = len(self.engines), self.engines[0].nsite
+        out = np.zeros((n, nsite, _lib.MAX_JUMP), dtype=np.int64)
+        _lib.check(self._lib.mitdvp_batch_jump_counts(self._handle(), out.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return out
+
+    def launches(self) -> int:
+        """kernel launches counted so far on replica 0, where the batch's launches are counted once"""
+        return int(self.engines[0].counters()["n_launch"])
 
     def _run(self, call):
         n = len(self.engines)

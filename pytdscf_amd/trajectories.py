@@ -2,6 +2,9 @@
 ``Simulator.propagate(reduced_density=...)``, the densities averaged afterwards: tests/test_mixedstate.py:239-318) as ONE
 ``TDVPBatch`` whose observables and ensemble means are formed on the device (``mitdvp_batch_run``).
 
+One-site gates (``Model(one_gate_to_apply=...)``) and sampled one-site Kraus channels (``jumps=``: quantum-jump
+trajectories at Hilbert-space cost) act between the two half-sweeps of every step, inside the batch (``k_batch_channel``).
+
 Nothing falls back: a model the batched kernels do not take raises with the library's message."""
 
 from __future__ import annotations
@@ -11,6 +14,47 @@ import numpy as np
 from . import units
 from .engine import TDVPBatch
 from .mps import product_state_cores
+
+
+_M64 = (1 << 64) - 1
+
+
+def _mix(z: int) -> int:
+    z ^= z >> 30
+    z = (z * 0xBF58476D1CE4E5B9) & _M64
+    z ^= z >> 27
+    z = (z * 0x94D049BB133111EB) & _M64
+    z ^= z >> 31
+    return z
+
+
+def jump_uniform(seed: int, trajectory_id: int, step: int, site: int) -> float:
+    """The uniform in [0, 1) that ``k_batch_channel`` draws for the jump channel on ``site`` of trajectory
+    ``trajectory_id`` in time step ``step`` (completed steps since the seed was set): counter-based, no state --
+    ``key = mix(mix(mix(seed ^ trajectory_id) + step) + site)``, ``u = (key >> 11) * 2**-53`` on 64-bit unsigned integers."""
+    seed, trajectory_id, step, site = (int(x) & _M64 for x in (seed, trajectory_id, step, site))
+    key = _mix((_mix((_mix(seed ^ trajectory_id) + step) & _M64) + site) & _M64)
+    return (key >> 11) * 2.0 ** -53
+
+
+def _jump_table(jumps, dims):
+    """{site: (K, d, d) complex} checked against the model's dimensions and the kernel's limits, before any engine exists"""
+    from ._lib import MAX_JUMP
+
+    table = {}
+    for site, B in dict(jumps).items():
+        site = int(site)
+        if not 0 <= site < len(dims):
+            raise ValueError(f"jumps: site {site} is out of range")
+        B = np.asarray(B, dtype=np.complex128)
+        if B.ndim != 3 or B.shape[1] != B.shape[2]:
+            raise ValueError(f"jumps[{site}] must have shape (K, d, d), got {B.shape}")
+        if B.shape[1] != dims[site]:
+            raise ValueError(f"jumps[{site}]: the operators are {B.shape[1]} x {B.shape[1]}, the site's dimension is {dims[site]}")
+        if not 2 <= B.shape[0] <= MAX_JUMP:
+            raise ValueError(f"jumps[{site}]: a jump channel has 2 to {MAX_JUMP} operators, got {B.shape[0]}")
+        table[site] = B
+    return table
 
 
 def _one_site_keys(keys, nsite):
@@ -27,15 +71,25 @@ def _one_site_keys(keys, nsite):
 
 
 def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, weights=None, integrator="lanczos",
-                           conserve_norm=True, per_trajectory=False, thresh_sil=1.0e-09, device=0):
+                           conserve_norm=True, per_trajectory=False, thresh_sil=1.0e-09, device=0, jumps=None, seed=0,
+                           replicas_per_start=1, first_trajectory=0):
     """Propagate every Hartree product of ``starts`` under ``model`` and average their one-site reduced densities.
 
-    ``model``: a ``Model`` as the shell takes it (one electronic state, Hilbert space, no gates or Kraus maps);
+    ``model``: a ``Model`` as the shell takes it (one electronic state, Hilbert space); its ``one_gate_to_apply``
+    (one-site gates only) becomes gates of the batch, applied between the half-sweeps of every step as the reference
+    applies them; ``kraus_op`` is refused (in the reference it means a purified state, not trajectories);
     ``starts``: a list of Hartree products as ``Model.init_HartreeProduct[0]`` takes them; ``stepsize`` in fs;
     ``reduced_density = ([(s, s), ...], every)`` as ``Simulator.propagate`` takes it.  As there, the state is observed
     BEFORE steps 0, every, 2 every, ... < ``maxstep``; steps after the last observation are not run.
     Returns ``{"time": (nrec,) in fs, "mean": {key: (nrec, d, d)}}`` and, with ``per_trajectory``,
-    ``"trajectories": {key: (nrec, len(starts), d, d)}``.  ``weights``: one number per start, default equal weights."""
+    ``"trajectories": {key: (nrec, len(starts), d, d)}``.  ``weights``: one number per start, default equal weights.
+
+    ``jumps={site: B (K, d, d)}``: a one-site Kraus channel per listed site (e.g. ``kraus.lindblad_to_kraus(ops, dt)``),
+    unravelled into quantum jumps: every trajectory picks one operator per site and step with the state's own
+    probabilities and keeps its norm, so the MEAN over many trajectories follows the channel.  ``replicas_per_start``
+    repeats every start that often (the trajectory axis and ``weights`` then run over the expanded list, start-major);
+    trajectory i of the expanded list draws ``jump_uniform(seed, first_trajectory + i, step, site)``, so an ensemble
+    cut into chunks (``first_trajectory`` = the chunk's offset) draws the same numbers as one big batch."""
     if integrator not in ("lanczos", "arnoldi"):
         raise ValueError(f"Invalid integrator: {integrator}")
     keys, every = reduced_density
@@ -47,21 +101,41 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
     key_sites = _one_site_keys(keys, nsite)
     if not keys:
         raise ValueError("reduced_density names no key")
-    if model.nstate != 1 or model.space != "hilbert" or model.one_gate_to_apply is not None or model.kraus_op:
-        raise NotImplementedError("propagate_trajectories: one electronic state in Hilbert space without gates or Kraus maps")
+    if model.nstate != 1 or model.space != "hilbert":
+        raise NotImplementedError("propagate_trajectories: one electronic state in Hilbert space")
+    if model.kraus_op:
+        raise NotImplementedError("propagate_trajectories: kraus_op means a purified state (a Kraus leg that grows); "
+                                  "pass a one-site channel as jumps={site: B} to sample it instead")
+    gates = model.one_gate_to_apply.one_site_gates(model.dims) if model.one_gate_to_apply is not None else {}
+    jump_table = _jump_table(jumps or {}, model.dims)
+    both = sorted(set(gates) & set(jump_table))
+    if both:
+        raise ValueError(f"site {both[0]} has a gate and a jump channel: a site carries one channel")
+    replicas_per_start, first_trajectory = int(replicas_per_start), int(first_trajectory)
+    if replicas_per_start < 1 or first_trajectory < 0:
+        raise ValueError("replicas_per_start must be >= 1 and first_trajectory >= 0")
     starts = list(starts)
     if not starts:
         raise ValueError("no start states")
+    nrep = len(starts) * replicas_per_start
     sites = sorted(set(key_sites))
     dt_au = stepsize / units.au_in_fs
     nsteps = (maxstep - 1) // every * every
     D = model.m_aux_max if model.m_aux_max is not None else 10**9
     mpo = model.project_mpo(model.hamiltonian.as_mpo(model.dims))
-    bt = TDVPBatch(len(starts), nsite, device=device, integrator=integrator, conserve_norm=conserve_norm, thresh=thresh_sil)
+    bt = TDVPBatch(nrep, nsite, device=device, integrator=integrator, conserve_norm=conserve_norm, thresh=thresh_sil)
     try:
-        for e, start in zip(bt.engines, starts):
+        for i, e in enumerate(bt.engines):
             e.set_mpo(mpo, 0, shift=model.hamiltonian.coupleJ[0][0])
-            e.set_mps(product_state_cores(start, D, space=model.space), canonicalize=True, scale=1.0)
+            if i % replicas_per_start == 0:  # a start is brought to canonical form once; its repeats get those very tensors
+                e.set_mps(product_state_cores(starts[i // replicas_per_start], D, space=model.space), canonicalize=True, scale=1.0)
+                canonical = e.get_mps()
+            else:
+                e.set_mps(canonical)
+        if gates:
+            bt.set_gates(gates)
+        if jump_table:
+            bt.set_jumps(jump_table, seed=seed, trajectory_ids=range(first_trajectory, first_trajectory + nrep))
         rec = bt.propagate(dt_au, nsteps, observe=dict(sites=sites, norm=False, weights=weights, per_replica=per_trajectory),
                            every=every)
     finally:
