@@ -181,6 +181,29 @@ int mitdvp_batch_observe(mitdvp_batch* b, const int* sites, int nsites, int what
                          const mitdvp_batch_out* out, size_t counts[3]);
 int mitdvp_batch_run(mitdvp_batch* b, double dt_au, int nsteps, int every, const int* sites, int nsites, int what,
                      const double* weights, const mitdvp_batch_out* out, size_t counts[3], int* statuses);
+/* Multi-site reduced densities of a batch (k_batch_density: one workgroup per replica, ONE launch forms every key of every
+ * replica; the one k_batch_mean launch of the call averages them with everything else).  A key is a row of nsite leg
+ * counts as mitdvp_reduced_density takes it -- 2: ket and bra leg kept, 1: the diagonal, 0: traced out -- and its values
+ * have that call's layout bit for bit: kept sites ascending, (ket, bra) per two-leg site, not symmetrised, not normalised.
+ * remain_nleg is [nkeys][nsite]; the keys' values are concatenated in list order, ndens complex numbers per replica:
+ * density[record][replica][ndens][2], mean_density[record][ndens][2]; either may be NULL.  sites / what / weights / out are
+ * those of mitdvp_batch_run, except that `what` may be 0 (and out NULL) when nkeys > 0; with nkeys == 0 the two calls ARE
+ * mitdvp_batch_observe / mitdvp_batch_run: the same bits, the same refusals.  counts (may be NULL) receives {records,
+ * replicas, nrdm, ndens}; with out == NULL && density == NULL && mean_density == NULL the call only validates what does
+ * not depend on the engines' state and returns the counts.  The state required is that of mitdvp_batch_observe (centre at
+ * site 0).  Launches: per record one more than without keys, and k_batch_observe is skipped when what == 0, so a record
+ * costs at most two; mitdvp_batch_run_keys makes at most 2 nsteps + 2 records + 1.  A replica that failed has zeros.
+ * MITDVP_EINVAL (message: mitdvp_last_error(NULL), naming the key and the limit; every engine untouched) when a leg count
+ * is outside 0 .. 2, a key keeps no leg, there are more than 64 keys, for some key and site (open physical legs collected
+ * before the site) x (the wider bond of the site)^2 exceeds 65536 complex elements (1 MB per replica and buffer: two
+ * two-leg sites at d = 4, D = 32 are 16 x 1024; at d = 8, D = 32 they are on the limit; three at d = 4 are refused), the
+ * site RDMs and all keys together exceed 65536 elements per replica, or the centre is not at site 0. */
+int mitdvp_batch_observe_keys(mitdvp_batch* b, const int* sites, int nsites, const int* remain_nleg, int nkeys, int what,
+                              const double* weights, const mitdvp_batch_out* out, double* density, double* mean_density,
+                              size_t counts[4]);
+int mitdvp_batch_run_keys(mitdvp_batch* b, double dt_au, int nsteps, int every, const int* sites, int nsites,
+                          const int* remain_nleg, int nkeys, int what, const double* weights, const mitdvp_batch_out* out,
+                          double* density, double* mean_density, size_t counts[4], int* statuses);
 /* One-site channels of a batch, applied between the two half-sweeps of every time step -- the slot of the reference's
  * one_gate_to_apply (_mps_cls.py:489-492) -- by ONE more launch per step for the whole batch (k_batch_channel: one workgroup
  * per replica walks the centre from site L-1 down to the lowest site with a channel, applying each site's channel to the

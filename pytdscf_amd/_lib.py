@@ -86,6 +86,7 @@ class BatchOut(C.Structure):
 OBS_NORM, OBS_AUTOCORR, OBS_ENERGY, OBS_RDM = 1, 2, 4, 8
 CHANNEL_GATE, CHANNEL_JUMP = 1, 2
 MAX_JUMP = 16  # operators of one jump channel (BATCH_MAX_JUMP)
+MAX_DENSITY_KEYS = 64  # keys of one density request (BATCH_DENS_MAX_KEYS)
 
 COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t)
 P2P_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t)  # mitdvp_p2p_fn
@@ -233,6 +234,8 @@ def load() -> C.CDLL:
         "mitdvp_batch_destroy": (None, [vp]),
         "mitdvp_batch_observe": (i, [vp, ip, i, i, dp, C.POINTER(BatchOut), C.POINTER(C.c_size_t)]),
         "mitdvp_batch_run": (i, [vp, d, i, i, ip, i, i, dp, C.POINTER(BatchOut), C.POINTER(C.c_size_t), ip]),
+        "mitdvp_batch_observe_keys": (i, [vp, ip, i, ip, i, i, dp, C.POINTER(BatchOut), dp, dp, C.POINTER(C.c_size_t)]),
+        "mitdvp_batch_run_keys": (i, [vp, d, i, i, ip, i, ip, i, i, dp, C.POINTER(BatchOut), dp, dp, C.POINTER(C.c_size_t), ip]),
         "mitdvp_batch_set_channel": (i, [vp, i, i, dp, i, i]),
         "mitdvp_batch_set_seed": (i, [vp, C.c_uint64, C.POINTER(C.c_uint64)]),
         "mitdvp_batch_jump_counts": (i, [vp, C.POINTER(C.c_longlong)]),

@@ -114,4 +114,40 @@ void batch_observe_launch(hipStream_t st, const BatchObsArgs& a, int nrep);
 // one launch: mean[q][e] = sum_r w[r] rec[q][r][e], r in index order, one thread per (q, e)
 void batch_mean_launch(hipStream_t st, const double* rec, const double* w, double* mean, int nrep, long rec_len, long nrec);
 
+// ---- batched multi-site reduced densities (k_batch_density) ----
+// A key keeps, per site, both legs (2: ket and bra), the diagonal (1) or nothing (0), as Engine::reduced_density takes
+// it.  Its values follow the site RDMs in the replica's record (rec_len = BOBS_HEAD + 2 nrdm + 2 ndens), key after key in
+// list order; within a key: kept sites ascending, (ket, bra) per two-leg site, not symmetrised, not normalised.
+// Envelope, decided on the host: at most BATCH_DENS_MAX_KEYS keys; legs 0 .. 2, at least one kept; for every key and
+// every site up to its last kept one, (open physical legs collected before the site) x (the wider bond of the site)^2
+// <= BATCH_OBS_MAX_OPEN complex elements (1 MB per replica and buffer: a pair of two-leg sites at d = 4, D = 32 is
+// 16 x 1024; at d = 8, D = 32 it is on the limit; three at d = 4, D = 32 are refused); site RDMs and keys together at
+// most BATCH_OBS_MAX_RDM elements per replica.
+constexpr int BATCH_DENS_MAX_KEYS = 64;
+constexpr long BATCH_OBS_MAX_OPEN = 65536;
+struct BatchDensPlan {
+  long ndens = 0;   // complex elements of all keys of one replica together
+  size_t need = 1;  // largest (open legs x bond matrix) any key reaches: one transfer buffer, complex elements
+};
+// false + a message naming the key and the limit; legs: [nkeys][L]; nrdm: what the site RDMs of the same record take
+bool batch_density_plan(const BatchShape* shp, int L, const int* legs, int nkeys, long nrdm, BatchDensPlan& plan, std::string& why);
+
+struct BatchDensArgs {
+  int L, nkeys, zero_head;  // zero_head: no k_batch_observe ran on this record, its head and site RDMs are zeroed here
+  const BatchShape* shp;    // [L], device
+  void* const* ptrs;        // the pointer table of BatchArgs
+  int ptr_stride;
+  const int* status;        // [B]: a replica whose word is set does no work, its densities are zeros
+  const int* legs;          // [nkeys][L], device
+  size_t carve;             // offset of the observation's carve in a replica's scratch area (U = T^T C lives there)
+  BatchObsPlan plan;
+  zc* tbuf;                 // [B][2][need]: the transfer blocks T_o of a replica and their successors
+  size_t need;
+  double* rec;              // [B][rec_len]: this observation's records
+  long rec_len, dens_off;   // dens_off = BOBS_HEAD + 2 nrdm: where the first key starts
+};
+// one launch: grid = nrep workgroups.  Precondition: centre at site 0, sites 1 .. L-1 in gauge B.  On the stream of
+// batch_observe_launch and behind it when both write one record (k_batch_observe zeroes the whole record first).
+void batch_density_launch(hipStream_t st, const BatchDensArgs& a, int nrep);
+
 }  // namespace mitdvp

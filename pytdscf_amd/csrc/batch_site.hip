@@ -760,6 +760,131 @@ __global__ __launch_bounds__(256) void k_batch_mean(const double* __restrict__ r
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Batched multi-site reduced densities: k_batch_density, ONE workgroup per replica as above, every key of the request
+// for every replica in one launch (BatchDensArgs in batch_site.h has the envelope and the record's layout).  The state
+// is k_batch_observe's: centre at site 0, sites 1 .. L-1 right-canonical, so everything right of a key's last kept site
+// drops out.  Per key the arithmetic of Engine::reduced_density: the open physical legs collected so far form an index o
+// (row-major over the earlier kept legs), T_o[a][a'] (ket bond, bra bond) is the transfer block of o, T = 1 before site
+// 0.  At site p, for each o in turn, U = T_o^T C (bd_tu), then by the key's leg count n at p
+//   n = 0            T'_o[s][s'] = sum_(a',j) U[a'][j][s] conj(C[a'][j][s'])                  as the one-site pass
+//   n = 2, p < last  T'_(o,j,j')[s][s'] = sum_a' U[a'][j][s] conj(C[a'][j'][s'])               ONE product (d dr) x (d dr)
+//                    over K = dl whose store scatters to the (o, j, j', s, s') order -- no permutation pass
+//   n = 1, p < last  the same with j' = j only: d products dr x dr over K = dl
+//   p = last         rho_o[j][j'] = sum_(a',s) U[a'][j][s] conj(C[a'][j'][s]) by bo_rdm's K-split reduction (n = 2), its
+//                    diagonal alone by bd_diag (n = 1), written straight into the record.
+// All three T' forms are ONE non-inlined product function, bd_uc, with one wg_gemm in it.
+// What is resident where: LDS holds the two operand tiles of wg_gemm and the reduction partials (17 472 bytes, as
+// k_batch_observe); U is the observation carve's U buffer (one o at a time); the T_o of a replica and their successors
+// are the batch's own device buffer [B][2][need], need = the largest (open legs x bond matrix) a key of the request
+// reaches.  Everything is written and re-read by this workgroup only and ordered by workgroup barriers.  Every element
+// has one owner thread and every sum one order: a replica's densities depend neither on B nor on the compute unit.  No
+// atomics, and every loop is bounded by the shapes and the keys.
+//
+// U[a'][n] = sum_a T[a][a'] C[a][n], n = (j, s)
+__device__ __noinline__ void bd_tu(const zc* T, const zc* C, zc* U, int dl, int ddr, zc* tiles) {
+  wg_gemm<false, false>(dl, ddr, dl, tiles,
+      [&](int m, int kk) { return T[(long)kk * dl + m]; },
+      [&](int kk, int n) { return C[(long)kk * ddr + n]; },
+      [&](int m, int n, zc z) { U[(long)m * ddr + n] = z; });
+}
+
+// out(m, n) = sum_k U[k * ldk + m] conj(C[k * ldk + n]) for m, n < mn; with m = (jm, sm), n = (jn, sn) in blocks of blk
+// the result goes to out[((jm * nb + jn) * blk + sm) * blk + sn]: blk = mn, nb = 1 is a plain row-major mn x mn matrix.
+__device__ __noinline__ void bd_uc(const zc* U, const zc* C, zc* out, int mn, int K, long ldk, int blk, int nb, zc* tiles) {
+  wg_gemm<false, false>(mn, mn, K, tiles,
+      [&](int m, int kk) { return U[kk * ldk + m]; },
+      [&](int kk, int n) { const zc z = C[kk * ldk + n]; return make_double2(z.x, -z.y); },
+      [&](int m, int n, zc z) {
+        const int jm = m / blk, sm = m - jm * blk, jn = n / blk, sn = n - jn * blk;
+        out[(((long)jm * nb + jn) * blk + sm) * blk + sn] = z;
+      });
+}
+
+// out[j] = sum_(a',s) U[a'][j][s] conj(C[a'][j][s]): the diagonal of bo_rdm's matrix, K split the same way
+__device__ __noinline__ void bd_diag(const zc* U, const zc* C, int dl, int d, int dr, double* out, const BtSh& sh) {
+  const int tid = threadIdx.x, K = dl * dr;
+  for (int j0 = 0; j0 < d; j0 += 4) {
+    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = tid; k < K; k += SS_THREADS) {
+      const int a = k / dr, s = k - a * dr;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (j0 + q < d) {
+          const long at = ((long)a * d + j0 + q) * dr + s;
+          const zc u = U[at], c = C[at];
+          acc[2 * q] += u.x * c.x + u.y * c.y;  // u conj(c)
+          acc[2 * q + 1] += u.y * c.x - u.x * c.y;
+        }
+    }
+    wg_reduce(acc, sh);
+    if (tid < 8 && 2 * j0 + tid < 2 * d) out[2 * j0 + tid] = sh.red[tid];
+  }
+  __syncthreads();
+}
+
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 148 VGPRs, occupancy 3 waves per
+// SIMD (still one workgroup per compute unit); no vector register spills, 13 scalar registers spilled to vector lanes
+// around the calls; 112 bytes of private memory per lane (the argument blocks of the calls of the stage functions, none
+// of it inside a product loop); 17 472 bytes of LDS.  The aim of no scalar spills is missed; DESIGN.md section 7.3.
+__global__ __launch_bounds__(SS_THREADS) void k_batch_density(BatchDensArgs g) {
+  __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
+  __shared__ double s_d[SS_WAVES * 8 + 8];
+  BtSh sh{};
+  sh.mats = s_tiles;
+  sh.wsh = s_d;
+  sh.red = s_d + SS_WAVES * 8;
+  zc* tiles = s_tiles;
+
+  const int r = blockIdx.x, tid = threadIdx.x, L = g.L;
+  double* rec = g.rec + (size_t)r * g.rec_len;
+  for (long e = (g.zero_head ? 0 : g.dens_off) + tid; e < g.rec_len; e += SS_THREADS) rec[e] = 0.0;
+  __syncthreads();
+  if (g.status[r] != SS_OK) return;  // a replica that failed: zeros
+  void* const* tab = g.ptrs + (size_t)r * g.ptr_stride;
+  const zc* const* site = reinterpret_cast<const zc* const*>(tab);
+  zc* U = reinterpret_cast<zc*>(tab[6 * L + 2]) + g.carve + g.plan.o_u;
+  zc* Ta = g.tbuf + (size_t)r * 2 * g.need;
+  zc* Tb = Ta + g.need;
+  double* out = rec + g.dens_off;
+
+  for (int k = 0; k < g.nkeys; ++k) {
+    const int* legs = g.legs + (size_t)k * L;
+    int last = 0;
+    for (int p = 0; p < L; ++p)
+      if (legs[p]) last = p;
+    zc *T = Ta, *T2 = Tb;
+    if (tid == 0) T[0] = make_double2(1.0, 0.0);
+    __syncthreads();
+    long no = 1;
+    for (int p = 0; p <= last; ++p) {
+      const BatchShape s = g.shp[p];
+      const int dl = s.dl, d = s.d, dr = s.dr, ddr = d * dr, n = legs[p];
+      const long tl = (long)dl * dl, tr = (long)dr * dr;
+      const zc* C = site[p];
+      for (long o = 0; o < no; ++o) {
+        bd_tu(T + o * tl, C, U, dl, ddr, tiles);
+        if (p < last) {
+          if (n == 0) bd_uc(U, C, T2 + o * tr, dr, dl * d, dr, dr, 1, tiles);
+          else if (n == 2) bd_uc(U, C, T2 + o * d * d * tr, ddr, dl, ddr, dr, d, tiles);
+          else
+            for (int j = 0; j < d; ++j) bd_uc(U + (long)j * dr, C + (long)j * dr, T2 + (o * d + j) * tr, dr, dl, ddr, dr, 1, tiles);
+        } else if (n == 2) {
+          bo_rdm(U, C, dl, d, dr, out + o * 2 * d * d, sh);
+        } else {
+          bd_diag(U, C, dl, d, dr, out + o * 2 * d, sh);
+        }
+      }
+      if (p < last) {
+        no *= n == 2 ? d * d : (n == 1 ? d : 1);
+        zc* t = T; T = T2; T2 = t;
+      } else {
+        out += 2 * no * (n == 2 ? d * d : d);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // One-site channels between the two half-sweeps of a time step: k_batch_channel, ONE workgroup per replica as above, one
 // launch per time step (the slot of Engine::step's gates: forward half-sweep, maps with the centre at L-1, backward
 // half-sweep).  Precondition: the state a forward half-sweep leaves (centre at L-1, sites 0 .. L-2 in gauge A).
@@ -996,6 +1121,53 @@ void batch_observe_launch(hipStream_t st, const BatchObsArgs& a, int nrep) {
   if (nrep < 1 || a.L < 1) throw ArgError("batch: nothing to launch");
   if (!(a.what & BOBS_ALL) || ((a.what & BOBS_RDM) != 0) != (a.nsites > 0)) throw ArgError("batch: nothing to observe");
   hipLaunchKernelGGL(k_batch_observe, dim3(nrep), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
+
+bool batch_density_plan(const BatchShape* shp, int L, const int* legs, int nkeys, long nrdm, BatchDensPlan& plan, std::string& why) {
+  plan = BatchDensPlan{};
+  if (nkeys < 0 || (nkeys > 0 && !legs)) { why = "batch: bad list of density keys"; return false; }
+  if (nkeys > BATCH_DENS_MAX_KEYS) {
+    why = "batch: " + std::to_string(nkeys) + " density keys, one call takes at most " + std::to_string(BATCH_DENS_MAX_KEYS);
+    return false;
+  }
+  for (int k = 0; k < nkeys; ++k) {
+    const int* lg = legs + (size_t)k * L;
+    std::string name = "batch: density key " + std::to_string(k) + " (legs";
+    for (int p = 0; p < L; ++p) name += " " + std::to_string(lg[p]);
+    name += "): ";
+    int last = -1;
+    for (int p = 0; p < L; ++p) {
+      if (lg[p] < 0 || lg[p] > 2) { why = name + "the number of legs of site " + std::to_string(p) + " must be 0, 1 or 2"; return false; }
+      if (lg[p]) last = p;
+    }
+    if (last < 0) { why = name + "it keeps no leg (the number of legs must be greater than 0 at one site at least)"; return false; }
+    long no = 1;
+    for (int p = 0; p <= last; ++p) {
+      const long dd = std::max(shp[p].dl, shp[p].dr), d = shp[p].d;
+      if (no * dd * dd > BATCH_OBS_MAX_OPEN) {
+        why = name + std::to_string(no) + " open legs reach site " + std::to_string(p) + " (bonds " + std::to_string(shp[p].dl) + ", " +
+              std::to_string(shp[p].dr) + "): " + std::to_string(no * dd * dd) + " elements of transfer blocks, the batched kernel takes at most " +
+              std::to_string(BATCH_OBS_MAX_OPEN);
+        return false;
+      }
+      plan.need = std::max(plan.need, (size_t)(no * dd * dd));
+      no *= lg[p] == 2 ? d * d : (lg[p] == 1 ? d : 1);  // <= 65536 * 64 * 64: no overflow
+    }
+    plan.ndens += no;
+    if (nrdm + plan.ndens > BATCH_OBS_MAX_RDM) {
+      why = name + "the site RDMs and the keys up to this one have more than " + std::to_string(BATCH_OBS_MAX_RDM) + " elements per replica";
+      return false;
+    }
+  }
+  return true;
+}
+
+void batch_density_launch(hipStream_t st, const BatchDensArgs& a, int nrep) {
+  if (nrep < 1 || a.L < 1) throw ArgError("batch: nothing to launch");
+  if (a.nkeys < 1 || !a.legs || !a.tbuf || a.need < 1 || a.dens_off < BOBS_HEAD || a.dens_off >= a.rec_len)
+    throw ArgError("batch: no density key to observe");
+  hipLaunchKernelGGL(k_batch_density, dim3(nrep), dim3(SS_THREADS), 0, st, a);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -232,24 +232,46 @@ int mitdvp_batch_sweep(mitdvp_batch* b, double dt_au, int forward, int* statuses
   if (rc != MITDVP_OK) return rc;
   return batch_finish(b, st, statuses);
 }
-int mitdvp_batch_run(mitdvp_batch* b, double dt_au, int nsteps, int every, const int* sites, int nsites, int what,
-                     const double* weights, const mitdvp_batch_out* out, size_t counts[3], int* statuses) {
+int mitdvp_batch_run_keys(mitdvp_batch* b, double dt_au, int nsteps, int every, const int* sites, int nsites,
+                          const int* remain_nleg, int nkeys, int what, const double* weights, const mitdvp_batch_out* out,
+                          double* density, double* mean_density, size_t counts[4], int* statuses) {
   if (!b || !b->b) { g_err = "null handle"; return MITDVP_EINVAL; }
   std::vector<int> st((size_t)b->b->size(), 0);
   const int rc = guard(nullptr, [&] {
     if (nsteps < 0 || every < 1 || nsteps % every != 0)
       throw mitdvp::ArgError("batch: nsteps must be >= 0 and a multiple of every >= 1");
+    if (nkeys < 0 || (nkeys > 0 && !remain_nleg)) throw mitdvp::ArgError("batch: bad list of density keys");
     HIP_CHECK(hipSetDevice(b->b->device()));
-    const long nrdm = b->b->observe_sizes(sites, nsites, what);
-    if (counts) { counts[0] = (size_t)(nsteps / every + 1); counts[1] = (size_t)b->b->size(); counts[2] = (size_t)nrdm; }
-    if (!out) return;  // size query
+    const long nrdm = b->b->observe_sizes(sites, nsites, what, nkeys > 0);
+    const long ndens = b->b->density_sizes(remain_nleg, nkeys, nrdm);
+    if (counts) {
+      counts[0] = (size_t)(nsteps / every + 1); counts[1] = (size_t)b->b->size(); counts[2] = (size_t)nrdm; counts[3] = (size_t)ndens;
+    }
+    if (!out && !density && !mean_density) return;  // size query
     mitdvp::Batch::ObsOut o;
-    o.norm = out->norm; o.autocorr = out->autocorr; o.energy = out->energy; o.rdm = out->rdm;
-    o.mean_norm2 = out->mean_norm2; o.mean_autocorr = out->mean_autocorr; o.mean_energy = out->mean_energy; o.mean_rdm = out->mean_rdm;
-    b->b->run(dt_au, nsteps, every, sites, nsites, what, weights, o, st.data());
+    if (out) {
+      o.norm = out->norm; o.autocorr = out->autocorr; o.energy = out->energy; o.rdm = out->rdm;
+      o.mean_norm2 = out->mean_norm2; o.mean_autocorr = out->mean_autocorr; o.mean_energy = out->mean_energy; o.mean_rdm = out->mean_rdm;
+    }
+    mitdvp::Batch::DensOut dn;
+    dn.legs = remain_nleg; dn.nkeys = nkeys; dn.density = density; dn.mean_density = mean_density;
+    b->b->run(dt_au, nsteps, every, sites, nsites, what, weights, o, st.data(), dn);
   });
   if (rc != MITDVP_OK) return rc;
   return batch_finish(b, st, statuses);
+}
+int mitdvp_batch_observe_keys(mitdvp_batch* b, const int* sites, int nsites, const int* remain_nleg, int nkeys, int what,
+                              const double* weights, const mitdvp_batch_out* out, double* density, double* mean_density,
+                              size_t counts[4]) {
+  return mitdvp_batch_run_keys(b, 0.0, 0, 1, sites, nsites, remain_nleg, nkeys, what, weights, out, density, mean_density, counts, nullptr);
+}
+// the nkeys = 0 case of mitdvp_batch_run_keys
+int mitdvp_batch_run(mitdvp_batch* b, double dt_au, int nsteps, int every, const int* sites, int nsites, int what,
+                     const double* weights, const mitdvp_batch_out* out, size_t counts[3], int* statuses) {
+  size_t c4[4] = {0, 0, 0, 0};
+  const int rc = mitdvp_batch_run_keys(b, dt_au, nsteps, every, sites, nsites, nullptr, 0, what, weights, out, nullptr, nullptr, c4, statuses);
+  if (counts && (rc == MITDVP_OK || c4[1] != 0)) { counts[0] = c4[0]; counts[1] = c4[1]; counts[2] = c4[2]; }
+  return rc;
 }
 int mitdvp_batch_observe(mitdvp_batch* b, const int* sites, int nsites, int what, const double* weights,
                          const mitdvp_batch_out* out, size_t counts[3]) {

@@ -37,14 +37,31 @@ class Batch {
     double *norm = nullptr, *autocorr = nullptr, *energy = nullptr, *rdm = nullptr;  // [nrec][B], [nrec][B][2], .., [nrec][B][nrdm][2]
     double *mean_norm2 = nullptr, *mean_autocorr = nullptr, *mean_energy = nullptr, *mean_rdm = nullptr;
   };
-  // validates the request (ArgError otherwise, every engine untouched): what non-empty, the RDM bit and the site list go
-  // together, sites in range and strictly ascending; returns sum d_p^2 over the listed sites
-  long observe_sizes(const int* sites, int nsites, int what);
+  // validates the request (ArgError otherwise, every engine untouched): what non-empty (it may be empty when density keys
+  // are asked: with_keys), the RDM bit and the site list go together, sites in range and strictly ascending; returns
+  // sum d_p^2 over the listed sites
+  long observe_sizes(const int* sites, int nsites, int what, bool with_keys = false);
+  // Multi-site reduced densities (k_batch_density): nkeys rows of L leg counts (2: ket and bra, 1: diagonal, 0: traced
+  // out), as Engine::reduced_density takes one.  density_sizes validates the keys against the envelope of
+  // batch_density_plan (ArgError naming the key and the limit otherwise, every engine untouched) and returns the complex
+  // elements of all keys of one replica together; nrdm: what observe_sizes returned for the same request.
+  struct DensOut {
+    const int* legs = nullptr;  // [nkeys][L]
+    int nkeys = 0;
+    double *density = nullptr, *mean_density = nullptr;  // [nrec][B][ndens][2], [nrec][ndens][2]; each may be null
+  };
+  long density_sizes(const int* legs, int nkeys, long nrdm);
   // records the state before step 0 and after every `every`-th of nsteps steps (nsteps = 0: one observation of the
   // current state): one k_batch_observe launch per record, ONE k_batch_mean launch for all of them, records on the device
-  // until the end, one host wait.  weights: B doubles or null (1 / B).
+  // until the end, one host wait.  weights: B doubles or null (1 / B).  With density keys (dens.nkeys > 0) one
+  // k_batch_density launch per record follows k_batch_observe on the same stream, and k_batch_observe is skipped when
+  // `what` is empty; the keys' values lie behind the site RDMs in the record and are averaged by the same k_batch_mean.
   void run(double dt, int nsteps, int every, const int* sites, int nsites, int what, const double* weights, const ObsOut& out,
-           int* statuses);
+           int* statuses, const DensOut& dens);
+  void run(double dt, int nsteps, int every, const int* sites, int nsites, int what, const double* weights, const ObsOut& out,
+           int* statuses) {
+    run(dt, nsteps, every, sites, nsites, what, weights, out, statuses, DensOut());
+  }
   std::string status_message(int code) const;
   int size() const { return (int)eng_.size(); }
   int device() const { return device_; }
@@ -83,6 +100,12 @@ class Batch {
   size_t rec_elems_ = 0, mean_elems_ = 0;
   std::vector<double> h_w_, h_rec_, h_mean_;
   std::vector<int> h_sites_;
+  // density keys: the leg table and the transfer blocks [B][2][need] of k_batch_density (both grow only)
+  BatchDensPlan dens_plan_;
+  int* d_legs_ = nullptr;
+  zc* d_tbuf_ = nullptr;
+  size_t legs_elems_ = 0, tbuf_elems_ = 0;
+  std::vector<int> h_legs_;
 
   // channels: the table and the operators (host copies and their device images), the generator's seed, ids and step
   // counter, the jump counters
@@ -113,6 +136,7 @@ class Batch {
   void prepare(bool forward, bool build_envs = true);
   void launch(double dt, bool forward);
   void launch_observe(int what, int nsites, long record, long rec_len);
+  void launch_density(int nkeys, bool zero_head, long record, long rec_len, long dens_off);
   void finish(bool ends_forward, int half_sweeps, int* statuses, int other_launches = 0, int channel_passes = 0);
   void finish_observe(int launches, int* statuses);
 };

@@ -141,6 +141,8 @@ Batch::~Batch() {
   if (d_ops_) (void)hipFree(d_ops_);
   if (d_ids_) (void)hipFree(d_ids_);
   if (d_counts_) (void)hipFree(d_counts_);
+  if (d_legs_) (void)hipFree(d_legs_);
+  if (d_tbuf_) (void)hipFree(d_tbuf_);
   if (st_) (void)hipStreamDestroy(st_);
 }
 
@@ -431,9 +433,9 @@ void Batch::jump_counts(long long* counts) {
 }
 
 // ---- observables (k_batch_observe, k_batch_mean) ----
-long Batch::observe_sizes(const int* sites, int nsites, int what) {
+long Batch::observe_sizes(const int* sites, int nsites, int what, bool with_keys) {
   validate();
-  if (!(what & BOBS_ALL) || (what & ~BOBS_ALL)) throw ArgError("batch: nothing to observe (what must be a non-empty set of MITDVP_OBS_* bits)");
+  if ((!(what & BOBS_ALL) && !(with_keys && what == 0)) || (what & ~BOBS_ALL)) throw ArgError("batch: nothing to observe (what must be a non-empty set of MITDVP_OBS_* bits)");
   if (nsites < 0 || (nsites > 0 && !sites)) throw ArgError("batch: bad list of observed sites");
   if (((what & BOBS_RDM) != 0) != (nsites > 0)) throw ArgError("batch: MITDVP_OBS_RDM and a non-empty list of sites go together");
   long nrdm = 0;
@@ -445,6 +447,33 @@ long Batch::observe_sizes(const int* sites, int nsites, int what) {
       throw ArgError("batch: the observed site RDMs have more than " + std::to_string(BATCH_OBS_MAX_RDM) + " elements per replica");
   }
   return nrdm;
+}
+
+long Batch::density_sizes(const int* legs, int nkeys, long nrdm) {
+  std::string why;
+  if (!batch_density_plan(shp_.data(), L_, legs, nkeys, nrdm, dens_plan_, why)) throw ArgError(why);
+  return dens_plan_.ndens;
+}
+
+void Batch::launch_density(int nkeys, bool zero_head, long record, long rec_len, long dens_off) {
+  BatchDensArgs a{};
+  a.L = L_;
+  a.nkeys = nkeys;
+  a.zero_head = zero_head ? 1 : 0;
+  a.shp = d_shp_;
+  a.ptrs = d_ptrs_;
+  a.ptr_stride = (int)ptrs_per_replica();
+  a.status = d_status_;
+  a.legs = d_legs_;
+  a.carve = carve_;
+  a.plan = obs_plan_;
+  a.tbuf = d_tbuf_;
+  a.need = dens_plan_.need;
+  a.rec = d_rec_ + (size_t)record * eng_.size() * rec_len;
+  a.rec_len = rec_len;
+  a.dens_off = dens_off;
+  batch_density_launch(st_, a, (int)eng_.size());
+  n_launch_ += 1;
 }
 
 void Batch::launch_observe(int what, int nsites, long record, long rec_len) {
@@ -474,22 +503,38 @@ void Batch::finish_observe(int launches, int* statuses) {
 }
 
 void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, int what, const double* weights, const ObsOut& out,
-                int* statuses) {
+                int* statuses, const DensOut& dens) {
   if (nsteps < 0) throw ArgError("batch: nsteps must be >= 0");
   if (every < 1) throw ArgError("batch: every must be >= 1");
   if (nsteps % every != 0) throw ArgError("batch: nsteps must be a multiple of every");
   HIP_CHECK(hipSetDevice(device_));
-  const long nrdm = observe_sizes(sites, nsites, what);
+  const int nkeys = dens.nkeys;
+  const long nrdm = observe_sizes(sites, nsites, what, nkeys > 0);
+  const long ndens = density_sizes(dens.legs, nkeys, nrdm);
   const size_t n = eng_.size();
-  const long nrec = nsteps / every + 1, rec_len = BOBS_HEAD + 2 * nrdm;
+  const long nrec = nsteps / every + 1, dens_off = BOBS_HEAD + 2 * nrdm, rec_len = dens_off + 2 * ndens;
+  const int per_rec = (what ? 1 : 0) + (nkeys ? 1 : 0);  // launches per record
   const bool chan = has_channels() && nsteps > 0;
   if (chan) check_channels();
   prepare(true, nsteps > 0 || (what & BOBS_ENERGY));
   if (chan) upload_channels();
   // buffers of the records and their means (grow only), the site list and the weights
   const size_t need_rec = (size_t)nrec * n * rec_len, need_mean = (size_t)nrec * rec_len;
-  if (need_rec > rec_elems_ || need_mean > mean_elems_) {
+  const size_t need_legs = (size_t)nkeys * L_, need_tbuf = nkeys ? n * 2 * dens_plan_.need : 0;
+  if (need_rec > rec_elems_ || need_mean > mean_elems_ || need_legs > legs_elems_ || need_tbuf > tbuf_elems_) {
     HIP_CHECK(hipStreamSynchronize(st_));
+    if (need_legs > legs_elems_) {
+      if (d_legs_) (void)hipFree(d_legs_);
+      d_legs_ = nullptr;
+      dev_alloc(d_legs_, need_legs);
+      legs_elems_ = need_legs;
+    }
+    if (need_tbuf > tbuf_elems_) {
+      if (d_tbuf_) (void)hipFree(d_tbuf_);
+      d_tbuf_ = nullptr;
+      dev_alloc(d_tbuf_, need_tbuf);
+      tbuf_elems_ = need_tbuf;
+    }
     if (need_rec > rec_elems_) {
       if (d_rec_) (void)hipFree(d_rec_);
       d_rec_ = nullptr;
@@ -508,17 +553,25 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   if (weights) h_w_.assign(weights, weights + n);
   if (nsites) HIP_CHECK(hipMemcpyAsync(d_sites_, h_sites_.data(), (size_t)nsites * sizeof(int), hipMemcpyHostToDevice, st_));
   HIP_CHECK(hipMemcpyAsync(d_w_, h_w_.data(), n * sizeof(double), hipMemcpyHostToDevice, st_));
+  if (nkeys) {
+    h_legs_.assign(dens.legs, dens.legs + need_legs);
+    HIP_CHECK(hipMemcpyAsync(d_legs_, h_legs_.data(), need_legs * sizeof(int), hipMemcpyHostToDevice, st_));
+  }
+  auto record = [&](long q) {
+    if (what) launch_observe(what, nsites, q, rec_len);
+    if (nkeys) launch_density(nkeys, what == 0, q, rec_len, dens_off);
+  };
 
-  launch_observe(what, nsites, 0, rec_len);
+  record(0);
   for (int s = 0; s < nsteps; ++s) {
     launch(dt, true);
     if (chan) launch_channel(steps_done_ + s);
     launch(dt, false);
-    if ((s + 1) % every == 0) launch_observe(what, nsites, (s + 1) / every, rec_len);
+    if ((s + 1) % every == 0) record((s + 1) / every);
   }
   batch_mean_launch(st_, d_rec_, d_w_, d_mean_, (int)n, rec_len, nrec);
   n_launch_ += 1;
-  const bool per_replica = out.norm || out.autocorr || out.energy || out.rdm;
+  const bool per_replica = out.norm || out.autocorr || out.energy || out.rdm || dens.density;
   h_mean_.resize(need_mean);
   HIP_CHECK(hipMemcpyAsync(h_mean_.data(), d_mean_, need_mean * sizeof(double), hipMemcpyDeviceToHost, st_));
   if (per_replica) {
@@ -526,8 +579,8 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
     HIP_CHECK(hipMemcpyAsync(h_rec_.data(), d_rec_, need_rec * sizeof(double), hipMemcpyDeviceToHost, st_));
   }
   steps_done_ += nsteps;
-  if (nsteps > 0) finish(false, nsteps * 2, statuses, (int)nrec + 1, chan ? nsteps : 0);
-  else finish_observe((int)nrec + 1, statuses);
+  if (nsteps > 0) finish(false, nsteps * 2, statuses, (int)nrec * per_rec + 1, chan ? nsteps : 0);
+  else finish_observe((int)nrec * per_rec + 1, statuses);
 
   for (long q = 0; q < nrec; ++q) {
     const double* m = h_mean_.data() + (size_t)q * rec_len;
@@ -535,6 +588,7 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
     if (out.mean_autocorr) { out.mean_autocorr[2 * q] = m[2]; out.mean_autocorr[2 * q + 1] = m[3]; }
     if (out.mean_energy) { out.mean_energy[2 * q] = m[4]; out.mean_energy[2 * q + 1] = m[5]; }
     if (out.mean_rdm && nrdm) std::memcpy(out.mean_rdm + (size_t)q * 2 * nrdm, m + BOBS_HEAD, (size_t)2 * nrdm * sizeof(double));
+    if (dens.mean_density && ndens) std::memcpy(dens.mean_density + (size_t)q * 2 * ndens, m + dens_off, (size_t)2 * ndens * sizeof(double));
     for (size_t i = 0; per_replica && i < n; ++i) {
       const double* r = h_rec_.data() + ((size_t)q * n + i) * rec_len;
       const size_t at = (size_t)q * n + i;
@@ -542,6 +596,7 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
       if (out.autocorr) { out.autocorr[2 * at] = r[2]; out.autocorr[2 * at + 1] = r[3]; }
       if (out.energy) { out.energy[2 * at] = r[4]; out.energy[2 * at + 1] = r[5]; }
       if (out.rdm && nrdm) std::memcpy(out.rdm + at * 2 * nrdm, r + BOBS_HEAD, (size_t)2 * nrdm * sizeof(double));
+      if (dens.density && ndens) std::memcpy(dens.density + at * 2 * ndens, r + dens_off, (size_t)2 * ndens * sizeof(double));
     }
   }
 }

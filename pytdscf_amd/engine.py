@@ -756,6 +756,29 @@ class TDVPEnsemble:
         self.engines = []
 
 
+def density_key_legs(key, nsite: int) -> list[int]:
+    """A reduced-density key in the reference's form -- a tuple of site indices, non-decreasing, each site once (its
+    diagonal) or twice (ket and bra leg) -- as the legs kept per site of an ``nsite`` chain: ``(0, 0, 2, 2)`` ->
+    ``[2, 0, 2]``, ``(0, 1)`` -> ``[1, 1]``.  ``ValueError`` naming the key otherwise.  Pure Python."""
+    try:
+        k = tuple(int(s) for s in key)
+    except TypeError:
+        raise ValueError(f"reduced-density key {key!r}: a key is a tuple of site indices") from None
+    if not k:
+        raise ValueError(f"reduced-density key {k}: it names no site")
+    if any(not 0 <= s < nsite for s in k):
+        raise ValueError(f"reduced-density key {k}: site out of range (the chain has {nsite} sites)")
+    if any(b < a for a, b in zip(k, k[1:])):
+        raise ValueError(f"reduced-density key {k}: the sites must be non-decreasing")
+    legs = [0] * nsite
+    for s in k:
+        legs[s] += 1
+        if legs[s] > 2:
+            raise ValueError(f"reduced-density key {k}: site {s} appears {k.count(s)} times, a site is named once (diagonal) "
+                             "or twice (ket and bra)")
+    return legs
+
+
 class TDVPBatch:
     """B independent trajectories (replicas) of one chain shape on ONE GPU, any B: one kernel launch per half-sweep for the
     whole batch (``mitdvp_batch_step`` / ``k_batch_sweep``: one workgroup owns one replica, the replica index is the
@@ -952,7 +975,10 @@ class TDVPBatch:
         ``observe=None``: nothing else, returns ``None``.  ``observe=dict(...)`` with the arguments of ``observe``: a
         recorded run (``mitdvp_batch_run``) -- the state before step 0 and after every ``every``-th step is observed on
         the device, one launch per record, and everything comes back at the end of the call; returns what ``observe``
-        returns with a leading record axis of ``nsteps // every + 1``."""
+        returns with a leading record axis of ``nsteps // every + 1``.  ``observe`` may also carry ``keys=[...]``, keys as
+        ``densities`` takes them: they are recorded in the same run by one more launch per record (``k_batch_density``) and
+        come back as ``mean_density`` / ``density``, record axis first; the other entries are bitwise what they are
+        without ``keys``."""
         if observe is None:
             self._run(lambda b, st: self._lib.mitdvp_batch_step(b, float(dt_au), int(nsteps), st))
             return None
@@ -970,8 +996,25 @@ class TDVPBatch:
                              per_replica=per_replica)
         return {k: ([x[0] for x in v] if isinstance(v, list) else v[0]) for k, v in rec.items()}
 
-    def _observed(self, dt_au, nsteps, every, sites=(), norm=True, autocorr=False, energy=False, weights=None, per_replica=True):
+    def densities(self, keys, weights=None, per_replica: bool = True):
+        """Multi-site reduced densities of the current state of every replica by ONE launch (``k_batch_density``), their
+        ensemble means by a second one (``mitdvp_batch_observe_keys``); all replicas must have their centre at site 0.
+        ``keys``: a list of keys in the reference's form, a tuple of site indices, non-decreasing, each site once (its
+        diagonal) or twice (ket and bra): ``(0, 0, 2, 2)``, ``(0, 1)``, ``(1, 2, 2)``.  Returns a dict: ``mean_density``,
+        a list with one array per key shaped like ``TDVPEngine.reduced_density(legs)``, and, with ``per_replica``,
+        ``density``, a list of ``(B, ...)`` arrays.  A malformed key is a ``ValueError`` naming it, raised before the GPU
+        is touched.  ``weights``: B numbers, default 1 / B each."""
+        keys = list(keys)
+        if not keys:
+            raise ValueError("densities: no key")
+        rec = self._observed(0.0, 0, 1, norm=False, weights=weights, per_replica=per_replica, keys=keys)
+        return {k: [x[0] for x in v] for k, v in rec.items()}
+
+    def _observed(self, dt_au, nsteps, every, sites=(), norm=True, autocorr=False, energy=False, weights=None, per_replica=True,
+                  keys=()):
         n = len(self.engines)
+        nsite = self.engines[0].nsite
+        legs = [density_key_legs(k, nsite) for k in keys]  # a malformed key raises here, before any library call
         sites = [int(p) for p in sites]
         what = ((_lib.OBS_NORM if norm else 0) | (_lib.OBS_AUTOCORR if autocorr else 0) | (_lib.OBS_ENERGY if energy else 0)
                 | (_lib.OBS_RDM if sites else 0))
@@ -982,10 +1025,20 @@ class TDVPBatch:
                 raise ValueError(f"weights must be {n} numbers, one per replica (got shape {w.shape})")
         b = self._handle()
         sarr = (C.c_int * max(len(sites), 1))(*sites)
-        cnt = (C.c_size_t * 3)()
+        cnt = (C.c_size_t * 4)()
         wp = None if w is None else _dp(w)
-        _lib.check(self._lib.mitdvp_batch_run(b, dt_au, nsteps, every, sarr, len(sites), what, wp, None, cnt, None))
-        nrec, _, nrdm = int(cnt[0]), int(cnt[1]), int(cnt[2])
+        larr = (C.c_int * max(len(legs) * nsite, 1))(*[x for row in legs for x in row])
+        dens = {"density": None, "mean_density": None}
+
+        def call(bb, outp, st):  # without keys: the entry point of before
+            if not legs:
+                return self._lib.mitdvp_batch_run(bb, dt_au, nsteps, every, sarr, len(sites), what, wp, outp, cnt, st)
+            dp = [None if a is None else _dp(a) for a in (dens["density"], dens["mean_density"])]
+            return self._lib.mitdvp_batch_run_keys(bb, dt_au, nsteps, every, sarr, len(sites), larr, len(legs), what, wp, outp,
+                                                   dp[0], dp[1], cnt, st)
+
+        _lib.check(call(b, None, None))
+        nrec, _, nrdm, ndens = (int(c) for c in cnt)
         out = _lib.BatchOut()
         keep = {}
 
@@ -1010,16 +1063,29 @@ class TDVPBatch:
                 want("energy", (nrec, n), np.complex128)
             if sites:
                 want("rdm", (nrec, n, nrdm), np.complex128)
+        if legs:
+            dens["mean_density"] = keep["mean_density"] = np.zeros((nrec, ndens), dtype=np.complex128)
+            if per_replica:
+                dens["density"] = keep["density"] = np.zeros((nrec, n, ndens), dtype=np.complex128)
         try:
-            self._run(lambda bb, st: self._lib.mitdvp_batch_run(bb, dt_au, nsteps, every, sarr, len(sites), what, wp,
-                                                                C.byref(out), cnt, st))
+            self._run(lambda bb, st: call(bb, C.byref(out), st))
         finally:
-            self.records = self._split(keep, sites)  # a replica that did not converge raises; what was recorded stays readable here
+            self.records = self._split(keep, sites, legs)  # a replica that did not converge raises; what was recorded stays readable here
         return self.records
 
-    def _split(self, keep, sites):
-        """the flat RDM axis cut into one (.., d, d) array per observed site"""
+    def _split(self, keep, sites, legs=()):
+        """the flat RDM axis cut into one (.., d, d) array per observed site, the flat density axis into one array per key"""
         res = dict(keep)
+        alld = [self.engines[0].get_site_shape(p)[1] for p in range(self.engines[0].nsite)] if legs else []
+        for name in ("mean_density", "density"):
+            if name in res:
+                flat, parts, at = res[name], [], 0
+                for row in legs:
+                    shape = tuple(alld[p] for p, k in enumerate(row) for _ in range(k))
+                    size = int(np.prod(shape))
+                    parts.append(flat[..., at:at + size].reshape(flat.shape[:-1] + shape))
+                    at += size
+                res[name] = parts
         dims = [self.engines[0].get_site_shape(p)[1] for p in sites]
         for name in ("mean_rdm", "rdm"):
             if name in res:

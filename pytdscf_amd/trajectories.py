@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import units
-from .engine import TDVPBatch
+from .engine import TDVPBatch, density_key_legs
 from .mps import product_state_cores
 
 
@@ -72,8 +72,8 @@ def _one_site_keys(keys, nsite):
 
 def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, weights=None, integrator="lanczos",
                            conserve_norm=True, per_trajectory=False, thresh_sil=1.0e-09, device=0, jumps=None, seed=0,
-                           replicas_per_start=1, first_trajectory=0):
-    """Propagate every Hartree product of ``starts`` under ``model`` and average their one-site reduced densities.
+                           replicas_per_start=1, first_trajectory=0, densities=None):
+    """Propagate every Hartree product of ``starts`` under ``model`` and average their reduced densities.
 
     ``model``: a ``Model`` as the shell takes it (one electronic state, Hilbert space); its ``one_gate_to_apply``
     (one-site gates only) becomes gates of the batch, applied between the half-sweeps of every step as the reference
@@ -83,6 +83,12 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
     BEFORE steps 0, every, 2 every, ... < ``maxstep``; steps after the last observation are not run.
     Returns ``{"time": (nrec,) in fs, "mean": {key: (nrec, d, d)}}`` and, with ``per_trajectory``,
     ``"trajectories": {key: (nrec, len(starts), d, d)}``.  ``weights``: one number per start, default equal weights.
+
+    ``densities``: a list of keys in the reference's general form -- a tuple of site indices, non-decreasing, each site
+    once (its diagonal) or twice (ket and bra): ``(0, 0, 2, 2)``, ``(0, 1)``, ``(1, 2, 2)`` -- recorded at the interval of
+    ``reduced_density`` in the same run (``k_batch_density``, one more launch per record) and returned under the same
+    ``"mean"`` / ``"trajectories"`` with their own shapes.  ``reduced_density`` keeps taking one-site keys only and may
+    name none when ``densities`` is given.
 
     ``jumps={site: B (K, d, d)}``: a one-site Kraus channel per listed site (e.g. ``kraus.lindblad_to_kraus(ops, dt)``),
     unravelled into quantum jumps: every trajectory picks one operator per site and step with the state's own
@@ -99,7 +105,10 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
         raise ValueError("maxstep and the reduced-density interval must be >= 1")
     nsite = len(model.dims)
     key_sites = _one_site_keys(keys, nsite)
-    if not keys:
+    dens_keys = [tuple(k) for k in densities] if densities is not None else []
+    for k in dens_keys:
+        density_key_legs(k, nsite)  # a malformed key raises here, before any engine exists
+    if not keys and not dens_keys:
         raise ValueError("reduced_density names no key")
     if model.nstate != 1 or model.space != "hilbert":
         raise NotImplementedError("propagate_trajectories: one electronic state in Hilbert space")
@@ -136,8 +145,10 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
             bt.set_gates(gates)
         if jump_table:
             bt.set_jumps(jump_table, seed=seed, trajectory_ids=range(first_trajectory, first_trajectory + nrep))
-        rec = bt.propagate(dt_au, nsteps, observe=dict(sites=sites, norm=False, weights=weights, per_replica=per_trajectory),
-                           every=every)
+        req = dict(sites=sites, norm=False, weights=weights, per_replica=per_trajectory)
+        if dens_keys:
+            req["keys"] = dens_keys
+        rec = bt.propagate(dt_au, nsteps, observe=req, every=every)
     finally:
         bt.close()
     nrec = nsteps // every + 1
@@ -145,4 +156,8 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
            "mean": {k: rec["mean_rdm"][sites.index(s)] for k, s in zip(keys, key_sites)}}
     if per_trajectory:
         out["trajectories"] = {k: rec["rdm"][sites.index(s)] for k, s in zip(keys, key_sites)}
+    for i, k in enumerate(dens_keys):  # a key given both ways is the general form's
+        out["mean"][k] = rec["mean_density"][i]
+        if per_trajectory:
+            out["trajectories"][k] = rec["density"][i]
     return out
