@@ -578,6 +578,12 @@ int mitdvp_gauge_trf(int device, int key, const double* psi, int dl, int d, int 
 int mitdvp_expm_dense(int device, int integrator, int conserve_norm, int lanczos_variant,
                       const double* mat, int n, const double* x, double scale_re, double scale_im,
                       double thresh, int k_prev, double* y_out, int* k_out);
+/* The same, and the counters of the engine that ran it (n_launch: the launches of the Krylov loop, the operator's
+ * own GEMM not counted; n_host_waits): which vector-step kernels the solve took is read off them. */
+int mitdvp_expm_dense_counted(int device, int integrator, int conserve_norm, int lanczos_variant,
+                              const double* mat, int n, const double* x, double scale_re, double scale_im,
+                              double thresh, int k_prev, double* y_out, int* k_out,
+                              mitdvp_counters* counters_out);
 
 /* -- kernel-level test / bench hooks (no reference counterpart) --------- */
 /* C = alpha*op(A)*op(B) + beta*C on the MFMA zgemm kernel, row-major. */

@@ -194,6 +194,7 @@ def load() -> C.CDLL:
         "mitdvp_env_update": (i, [i, i, dp, dp, dp, i, i, i, i, i, dp]),
         "mitdvp_gauge_trf": (i, [i, i, dp, i, i, i, dp, dp]),
         "mitdvp_expm_dense": (i, [i, i, i, i, dp, i, dp, d, d, d, i, dp, ip]),
+        "mitdvp_expm_dense_counted": (i, [i, i, i, i, dp, i, dp, d, d, d, i, dp, ip, C.POINTER(Counters)]),
         "mitdvp_zgemm": (i, [i, i, i, i, i, i, i, i, dp, dp, dp, dp, dp, i, i, dp]),
         "mitdvp_bench_heff": (i, [i, i, i, i, i, i, i, i, dp]),
         "mitdvp_heff_selfcheck": (i, [i, i, i, i, i, i, dp]),

@@ -630,9 +630,9 @@ int mitdvp_gauge_trf(int device, int key, const double* psi, int dl, int d, int 
   });
 }
 
-int mitdvp_expm_dense(int device, int integrator, int conserve_norm, int lanczos_variant, const double* mat, int n,
-                      const double* x, double scale_re, double scale_im, double thresh, int k_prev, double* y_out,
-                      int* k_out) {
+int mitdvp_expm_dense_counted(int device, int integrator, int conserve_norm, int lanczos_variant, const double* mat, int n,
+                              const double* x, double scale_re, double scale_im, double thresh, int k_prev, double* y_out,
+                              int* k_out, mitdvp_counters* counters_out) {
   return guard(nullptr, [&] {
     using namespace mitdvp;
     mitdvp_config c = unit_cfg(device);
@@ -644,14 +644,22 @@ int mitdvp_expm_dense(int device, int integrator, int conserve_norm, int lanczos
     hipStream_t st = e.stream();
     e.ensure_work(n, 1, 1, 1, 1);
     Dev dm(st, mat, (size_t)n * n), dx(st, x, n);
-    auto mv = [&](const zc* in, zc* out) {
+    auto mv = [&](const zc* in, zc* out) {  // not counted: n_launch holds the launches of the Krylov loop alone
       ZgemmDesc g = zgemm_desc(dm.p(), in, out, n, 1, n);
       zgemm(st, g);
     };
     const int k = e.krylov_exp(hzc(scale_re, scale_im), mv, dx.p(), n, k_prev);
     if (k_out) *k_out = k;
+    if (counters_out) e.counters_get(counters_out);
     to_host(st, y_out, dx.p(), n);
   });
+}
+
+int mitdvp_expm_dense(int device, int integrator, int conserve_norm, int lanczos_variant, const double* mat, int n,
+                      const double* x, double scale_re, double scale_im, double thresh, int k_prev, double* y_out,
+                      int* k_out) {
+  return mitdvp_expm_dense_counted(device, integrator, conserve_norm, lanczos_variant, mat, n, x, scale_re, scale_im, thresh,
+                                   k_prev, y_out, k_out, nullptr);
 }
 
 // ---- kernel-level hooks ---------------------------------------------------

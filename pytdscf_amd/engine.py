@@ -621,13 +621,16 @@ def gauge_trf(psi, key: str, device=0):
     return site, sig
 
 
-def expm_dense(mat, x, scale, integrator="lanczos", conserve_norm=True, thresh=1e-9, k_prev=0, variant="reference", device=0):
+def expm_dense(mat, x, scale, integrator="lanczos", conserve_norm=True, thresh=1e-9, k_prev=0, variant="reference", device=0,
+               counters=False):
+    """``counters=True``: also the counters of the engine that ran the solve (``n_launch`` without the operator's GEMM)"""
     mat, xx = _c128(mat), _c128(x)
     y = np.empty_like(xx)
     k = C.c_int()
+    cnt = _lib.Counters()
     s = complex(scale)
     _lib.check(
-        _lib.load().mitdvp_expm_dense(
+        _lib.load().mitdvp_expm_dense_counted(
             device,
             {"lanczos": 0, "arnoldi": 1}[integrator],
             int(conserve_norm),
@@ -641,9 +644,10 @@ def expm_dense(mat, x, scale, integrator="lanczos", conserve_norm=True, thresh=1
             k_prev,
             _dp(y),
             C.byref(k),
+            C.byref(cnt),
         )
     )
-    return y, k.value
+    return (y, k.value, cnt.as_dict()) if counters else (y, k.value)
 
 
 def zgemm(A, B, C0=None, transA=False, conjA=False, transB=False, conjB=False, alpha=1.0, beta=0.0, tile_cfg=-1, reps=0, device=0):

@@ -10,12 +10,12 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _serial(L, mpo, dims, D, seed, nsteps, dt, **kw):
+def _serial(L, mpo, dims, D, seed, nsteps, dt, shift=0.0, **kw):
     from pytdscf_amd import TDVPEngine
 
     e = TDVPEngine(L, **kw)
     e.set_small_kernels(False)
-    e.set_mpo(mpo)
+    e.set_mpo(mpo, shift=shift)
     e.init_random(dims, D, seed=seed)
     for _ in range(nsteps):
         e.propagate(dt)
@@ -42,13 +42,18 @@ def _batch(B, L, mpo, dims, D, seeds, **kw):
     return bt
 
 
+def _same_state(a, b, what):
+    """the bar between two paths to one state (module docstring)"""
+    f = _fid(a, b)
+    print(f"{what}: fidelity defect {f:.2e}")
+    assert f < 1e-10, (what, f)
+
+
 def _against_serial(bt, mpos, dims, D, seeds, nsteps, dt, which=None, **kw):
     L = len(dims)
     for r in (range(len(bt)) if which is None else which):
         ser = _serial(L, mpos[r] if isinstance(mpos, dict) else mpos, dims, D, seeds[r], nsteps, dt, **kw)
-        f = _fid(ser.get_mps(), bt[r].get_mps())
-        print(f"replica {r}: fidelity defect {f:.2e}, krylov {bt[r].krylov_stats()}")
-        assert f < 1e-10, (r, f)
+        _same_state(ser.get_mps(), bt[r].get_mps(), f"replica {r}, krylov {bt[r].krylov_stats()}")
         assert ser.krylov_stats() == bt[r].krylov_stats(), r
         ser.close()
 
