@@ -590,6 +590,36 @@ int mitdvp_expm_dense_counted(int device, int integrator, int conserve_norm, int
 int mitdvp_zgemm(int device, int transA, int conjA, int transB, int conjB, int m, int n, int k,
                  const double* A, const double* B, double* C, const double alpha[2], const double beta[2],
                  int tile_cfg, int reps, double* ms_out);
+/* The same kernel through its whole descriptor (ZgemmDesc), one call, no timing:
+ *   C[b] = alpha * op(A[b]) * op(B[b]) + beta * C[b],  b < batch, row-major, operand b at off + b * stride elements
+ * of its buffer.  A, B, C are WHOLE buffers of nA, nB, nC complex elements: all three are copied to the device, the
+ * product runs once, and all of C comes back (so that what lies around the view can be checked too).
+ *   arow_skip (0 = off, else >= 2; A untransposed): logical row r of A is stored at row r + r / (arow_skip - 1) + 1;
+ *   rowmap_p > 0: row r of C is stored at ((r + r0) % p) * s1 + ((r + r0) / p) * s2 instead of r * ldc;
+ *   klist (NULL = dense; NN operands, K % 16 == 0, tile_cfg 1): for each 64-row tile tm, klist[tm * klist_stride] =
+ *   number of 16-wide K tiles to visit, then their ascending indices; klist_stride >= 1 + K / 16; the other tiles of A
+ *   count as zero.
+ * Before any HIP call the footprint of the descriptor is computed on the host -- first and last element the operation
+ * may touch in A, B (dense views, the arow_skip map included), C (ldc or the row map) and the list (ntm rows of
+ * klist_stride) -- and MITDVP_EINVAL is returned if any index falls outside nA / nB / nC / nklist, or if the kernel
+ * does not serve the combination (batch > 65535, arow_skip 1 or with transA or a list, a list with a transpose or
+ * K % 16 != 0, tile_cfg outside -1..2).  m, n or batch of 0: success, C unchanged.  k = 0: C = beta * C. */
+typedef struct mitdvp_zgemm_args {
+  int m, n, k, batch;
+  int transA, conjA, transB, conjB;
+  long lda, ldb, ldc;             /* leading dimensions, complex elements */
+  long strideA, strideB, strideC; /* batch strides (0 = shared operand) */
+  long offA, offB, offC;          /* first operand element inside its buffer */
+  double alpha[2], beta[2];
+  int tile_cfg, mode3m;           /* -1 = library default */
+  int arow_skip;
+  int rowmap_p;
+  long rowmap_s1, rowmap_s2;
+  int rowmap_r0;
+  int klist_stride;
+} mitdvp_zgemm_args;
+int mitdvp_zgemm_desc(int device, const mitdvp_zgemm_args* a, const double* A, size_t nA, const double* B, size_t nB,
+                      double* C, size_t nC, const int* klist, size_t nklist);
 /* Complex-product form of the MFMA zgemm kernel for everything that follows:
  * 0 = "4M" (textbook, 4 real MFMA products), 1 = "3M" (Karatsuba, 3 products,
  * normwise stable); the library default is 1 unless MITDVP_ZGEMM=4m is set. */

@@ -83,6 +83,25 @@ class BatchOut(C.Structure):
                 ("norm", "autocorr", "energy", "rdm", "mean_norm2", "mean_autocorr", "mean_energy", "mean_rdm")]
 
 
+class ZgemmArgs(C.Structure):
+    """mitdvp_zgemm_args: the descriptor of one (batched, strided, mapped) product of mitdvp_zgemm_desc"""
+
+    _fields_ = [
+        ("m", C.c_int), ("n", C.c_int), ("k", C.c_int), ("batch", C.c_int),
+        ("transA", C.c_int), ("conjA", C.c_int), ("transB", C.c_int), ("conjB", C.c_int),
+        ("lda", C.c_long), ("ldb", C.c_long), ("ldc", C.c_long),
+        ("strideA", C.c_long), ("strideB", C.c_long), ("strideC", C.c_long),
+        ("offA", C.c_long), ("offB", C.c_long), ("offC", C.c_long),
+        ("alpha", C.c_double * 2), ("beta", C.c_double * 2),
+        ("tile_cfg", C.c_int), ("mode3m", C.c_int),
+        ("arow_skip", C.c_int),
+        ("rowmap_p", C.c_int),
+        ("rowmap_s1", C.c_long), ("rowmap_s2", C.c_long),
+        ("rowmap_r0", C.c_int),
+        ("klist_stride", C.c_int),
+    ]
+
+
 OBS_NORM, OBS_AUTOCORR, OBS_ENERGY, OBS_RDM = 1, 2, 4, 8
 CHANNEL_GATE, CHANNEL_JUMP = 1, 2
 MAX_JUMP = 16  # operators of one jump channel (BATCH_MAX_JUMP)
@@ -196,6 +215,7 @@ def load() -> C.CDLL:
         "mitdvp_expm_dense": (i, [i, i, i, i, dp, i, dp, d, d, d, i, dp, ip]),
         "mitdvp_expm_dense_counted": (i, [i, i, i, i, dp, i, dp, d, d, d, i, dp, ip, C.POINTER(Counters)]),
         "mitdvp_zgemm": (i, [i, i, i, i, i, i, i, i, dp, dp, dp, dp, dp, i, i, dp]),
+        "mitdvp_zgemm_desc": (i, [i, C.POINTER(ZgemmArgs), dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, ip, C.c_size_t]),
         "mitdvp_bench_heff": (i, [i, i, i, i, i, i, i, i, dp]),
         "mitdvp_heff_selfcheck": (i, [i, i, i, i, i, i, dp]),
         "mitdvp_set_gemm_mode": (i, [i]),

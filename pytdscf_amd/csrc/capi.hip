@@ -7,6 +7,7 @@
 #include "engine_batch.h"
 #include "engine_internal.h"
 #include "engine_krylov.inc"
+#include "zgemm_args_check.h"
 
 namespace {
 thread_local std::string g_err;
@@ -700,6 +701,40 @@ int mitdvp_zgemm(int device, int transA, int conjA, int transB, int conjB, int m
         HIP_CHECK(hipEventDestroy(b));
       }
     }
+    HIP_CHECK(hipStreamDestroy(st));
+  });
+}
+
+// one product through the whole descriptor on the caller's whole buffers (zgemm_args_check.h refuses, before any HIP
+// call, whatever would leave them); all of C comes back
+int mitdvp_zgemm_desc(int device, const mitdvp_zgemm_args* a, const double* A, size_t nA, const double* B, size_t nB,
+                      double* C, size_t nC, const int* klist, size_t nklist) {
+  return guard(nullptr, [&] {
+    using namespace mitdvp;
+    zgemm_args_check(a, A, nA, B, nB, C, nC, klist, nklist);
+    HIP_CHECK(hipSetDevice(device));
+    hipStream_t st;
+    HIP_CHECK(hipStreamCreate(&st));
+    {
+      Dev dA(st, A, nA), dB(st, B, nB), dC(st, C, nC), dK((nklist * sizeof(int) + sizeof(zc) - 1) / sizeof(zc));
+      if (klist && nklist) HIP_CHECK(hipMemcpyAsync(dK.p(), klist, nklist * sizeof(int), hipMemcpyHostToDevice, st));
+      ZgemmDesc g = zgemm_desc(dA.p() + a->offA, dB.p() + a->offB, dC.p() + a->offC, a->m, a->n, a->k);
+      g.transA = a->transA; g.conjA = a->conjA; g.transB = a->transB; g.conjB = a->conjB;
+      g.lda = a->lda; g.ldb = a->ldb; g.ldc = a->ldc;
+      g.strideA = a->strideA; g.strideB = a->strideB; g.strideC = a->strideC;
+      g.batch = a->batch;
+      g.alpha = make_double2(a->alpha[0], a->alpha[1]);
+      g.beta = make_double2(a->beta[0], a->beta[1]);
+      g.tile_cfg = a->tile_cfg;
+      g.mode3m = a->mode3m;
+      g.arow_skip = a->arow_skip;
+      g.rowmap_p = a->rowmap_p; g.rowmap_s1 = a->rowmap_s1; g.rowmap_s2 = a->rowmap_s2; g.rowmap_r0 = a->rowmap_r0;
+      if (klist) { g.klist = reinterpret_cast<const int*>(dK.p()); g.klist_stride = a->klist_stride; }
+      zgemm(st, g);
+      if (nC) to_host(st, C, dC.p(), nC);
+      else HIP_CHECK(hipStreamSynchronize(st));
+    }
+    zgemm_release_stream(st);
     HIP_CHECK(hipStreamDestroy(st));
   });
 }

@@ -667,6 +667,40 @@ def zgemm(A, B, C0=None, transA=False, conjA=False, transB=False, conjB=False, a
     return (Cm, ms.value) if reps else Cm
 
 
+ZGEMM_DESC_DEFAULTS = dict(
+    m=0, n=0, k=0, batch=1, transA=0, conjA=0, transB=0, conjB=0, lda=0, ldb=0, ldc=0, strideA=0, strideB=0, strideC=0,
+    offA=0, offB=0, offC=0, alpha=1.0, beta=0.0, tile_cfg=-1, mode3m=-1, arow_skip=0, rowmap_p=0, rowmap_s1=0, rowmap_s2=0,
+    rowmap_r0=0, klist_stride=0)
+
+
+def zgemm_desc(args: dict, A, B, Cbuf, klist=None, device=0) -> np.ndarray:
+    """One product of the MFMA kernel through its whole descriptor (``mitdvp_zgemm_desc``): ``args`` holds the fields of
+    ``mitdvp_zgemm_args`` (missing ones as in ``ZGEMM_DESC_DEFAULTS``), ``A``, ``B``, ``Cbuf`` are whole flat buffers
+    that the views of the descriptor lie in.  Returns the whole C buffer after the product; ``Cbuf`` is not modified.
+    A descriptor that leaves a buffer, or that the kernel does not serve, raises ValueError before the GPU is touched."""
+    unknown = set(args) - set(ZGEMM_DESC_DEFAULTS)
+    if unknown:
+        raise TypeError(f"zgemm_desc: unknown descriptor fields {sorted(unknown)}")
+    v = dict(ZGEMM_DESC_DEFAULTS, **args)
+    a = _lib.ZgemmArgs()
+    for name, val in v.items():
+        if name in ("alpha", "beta"):
+            z = complex(val)
+            setattr(a, name, (C.c_double * 2)(z.real, z.imag))
+        else:
+            setattr(a, name, int(val))
+    A, B = _c128(A).reshape(-1), _c128(B).reshape(-1)
+    out = _c128(Cbuf).reshape(-1).copy()
+    kl = None if klist is None else np.ascontiguousarray(klist, dtype=np.intc).reshape(-1)
+    _lib.check(
+        _lib.load().mitdvp_zgemm_desc(
+            device, C.byref(a), _dp(A), A.size, _dp(B), B.size, _dp(out), out.size,
+            None if kl is None else kl.ctypes.data_as(C.POINTER(C.c_int)), 0 if kl is None else kl.size,
+        )
+    )
+    return out
+
+
 def thin_to_full(site, gauge: str, delta_rank: int, device=0) -> np.ndarray:
     """``SiteCoef.thin_to_full``: widen an "A" (or "B") isometry by ``delta_rank``
     orthonormal columns (rows) of its orthogonal complement (capped at its dimension)."""
