@@ -234,6 +234,32 @@ int mitdvp_batch_run_keys(mitdvp_batch* b, double dt_au, int nsteps, int every, 
 int mitdvp_batch_set_channel(mitdvp_batch* b, int site, int kind, const double* ops_reim, int nops, int d);
 int mitdvp_batch_set_seed(mitdvp_batch* b, unsigned long long seed, const unsigned long long* trajectory_ids);
 int mitdvp_batch_jump_counts(mitdvp_batch* b, long long* counts);
+/* Nearest-neighbour (pair) channels of a batch, in the same walk between the two half-sweeps: while at least one is set
+ * the walk is run by k_batch_pair in the place of k_batch_channel -- still ONE more launch per step for the whole batch;
+ * with none set nothing changes.  A pair channel sits on the bond (site, site + 1), 0 <= site < nsite - 1.  Walking
+ * down with the centre at p, the one-site channel of p acts first; then, if bond (p-1, p) carries a pair channel, it
+ * takes the place of that step's gauge move: merge theta[a,i,j,s] = sum_b A_{p-1}[a,i,b] C_p[b,j,s], apply the operator
+ * on (i, j), split theta ~ C'_{p-1} B_p with B_p of r orthonormal rows, r the bond's dimension as it is (shapes never
+ * change; one-sided Jacobi SVD inside the workgroup), C'_{p-1} = theta B_p^+.  The walk goes down to the lowest site
+ * that any channel touches (a pair on (q, q+1) touches q).
+ *   mitdvp_batch_set_pair_channel: `ops_reim` holds nops matrices (d0 d1) x (d0 d1), row-major over (i_site, i_site+1)
+ *       for rows and columns alike, [k][out][in], interleaved re / im; NULL removes the bond's channel.
+ *       MITDVP_CHANNEL_GATE (nops == 1): applied as it is, no rescale: what the truncation removes is lost and reported
+ *       by mitdvp_batch_discarded_weight.  MITDVP_CHANNEL_JUMP (2 <= nops <= 16): the selection rule of the one-site
+ *       jump channel bit for bit, on w_k = |B_k theta|^2, with the uniform of "site" nsite + site (distinct from every
+ *       one-site draw); afterwards C' is rescaled so that the norm after the split equals the norm before the jump.
+ *       W == 0 stops that replica only, as for a one-site channel; so does a split that does not converge in 30 sweeps
+ *       (MITDVP_ENOTCONV in its status).  MITDVP_EINVAL (message: mitdvp_last_error(NULL), naming the bond and the limit;
+ *       nothing changed, every engine untouched) when the bond is out of range, d0 / d1 are not the two sites' physical
+ *       dimensions, nops is out of range for the kind, dl d0 or d1 dr exceeds 128, theta and its copy do not fit the
+ *       Krylov-basis part of the replica's scratch area, or the replicas run in imaginary time (relax == 1).
+ *   mitdvp_batch_pair_jump_counts: counts[n][nsite][16] (long long), row q for the bond (q, q + 1), since the last
+ *       mitdvp_batch_set_seed.  One host wait.
+ *   mitdvp_batch_discarded_weight: weights[n], per replica the sum over its splits of
+ *       sum_{j>r} sigma_j^2 / sum_j sigma_j^2 since the seed or a channel was last set.  One host wait. */
+int mitdvp_batch_set_pair_channel(mitdvp_batch* b, int site, int kind, const double* ops_reim, int nops, int d0, int d1);
+int mitdvp_batch_pair_jump_counts(mitdvp_batch* b, long long* counts);
+int mitdvp_batch_discarded_weight(mitdvp_batch* b, double* weights);
 /* propagate_along_sweep (_mps_cls.py:798-1014), one direction only. */
 int mitdvp_sweep(mitdvp_engine* h, double dt_au, int forward);
 /* The same half-sweep in parts: the next `nsites` local updates of the half-sweep in progress (one is started when none

@@ -260,6 +260,9 @@ def load() -> C.CDLL:
         "mitdvp_batch_set_channel": (i, [vp, i, i, dp, i, i]),
         "mitdvp_batch_set_seed": (i, [vp, C.c_uint64, C.POINTER(C.c_uint64)]),
         "mitdvp_batch_jump_counts": (i, [vp, C.POINTER(C.c_longlong)]),
+        "mitdvp_batch_set_pair_channel": (i, [vp, i, i, dp, i, i, i]),
+        "mitdvp_batch_pair_jump_counts": (i, [vp, C.POINTER(C.c_longlong)]),
+        "mitdvp_batch_discarded_weight": (i, [vp, dp]),
         "mitdvp_cu_mask_probe": (i, [i, C.POINTER(C.c_uint), i, i, C.c_size_t, i, ip]),
     }
     for name, (res, args) in sig.items():

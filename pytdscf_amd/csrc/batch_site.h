@@ -79,6 +79,26 @@ struct BatchChanArgs {
 // blocks (the state a forward half-sweep leaves); the same state is left, with the channels applied.
 void batch_channel_launch(hipStream_t st, const BatchChanArgs& a, int nrep);
 
+// ---- nearest-neighbour (pair) channels in the same walk (k_batch_pair) ----
+// A pair channel sits on a bond (q, q+1): a gate (one matrix) or a jump channel (2 .. BATCH_MAX_JUMP matrices), each
+// (d_q d_{q+1}) x (d_q d_{q+1}), row-major over (i_q, i_{q+1}).  Envelope, decided on the host (batch_pair_fits): the
+// two-site tensor theta, seen as (dl d_q) x (d_{q+1} dr), has at most BATCH_PAIR_MAX_DIM rows and columns (row norms,
+// ranks and rotation scalars of the split live in LDS), and theta and its copy fit the Krylov-basis carve of the
+// replica's scratch area (BatchPlan::o_u), which is idle during the walk.
+constexpr int BATCH_PAIR_MAX_DIM = 128;
+constexpr int BATCH_PAIR_MAX_SWEEPS = 30;  // Jacobi sweeps of one split; a replica that reaches it gets SS_ENOTCONV
+// false + a message naming the bond and the limit
+bool batch_pair_fits(const BatchShape* shp, int L, const BatchPlan& plan, int q, std::string& why);
+struct BatchPairArgs {
+  BatchChanArgs c;            // the walk's own arguments; c.lo: the lowest site that ANY channel touches (a pair on
+                              // (q, q+1) touches q); c.ops holds the pair operators too
+  const BatchChanSite* pair;  // [L], device: entry q is the channel of bond (q, q+1); entry L-1 is BCH_NONE
+  long long* pcounts;         // [B][L][BATCH_MAX_JUMP]: how often operator k of bond (q, q+1) was picked, row q
+  double* disc;               // [B]: discarded weight sum_{j>r} sigma_j^2 / sum_j sigma_j^2, added up over the splits
+};
+// one launch: grid = nrep workgroups; precondition and result as batch_channel_launch
+void batch_pair_launch(hipStream_t st, const BatchPairArgs& a, int nrep);
+
 // ---- batched observables (k_batch_observe, k_batch_mean) ----
 // what is wanted of an observation: the values of MITDVP_OBS_* (include/mitdvp.h)
 enum { BOBS_NORM = 1, BOBS_AUTOCORR = 2, BOBS_ENERGY = 4, BOBS_RDM = 8, BOBS_ALL = 15 };

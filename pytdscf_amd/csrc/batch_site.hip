@@ -1,6 +1,7 @@
 // batch_site.hip -- batched trajectories: k_batch_sweep, ONE workgroup per replica, a whole half-sweep per launch.
 // (Further down: k_batch_observe / k_batch_mean, the observables of every replica and their ensemble means, one launch each;
-// k_batch_channel, one-site gates and quantum-jump channels between the two half-sweeps of a time step, one launch.)
+// k_batch_channel, one-site gates and quantum-jump channels between the two half-sweeps of a time step, one launch;
+// k_batch_pair, the same walk with nearest-neighbour gates and jump channels: merge, apply, truncated re-split.)
 //
 // At trajectory shapes (d = 2..4, D <= 32, M <= 16) a local problem is a few tens of kilobytes, so one workgroup can own
 // one replica completely: the replica index is blockIdx.x, nothing is exchanged between workgroups, and therefore there is
@@ -1048,7 +1049,461 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_channel(BatchChanArgs g) {
   if (rc != SS_OK && tid == 0) g.status[r] = rc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The same walk with nearest-neighbour (pair) channels: k_batch_pair, ONE workgroup per replica, one launch per time step
+// in the place of k_batch_channel whenever a pair channel is set (k_batch_channel itself is untouched and stays in use
+// otherwise).  Walking down with the centre at p the one-site channel of p acts as above; then, if bond (p-1, p) carries
+// a pair channel, it takes the place of that step's bt_qr + absorb:
+//   merge   theta[(a,i)][(j,s)] = sum_b A(p-1)[(a,i)][b] C(p)[b][(j,s)]                       (wg_gemm; m x n, m = dl d_{p-1},
+//           n = d_p dr, both <= BATCH_PAIR_MAX_DIM)
+//   apply   theta <- Op theta on (i, j); a jump channel first picks its operator by the rule of the one-site channel, with
+//           w_k = |B_k theta|^2 computed directly and the uniform of "site" L + (p-1)         (bp_weights / bp_apply)
+//   split   theta ~ C'(p-1) . B(p), B(p) with r = dl(p) orthonormal rows (the bond keeps its dimension): a one-sided
+//           (Hestenes) Jacobi SVD on the ROWS of a work copy of theta -- pairs of rows in a fixed round-robin order are
+//           rotated until all are mutually orthogonal (|<x, y>|^2 <= BP_TOL2 |x|^2 |y|^2); the rows are then sigma_j v_j^+,
+//           the r of largest norm, normalised, are B(p), and C'(p-1) = theta B(p)^+ from the kept copy: no U, no V.
+//           Rows whose norm^2 is <= BP_TINY |theta|^2 (|theta|^2 lies between the largest sigma^2 and m times it; a
+//           rank-deficient theta: a product start padded to D) are rounding noise: they are left out of the rotations,
+//           and those among the selected r are replaced by an orthonormal completion (bp_select), so B(p) B(p)^+ = 1
+//           whatever the rank.
+// After a jump C' is rescaled so that the norm after the split is the norm before the jump (operator and truncation
+// together); after a gate nothing is rescaled and the discarded weight sum_{j>r} sigma_j^2 / sum_j sigma_j^2 of every
+// split is added to disc[replica] by thread 0.  A split that does not converge in BATCH_PAIR_MAX_SWEEPS sweeps is
+// SS_ENOTCONV for that replica only.
+// What is resident where: theta and its work copy are the first 2 m n elements of the Krylov-basis carve of the scratch
+// area (idle during the walk; global memory, L2-resident), written and re-read by this workgroup only between workgroup
+// barriers.  LDS: the operand tiles of wg_gemm, the Householder scalars, the reduction partials and weights of
+// k_batch_channel, and for the split the rotation scalars of a round (c, s, phase per pair), the row norms, their ranks,
+// the selection and the coefficients of the completion.  A round is two phases with a barrier each: the wave that owns
+// a pair forms its three inner products (lane l holds columns l and l + 64; wave tree) and publishes the rotation, then
+// element (pair, column) is rotated by thread (pair * n + column) % 512.  Every element has one owner per phase and
+// every sum one order; no atomics; the loops are bounded by the shapes and BATCH_PAIR_MAX_SWEEPS.
+constexpr double BP_TOL2 = 1.6e-29;  // (4e-15)^2: sqrt(128) eps = 2.5e-15 is what a 128-term inner product carries
+constexpr double BP_TINY = 1e-28;    // (1e-14)^2: a row this small against |theta| is rounding noise, not a direction
+
+struct BpSh {
+  double* rot;   // [4 * BATCH_PAIR_MAX_DIM / 2]  c, s, phase (re, im) of the round's pairs; s == 0: no rotation
+  double* nrm;   // [BATCH_PAIR_MAX_DIM] squared row norms after the last sweep
+  double* res;   // [BATCH_PAIR_MAX_DIM] completion: 1 - sum_k |B_k[c]|^2
+  double* scal;  // [3] kept weight sum_{j<=r} sigma_j^2, discarded fraction, BP_TINY |theta|^2
+  zc* h;         // [BATCH_MAX_BOND] completion: <B_k | v>
+  int* rank;     // [BATCH_PAIR_MAX_DIM]
+  int* sel;      // [BATCH_MAX_BOND] rows in descending order of norm
+  int* flag;     // [2] a rotation happened in this sweep; number of selected rows that are kept as they are
+};
+
+// the selection rule of a jump channel on the weights wk[0 .. K): W in index order, the smallest k whose running sum
+// exceeds u W, else the last k with w_k > 0; -1 when W == 0
+__device__ __forceinline__ int bc_pick(const double* wk, int K, double u) {
+  double W = 0.0;
+  for (int k = 0; k < K; ++k) W += wk[k];
+  if (!(W > 0.0)) return -1;
+  const double thr = u * W;
+  int pick = -1, lastpos = 0;
+  double run = 0.0;
+  for (int k = 0; k < K; ++k) {
+    run += wk[k];
+    if (wk[k] > 0.0) lastpos = k;
+    if (pick < 0 && run > thr) pick = k;
+  }
+  return pick < 0 ? lastpos : pick;
+}
+
+// the pair of round t that slot k of the round-robin (circle) schedule over mp = 2 np players holds
+__device__ __forceinline__ void bp_pair(int k, int t, int mp, int& i, int& j) {
+  const int ring = mp - 1;
+  if (k == 0) { i = ring; j = t; return; }
+  i = t + k; if (i >= ring) i -= ring;
+  j = t - k; if (j < 0) j += ring;
+}
+
+// T[(a,i)][(j,s)] = sum_b A[(a,i)][b] C[b][(j,s)]
+__device__ __noinline__ void bp_merge(const zc* A, const zc* C, zc* T, int m, int n, int r, zc* tiles) {
+  wg_gemm<true, false>(m, n, r, tiles,
+      [&](int mm, int k) { return A[(long)mm * r + k]; },
+      [&](int k, int nn) { return C[(long)k * n + nn]; },
+      [&](int mm, int nn, zc z) { T[(long)mm * n + nn] = z; });
+}
+
+// wk[k] = |B_k T|^2 for k < K, wk[BATCH_MAX_JUMP] = |T|^2, B_k (d0 d1) x (d0 d1) on the legs (i, j) of T[a][i][j][s]:
+// bc_weights with d0 d1 in the place of d
+__device__ __noinline__ void bp_weights(const zc* ops, int K, const zc* T, int dl, int d0, int d1, int dr, double* wk, const BtSh& sh) {
+  const int tid = threadIdx.x, n = d1 * dr, dd = d0 * d1;
+  const long N = (long)dl * d0 * n;
+  for (int k0 = 0; k0 < K; k0 += 4) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (long e = tid; e < N; e += SS_THREADS) {
+      const int row = (int)(e / n), col = (int)(e - (long)row * n), a = row / d0, i = row - a * d0, j = col / dr, s = col - j * dr;
+      const zc* src = T + (long)a * d0 * n + s;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (k0 + q < K) {
+          const zc* oprow = ops + ((long)(k0 + q) * dd + i * d1 + j) * dd;
+          double re = 0.0, im = 0.0;
+          for (int ip = 0; ip < d0; ++ip)
+            for (int jp = 0; jp < d1; ++jp) {
+              const zc b = oprow[ip * d1 + jp], c = src[(long)ip * n + jp * dr];
+              re = fma(b.x, c.x, re); re = fma(-b.y, c.y, re);
+              im = fma(b.x, c.y, im); im = fma(b.y, c.x, im);
+            }
+          acc[q] += re * re + im * im;
+        }
+    }
+    wg_reduce(acc, sh);
+    if (tid < 4 && k0 + tid < K) wk[k0 + tid] = sh.red[tid];
+  }
+  double s1[1] = {0.0};
+  for (long e = tid; e < N; e += SS_THREADS) { const zc z = T[e]; s1[0] += z.x * z.x + z.y * z.y; }
+  wg_reduce(s1, sh);
+  if (tid == 0) wk[BATCH_MAX_JUMP] = sh.red[0];
+  __syncthreads();
+}
+
+// T1[a,i,j,s] = sum_(i',j') Op[(i,j)][(i',j')] T0[a,i',j',s], then T0 <- T1 (the work copy of the split); element e
+// belongs to thread e % 512 in both passes
+__device__ __noinline__ void bp_apply(const zc* Op, zc* T0, zc* T1, int dl, int d0, int d1, int dr) {
+  const int n = d1 * dr, dd = d0 * d1;
+  const long N = (long)dl * d0 * n;
+  for (long e = threadIdx.x; e < N; e += SS_THREADS) {
+    const int row = (int)(e / n), col = (int)(e - (long)row * n), a = row / d0, i = row - a * d0, j = col / dr, s = col - j * dr;
+    const zc* src = T0 + (long)a * d0 * n + s;
+    const zc* oprow = Op + (long)(i * d1 + j) * dd;
+    double re = 0.0, im = 0.0;
+    for (int ip = 0; ip < d0; ++ip)
+      for (int jp = 0; jp < d1; ++jp) {
+        const zc b = oprow[ip * d1 + jp], c = src[(long)ip * n + jp * dr];
+        re = fma(b.x, c.x, re); re = fma(-b.y, c.y, re);
+        im = fma(b.x, c.y, im); im = fma(b.y, c.x, im);
+      }
+    T1[e] = make_double2(re, im);
+  }
+  __syncthreads();
+  for (long e = threadIdx.x; e < N; e += SS_THREADS) T0[e] = T1[e];
+  __syncthreads();
+}
+
+// One-sided Jacobi on the rows of T (m x n, row-major, in place): on return (SS_OK) the rows are mutually orthogonal and
+// ps.nrm[i] = |row i|^2.  With g = <x, y> = sum_c x[c] conj(y[c]) = |g| e^(i phi), a = |x|^2, b = |y|^2 the rotation is
+// x' = c x + s e^(i phi) y, y' = -s x + c e^(i phi) y, t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)), zeta = (a - b) / 2|g|.
+__device__ __noinline__ int bp_jacobi(zc* T, int m, int n, const BpSh& ps, const BtSh& sh) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int mp = (m + 1) & ~1, np = mp >> 1;
+  double tiny;
+  {  // |T|^2 is invariant under the rotations: the scale of "zero" for the whole split
+    double s1[1] = {0.0};
+    for (long e = tid; e < (long)m * n; e += SS_THREADS) { const zc z = T[e]; s1[0] += z.x * z.x + z.y * z.y; }
+    wg_reduce(s1, sh);
+    tiny = BP_TINY * sh.red[0];
+    if (tid == 0) ps.scal[2] = tiny;
+  }
+  int rc = SS_ENOTCONV;
+  for (int sweep = 0; sweep < BATCH_PAIR_MAX_SWEEPS; ++sweep) {
+    if (tid == 0) ps.flag[0] = 0;
+    __syncthreads();
+    for (int t = 0; t < mp - 1; ++t) {
+      for (int k = w; k < np; k += SS_WAVES) {  // the wave that owns slot k: inner products, rotation scalars
+        int i, j;
+        bp_pair(k, t, mp, i, j);
+        double c = 1.0, s = 0.0, px = 1.0, py = 0.0;
+        if (i < m && j < m) {  // m odd: the slot with the padding player rests
+          const zc* x = T + (long)i * n;
+          const zc* y = T + (long)j * n;
+          double a = 0.0, b = 0.0, gr = 0.0, gi = 0.0;
+          for (int cc = lane; cc < n; cc += 64) {
+            const zc zx = x[cc], zy = y[cc];
+            a += zx.x * zx.x + zx.y * zx.y;
+            b += zy.x * zy.x + zy.y * zy.y;
+            gr += zx.x * zy.x + zx.y * zy.y;  // x conj(y)
+            gi += zx.y * zy.x - zx.x * zy.y;
+          }
+          a = __shfl(wave_sum64(a), 0, 64);
+          b = __shfl(wave_sum64(b), 0, 64);
+          gr = __shfl(wave_sum64(gr), 0, 64);
+          gi = __shfl(wave_sum64(gi), 0, 64);
+          const double g2 = gr * gr + gi * gi;
+          if (g2 > BP_TOL2 * a * b && a > tiny && b > tiny) {  // a row at rounding level takes no part: it is never kept
+            const double ag = sqrt(g2), zeta = (a - b) / (2.0 * ag);
+            const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+            c = 1.0 / sqrt(1.0 + tt * tt);
+            s = c * tt;
+            px = gr / ag;
+            py = gi / ag;
+          }
+        }
+        if (lane == 0) {
+          ps.rot[4 * k] = c; ps.rot[4 * k + 1] = s; ps.rot[4 * k + 2] = px; ps.rot[4 * k + 3] = py;
+          if (s != 0.0) ps.flag[0] = 1;  // the same value from every writer
+        }
+      }
+      __syncthreads();
+      for (int e = tid; e < np * n; e += SS_THREADS) {  // element (slot, column): both rows of the slot at that column
+        const int k = e / n, cc = e - k * n;
+        const double s = ps.rot[4 * k + 1];
+        if (s == 0.0) continue;
+        const double c = ps.rot[4 * k], px = ps.rot[4 * k + 2], py = ps.rot[4 * k + 3];
+        int i, j;
+        bp_pair(k, t, mp, i, j);
+        const zc zx = T[(long)i * n + cc], zy = T[(long)j * n + cc];
+        const double yr = px * zy.x - py * zy.y, yi = px * zy.y + py * zy.x;
+        T[(long)i * n + cc] = make_double2(c * zx.x + s * yr, c * zx.y + s * yi);
+        T[(long)j * n + cc] = make_double2(c * yr - s * zx.x, c * yi - s * zx.y);
+      }
+      __syncthreads();
+    }
+    const int any = ps.flag[0];
+    __syncthreads();  // everyone has read the flag before the next sweep resets it
+    if (!any) { rc = SS_OK; break; }
+  }
+  for (int i = w; i < m; i += SS_WAVES) {
+    double a = 0.0;
+    for (int cc = lane; cc < n; cc += 64) { const zc z = T[(long)i * n + cc]; a += z.x * z.x + z.y * z.y; }
+    a = wave_sum64(a);
+    if (lane == 0) ps.nrm[i] = a;
+  }
+  __syncthreads();
+  return rc;
+}
+
+// Bp (r x n) from the orthogonal rows of T (m x n, squared norms ps.nrm): the r rows of largest norm (ties: the lower
+// index first), normalised; those of them at or below BP_TINY |theta|^2 (ps.scal[2]) are replaced one after the other by
+// the unit vector e_c furthest from the span so far (largest 1 - sum_k |B_k[c]|^2 >= 1 / n, the lowest c on a tie),
+// orthogonalised against it twice (classical Gram-Schmidt) and normalised.  ps.scal: kept weight, discarded fraction.
+__device__ __noinline__ void bp_select(const zc* T, zc* Bp, int m, int n, int r, const BpSh& ps, const BtSh& sh) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (tid < r) ps.sel[tid] = tid;  // in range whatever the norms are (NaN compares false everywhere)
+  __syncthreads();
+  if (tid < m) {
+    const double mine = ps.nrm[tid];
+    int rk = 0;
+    for (int j = 0; j < m; ++j) {
+      const double v = ps.nrm[j];
+      rk += (v > mine || (v == mine && j < tid)) ? 1 : 0;
+    }
+    ps.rank[tid] = rk;
+    if (rk < r) ps.sel[rk] = tid;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double tot = 0.0, disc = 0.0, kept = 0.0;
+    for (int i = 0; i < m; ++i) {
+      tot += ps.nrm[i];
+      if (ps.rank[i] >= r) disc += ps.nrm[i];
+    }
+    const double tiny = ps.scal[2];
+    int nz = 0;
+    for (int k = 0; k < r; ++k) {
+      const double v = ps.nrm[ps.sel[k]];
+      kept += v;
+      if (v > tiny) nz = k + 1;  // descending: the kept rows are the first nz
+    }
+    ps.scal[0] = kept;
+    ps.scal[1] = tot > 0.0 ? disc / tot : 0.0;
+    ps.flag[1] = nz;
+  }
+  __syncthreads();
+  const int nz = ps.flag[1];
+  for (int e = tid; e < r * n; e += SS_THREADS) {
+    const int k = e / n, cc = e - k * n;
+    zc z = make_double2(0.0, 0.0);
+    if (k < nz) {
+      const int i = ps.sel[k];
+      const double inv = 1.0 / sqrt(ps.nrm[i]);
+      z = T[(long)i * n + cc];
+      z.x *= inv; z.y *= inv;
+    }
+    Bp[e] = z;
+  }
+  __syncthreads();
+  for (int k = nz; k < r; ++k) {  // the orthonormal completion, one row at a time (r <= n: there is always room)
+    if (tid < n) {
+      double acc = 1.0;
+      for (int kk = 0; kk < k; ++kk) { const zc z = Bp[(long)kk * n + tid]; acc -= z.x * z.x + z.y * z.y; }
+      ps.res[tid] = acc;
+    }
+    __syncthreads();
+    int cs = 0;
+    double best = ps.res[0];
+    for (int cc = 1; cc < n; ++cc) {
+      const double v = ps.res[cc];
+      if (v > best) { best = v; cs = cc; }
+    }
+    if (tid < n) {  // v = e_cs - sum_kk B_kk conj(B_kk[cs])
+      double re = tid == cs ? 1.0 : 0.0, im = 0.0;
+      for (int kk = 0; kk < k; ++kk) {
+        const zc b = Bp[(long)kk * n + tid], q = Bp[(long)kk * n + cs];
+        re -= b.x * q.x + b.y * q.y;
+        im -= b.y * q.x - b.x * q.y;
+      }
+      Bp[(long)k * n + tid] = make_double2(re, im);
+    }
+    __syncthreads();
+    for (int kk = w; kk < k; kk += SS_WAVES) {  // h_kk = <B_kk | v>
+      double hr = 0.0, hi = 0.0;
+      for (int cc = lane; cc < n; cc += 64) {
+        const zc b = Bp[(long)kk * n + cc], v = Bp[(long)k * n + cc];
+        hr += b.x * v.x + b.y * v.y;
+        hi += b.x * v.y - b.y * v.x;
+      }
+      hr = wave_sum64(hr);
+      hi = wave_sum64(hi);
+      if (lane == 0) ps.h[kk] = make_double2(hr, hi);
+    }
+    __syncthreads();
+    zc v = make_double2(0.0, 0.0);
+    double s1[1] = {0.0};
+    if (tid < n) {
+      v = Bp[(long)k * n + tid];
+      for (int kk = 0; kk < k; ++kk) {
+        const zc hh = ps.h[kk], b = Bp[(long)kk * n + tid];
+        v.x -= hh.x * b.x - hh.y * b.y;
+        v.y -= hh.x * b.y + hh.y * b.x;
+      }
+      s1[0] = v.x * v.x + v.y * v.y;
+    }
+    wg_reduce(s1, sh);
+    const double inv = 1.0 / sqrt(sh.red[0]);
+    if (tid < n) Bp[(long)k * n + tid] = make_double2(v.x * inv, v.y * inv);
+    __syncthreads();
+  }
+}
+
+// Cp[(a,i)][b] = scl * sum_c T[(a,i)][c] conj(Bp[b][c])
+__device__ __noinline__ void bp_cprime(const zc* T, const zc* Bp, zc* Cp, int m, int n, int r, double scl, zc* tiles) {
+  wg_gemm<true, true>(m, r, n, tiles,
+      [&](int mm, int k) { return T[(long)mm * n + k]; },
+      [&](int k, int nn) { const zc z = Bp[(long)nn * n + k]; return make_double2(z.x, -z.y); },
+      [&](int mm, int nn, zc z) { Cp[(long)mm * r + nn] = make_double2(z.x * scl, z.y * scl); });
+}
+
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): see DESIGN.md section 7.3.
+__global__ __launch_bounds__(SS_THREADS) void k_batch_pair(BatchPairArgs gp) {
+  __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
+  __shared__ zc s_z[3 * BATCH_MAX_BOND];
+  __shared__ double s_d[SS_WAVES * 8 + 8 + BATCH_MAX_BOND + BATCH_MAX_JUMP + 1 + 2 * BATCH_PAIR_MAX_DIM + 2 * BATCH_PAIR_MAX_DIM + 3];
+  __shared__ int s_i[BATCH_PAIR_MAX_DIM + BATCH_MAX_BOND + 2];
+  BtSh sh{};
+  sh.mats = s_tiles;
+  sh.udiag = s_z; sh.rdiag = s_z + BATCH_MAX_BOND;
+  sh.wsh = s_d; sh.red = sh.wsh + SS_WAVES * 8; sh.gam = sh.red + 8;
+  double* wk = sh.gam + BATCH_MAX_BOND;  // [BATCH_MAX_JUMP + 1]
+  BpSh ps;
+  ps.rot = wk + BATCH_MAX_JUMP + 1; ps.nrm = ps.rot + 2 * BATCH_PAIR_MAX_DIM; ps.res = ps.nrm + BATCH_PAIR_MAX_DIM;
+  ps.scal = ps.res + BATCH_PAIR_MAX_DIM;  // [3]
+  ps.h = s_z + 2 * BATCH_MAX_BOND;
+  ps.rank = s_i; ps.sel = s_i + BATCH_PAIR_MAX_DIM; ps.flag = ps.sel + BATCH_MAX_BOND;
+  zc* tiles = s_tiles;
+
+  const BatchChanArgs& g = gp.c;
+  const int r = blockIdx.x, tid = threadIdx.x, L = g.L;
+  if (g.status[r] != SS_OK) return;  // a replica that failed in an earlier launch of the call does no more work
+  void* const* tab = g.ptrs + (size_t)r * g.ptr_stride;
+  zc* const* site = reinterpret_cast<zc* const*>(tab);
+  zc* const* envL = reinterpret_cast<zc* const*>(tab + L);
+  const zc* const* w2el = reinterpret_cast<const zc* const*>(tab + 4 * L + 2);
+  zc* scr = reinterpret_cast<zc*>(tab[6 * L + 2]);
+  zc* sig = scr + g.plan.o_sig;
+  zc* spare = scr + g.plan.o_spare;
+  zc* work = scr + g.plan.o_work;
+  zc* X = scr + g.plan.o_x;
+  zc* Y = scr + g.plan.o_y;
+  zc* T0 = scr + g.plan.o_u;  // the work copy of theta; theta itself follows it
+  const int lo = g.lo;
+
+  int rc = SS_OK;
+  for (int p = L - 1; p >= lo; --p) {
+    const BatchShape s = g.shp[p];
+    const int dl = s.dl, d = s.d, dr = s.dr;
+    const BatchChanSite ch = g.chan[p];
+    const zc* ops = g.ops + ch.off;
+    // the one-site channel of p, as k_batch_channel applies it
+    if (ch.kind == BCH_GATE) {
+      bc_apply(ops, 1.0, site[p], spare, dl, d, dr);
+    } else if (ch.kind == BCH_JUMP) {
+      bc_weights(ops, ch.nops, site[p], dl, d, dr, wk, sh);
+      const int pick = bc_pick(wk, ch.nops, bc_uniform(g.seed, g.ids[r], (unsigned long long)g.step, (unsigned long long)p));
+      if (pick < 0) { rc = SS_EZERO; break; }
+      const double scl = sqrt(wk[BATCH_MAX_JUMP] / wk[pick]);
+      bc_apply(ops + (long)pick * d * d, scl, site[p], spare, dl, d, dr);  // its barriers order the reads of wk above
+      if (tid == 0) g.counts[((size_t)r * L + p) * BATCH_MAX_JUMP + pick] += 1;
+    }
+    if (p == lo) break;
+    const BatchShape q = g.shp[p - 1];
+    const BatchChanSite pc = gp.pair[p - 1];
+    if (pc.kind == BCH_NONE) {
+      // Psi2sigmaB and Psi(p - 1) = A(p - 1) . sigma, as the backward sweep
+      const int mq = d * dr;
+      bt_qr(site[p], site[p], 1, mq, sig, 1, dl, mq, dl, work, sh);
+      bt_matmul(site[p - 1], sig, spare, site[p - 1], q.dl * q.d, dl, dl, tiles);
+      continue;
+    }
+    // the pair channel of bond (p - 1, p): merge, apply, split
+    const int m = q.dl * q.d, n = d * dr, dd = q.d * d;
+    zc* T1 = T0 + (long)m * n;
+    const zc* pops = g.ops + pc.off;
+    bp_merge(site[p - 1], site[p], T0, m, n, dl, tiles);
+    int pick = 0;
+    double before = 0.0;
+    if (pc.kind == BCH_JUMP) {
+      bp_weights(pops, pc.nops, T0, q.dl, q.d, d, dr, wk, sh);
+      pick = bc_pick(wk, pc.nops, bc_uniform(g.seed, g.ids[r], (unsigned long long)g.step, (unsigned long long)(L + p - 1)));
+      if (pick < 0) { rc = SS_EZERO; break; }
+      before = wk[BATCH_MAX_JUMP];
+    }
+    bp_apply(pops + (long)pick * dd * dd, T0, T1, q.dl, q.d, d, dr);  // its barriers order the reads of wk above
+    rc = bp_jacobi(T0, m, n, ps, sh);
+    if (rc != SS_OK) break;
+    bp_select(T0, site[p], m, n, dl, ps, sh);
+    const double scl = pc.kind == BCH_JUMP ? sqrt(before / ps.scal[0]) : 1.0;
+    bp_cprime(T1, site[p], site[p - 1], m, n, dl, scl, tiles);  // its barriers order the reads of ps.scal
+    if (tid == 0) {
+      gp.disc[r] += ps.scal[1];
+      if (pc.kind == BCH_JUMP) gp.pcounts[((size_t)r * L + p - 1) * BATCH_MAX_JUMP + pick] += 1;
+    }
+  }
+  if (rc == SS_OK)
+    for (int p = lo; p < L - 1; ++p) {
+      const BatchShape s = g.shp[p];
+      const int dl = s.dl, d = s.d, dr = s.dr;
+      // Psi2Asigma, L[p + 1], Psi(p + 1) = sigma . B(p + 1), as the forward sweep
+      bt_qr(site[p], site[p], dr, 1, sig, dr, 1, dl * d, dr, work, sh);
+      bt_env(envL[p], site[p], (long)d * dr, dr, 1, w2el[p], dl, s.ml, d, dr, s.mr, X, Y, envL[p + 1], tiles);
+      const BatchShape q = g.shp[p + 1];
+      zc* nxt = site[p + 1];
+      bt_matmul(sig, nxt, spare, nxt, dr, q.d * q.dr, dr, tiles);
+    }
+  if (rc != SS_OK && tid == 0) g.status[r] = rc;
+}
+
 }  // namespace
+
+bool batch_pair_fits(const BatchShape* shp, int L, const BatchPlan& plan, int q, std::string& why) {
+  const std::string at = "batch: pair channel on bond (" + std::to_string(q) + ", " + std::to_string(q + 1) + "): ";
+  if (q < 0 || q + 1 >= L) {
+    why = at + "out of range (the chain has " + std::to_string(L) + " sites, bonds (0, 1) to (" + std::to_string(L - 2) + ", " +
+          std::to_string(L - 1) + "))";
+    return false;
+  }
+  const long m = (long)shp[q].dl * shp[q].d, n = (long)shp[q + 1].d * shp[q + 1].dr;
+  if (m > BATCH_PAIR_MAX_DIM || n > BATCH_PAIR_MAX_DIM) {
+    why = at + "the two-site tensor is " + std::to_string(m) + " x " + std::to_string(n) + " (dl d_q x d_{q+1} dr), the split takes at most " +
+          std::to_string(BATCH_PAIR_MAX_DIM) + " rows and " + std::to_string(BATCH_PAIR_MAX_DIM) + " columns";
+    return false;
+  }
+  const long room = (long)MAXK * std::max(plan.max_site, plan.max_bond);
+  if (2 * m * n > room) {
+    why = at + "the two-site tensor and its copy take " + std::to_string(2 * m * n) + " elements, the Krylov-basis carve of the scratch area has " +
+          std::to_string(room);
+    return false;
+  }
+  return true;
+}
+
+void batch_pair_launch(hipStream_t st, const BatchPairArgs& a, int nrep) {
+  if (nrep < 1 || a.c.L < 2) throw ArgError("batch: nothing to launch");
+  if (a.c.lo < 0 || a.c.lo >= a.c.L - 1 || !a.pair || !a.pcounts || !a.disc) throw ArgError("batch: no pair channel is set");
+  hipLaunchKernelGGL(k_batch_pair, dim3(nrep), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
 
 bool batch_plan(const BatchShape* shp, int L, BatchPlan& plan, std::string& why) {
   plan = BatchPlan{};

@@ -290,6 +290,18 @@ int mitdvp_batch_jump_counts(mitdvp_batch* b, long long* counts) {
   if (!b || !b->b) { g_err = "null handle"; return MITDVP_EINVAL; }
   return guard(nullptr, [&] { b->b->jump_counts(counts); });
 }
+int mitdvp_batch_set_pair_channel(mitdvp_batch* b, int site, int kind, const double* ops_reim, int nops, int d0, int d1) {
+  if (!b || !b->b) { g_err = "null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->set_pair_channel(site, kind, ops_reim, nops, d0, d1); });
+}
+int mitdvp_batch_pair_jump_counts(mitdvp_batch* b, long long* counts) {
+  if (!b || !b->b) { g_err = "null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->pair_jump_counts(counts); });
+}
+int mitdvp_batch_discarded_weight(mitdvp_batch* b, double* weights) {
+  if (!b || !b->b) { g_err = "null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->discarded_weight(weights); });
+}
 void mitdvp_batch_destroy(mitdvp_batch* b) { delete b; }
 int mitdvp_invalidate_env(mitdvp_engine* h) { ENG_CALL(h, h->e->invalidate_env()); }
 int mitdvp_replace_site(mitdvp_engine* h, int isite, const double* reim, int gauge) {

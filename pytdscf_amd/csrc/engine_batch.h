@@ -1,5 +1,6 @@
 // engine_batch.h -- batched trajectories (engine_batch.hip): B borrowed engines stepped by one launch per half-sweep.
-// One-site gates and quantum-jump channels set on the batch act between the two half-sweeps of a time step: one more launch.
+// One-site and nearest-neighbour gates and quantum-jump channels set on the batch act between the two half-sweeps of a
+// time step: one more launch.
 #pragma once
 #include <string>
 #include <vector>
@@ -31,6 +32,16 @@ class Batch {
   void set_seed(unsigned long long seed, const unsigned long long* ids);
   void jump_counts(long long* counts);  // [B][L][BATCH_MAX_JUMP], zeros where no jump channel acted
   bool has_channels() const { return chan_lo_ >= 0; }
+  // Pair channels on the bond (site, site + 1), in the same walk (k_batch_pair takes the place of k_batch_channel while
+  // at least one is set: still one more launch per step).  ops_reim: nops matrices (d0 d1) x (d0 d1), row-major over
+  // (i_site, i_site+1), interleaved re / im; null removes the bond's channel.  ArgError naming the bond and the limit
+  // (nothing changed) when the bond is out of range, d0 / d1 are not the two physical dimensions, nops is out of range,
+  // the two-site tensor is outside batch_pair_fits, or the replicas run in imaginary time.
+  void set_pair_channel(int site, int kind, const double* ops_reim, int nops, int d0, int d1);
+  void pair_jump_counts(long long* counts);  // [B][L][BATCH_MAX_JUMP], row q: bond (q, q + 1)
+  // [B]: sum over the splits since the seed or a channel was last set of the weight each split discarded
+  void discarded_weight(double* out);
+  bool has_pairs() const { return npair_ > 0; }
 
   // Host destinations of the observables, every one may be null; nrec records on the leading axis (mitdvp_batch_out).
   struct ObsOut {
@@ -126,10 +137,18 @@ class Batch {
   std::vector<unsigned long long> h_ids_;
   unsigned long long* d_ids_ = nullptr;
   long long* d_counts_ = nullptr;
+  // pair channels: entry q is bond (q, q + 1); their operators follow the one-site ones in h_ops_ / d_ops_
+  std::vector<BatchChanSite> pair_, h_pair_;  // [L]
+  std::vector<std::vector<zc>> pair_ops_;     // [L]
+  int npair_ = 0;
+  BatchChanSite* d_pair_ = nullptr;
+  long long* d_pcounts_ = nullptr;
+  double* d_disc_ = nullptr;
 
   static std::vector<BatchShape> shapes_of(Engine& e);
   void check_channels() const;
   void upload_channels();
+  void channels_changed();  // chan_lo_, npair_, the dirty flag, and the discarded weights back to zero
   void launch_channel(long long step);
   void reset_generator(unsigned long long seed, const unsigned long long* ids);  // set_seed without its wait for the stream
   void validate();

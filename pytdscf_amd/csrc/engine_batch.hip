@@ -2,7 +2,8 @@
 // its own MPO), owns the pointer tables, the status words and the per-replica scratch of k_batch_sweep (batch_site.hip),
 // and steps all replicas with ONE launch per half-sweep (and, while one-site channels are set on the batch -- gates,
 // quantum-jump channels: the table, the operators, the generator's seed / ids / step counter and the jump counters are the
-// batch's -- ONE launch of k_batch_channel between the two half-sweeps of a time step).  No host threads, no compute-unit masks, no persistent-launch
+// batch's -- ONE launch of k_batch_channel between the two half-sweeps of a time step, or of k_batch_pair in its place
+// while a nearest-neighbour channel is set: its table, counters and discarded weights are the batch's too).  No host threads, no compute-unit masks, no persistent-launch
 // admission: the kernel's workgroups never wait for each other.  Host waits of a call: ONE stream synchronisation, behind
 // the copy of the status words at its end (plain hipStreamSynchronize: the library's wait helper, wait_published, spins on
 // a mapped word, which this path has none of); besides it only what the engines' own preparation does on first use
@@ -116,8 +117,13 @@ Batch::Batch(const std::vector<Engine*>& engines) : eng_(engines) {
   dev_alloc(d_chan_, (size_t)L_);
   dev_alloc(d_ids_, n);
   dev_alloc(d_counts_, n * L_ * BATCH_MAX_JUMP);
+  dev_alloc(d_pair_, (size_t)L_);
+  dev_alloc(d_pcounts_, n * L_ * BATCH_MAX_JUMP);
+  dev_alloc(d_disc_, n);
   chan_.assign((size_t)L_, BatchChanSite{BCH_NONE, 0, 0});
   chan_ops_.assign((size_t)L_, {});
+  pair_.assign((size_t)L_, BatchChanSite{BCH_NONE, 0, 0});
+  pair_ops_.assign((size_t)L_, {});
   reset_generator(0, nullptr);  // nothing is queued on the new stream: no wait; a batch without channels pays two small async operations
 }
 
@@ -141,6 +147,9 @@ Batch::~Batch() {
   if (d_ops_) (void)hipFree(d_ops_);
   if (d_ids_) (void)hipFree(d_ids_);
   if (d_counts_) (void)hipFree(d_counts_);
+  if (d_pair_) (void)hipFree(d_pair_);
+  if (d_pcounts_) (void)hipFree(d_pcounts_);
+  if (d_disc_) (void)hipFree(d_disc_);
   if (d_legs_) (void)hipFree(d_legs_);
   if (d_tbuf_) (void)hipFree(d_tbuf_);
   if (st_) (void)hipStreamDestroy(st_);
@@ -324,7 +333,8 @@ void Batch::sweep(double dt, bool forward, int* statuses) {
   validate();
   if (has_channels())
     throw ArgError("batch: a single half-sweep is refused while channels are set (site " + std::to_string(chan_lo_) +
-                   " carries one): they act between the two half-sweeps of a time step");
+                   (chan_[chan_lo_].kind != BCH_NONE ? " carries one" : " is the lower end of a pair channel") +
+                   "): they act between the two half-sweeps of a time step");
   prepare(forward);
   launch(dt, forward);
   finish(L_ > 1 ? forward : false, 1, statuses);
@@ -354,10 +364,48 @@ void Batch::set_channel(int site, int kind, const double* ops_reim, int nops, in
     chan_ops_[site].clear();
     chan_[site] = BatchChanSite{BCH_NONE, 0, 0};
   }
+  channels_changed();
+}
+
+void Batch::channels_changed() {
   chan_lo_ = -1;
-  for (int p = L_ - 1; p >= 0; --p)
-    if (chan_[p].kind != BCH_NONE) chan_lo_ = p;
+  npair_ = 0;
+  for (int p = L_ - 1; p >= 0; --p) {
+    if (chan_[p].kind != BCH_NONE || pair_[p].kind != BCH_NONE) chan_lo_ = p;  // a pair on (p, p + 1) touches p
+    if (pair_[p].kind != BCH_NONE) npair_ += 1;
+  }
   chan_dirty_ = true;
+  HIP_CHECK(hipMemsetAsync(d_disc_, 0, eng_.size() * sizeof(double), st_));
+}
+
+void Batch::set_pair_channel(int site, int kind, const double* ops_reim, int nops, int d0, int d1) {
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  if (site < 0 || site + 1 >= L_ || ops_reim) {  // removing a channel needs a bond in range, setting one the whole envelope
+    std::string why;
+    if (!batch_pair_fits(shp_.data(), L_, plan_, site, why)) throw ArgError(why);
+  }
+  const std::string at = "batch: pair channel on bond (" + std::to_string(site) + ", " + std::to_string(site + 1) + "): ";
+  if (ops_reim) {
+    if (kind != BCH_GATE && kind != BCH_JUMP) throw ArgError(at + "kind must be MITDVP_CHANNEL_GATE or MITDVP_CHANNEL_JUMP");
+    if (kind == BCH_GATE && nops != 1) throw ArgError(at + "a gate is one matrix (got " + std::to_string(nops) + ")");
+    if (kind == BCH_JUMP && (nops < 2 || nops > BATCH_MAX_JUMP))
+      throw ArgError(at + "a jump channel has 2 to " + std::to_string(BATCH_MAX_JUMP) + " operators (got " + std::to_string(nops) + ")");
+    if (d0 != shp_[site].d || d1 != shp_[site + 1].d)
+      throw ArgError(at + "the operators act on dimensions " + std::to_string(d0) + " x " + std::to_string(d1) + " (matrices of order " +
+                     std::to_string((long)d0 * d1) + "), the sites' physical dimensions are " + std::to_string(shp_[site].d) + " x " +
+                     std::to_string(shp_[site + 1].d) + " (order " + std::to_string((long)shp_[site].d * shp_[site + 1].d) + ")");
+    if (eng_[0]->cfg.relax != 0) throw ArgError(at + "channels do not go with imaginary time (relax must be 0)");
+    const size_t dd = (size_t)d0 * d1, ne = (size_t)nops * dd * dd;
+    std::vector<zc> ops(ne);
+    for (size_t e = 0; e < ne; ++e) ops[e] = make_double2(ops_reim[2 * e], ops_reim[2 * e + 1]);
+    pair_ops_[site] = std::move(ops);
+    pair_[site] = BatchChanSite{kind, nops, 0};
+  } else {
+    pair_ops_[site].clear();
+    pair_[site] = BatchChanSite{BCH_NONE, 0, 0};
+  }
+  channels_changed();
 }
 
 // what may have changed on the engines since the channels were set (validate() has just refreshed shp_)
@@ -368,6 +416,16 @@ void Batch::check_channels() const {
     if (chan_[p].kind != BCH_NONE && chan_ops_[p].size() != (size_t)chan_[p].nops * shp_[p].d * shp_[p].d)
       throw ArgError("batch: channel on site " + std::to_string(p) + ": the operators no longer match the site's physical dimension " +
                      std::to_string(shp_[p].d));
+  for (int q = 0; q + 1 < L_; ++q) {
+    if (pair_[q].kind == BCH_NONE) continue;
+    std::string why;
+    if (!batch_pair_fits(shp_.data(), L_, plan_, q, why)) throw ArgError(why);
+    const size_t dd = (size_t)shp_[q].d * shp_[q + 1].d;
+    if (pair_ops_[q].size() != (size_t)pair_[q].nops * dd * dd)
+      throw ArgError("batch: pair channel on bond (" + std::to_string(q) + ", " + std::to_string(q + 1) +
+                     "): the operators no longer match the sites' physical dimensions " + std::to_string(shp_[q].d) + " x " +
+                     std::to_string(shp_[q + 1].d));
+  }
 }
 
 void Batch::upload_channels() {
@@ -378,6 +436,11 @@ void Batch::upload_channels() {
     h_chan_[p].off = (long long)h_ops_.size();
     h_ops_.insert(h_ops_.end(), chan_ops_[p].begin(), chan_ops_[p].end());
   }
+  h_pair_ = pair_;
+  for (int q = 0; q < L_; ++q) {
+    h_pair_[q].off = (long long)h_ops_.size();
+    h_ops_.insert(h_ops_.end(), pair_ops_[q].begin(), pair_ops_[q].end());
+  }
   if (h_ops_.size() > ops_elems_) {
     HIP_CHECK(hipStreamSynchronize(st_));
     if (d_ops_) (void)hipFree(d_ops_);
@@ -386,6 +449,7 @@ void Batch::upload_channels() {
     ops_elems_ = h_ops_.size();
   }
   HIP_CHECK(hipMemcpyAsync(d_chan_, h_chan_.data(), h_chan_.size() * sizeof(BatchChanSite), hipMemcpyHostToDevice, st_));
+  if (npair_) HIP_CHECK(hipMemcpyAsync(d_pair_, h_pair_.data(), h_pair_.size() * sizeof(BatchChanSite), hipMemcpyHostToDevice, st_));
   if (!h_ops_.empty()) HIP_CHECK(hipMemcpyAsync(d_ops_, h_ops_.data(), h_ops_.size() * sizeof(zc), hipMemcpyHostToDevice, st_));
   chan_dirty_ = false;
 }
@@ -405,7 +469,16 @@ void Batch::launch_channel(long long step) {
   a.step = step;
   a.ids = d_ids_;
   a.counts = d_counts_;
-  batch_channel_launch(st_, a, (int)eng_.size());
+  if (npair_) {  // the walk with pair channels is a kernel of its own; without one k_batch_channel runs as before
+    BatchPairArgs pa{};
+    pa.c = a;
+    pa.pair = d_pair_;
+    pa.pcounts = d_pcounts_;
+    pa.disc = d_disc_;
+    batch_pair_launch(st_, pa, (int)eng_.size());
+  } else {
+    batch_channel_launch(st_, a, (int)eng_.size());
+  }
   n_launch_ += 1;
 }
 
@@ -423,12 +496,28 @@ void Batch::reset_generator(unsigned long long seed, const unsigned long long* i
   for (size_t i = 0; i < n; ++i) h_ids_[i] = ids ? ids[i] : (unsigned long long)i;
   HIP_CHECK(hipMemcpyAsync(d_ids_, h_ids_.data(), n * sizeof(unsigned long long), hipMemcpyHostToDevice, st_));
   HIP_CHECK(hipMemsetAsync(d_counts_, 0, n * L_ * BATCH_MAX_JUMP * sizeof(long long), st_));
+  HIP_CHECK(hipMemsetAsync(d_pcounts_, 0, n * L_ * BATCH_MAX_JUMP * sizeof(long long), st_));
+  HIP_CHECK(hipMemsetAsync(d_disc_, 0, n * sizeof(double), st_));
 }
 
 void Batch::jump_counts(long long* counts) {
   if (!counts) throw ArgError("batch: null destination for the jump counters");
   HIP_CHECK(hipSetDevice(device_));
   HIP_CHECK(hipMemcpyAsync(counts, d_counts_, eng_.size() * L_ * BATCH_MAX_JUMP * sizeof(long long), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+void Batch::pair_jump_counts(long long* counts) {
+  if (!counts) throw ArgError("batch: null destination for the pair jump counters");
+  HIP_CHECK(hipSetDevice(device_));
+  HIP_CHECK(hipMemcpyAsync(counts, d_pcounts_, eng_.size() * L_ * BATCH_MAX_JUMP * sizeof(long long), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+void Batch::discarded_weight(double* out) {
+  if (!out) throw ArgError("batch: null destination for the discarded weights");
+  HIP_CHECK(hipSetDevice(device_));
+  HIP_CHECK(hipMemcpyAsync(out, d_disc_, eng_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
   HIP_CHECK(hipStreamSynchronize(st_));
 }
 
@@ -604,7 +693,8 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
 std::string Batch::status_message(int code) const {
   const Engine& e0 = *eng_[0];
   if (code == SS_ENOTCONV)
-    return std::string(e0.cfg.integrator == MITDVP_LANCZOS ? "Short Iterative Lanczos" : "Short Iterative Arnoldi") +
+    return std::string(has_pairs() ? "The split of a pair channel is not converged in " + std::to_string(BATCH_PAIR_MAX_SWEEPS) + " Jacobi sweeps, or " : "") +
+           std::string(e0.cfg.integrator == MITDVP_LANCZOS ? "Short Iterative Lanczos" : "Short Iterative Arnoldi") +
            " is not converged in " + std::to_string(e0.cfg.max_krylov) + " basis. Try shorter time interval.";
   if (code == SS_EZERO)
     return has_channels() ? "Initial psi has zero norm, or every operator of a jump channel gave it zero weight." : "Initial psi has zero norm.";

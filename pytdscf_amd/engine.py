@@ -817,6 +817,22 @@ def density_key_legs(key, nsite: int) -> list[int]:
     return legs
 
 
+def pair_key(key, nsite: int) -> tuple[int, int]:
+    """The bond of a pair channel, ``(q, q + 1)`` with ``0 <= q < nsite - 1``, from a key given as a tuple;
+    ``ValueError`` naming the key otherwise (not two sites, not neighbours, descending, out of range).  Pure Python."""
+    try:
+        k = tuple(int(s) for s in key)
+    except TypeError:
+        raise ValueError(f"pair channel key {key!r}: a key is a tuple of two neighbouring sites (q, q + 1)") from None
+    if len(k) != 2:
+        raise ValueError(f"pair channel key {k}: a key names two neighbouring sites (q, q + 1)")
+    if k[1] != k[0] + 1:
+        raise ValueError(f"pair channel key {k}: the sites must be nearest neighbours in ascending order, (q, q + 1)")
+    if not 0 <= k[0] < nsite - 1:
+        raise ValueError(f"pair channel key {k}: bond out of range (the chain has {nsite} sites)")
+    return k
+
+
 class TDVPBatch:
     """B independent trajectories (replicas) of one chain shape on ONE GPU, any B: one kernel launch per half-sweep for the
     whole batch (``mitdvp_batch_step`` / ``k_batch_sweep``: one workgroup owns one replica, the replica index is the
@@ -905,10 +921,35 @@ class TDVPBatch:
 
     # ---- one-site channels between the two half-sweeps of a time step (mitdvp_batch_set_channel) ----
     def _push_channel(self, site, kind, ops):
-        if ops is None:
+        if isinstance(site, tuple):  # a pair channel on the bond (q, q + 1); ops (K, d0, d1, d0, d1)
+            if ops is None:
+                _lib.check(self._lib.mitdvp_batch_set_pair_channel(self._b, site[0], 0, None, 0, 0, 0))
+            else:
+                _lib.check(self._lib.mitdvp_batch_set_pair_channel(self._b, site[0], kind, _dp(ops), ops.shape[0], ops.shape[1],
+                                                                   ops.shape[2]))
+        elif ops is None:
             _lib.check(self._lib.mitdvp_batch_set_channel(self._b, int(site), 0, None, 0, 0))
         else:
             _lib.check(self._lib.mitdvp_batch_set_channel(self._b, int(site), kind, _dp(ops), ops.shape[0], ops.shape[1]))
+
+    def _pair_ops(self, kind, key, ops):
+        """the operators of a pair channel as (K, d0, d1, d0, d1) from (dd, dd) / (K, dd, dd) or the four-leg forms"""
+        q = key[0]
+        gate = kind == _lib.CHANNEL_GATE
+        if gate and ops.ndim in (2, 4):
+            ops = ops[None]
+        if ops.ndim == 5:
+            if ops.shape[1:3] != ops.shape[3:5]:
+                raise ValueError(f"bond {key}: four-leg operators are (d0, d1, d0, d1), got shape {ops.shape[1:]}")
+            return np.ascontiguousarray(ops)
+        if ops.ndim != 3 or ops.shape[1] != ops.shape[2]:
+            raise ValueError(f"bond {key}: the operators must be square matrices of order d0 d1 or four-leg tensors "
+                             f"(d0, d1, d0, d1); got shape {ops.shape}")
+        d0, d1 = (self.engines[0].get_site_shape(p)[1] for p in key)
+        if ops.shape[1] != d0 * d1:
+            raise ValueError(f"bond {key}: the operators are of order {ops.shape[1]}, the sites' physical dimensions are "
+                             f"{d0} x {d1} (order {d0 * d1})")
+        return np.ascontiguousarray(ops.reshape(ops.shape[0], d0, d1, d0, d1))
 
     def _push_seed(self, seed, ids):
         arr = None if ids is None else (C.c_uint64 * len(ids))(*ids)
@@ -918,6 +959,10 @@ class TDVPBatch:
         """``table``: {site: operators (K, d, d) or None}.  The library validates; a refused table changes nothing."""
         new = {}
         for site, ops in dict(table).items():
+            if isinstance(site, (tuple, list)):
+                key = pair_key(site, self.engines[0].nsite)
+                new[key] = (kind, None if ops is None else self._pair_ops(kind, key, _c128(ops)))
+                continue
             if ops is not None:
                 ops = _c128(ops)
                 if kind == _lib.CHANNEL_GATE and ops.ndim == 1:  # a diagonal gate, as TDVPEngine.set_gates takes it
@@ -948,7 +993,11 @@ class TDVPBatch:
         """``{site: U (d, d) or a length-d diagonal}``: one-site gates applied to every replica between the two half-sweeps of each time step
         (the reference's ``one_gate_to_apply``), as they are -- ``U`` need not be unitary.  ``{site: None}`` removes a
         site's channel.  One more launch per time step while any channel is set.  The replicas must have their tensors
-        and MPOs already (the library checks the physical dimensions)."""
+        and MPOs already (the library checks the physical dimensions).
+
+        A key may be a bond ``(q, q + 1)``: a two-site gate ``(d0 d1, d0 d1)``, row-major over the two physical indices, or
+        ``(d0, d1, d0, d1)``.  It is applied to the merged two-site tensor, which is split again at the bond's dimension
+        as it is (``k_batch_pair``); nothing is rescaled, what the split discards adds to ``discarded_weight()``."""
         self._set_channels(_lib.CHANNEL_GATE, gates)
 
     def set_jumps(self, jumps: dict, seed: int = 0, trajectory_ids=None):
@@ -962,7 +1011,11 @@ class TDVPBatch:
         list ``engines`` is changed between calls (an engine replaced, added or taken out); the channels and the seed
         are then set again on the new one, so the step counter and the jump counters start again from zero in the
         middle of an ensemble, and ``trajectory_ids`` given for another number of replicas raise ``ValueError`` until
-        ``set_jumps`` is called again."""
+        ``set_jumps`` is called again.
+
+        A key may be a bond ``(q, q + 1)`` with ``B`` of shape ``(K, d0 d1, d0 d1)`` or ``(K, d0, d1, d0, d1)``: the same
+        rule on the merged two-site tensor with the uniform ``jump_uniform(seed, trajectory_id, step, L + q)``; the norm
+        after the re-split equals the norm before the jump.  Counted in ``pair_jump_counts()``."""
         n = len(self.engines)
         ids = None
         if trajectory_ids is not None:
@@ -990,6 +1043,21 @@ class TDVPBatch:
         n, nsite = len(self.engines), self.engines[0].nsite
         out = np.zeros((n, nsite, _lib.MAX_JUMP), dtype=np.int64)
         _lib.check(self._lib.mitdvp_batch_jump_counts(self._handle(), out.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return out
+
+    def pair_jump_counts(self):
+        """(B, L, 16) integers: how often operator k of the pair jump channel on bond (q, q + 1) -- row q -- was picked by
+        replica r since the seed was set; they start again from zero when ``jump_counts()`` does."""
+        n, nsite = len(self.engines), self.engines[0].nsite
+        out = np.zeros((n, nsite, _lib.MAX_JUMP), dtype=np.int64)
+        _lib.check(self._lib.mitdvp_batch_pair_jump_counts(self._handle(), out.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return out
+
+    def discarded_weight(self):
+        """(B,) numbers: per replica the sum over the splits of its pair channels of the weight each split discarded,
+        ``sum_{j>r} sigma_j^2 / sum_j sigma_j^2`` (r: the bond's dimension), since the seed or a channel was last set."""
+        out = np.zeros(len(self.engines), dtype=np.float64)
+        _lib.check(self._lib.mitdvp_batch_discarded_weight(self._handle(), _dp(out)))
         return out
 
     def launches(self) -> int:

@@ -3,7 +3,9 @@
 ``TDVPBatch`` whose observables and ensemble means are formed on the device (``mitdvp_batch_run``).
 
 One-site gates (``Model(one_gate_to_apply=...)``) and sampled one-site Kraus channels (``jumps=``: quantum-jump
-trajectories at Hilbert-space cost) act between the two half-sweeps of every step, inside the batch (``k_batch_channel``).
+trajectories at Hilbert-space cost) act between the two half-sweeps of every step, inside the batch (``k_batch_channel``);
+so do sampled nearest-neighbour channels (``jumps={(q, q + 1): B}``: incoherent hopping, correlated decay), which the batch
+applies to the merged two-site tensor and splits again at the bond's dimension (``k_batch_pair``).
 
 Nothing falls back: a model the batched kernels do not take raises with the library's message."""
 
@@ -12,7 +14,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import units
-from .engine import TDVPBatch, density_key_legs
+from .engine import TDVPBatch, density_key_legs, pair_key
 from .mps import product_state_cores
 
 
@@ -38,11 +40,28 @@ def jump_uniform(seed: int, trajectory_id: int, step: int, site: int) -> float:
 
 
 def _jump_table(jumps, dims):
-    """{site: (K, d, d) complex} checked against the model's dimensions and the kernel's limits, before any engine exists"""
+    """{site: (K, d, d) complex, (q, q + 1): (K, d0 d1, d0 d1) complex} checked against the model's dimensions and the
+    kernel's limits, before any engine exists"""
     from ._lib import MAX_JUMP
 
     table = {}
     for site, B in dict(jumps).items():
+        if isinstance(site, (tuple, list)):  # a pair channel on the bond (q, q + 1)
+            key = pair_key(site, len(dims))
+            d0, d1 = dims[key[0]], dims[key[1]]
+            B = np.asarray(B, dtype=np.complex128)
+            if B.ndim == 5 and B.shape[1:] == (d0, d1, d0, d1):
+                B = B.reshape(B.shape[0], d0 * d1, d0 * d1)
+            if B.ndim != 3 or B.shape[1] != B.shape[2]:
+                raise ValueError(f"jumps[{key}] must have shape (K, d0 d1, d0 d1) or (K, d0, d1, d0, d1) with d0, d1 = {d0}, {d1}; "
+                                 f"got {B.shape}")
+            if B.shape[1] != d0 * d1:
+                raise ValueError(f"jumps[{key}]: the operators are of order {B.shape[1]}, the sites' dimensions are {d0} x {d1} "
+                                 f"(order {d0 * d1})")
+            if not 2 <= B.shape[0] <= MAX_JUMP:
+                raise ValueError(f"jumps[{key}]: a jump channel has 2 to {MAX_JUMP} operators, got {B.shape[0]}")
+            table[key] = B
+            continue
         site = int(site)
         if not 0 <= site < len(dims):
             raise ValueError(f"jumps: site {site} is out of range")
@@ -95,7 +114,13 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
     probabilities and keeps its norm, so the MEAN over many trajectories follows the channel.  ``replicas_per_start``
     repeats every start that often (the trajectory axis and ``weights`` then run over the expanded list, start-major);
     trajectory i of the expanded list draws ``jump_uniform(seed, first_trajectory + i, step, site)``, so an ensemble
-    cut into chunks (``first_trajectory`` = the chunk's offset) draws the same numbers as one big batch."""
+    cut into chunks (``first_trajectory`` = the chunk's offset) draws the same numbers as one big batch.
+
+    A key of ``jumps`` may also be a bond ``(q, q + 1)`` with ``B`` of shape ``(K, d_q d_{q+1}, d_q d_{q+1})`` (row-major
+    over the two physical indices) or ``(K, d_q, d_{q+1}, d_q, d_{q+1})``: a nearest-neighbour Kraus channel, sampled by the
+    same rule with the uniform ``jump_uniform(seed, trajectory, step, nsite + q)``; the bond keeps its dimension, so what
+    the re-split truncates is lost (``TDVPBatch.discarded_weight``).  A key that is not an ascending pair of neighbours is
+    a ``ValueError`` naming it.  ``model.one_gate_to_apply`` stays one-site."""
     if integrator not in ("lanczos", "arnoldi"):
         raise ValueError(f"Invalid integrator: {integrator}")
     keys, every = reduced_density
