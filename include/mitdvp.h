@@ -349,7 +349,9 @@ int mitdvp_site_exp(mitdvp_engine* h, double dt_au);      /* exp_superH_propagat
  * bit 2 block-sparse W stage, bit 3 the one-launch small-bond kernel, bit 4 the two-product form of an edge-structured
  * core (reducing epilogue, no intermediates; then bits 0-2 are clear); with bit 4, bit 5 (0x20) = its R side and bit 6
  * (0x40) = its L side ran the folded variant (the reduced core contracted into the environment block once per local
- * solve, the side one plain GEMM; MITDVP_FOLD_APPLY=0 never, 1 wherever valid).  For parity tests of the kernels a sweep runs. */
+ * solve, the side one plain GEMM; MITDVP_FOLD_APPLY=0 never, 1 wherever valid); bit 7 (0x80) / bit 8 (0x100) = that folded
+ * R / L side ran as seven half-size products (one Strassen level; MITDVP_FOLD_STRASSEN=0 never, 1 wherever its sizes are
+ * even).  For parity tests of the kernels a sweep runs. */
 int mitdvp_heff_apply_center(mitdvp_engine* h, const double* reim_in, double* reim_out, int* flags);
 /* trans_next_psite_AsigmaB (:1798-1850): centre -> A sigma (forward) or sigma B; the block through the site is built,
  * sigma stays in the engine as the pending bond matrix */

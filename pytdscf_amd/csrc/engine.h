@@ -59,9 +59,12 @@ struct DevBuf {
 // handed to each of its applies.  trim_l / trim_r: the FIRST MPO-bond block of the left / the last one of the right
 // environment is the identity (the sites on that side are canonical and the MPO passes "nothing applied yet" through;
 // the reference short-circuits such blocks as well, _mps_mpo.py:510-523) and stage S1 / S3 skips it; edge: the applies
-// take heff_apply_edge, fold_l / fold_r: with that side folded.  The default is the plain three-stage chain, which is
-// what every apply outside such a solve gets.
-struct ApplyPlan { bool trim_l = false, trim_r = false, edge = false, fold_l = false, fold_r = false; };
+// take heff_apply_edge, fold_l / fold_r: with that side folded, strassen_l / strassen_r: the folded side's product as seven
+// half-size products (one Strassen level) on the factors choose_apply_forms packed.  The default is the plain three-stage
+// chain, which is what every apply outside such a solve gets.
+struct ApplyPlan {
+  bool trim_l = false, trim_r = false, edge = false, fold_l = false, fold_r = false, strassen_l = false, strassen_r = false;
+};
 
 struct MpoSite {
   int ml = 0, d = 0, mr = 0;
@@ -323,6 +326,17 @@ class Engine {
   // the folded variant of the edge form, per side (ApplyPlan::fold_r / fold_l): the reduced core contracted into the
   // environment block once per local solve (choose_apply_forms, operators in Y_ / X_), the side's apply one plain GEMM
   int fold_mode_ = -1;         // MITDVP_FOLD_APPLY: 0 never, 1 wherever the edge form is valid, -1 (default) the rule of choose_apply_forms
+  // One Strassen level over a folded side (ApplyPlan::strassen_l / strassen_r): the side's GEMM as seven half-size
+  // products instead of eight.  The operator's seven factors are packed once per local solve (str_l_ / str_r_, beside
+  // GL / GR, which stay in X_ / Y_), the vector's seven per apply (str_v_), the products go to str_m_ and one pass
+  // combines them into (or onto) sigma.  MITDVP_FOLD_STRASSEN: 0 never, 1 wherever a folded side has even halves, -1
+  // (default) the rule of choose_apply_forms.  The buffers are allocated the first time a side takes the form and grow
+  // only; a side whose buffers cannot be allocated keeps the plain GEMM.
+  int strassen_mode_ = -1;
+  bool strassen_batched_ = true;  // MITDVP_STRASSEN_BATCH=0: seven launches instead of one batched launch (A/B testing)
+  DevBuf str_l_, str_r_, str_v_, str_m_;
+  static bool try_reserve(DevBuf& b, size_t elems);
+  void strassen_side(const zc* fixed, bool fixed_is_a, const zc* psi, long ldpsi, zc* out, long hm, long hn, long hk, bool accumulate);
   // MITDVP_FOLD_ENV: the structured environment update (env_update_fold): 0 never, 1 wherever it is valid, -1 (default) the
   // rule of env_fold_ok.  The identity sets it relies on are those the last choose_apply_forms found for exactly these
   // blocks of this site: env_chk_, set there and nowhere else.  It outlives the call (in segment mode site_exp and

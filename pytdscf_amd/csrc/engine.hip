@@ -29,6 +29,8 @@ Engine::Engine(const mitdvp_config& c) : cfg(c), L_(c.nsite) {
   if (const char* e = std::getenv("MITDVP_TRIM_IDENTITY")) trim_identity_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_EDGE_APPLY")) edge_mode_ = std::atoi(e);
   if (const char* e = std::getenv("MITDVP_FOLD_APPLY")) fold_mode_ = std::atoi(e);
+  if (const char* e = std::getenv("MITDVP_FOLD_STRASSEN")) strassen_mode_ = std::atoi(e);
+  if (const char* e = std::getenv("MITDVP_STRASSEN_BATCH")) strassen_batched_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_FOLD_ENV")) fold_env_mode_ = std::atoi(e);
   if (const char* e = std::getenv("MITDVP_QR_GAUGE_FREE")) qr_gauge_free_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_KEFF_IDENT")) keff_ident_ = std::atoi(e) != 0;

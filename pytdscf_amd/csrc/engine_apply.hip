@@ -4,6 +4,12 @@
 
 namespace mitdvp {
 
+// 64 x 64 tiles each half-size product of a Strassen level must have for a folded side to take it by default
+// (choose_apply_forms): one whole round on the 256 compute units, seven in the batched launch.  Measured per apply
+// (profiles/fold_strassen_ab.txt): 1024 tiles (C4, 1024 x 16 x 1024) -12.5 %, 256 tiles (512 x 16 x 512) -11 %, 64 tiles
+// (C5, 512 x 4 x 512) +1 % and the factors to pack on top; nothing between 64 and 256 has been measured.
+constexpr long STRASSEN_MIN_TILES = 256;
+
 // W stage: Y_b[(i,q)][n] = W2[(i,q)][(p,j)] X_b[(p,j)][n] for nbatch slabs b (X_, Y_ workspaces).  With a
 // finite-state-machine MPO most (p, q) blocks of W are zero: rows of W2 ordered (q, i), per 64-row tile the list of
 // 16-wide K tiles that hold a non-zero; row ranges that need most K tiles go through the plain kernel, the others
@@ -100,6 +106,41 @@ void Engine::heff_apply_rect(const zc* L, const MpoSite& w, const zc* R, const z
   cnt_.heff_stage_flops[2] += 8.0 * (double)na * d * dro * (trim ? mr - 1 : mr) * dri;
 }
 
+bool Engine::try_reserve(DevBuf& b, size_t elems) {
+  if (elems <= b.n) return true;
+  b.release();
+  zc* q = nullptr;
+  if (hipMalloc(&q, elems * sizeof(zc)) != hipSuccess) { (void)hipGetLastError(); return false; }
+  b.p = q; b.n = elems;
+  return true;
+}
+
+// One folded side of an apply as seven half-size products (ApplyPlan::strassen_l / strassen_r; the formulas: vecops.h).
+// out ((2 hm) x (2 hn), leading dimension ldpsi) (+)= A B with the contraction 2 hk long.  fixed: the operator's seven
+// packed factors, the left ones of GL (fixed_is_a; psi is B, (2 hk) x (2 hn)) or the right ones of GR^T as stored, each
+// hn x hk for a transB product (psi is A, (2 hm) x (2 hk)).  Every summation order is fixed: the same bits every run.
+void Engine::strassen_side(const zc* fixed, bool fixed_is_a, const zc* psi, long ldpsi, zc* out, long hm, long hn, long hk,
+                           bool accumulate) {
+  if (fixed_is_a) strassen_operands(st_, psi, ldpsi, hk, hn, str_v_.p, STRASSEN_B);
+  else strassen_operands(st_, psi, ldpsi, hm, hk, str_v_.p, STRASSEN_A);
+  const zc* A = fixed_is_a ? fixed : str_v_.p;
+  const zc* B = fixed_is_a ? str_v_.p : fixed;
+  ZgemmDesc g = zgemm_desc(A, B, str_m_.p, (int)hm, (int)hn, (int)hk);
+  if (!fixed_is_a) { g.transB = 1; g.ldb = hk; }
+  if (strassen_batched_) {
+    g.batch = 7; g.strideA = hm * hk; g.strideB = hk * hn; g.strideC = hm * hn;
+    zgemm(st_, g);
+  } else {
+    for (int k = 0; k < 7; ++k) {
+      ZgemmDesc h = g;
+      h.A = A + k * hm * hk; h.B = B + k * hk * hn; h.C = str_m_.p + k * hm * hn;
+      zgemm(st_, h);
+    }
+  }
+  strassen_combine(st_, str_m_.p, hm, hn, out, ldpsi, accumulate);
+  cnt_.n_launch += 2 + (strassen_batched_ ? 1 : 7);
+}
+
 // The apply for an edge-structured core between canonical environments (MpoSite::EdgeCache; L[:, 0, :] = R[:, mr-1, :] = 1,
 // verified numerically by choose_apply_forms).  All terms with c = 0 see X_0 = psi, all terms with t = mr - 1 see the
 // identity on the right, and there are no others:
@@ -120,7 +161,14 @@ void Engine::heff_apply_edge(const zc* L, const MpoSite& w, const zc* R, const z
   const MpoSite::EdgeCache& c = w.edge;
   bool first = true;
   double exe = 0.0;
-  if (c.has_r && plan.fold_r) {
+  if (c.has_r && plan.fold_r && plan.strassen_r) {  // sigma[a][(i,r)] = psi GR^T: psi's factors per apply, GR's in str_r_
+    timer_begin(12);
+    strassen_side(str_r_.p, false, psi, (long)d * dr, out, dl / 2, (long)d * dr / 2, (long)d * dr / 2, false);
+    timer_end();
+    first = false;
+    exe += 7.0 * (double)dl * d * dr * d * dr;
+    cnt_.heff_stage_flops[2] += 7.0 * (double)dl * d * dr * d * dr;
+  } else if (c.has_r && plan.fold_r) {
     timer_begin(12);
     ZgemmDesc g = zgemm_desc(psi, Y_.p, out, dl, d * dr, d * dr);
     g.transB = 1; g.ldb = (long)d * dr;
@@ -144,7 +192,14 @@ void Engine::heff_apply_edge(const zc* L, const MpoSite& w, const zc* R, const z
     exe += 8.0 * ((double)dl * d * dr * mr * dr + (double)dl * dr * d * d * mr);
     cnt_.heff_stage_flops[2] += 8.0 * ((double)dl * d * dr * mr * dr + (double)dl * dr * d * d * mr);
   }
-  if (c.has_l && plan.fold_l) {
+  if (c.has_l && plan.fold_l && plan.strassen_l) {  // sigma[(a,i)][r] (+)= GL psi: GL's factors in str_l_, psi's per apply;
+    timer_begin(10);                                 // the combining pass adds to what the R side wrote
+    strassen_side(str_l_.p, true, psi, dr, out, (long)dl * d / 2, dr / 2, (long)dl * d / 2, !first);
+    timer_end();
+    first = false;
+    exe += 7.0 * (double)dl * d * dl * d * dr;
+    cnt_.heff_stage_flops[0] += 7.0 * (double)dl * d * dl * d * dr;
+  } else if (c.has_l && plan.fold_l) {
     timer_begin(10);
     ZgemmDesc g = zgemm_desc(X_.p, psi, out, dl * d, dr, dl * d);
     if (!first) g.beta = make_double2(1.0, 0.0);
@@ -342,8 +397,36 @@ ApplyPlan Engine::choose_apply_forms(const zc* Lb, const MpoSite& w, const zc* R
     timer_begin(11);
     if (plan.fold_r) fold_env_core(st_, Rb, w.edge.w_r.p, Y_.p, dr, mr, d, (long)d * mr, mr, 1, (long)dr * d * dr, (long)d * dr, dr, 1);
     if (plan.fold_l) fold_env_core(st_, Lb, w.edge.w_l.p, X_.p, dl, ml, d, (long)ml * d, 1, d, (long)dl * d, (long)d * dl * d, 1, d);
+    // One Strassen level over a folded side: its rows, columns and contraction length even, and (the rule) the half-size
+    // products still at least one whole round of 64 x 64 tiles on the device -- STRASSEN_MIN_TILES per product, measured:
+    // profiles/fold_strassen_ab.txt.  The operator's seven factors are packed here, once per local solve, from GL / GR,
+    // which stay where they are; buffers that cannot be had leave the side with its plain GEMM.
+    const size_t quarter = (size_t)dl * d * dr / 4;
+    auto halves_fill = [](long hm, long hn) { return ((hm + 63) / 64) * ((hn + 63) / 64) >= STRASSEN_MIN_TILES; };
+    if (plan.fold_r && strassen_mode_ != 0 && dl % 2 == 0 && ((long)d * dr) % 2 == 0 &&
+        (strassen_mode_ > 0 || halves_fill(dl / 2, (long)d * dr / 2))) {
+      const long h = (long)d * dr / 2;
+      if (try_reserve(str_r_, 7 * (size_t)h * h) && try_reserve(str_v_, 7 * quarter) && try_reserve(str_m_, 7 * quarter)) {
+        strassen_operands(st_, Y_.p, 2 * h, h, h, str_r_.p, STRASSEN_BT);
+        plan.strassen_r = true;
+        cnt_.n_launch += 1;
+      }
+    }
+    if (plan.fold_l && strassen_mode_ != 0 && ((long)dl * d) % 2 == 0 && dr % 2 == 0 &&
+        (strassen_mode_ > 0 || halves_fill((long)dl * d / 2, dr / 2))) {
+      const long h = (long)dl * d / 2;
+      if (try_reserve(str_l_, 7 * (size_t)h * h) && try_reserve(str_v_, 7 * quarter) && try_reserve(str_m_, 7 * quarter)) {
+        strassen_operands(st_, X_.p, 2 * h, h, h, str_l_.p, STRASSEN_A);
+        plan.strassen_l = true;
+        cnt_.n_launch += 1;
+      }
+    }
     timer_end();
     cnt_.n_launch += (plan.fold_r ? 1 : 0) + (plan.fold_l ? 1 : 0);
+    if (std::getenv("MITDVP_EDGE_TRACE"))
+      fprintf(stderr, "[mitdvp] folded sides of a site: R %s, L %s\n",
+              plan.strassen_r ? "seven half-size products" : plan.fold_r ? "plain product" : "not folded",
+              plan.strassen_l ? "seven half-size products" : plan.fold_l ? "plain product" : "not folded");
   }
   return plan;
 }

@@ -97,7 +97,8 @@ void Engine::site_exp(double dt) {
 // One H_eff apply at the centre site EXACTLY as a local exponential issues it (local_site_exp): the identity checks of
 // both environment blocks decide the trimmed S1 / S3 forms, the MPO's zero blocks the list kernel of the W stage.
 // in == nullptr: the centre tensor itself.  flags: bit 0 S1 trimmed, bit 1 S3 trimmed, bit 2 block-sparse W stage,
-// bit 3 the one-launch small-bond kernel took the apply, bit 4 the edge form, bits 5 / 6 its R / L side folded.
+// bit 3 the one-launch small-bond kernel took the apply, bit 4 the edge form, bits 5 / 6 its R / L side folded, bits 7 / 8
+// (0x80 / 0x100) that folded R / L side as seven half-size products.
 void Engine::heff_apply_center(const double* in, double* out, int* flags) {
   require_ready();
   if (center_ < 0) throw ArgError("heff_apply_center: no centre site");
@@ -119,7 +120,8 @@ void Engine::heff_apply_center(const double* in, double* out, int* flags) {
   const bool sparse = !small && !edge && sparse_w_ && dr >= 64 && w.kl_l.p && w.sp_frac_l <= 0.6;
   if (flags)
     *flags = (plan.trim_l && !small && !edge ? 1 : 0) | (plan.trim_r && !small && !edge ? 2 : 0) | (sparse ? 4 : 0) | (small ? 8 : 0) |
-             (edge ? 16 : 0) | (edge && plan.fold_r ? 0x20 : 0) | (edge && plan.fold_l ? 0x40 : 0);
+             (edge ? 16 : 0) | (edge && plan.fold_r ? 0x20 : 0) | (edge && plan.fold_l ? 0x40 : 0) |
+             (edge && plan.strassen_r ? 0x80 : 0) | (edge && plan.strassen_l ? 0x100 : 0);
   heff_apply(Lb, w, Rb, x.p, y.p, dl, d, dr, op(0).shift, plan);
   copy_out(out, y.p, n);
   pool_put(std::move(x)); pool_put(std::move(y));

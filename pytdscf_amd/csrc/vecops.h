@@ -59,6 +59,20 @@ void gram_env_core(hipStream_t st, const zc* G, const zc* ws, zc* out, int n, in
 // The lower block half of that Gram matrix from its upper one, in place: blocks (i, j), i > j, become the conjugate
 // transposes of the blocks (j, i) (n x n each); blocks i <= j are only read.  d <= 64.
 void gram_mirror_lower(hipStream_t st, zc* G, int n, int d);
+// One Strassen level over a (2 hr) x (2 hc) matrix in quadrants S11 S12 / S21 S22 (Engine::heff_apply_edge, a folded side
+// taking seven half-size products instead of eight).  With C = A B in 2 x 2 blocks,
+//   M1 = (A11 + A22)(B11 + B22)  M2 = (A21 + A22) B11  M3 = A11 (B12 - B22)  M4 = A22 (B21 - B11)
+//   M5 = (A11 + A12) B22  M6 = (A21 - A11)(B11 + B12)  M7 = (A12 - A22)(B21 + B22),
+// strassen_operands writes the seven left (STRASSEN_A) or right (STRASSEN_B) factors of src, packed: factor k is an
+// hr x hc matrix with leading dimension hc at dst + k * hr * hc.  STRASSEN_BT: src holds B transposed (the operand of a
+// transB = 1 product), so block (k, l) of B is the transpose of src's quadrant (l, k), and the factors are written as
+// they are stored, untransposed.  src (leading dimension ld >= 2 hc) and dst must not overlap.
+enum { STRASSEN_A = 0, STRASSEN_B = 1, STRASSEN_BT = 2 };
+void strassen_operands(hipStream_t st, const zc* src, long ld, long hr, long hc, zc* dst, int which);
+// out (2 hr) x (2 hc), leading dimension ldo, from the seven products M (packed as above):
+//   C11 = M1 + M4 - M5 + M7   C12 = M3 + M5   C21 = M2 + M4   C22 = M1 - M2 + M3 + M6,
+// summed in this order; accumulate: added to what out holds.
+void strassen_combine(hipStream_t st, const zc* M, long hr, long hc, zc* out, long ldo, bool accumulate);
 void copy2d(hipStream_t st, zc* dst, long ldd, const zc* src, long lds, long rows, int cols, int zero_to, zc a,
             bool accumulate);
 // Block lists of the K_eff apply with identity states skipped (Engine::keff_prepare): up to 64 blocks, scalars by value.

@@ -1046,6 +1046,79 @@ void gram_mirror_lower(hipStream_t st, zc* G, int n, int d) {
   HIP_CHECK(hipGetLastError());
 }
 
+// The seven factors of one Strassen level (strassen_operands): factor k = quadrant q1[k] + sg[k] * quadrant q2[k]
+// (quadrant index 2 * row half + column half; sg = 0: the quadrant alone).  One thread per column of the half-size
+// matrix, rows strided over blockIdx.y: four 16-byte loads and seven 16-byte stores per element, all contiguous along a row.
+struct StrassenTab { int q1[7], q2[7], sg[7]; };
+// quadrants 0 = S11, 1 = S12, 2 = S21, 3 = S22
+constexpr StrassenTab kStrassenTabs[3] = {
+    {{0, 2, 0, 3, 0, 2, 1}, {3, 3, 0, 0, 1, 0, 3}, {1, 1, 0, 0, 1, -1, -1}},   // A11+A22 A21+A22 A11 A22 A11+A12 A21-A11 A12-A22
+    {{0, 0, 1, 2, 3, 0, 2}, {3, 0, 3, 0, 0, 1, 3}, {1, 0, -1, -1, 0, 1, 1}},   // B11+B22 B11 B12-B22 B21-B11 B22 B11+B12 B21+B22
+    {{0, 0, 2, 1, 3, 0, 1}, {3, 0, 3, 0, 0, 2, 3}, {1, 0, -1, -1, 0, 1, 1}}};  // the same with S12 <-> S21
+template <int W>
+__global__ __launch_bounds__(256) void k_strassen_operands(const zc* __restrict__ src, long ld, long hr, long hc,
+                                                           zc* __restrict__ dst) {
+  constexpr StrassenTab t = kStrassenTabs[W];
+  const long c = (long)blockIdx.x * 256 + threadIdx.x;
+  if (c >= hc) return;
+  const long blk = hr * hc;
+  for (long r = blockIdx.y; r < hr; r += gridDim.y) {
+    zc q[4];
+    q[0] = src[r * ld + c];
+    q[1] = src[r * ld + hc + c];
+    q[2] = src[(hr + r) * ld + c];
+    q[3] = src[(hr + r) * ld + hc + c];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+      const zc a = q[t.q1[k]], b = q[t.q2[k]];
+      zc o = a;
+      if (t.sg[k] > 0) { o.x += b.x; o.y += b.y; }
+      if (t.sg[k] < 0) { o.x -= b.x; o.y -= b.y; }
+      dst[k * blk + r * hc + c] = o;
+    }
+  }
+}
+// The four output quadrants from the seven products (strassen_combine), the sums in the order written in vecops.h.
+__global__ __launch_bounds__(256) void k_strassen_combine(const zc* __restrict__ M, long hr, long hc, zc* __restrict__ out,
+                                                          long ldo, int acc) {
+  const long c = (long)blockIdx.x * 256 + threadIdx.x;
+  if (c >= hc) return;
+  const long blk = hr * hc;
+  for (long r = blockIdx.y; r < hr; r += gridDim.y) {
+    zc m[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) m[k] = M[k * blk + r * hc + c];
+    zc o[4];
+    o[0] = make_double2(((m[0].x + m[3].x) - m[4].x) + m[6].x, ((m[0].y + m[3].y) - m[4].y) + m[6].y);
+    o[1] = make_double2(m[2].x + m[4].x, m[2].y + m[4].y);
+    o[2] = make_double2(m[1].x + m[3].x, m[1].y + m[3].y);
+    o[3] = make_double2(((m[0].x - m[1].x) + m[2].x) + m[5].x, ((m[0].y - m[1].y) + m[2].y) + m[5].y);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      zc* p = out + ((u >> 1) * hr + r) * ldo + (u & 1) * hc + c;
+      if (acc) { const zc v = *p; o[u].x += v.x; o[u].y += v.y; }
+      *p = o[u];
+    }
+  }
+}
+void strassen_operands(hipStream_t st, const zc* src, long ld, long hr, long hc, zc* dst, int which) {
+  if (hr < 1 || hc < 1) return;
+  if (ld < 2 * hc) throw ArgError("strassen_operands: leading dimension below the matrix width");
+  if (which < 0 || which > 2) throw ArgError("strassen_operands: bad factor set");
+  const dim3 grid((unsigned)((hc + 255) / 256), (unsigned)std::min<long>(hr, 32768));
+  if (which == STRASSEN_A) hipLaunchKernelGGL(k_strassen_operands<STRASSEN_A>, grid, dim3(256), 0, st, src, ld, hr, hc, dst);
+  else if (which == STRASSEN_B) hipLaunchKernelGGL(k_strassen_operands<STRASSEN_B>, grid, dim3(256), 0, st, src, ld, hr, hc, dst);
+  else hipLaunchKernelGGL(k_strassen_operands<STRASSEN_BT>, grid, dim3(256), 0, st, src, ld, hr, hc, dst);
+  HIP_CHECK(hipGetLastError());
+}
+void strassen_combine(hipStream_t st, const zc* M, long hr, long hc, zc* out, long ldo, bool accumulate) {
+  if (hr < 1 || hc < 1) return;
+  if (ldo < 2 * hc) throw ArgError("strassen_combine: leading dimension below the matrix width");
+  const dim3 grid((unsigned)((hc + 255) / 256), (unsigned)std::min<long>(hr, 32768));
+  hipLaunchKernelGGL(k_strassen_combine, grid, dim3(256), 0, st, M, hr, hc, out, ldo, accumulate ? 1 : 0);
+  HIP_CHECK(hipGetLastError());
+}
+
 // out[p][t][q] = sum_{i, j} ws[(i * d + j) * m + t] * G[(i, p)][(j, q)]   (G: (d n) x (d n) row-major; out: n x m x n)
 void gram_env_core(hipStream_t st, const zc* G, const zc* ws, zc* out, int n, int m, int d) {
   if (n < 1 || d < 1) return;

@@ -103,7 +103,8 @@ class TDVPEngine:
     def heff_apply_center(self, x=None):
         """sigma = H_eff x at the centre site, through the very kernels a local exponential uses; returns
         (sigma, flags): bit 0 / 1 identity block of the left / right environment short-circuited, bit 2 block-sparse
-        W stage, bit 3 one-launch small-bond kernel."""
+        W stage, bit 3 one-launch small-bond kernel, 0x10 the edge form, 0x20 / 0x40 its R / L side folded, 0x80 / 0x100
+        that folded R / L side as seven half-size products."""
         c = next(p for p in range(self.nsite) if self.get_site_shape(p)[3] == _lib.GAUGE_PSI)
         l, n, r, _ = self.get_site_shape(c)
         out = np.empty((l, n, r), dtype=np.complex128)
