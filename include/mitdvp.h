@@ -351,7 +351,9 @@ int mitdvp_site_exp(mitdvp_engine* h, double dt_au);      /* exp_superH_propagat
  * (0x40) = its L side ran the folded variant (the reduced core contracted into the environment block once per local
  * solve, the side one plain GEMM; MITDVP_FOLD_APPLY=0 never, 1 wherever valid); bit 7 (0x80) / bit 8 (0x100) = that folded
  * R / L side ran as seven half-size products (one Strassen level; MITDVP_FOLD_STRASSEN=0 never, 1 wherever its sizes are
- * even).  For parity tests of the kernels a sweep runs. */
+ * even); bit 9 (0x200) / bit 10 (0x400), set together with 0x80 / 0x100 = each of those seven ran as seven quarter-size
+ * products (two levels, 49 products in one launch; MITDVP_FOLD_STRASSEN=2 wherever the side's sizes are divisible by 4, else
+ * as 1).  For parity tests of the kernels a sweep runs. */
 int mitdvp_heff_apply_center(mitdvp_engine* h, const double* reim_in, double* reim_out, int* flags);
 /* trans_next_psite_AsigmaB (:1798-1850): centre -> A sigma (forward) or sigma B; the block through the site is built,
  * sigma stays in the engine as the pending bond matrix */

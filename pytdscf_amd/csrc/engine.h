@@ -59,11 +59,12 @@ struct DevBuf {
 // handed to each of its applies.  trim_l / trim_r: the FIRST MPO-bond block of the left / the last one of the right
 // environment is the identity (the sites on that side are canonical and the MPO passes "nothing applied yet" through;
 // the reference short-circuits such blocks as well, _mps_mpo.py:510-523) and stage S1 / S3 skips it; edge: the applies
-// take heff_apply_edge, fold_l / fold_r: with that side folded, strassen_l / strassen_r: the folded side's product as seven
-// half-size products (one Strassen level) on the factors choose_apply_forms packed.  The default is the plain three-stage
-// chain, which is what every apply outside such a solve gets.
+// take heff_apply_edge, fold_l / fold_r: with that side folded, strassen_l / strassen_r: the Strassen levels of the folded
+// side's product on the factors choose_apply_forms packed (0 the plain GEMM, 1 seven half-size products, 2 forty-nine
+// quarter-size products).  The default is the plain three-stage chain, which is what every apply outside such a solve gets.
 struct ApplyPlan {
-  bool trim_l = false, trim_r = false, edge = false, fold_l = false, fold_r = false, strassen_l = false, strassen_r = false;
+  bool trim_l = false, trim_r = false, edge = false, fold_l = false, fold_r = false;
+  int strassen_l = 0, strassen_r = 0;
 };
 
 struct MpoSite {
@@ -329,14 +330,18 @@ class Engine {
   // One Strassen level over a folded side (ApplyPlan::strassen_l / strassen_r): the side's GEMM as seven half-size
   // products instead of eight.  The operator's seven factors are packed once per local solve (str_l_ / str_r_, beside
   // GL / GR, which stay in X_ / Y_), the vector's seven per apply (str_v_), the products go to str_m_ and one pass
-  // combines them into (or onto) sigma.  MITDVP_FOLD_STRASSEN: 0 never, 1 wherever a folded side has even halves, -1
-  // (default) the rule of choose_apply_forms.  The buffers are allocated the first time a side takes the form and grow
-  // only; a side whose buffers cannot be allocated keeps the plain GEMM.
+  // combines them into (or onto) sigma.  A second level does the same to each of the seven: the operator's 49 quarter-size
+  // factors (in str_l_ / str_r_ in place of the seven, factor (k1, k2) at (7 k1 + k2) quarter-size matrices, packed straight
+  // from GL / GR), the vector's 49 and the 49 products behind the level-1 ones in str_v_ / str_m_, one batched launch, a
+  // combine 49 -> 7 and the level-1 combine.  MITDVP_FOLD_STRASSEN: 0 never, 1 one level wherever a folded side has even halves, 2 two levels
+  // wherever its sizes are divisible by 4 (else as 1), -1 (default) the rule of choose_apply_forms.  The buffers are
+  // allocated the first time a side takes the form and grow only; a side whose buffers cannot be allocated drops a level.
   int strassen_mode_ = -1;
-  bool strassen_batched_ = true;  // MITDVP_STRASSEN_BATCH=0: seven launches instead of one batched launch (A/B testing)
+  bool strassen_batched_ = true;  // MITDVP_STRASSEN_BATCH=0: 7 / 49 launches instead of one batched launch (A/B testing)
   DevBuf str_l_, str_r_, str_v_, str_m_;
   static bool try_reserve(DevBuf& b, size_t elems);
-  void strassen_side(const zc* fixed, bool fixed_is_a, const zc* psi, long ldpsi, zc* out, long hm, long hn, long hk, bool accumulate);
+  void strassen_side(const zc* fixed, bool fixed_is_a, const zc* psi, long ldpsi, zc* out, long hm, long hn, long hk, bool accumulate,
+                     int level);
   // MITDVP_FOLD_ENV: the structured environment update (env_update_fold): 0 never, 1 wherever it is valid, -1 (default) the
   // rule of env_fold_ok.  The identity sets it relies on are those the last choose_apply_forms found for exactly these
   // blocks of this site: env_chk_, set there and nowhere else.  It outlives the call (in segment mode site_exp and

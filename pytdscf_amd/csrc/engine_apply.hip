@@ -4,10 +4,12 @@
 
 namespace mitdvp {
 
-// 64 x 64 tiles each half-size product of a Strassen level must have for a folded side to take it by default
-// (choose_apply_forms): one whole round on the 256 compute units, seven in the batched launch.  Measured per apply
+// 64 x 64 tiles each product of a Strassen level must have for a folded side to take that level by default
+// (choose_apply_forms): one whole round on the 256 compute units, seven or 49 in the batched launch.  Measured per apply
 // (profiles/fold_strassen_ab.txt): 1024 tiles (C4, 1024 x 16 x 1024) -12.5 %, 256 tiles (512 x 16 x 512) -11 %, 64 tiles
-// (C5, 512 x 4 x 512) +1 % and the factors to pack on top; nothing between 64 and 256 has been measured.
+// (C5, 512 x 4 x 512) +1 % and the factors to pack on top; nothing between 64 and 256 has been measured.  The second level
+// (profiles/fold_strassen2_ab.txt): 256 tiles per quarter-size product (C4) -9.5 % per apply on top of the first and +2.8 ms
+// of packing per solve; 64 tiles (512 x 16 x 512) -1.7 % per apply, which the 0.52 ms of extra packing takes back.
 constexpr long STRASSEN_MIN_TILES = 256;
 
 // W stage: Y_b[(i,q)][n] = W2[(i,q)][(p,j)] X_b[(p,j)][n] for nbatch slabs b (X_, Y_ workspaces).  With a
@@ -108,9 +110,9 @@ void Engine::heff_apply_rect(const zc* L, const MpoSite& w, const zc* R, const z
 
 bool Engine::try_reserve(DevBuf& b, size_t elems) {
   if (elems <= b.n) return true;
-  b.release();
-  zc* q = nullptr;
+  zc* q = nullptr;  // the new buffer first: a refusal leaves the old one, which an earlier side's plan may count on
   if (hipMalloc(&q, elems * sizeof(zc)) != hipSuccess) { (void)hipGetLastError(); return false; }
+  b.release();
   b.p = q; b.n = elems;
   return true;
 }
@@ -119,26 +121,44 @@ bool Engine::try_reserve(DevBuf& b, size_t elems) {
 // out ((2 hm) x (2 hn), leading dimension ldpsi) (+)= A B with the contraction 2 hk long.  fixed: the operator's seven
 // packed factors, the left ones of GL (fixed_is_a; psi is B, (2 hk) x (2 hn)) or the right ones of GR^T as stored, each
 // hn x hk for a transB product (psi is A, (2 hm) x (2 hk)).  Every summation order is fixed: the same bits every run.
+//
+// level 2: each of the seven is itself seven quarter-size products.  fixed then holds the operator's 49 quarter-size factors,
+// (k1, k2) at (7 k1 + k2) quarter-size matrices; psi's seven level-1 factors go to the head of str_v_ and their 49 factors
+// behind them (one batched packing launch over the seven); the 49 products go behind the level-1 area of str_m_, one batched
+// pass combines them into the seven half-size products at its head (written, never added to), and the level-1 pass ends.
 void Engine::strassen_side(const zc* fixed, bool fixed_is_a, const zc* psi, long ldpsi, zc* out, long hm, long hn, long hk,
-                           bool accumulate) {
-  if (fixed_is_a) strassen_operands(st_, psi, ldpsi, hk, hn, str_v_.p, STRASSEN_B);
-  else strassen_operands(st_, psi, ldpsi, hm, hk, str_v_.p, STRASSEN_A);
-  const zc* A = fixed_is_a ? fixed : str_v_.p;
-  const zc* B = fixed_is_a ? str_v_.p : fixed;
-  ZgemmDesc g = zgemm_desc(A, B, str_m_.p, (int)hm, (int)hn, (int)hk);
-  if (!fixed_is_a) { g.transB = 1; g.ldb = hk; }
+                           bool accumulate, int level) {
+  const long vr = fixed_is_a ? hk : hm, vc = fixed_is_a ? hn : hk;  // psi's level-1 factors: vr x vc
+  const int vset = fixed_is_a ? STRASSEN_B : STRASSEN_A;
+  strassen_operands(st_, psi, ldpsi, vr, vc, str_v_.p, vset);
+  int np = 7;
+  long pm = hm, pn = hn, pk = hk;
+  const zc* V = str_v_.p;
+  zc* Mp = str_m_.p;
+  if (level == 2) {
+    zc* v2 = str_v_.p + 7 * vr * vc;
+    strassen_operands(st_, str_v_.p, vc, vr / 2, vc / 2, v2, vset, 7, vr * vc, 7 * (vr / 2) * (vc / 2));
+    np = 49; pm = hm / 2; pn = hn / 2; pk = hk / 2;
+    V = v2;
+    Mp = str_m_.p + 7 * hm * hn;
+  }
+  const zc* A = fixed_is_a ? fixed : V;
+  const zc* B = fixed_is_a ? V : fixed;
+  ZgemmDesc g = zgemm_desc(A, B, Mp, (int)pm, (int)pn, (int)pk);
+  if (!fixed_is_a) { g.transB = 1; g.ldb = pk; }
   if (strassen_batched_) {
-    g.batch = 7; g.strideA = hm * hk; g.strideB = hk * hn; g.strideC = hm * hn;
+    g.batch = np; g.strideA = pm * pk; g.strideB = pk * pn; g.strideC = pm * pn;
     zgemm(st_, g);
   } else {
-    for (int k = 0; k < 7; ++k) {
+    for (int k = 0; k < np; ++k) {
       ZgemmDesc h = g;
-      h.A = A + k * hm * hk; h.B = B + k * hk * hn; h.C = str_m_.p + k * hm * hn;
+      h.A = A + k * pm * pk; h.B = B + k * pk * pn; h.C = Mp + k * pm * pn;
       zgemm(st_, h);
     }
   }
+  if (level == 2) strassen_combine(st_, Mp, pm, pn, str_m_.p, hn, false, 7, 7 * pm * pn, hm * hn);
   strassen_combine(st_, str_m_.p, hm, hn, out, ldpsi, accumulate);
-  cnt_.n_launch += 2 + (strassen_batched_ ? 1 : 7);
+  cnt_.n_launch += (level == 2 ? 4 : 2) + (strassen_batched_ ? 1 : np);
 }
 
 // The apply for an edge-structured core between canonical environments (MpoSite::EdgeCache; L[:, 0, :] = R[:, mr-1, :] = 1,
@@ -163,11 +183,14 @@ void Engine::heff_apply_edge(const zc* L, const MpoSite& w, const zc* R, const z
   double exe = 0.0;
   if (c.has_r && plan.fold_r && plan.strassen_r) {  // sigma[a][(i,r)] = psi GR^T: psi's factors per apply, GR's in str_r_
     timer_begin(12);
-    strassen_side(str_r_.p, false, psi, (long)d * dr, out, dl / 2, (long)d * dr / 2, (long)d * dr / 2, false);
+    const bool two = plan.strassen_r == 2;
+    strassen_side(str_r_.p, false, psi, (long)d * dr, out, dl / 2, (long)d * dr / 2, (long)d * dr / 2, false,
+                  plan.strassen_r);
     timer_end();
     first = false;
-    exe += 7.0 * (double)dl * d * dr * d * dr;
-    cnt_.heff_stage_flops[2] += 7.0 * (double)dl * d * dr * d * dr;
+    const double f = (two ? 49.0 / 8.0 : 7.0) * (double)dl * d * dr * d * dr;
+    exe += f;
+    cnt_.heff_stage_flops[2] += f;
   } else if (c.has_r && plan.fold_r) {
     timer_begin(12);
     ZgemmDesc g = zgemm_desc(psi, Y_.p, out, dl, d * dr, d * dr);
@@ -194,11 +217,13 @@ void Engine::heff_apply_edge(const zc* L, const MpoSite& w, const zc* R, const z
   }
   if (c.has_l && plan.fold_l && plan.strassen_l) {  // sigma[(a,i)][r] (+)= GL psi: GL's factors in str_l_, psi's per apply;
     timer_begin(10);                                 // the combining pass adds to what the R side wrote
-    strassen_side(str_l_.p, true, psi, dr, out, (long)dl * d / 2, dr / 2, (long)dl * d / 2, !first);
+    const bool two = plan.strassen_l == 2;
+    strassen_side(str_l_.p, true, psi, dr, out, (long)dl * d / 2, dr / 2, (long)dl * d / 2, !first, plan.strassen_l);
     timer_end();
     first = false;
-    exe += 7.0 * (double)dl * d * dl * d * dr;
-    cnt_.heff_stage_flops[0] += 7.0 * (double)dl * d * dl * d * dr;
+    const double f = (two ? 49.0 / 8.0 : 7.0) * (double)dl * d * dl * d * dr;
+    exe += f;
+    cnt_.heff_stage_flops[0] += f;
   } else if (c.has_l && plan.fold_l) {
     timer_begin(10);
     ZgemmDesc g = zgemm_desc(X_.p, psi, out, dl * d, dr, dl * d);
@@ -397,36 +422,45 @@ ApplyPlan Engine::choose_apply_forms(const zc* Lb, const MpoSite& w, const zc* R
     timer_begin(11);
     if (plan.fold_r) fold_env_core(st_, Rb, w.edge.w_r.p, Y_.p, dr, mr, d, (long)d * mr, mr, 1, (long)dr * d * dr, (long)d * dr, dr, 1);
     if (plan.fold_l) fold_env_core(st_, Lb, w.edge.w_l.p, X_.p, dl, ml, d, (long)ml * d, 1, d, (long)dl * d, (long)d * dl * d, 1, d);
-    // One Strassen level over a folded side: its rows, columns and contraction length even, and (the rule) the half-size
-    // products still at least one whole round of 64 x 64 tiles on the device -- STRASSEN_MIN_TILES per product, measured:
-    // profiles/fold_strassen_ab.txt.  The operator's seven factors are packed here, once per local solve, from GL / GR,
-    // which stay where they are; buffers that cannot be had leave the side with its plain GEMM.
+    // Strassen levels over a folded side.  One level: its rows, columns and contraction length even, and (the rule) the
+    // half-size products still at least one whole round of 64 x 64 tiles on the device -- STRASSEN_MIN_TILES per product,
+    // measured: profiles/fold_strassen_ab.txt.  Two levels: all three divisible by 4 and the same of the quarter-size
+    // products.  The operator's seven or 49 factors are packed here, once per local solve, from GL / GR, which stay where
+    // they are; both levels use the same table (a level-1 factor of GR is an untransposed sum of GR's quadrants and stands
+    // for the transposed B factor just as GR does), and a side with two levels never writes its seven.  Buffers that cannot
+    // be had drop the side a level.
     const size_t quarter = (size_t)dl * d * dr / 4;
-    auto halves_fill = [](long hm, long hn) { return ((hm + 63) / 64) * ((hn + 63) / 64) >= STRASSEN_MIN_TILES; };
-    if (plan.fold_r && strassen_mode_ != 0 && dl % 2 == 0 && ((long)d * dr) % 2 == 0 &&
-        (strassen_mode_ > 0 || halves_fill(dl / 2, (long)d * dr / 2))) {
-      const long h = (long)d * dr / 2;
-      if (try_reserve(str_r_, 7 * (size_t)h * h) && try_reserve(str_v_, 7 * quarter) && try_reserve(str_m_, 7 * quarter)) {
-        strassen_operands(st_, Y_.p, 2 * h, h, h, str_r_.p, STRASSEN_BT);
-        plan.strassen_r = true;
+    auto tiles_fill = [](long pm, long pn) { return ((pm + 63) / 64) * ((pn + 63) / 64) >= STRASSEN_MIN_TILES; };
+    auto level_of = [&](long rows, long cols, long klen) {  // the levels the sizes and the switch allow
+      if (strassen_mode_ == 0 || rows % 2 || cols % 2 || klen % 2) return 0;
+      const bool four = rows % 4 == 0 && cols % 4 == 0 && klen % 4 == 0;
+      if (strassen_mode_ > 0) return strassen_mode_ >= 2 && four ? 2 : 1;
+      if (four && tiles_fill(rows / 4, cols / 4)) return 2;
+      return tiles_fill(rows / 2, cols / 2) ? 1 : 0;
+    };
+    auto pack = [&](const zc* op, long n, DevBuf& f, int which, int want) {  // the n x n operator's factors, 49 or seven, in f
+      const long h = n / 2, q = n / 4;
+      // (the contents of str_v_ / str_m_ are per-apply scratch: growing them here loses nothing)
+      const size_t two = 7 * quarter + 49 * (quarter / 4);
+      if (want == 2 && try_reserve(f, 49 * (size_t)q * q) && try_reserve(str_v_, two) && try_reserve(str_m_, two)) {
+        strassen_operands2(st_, op, n, q, q, f.p, which);  // the 49 straight from the operator's 16 blocks
         cnt_.n_launch += 1;
+        return 2;
       }
-    }
-    if (plan.fold_l && strassen_mode_ != 0 && ((long)dl * d) % 2 == 0 && dr % 2 == 0 &&
-        (strassen_mode_ > 0 || halves_fill((long)dl * d / 2, dr / 2))) {
-      const long h = (long)dl * d / 2;
-      if (try_reserve(str_l_, 7 * (size_t)h * h) && try_reserve(str_v_, 7 * quarter) && try_reserve(str_m_, 7 * quarter)) {
-        strassen_operands(st_, X_.p, 2 * h, h, h, str_l_.p, STRASSEN_A);
-        plan.strassen_l = true;
-        cnt_.n_launch += 1;
-      }
-    }
+      if (want == 0 || !try_reserve(f, 7 * (size_t)h * h) || !try_reserve(str_v_, 7 * quarter) || !try_reserve(str_m_, 7 * quarter))
+        return 0;
+      strassen_operands(st_, op, n, h, h, f.p, which);
+      cnt_.n_launch += 1;
+      return 1;
+    };
+    if (plan.fold_r) plan.strassen_r = pack(Y_.p, (long)d * dr, str_r_, STRASSEN_BT, level_of(dl, (long)d * dr, (long)d * dr));
+    if (plan.fold_l) plan.strassen_l = pack(X_.p, (long)dl * d, str_l_, STRASSEN_A, level_of((long)dl * d, dr, (long)dl * d));
     timer_end();
     cnt_.n_launch += (plan.fold_r ? 1 : 0) + (plan.fold_l ? 1 : 0);
     if (std::getenv("MITDVP_EDGE_TRACE"))
       fprintf(stderr, "[mitdvp] folded sides of a site: R %s, L %s\n",
-              plan.strassen_r ? "seven half-size products" : plan.fold_r ? "plain product" : "not folded",
-              plan.strassen_l ? "seven half-size products" : plan.fold_l ? "plain product" : "not folded");
+              plan.strassen_r == 2 ? "49 quarter-size products" : plan.strassen_r ? "seven half-size products" : plan.fold_r ? "plain product" : "not folded",
+              plan.strassen_l == 2 ? "49 quarter-size products" : plan.strassen_l ? "seven half-size products" : plan.fold_l ? "plain product" : "not folded");
   }
   return plan;
 }

@@ -98,7 +98,8 @@ void Engine::site_exp(double dt) {
 // both environment blocks decide the trimmed S1 / S3 forms, the MPO's zero blocks the list kernel of the W stage.
 // in == nullptr: the centre tensor itself.  flags: bit 0 S1 trimmed, bit 1 S3 trimmed, bit 2 block-sparse W stage,
 // bit 3 the one-launch small-bond kernel took the apply, bit 4 the edge form, bits 5 / 6 its R / L side folded, bits 7 / 8
-// (0x80 / 0x100) that folded R / L side as seven half-size products.
+// (0x80 / 0x100) that folded R / L side as seven half-size products, bits 9 / 10 (0x200 / 0x400, with 0x80 / 0x100) each of
+// those seven as seven quarter-size products.
 void Engine::heff_apply_center(const double* in, double* out, int* flags) {
   require_ready();
   if (center_ < 0) throw ArgError("heff_apply_center: no centre site");
@@ -121,7 +122,8 @@ void Engine::heff_apply_center(const double* in, double* out, int* flags) {
   if (flags)
     *flags = (plan.trim_l && !small && !edge ? 1 : 0) | (plan.trim_r && !small && !edge ? 2 : 0) | (sparse ? 4 : 0) | (small ? 8 : 0) |
              (edge ? 16 : 0) | (edge && plan.fold_r ? 0x20 : 0) | (edge && plan.fold_l ? 0x40 : 0) |
-             (edge && plan.strassen_r ? 0x80 : 0) | (edge && plan.strassen_l ? 0x100 : 0);
+             (edge && plan.strassen_r ? 0x80 : 0) | (edge && plan.strassen_l ? 0x100 : 0) |
+             (edge && plan.strassen_r == 2 ? 0x200 : 0) | (edge && plan.strassen_l == 2 ? 0x400 : 0);
   heff_apply(Lb, w, Rb, x.p, y.p, dl, d, dr, op(0).shift, plan);
   copy_out(out, y.p, n);
   pool_put(std::move(x)); pool_put(std::move(y));

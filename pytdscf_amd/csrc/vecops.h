@@ -68,11 +68,20 @@ void gram_mirror_lower(hipStream_t st, zc* G, int n, int d);
 // transB = 1 product), so block (k, l) of B is the transpose of src's quadrant (l, k), and the factors are written as
 // they are stored, untransposed.  src (leading dimension ld >= 2 hc) and dst must not overlap.
 enum { STRASSEN_A = 0, STRASSEN_B = 1, STRASSEN_BT = 2 };
-void strassen_operands(hipStream_t st, const zc* src, long ld, long hr, long hc, zc* dst, int which);
+// batch > 1: the same for batch matrices, sstride / dstride elements apart (a second level over the seven factors of a first:
+// sstride = the factor's size, dstride = 7 quarter-size factors, so that factor (k1, k2) lands at (7 k1 + k2) * hr * hc).
+void strassen_operands(hipStream_t st, const zc* src, long ld, long hr, long hc, zc* dst, int which, int batch = 1,
+                       long sstride = 0, long dstride = 0);
+// Two levels in one pass over a (4 qr) x (4 qc) matrix: the 49 factors the batched second level above would make of the seven
+// (the same bits), factor (k1, k2) a qr x qc matrix with leading dimension qc at dst + (7 k1 + k2) * qr * qc, without the
+// seven half-size factors being written.  ld >= 4 qc; src and dst must not overlap.
+void strassen_operands2(hipStream_t st, const zc* src, long ld, long qr, long qc, zc* dst, int which);
 // out (2 hr) x (2 hc), leading dimension ldo, from the seven products M (packed as above):
 //   C11 = M1 + M4 - M5 + M7   C12 = M3 + M5   C21 = M2 + M4   C22 = M1 - M2 + M3 + M6,
 // summed in this order; accumulate: added to what out holds.
-void strassen_combine(hipStream_t st, const zc* M, long hr, long hc, zc* out, long ldo, bool accumulate);
+// batch > 1: batch sets of seven products mstride apart into batch outputs ostride apart.
+void strassen_combine(hipStream_t st, const zc* M, long hr, long hc, zc* out, long ldo, bool accumulate, int batch = 1,
+                      long mstride = 0, long ostride = 0);
 void copy2d(hipStream_t st, zc* dst, long ldd, const zc* src, long lds, long rows, int cols, int zero_to, zc a,
             bool accumulate);
 // Block lists of the K_eff apply with identity states skipped (Engine::keff_prepare): up to 64 blocks, scalars by value.

@@ -1057,11 +1057,13 @@ constexpr StrassenTab kStrassenTabs[3] = {
     {{0, 0, 2, 1, 3, 0, 1}, {3, 0, 3, 0, 0, 2, 3}, {1, 0, -1, -1, 0, 1, 1}}};  // the same with S12 <-> S21
 template <int W>
 __global__ __launch_bounds__(256) void k_strassen_operands(const zc* __restrict__ src, long ld, long hr, long hc,
-                                                           zc* __restrict__ dst) {
+                                                           zc* __restrict__ dst, long sstride, long dstride) {
   constexpr StrassenTab t = kStrassenTabs[W];
   const long c = (long)blockIdx.x * 256 + threadIdx.x;
   if (c >= hc) return;
   const long blk = hr * hc;
+  src += blockIdx.z * sstride;  // one matrix of the batch per blockIdx.z
+  dst += blockIdx.z * dstride;
   for (long r = blockIdx.y; r < hr; r += gridDim.y) {
     zc q[4];
     q[0] = src[r * ld + c];
@@ -1078,12 +1080,53 @@ __global__ __launch_bounds__(256) void k_strassen_operands(const zc* __restrict_
     }
   }
 }
+// The 49 factors of two Strassen levels straight from the 16 blocks of src (strassen_operands2): factor (k1, k2) is factor k2
+// of factor k1, each level's sum formed as the recursion forms it (first the level-1 sums of blocks, then their level-2 sum:
+// the same bits), without the seven half-size factors ever being written: one read of src and one write of the factors.
+template <int W>
+__global__ __launch_bounds__(256) void k_strassen_operands2(const zc* __restrict__ src, long ld, long qr, long qc,
+                                                            zc* __restrict__ dst) {
+  constexpr StrassenTab t = kStrassenTabs[W];
+  const long c = (long)blockIdx.x * 256 + threadIdx.x;
+  if (c >= qc) return;
+  const long blk = qr * qc;
+  for (long r = blockIdx.y; r < qr; r += gridDim.y) {
+    zc b[16];  // block (I, J) of the 4 x 4 grid at 4 I + J
+#pragma unroll
+    for (int I = 0; I < 4; ++I)
+#pragma unroll
+      for (int J = 0; J < 4; ++J) b[4 * I + J] = src[(I * qr + r) * ld + J * qc + c];
+#pragma unroll
+    for (int k1 = 0; k1 < 7; ++k1)
+#pragma unroll
+      for (int k2 = 0; k2 < 7; ++k2) {
+        zc o = make_double2(0.0, 0.0);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {  // the two quadrants of the level-1 factor that make its level-2 factor
+          const int P = h == 0 ? t.q1[k2] : t.q2[k2];
+          if (h == 1 && t.sg[k2] == 0) continue;
+          // quadrant P of level-1 factor k1 = block P of quadrant q1[k1] (+-) block P of quadrant q2[k1]
+          const int Q1 = t.q1[k1], Q2 = t.q2[k1];
+          zc x = b[4 * (2 * (Q1 >> 1) + (P >> 1)) + 2 * (Q1 & 1) + (P & 1)];
+          const zc y = b[4 * (2 * (Q2 >> 1) + (P >> 1)) + 2 * (Q2 & 1) + (P & 1)];
+          if (t.sg[k1] > 0) { x.x += y.x; x.y += y.y; }
+          if (t.sg[k1] < 0) { x.x -= y.x; x.y -= y.y; }
+          if (h == 0) o = x;
+          else if (t.sg[k2] > 0) { o.x += x.x; o.y += x.y; }
+          else { o.x -= x.x; o.y -= x.y; }
+        }
+        dst[(7 * k1 + k2) * blk + r * qc + c] = o;
+      }
+  }
+}
 // The four output quadrants from the seven products (strassen_combine), the sums in the order written in vecops.h.
 __global__ __launch_bounds__(256) void k_strassen_combine(const zc* __restrict__ M, long hr, long hc, zc* __restrict__ out,
-                                                          long ldo, int acc) {
+                                                          long ldo, int acc, long mstride, long ostride) {
   const long c = (long)blockIdx.x * 256 + threadIdx.x;
   if (c >= hc) return;
   const long blk = hr * hc;
+  M += blockIdx.z * mstride;  // one matrix of the batch per blockIdx.z
+  out += blockIdx.z * ostride;
   for (long r = blockIdx.y; r < hr; r += gridDim.y) {
     zc m[7];
 #pragma unroll
@@ -1101,21 +1144,37 @@ __global__ __launch_bounds__(256) void k_strassen_combine(const zc* __restrict__
     }
   }
 }
-void strassen_operands(hipStream_t st, const zc* src, long ld, long hr, long hc, zc* dst, int which) {
-  if (hr < 1 || hc < 1) return;
+void strassen_operands(hipStream_t st, const zc* src, long ld, long hr, long hc, zc* dst, int which, int batch, long sstride,
+                       long dstride) {
+  if (hr < 1 || hc < 1 || batch < 1) return;
   if (ld < 2 * hc) throw ArgError("strassen_operands: leading dimension below the matrix width");
   if (which < 0 || which > 2) throw ArgError("strassen_operands: bad factor set");
-  const dim3 grid((unsigned)((hc + 255) / 256), (unsigned)std::min<long>(hr, 32768));
-  if (which == STRASSEN_A) hipLaunchKernelGGL(k_strassen_operands<STRASSEN_A>, grid, dim3(256), 0, st, src, ld, hr, hc, dst);
-  else if (which == STRASSEN_B) hipLaunchKernelGGL(k_strassen_operands<STRASSEN_B>, grid, dim3(256), 0, st, src, ld, hr, hc, dst);
-  else hipLaunchKernelGGL(k_strassen_operands<STRASSEN_BT>, grid, dim3(256), 0, st, src, ld, hr, hc, dst);
+  if (batch > 65535) throw ArgError("strassen_operands: batch above 65535");
+  const dim3 grid((unsigned)((hc + 255) / 256), (unsigned)std::min<long>(hr, 32768), (unsigned)batch);
+  if (which == STRASSEN_A)
+    hipLaunchKernelGGL(k_strassen_operands<STRASSEN_A>, grid, dim3(256), 0, st, src, ld, hr, hc, dst, sstride, dstride);
+  else if (which == STRASSEN_B)
+    hipLaunchKernelGGL(k_strassen_operands<STRASSEN_B>, grid, dim3(256), 0, st, src, ld, hr, hc, dst, sstride, dstride);
+  else hipLaunchKernelGGL(k_strassen_operands<STRASSEN_BT>, grid, dim3(256), 0, st, src, ld, hr, hc, dst, sstride, dstride);
   HIP_CHECK(hipGetLastError());
 }
-void strassen_combine(hipStream_t st, const zc* M, long hr, long hc, zc* out, long ldo, bool accumulate) {
-  if (hr < 1 || hc < 1) return;
+void strassen_operands2(hipStream_t st, const zc* src, long ld, long qr, long qc, zc* dst, int which) {
+  if (qr < 1 || qc < 1) return;
+  if (ld < 4 * qc) throw ArgError("strassen_operands2: leading dimension below the matrix width");
+  if (which < 0 || which > 2) throw ArgError("strassen_operands2: bad factor set");
+  const dim3 grid((unsigned)((qc + 255) / 256), (unsigned)std::min<long>(qr, 32768));
+  if (which == STRASSEN_A) hipLaunchKernelGGL(k_strassen_operands2<STRASSEN_A>, grid, dim3(256), 0, st, src, ld, qr, qc, dst);
+  else if (which == STRASSEN_B) hipLaunchKernelGGL(k_strassen_operands2<STRASSEN_B>, grid, dim3(256), 0, st, src, ld, qr, qc, dst);
+  else hipLaunchKernelGGL(k_strassen_operands2<STRASSEN_BT>, grid, dim3(256), 0, st, src, ld, qr, qc, dst);
+  HIP_CHECK(hipGetLastError());
+}
+void strassen_combine(hipStream_t st, const zc* M, long hr, long hc, zc* out, long ldo, bool accumulate, int batch, long mstride,
+                      long ostride) {
+  if (hr < 1 || hc < 1 || batch < 1) return;
   if (ldo < 2 * hc) throw ArgError("strassen_combine: leading dimension below the matrix width");
-  const dim3 grid((unsigned)((hc + 255) / 256), (unsigned)std::min<long>(hr, 32768));
-  hipLaunchKernelGGL(k_strassen_combine, grid, dim3(256), 0, st, M, hr, hc, out, ldo, accumulate ? 1 : 0);
+  if (batch > 65535) throw ArgError("strassen_combine: batch above 65535");
+  const dim3 grid((unsigned)((hc + 255) / 256), (unsigned)std::min<long>(hr, 32768), (unsigned)batch);
+  hipLaunchKernelGGL(k_strassen_combine, grid, dim3(256), 0, st, M, hr, hc, out, ldo, accumulate ? 1 : 0, mstride, ostride);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -104,7 +104,8 @@ class TDVPEngine:
         """sigma = H_eff x at the centre site, through the very kernels a local exponential uses; returns
         (sigma, flags): bit 0 / 1 identity block of the left / right environment short-circuited, bit 2 block-sparse
         W stage, bit 3 one-launch small-bond kernel, 0x10 the edge form, 0x20 / 0x40 its R / L side folded, 0x80 / 0x100
-        that folded R / L side as seven half-size products."""
+        that folded R / L side as seven half-size products, 0x200 / 0x400 (with 0x80 / 0x100) each of those seven as seven
+        quarter-size products."""
         c = next(p for p in range(self.nsite) if self.get_site_shape(p)[3] == _lib.GAUGE_PSI)
         l, n, r, _ = self.get_site_shape(c)
         out = np.empty((l, n, r), dtype=np.complex128)

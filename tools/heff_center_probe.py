@@ -4,9 +4,11 @@ reps times after one warm-up, for rocprofv3 kernel-trace / PMC passes.  Every ca
 folded variant of the edge form it builds the folded operators once and applies them once: the device timers printed at
 the end give both (stage 1 = the build, or the transpose of an unfolded L side; stages 0 / 2 = the L / R side products).
 With MITDVP_FOLD_STRASSEN=1 the build also packs the seven factors of each folded operator and stages 0 / 2 are the seven
-half-size products with their two small kernels (MITDVP_STRASSEN_BATCH=1: one batched launch).  groups > 1 repeats the
-timed loop and prints one PROBE_END line per group: the spread of repeated timings.
-    [MITDVP_EDGE_APPLY=0|1] [MITDVP_FOLD_APPLY=0|1] [MITDVP_FOLD_STRASSEN=0|1] [MITDVP_STRASSEN_BATCH=1]
+half-size products with their two small kernels (MITDVP_STRASSEN_BATCH=1: one batched launch); with =2 the build packs 49
+factors per operator and the stages are 49 quarter-size products with their four small kernels.  PROBE_BEGIN names the
+Strassen levels the two sides took.  groups > 1 repeats the timed loop and prints one PROBE_END line per group: the
+spread of repeated timings.
+    [MITDVP_EDGE_APPLY=0|1] [MITDVP_FOLD_APPLY=0|1] [MITDVP_FOLD_STRASSEN=0|1|2] [MITDVP_STRASSEN_BATCH=1]
         python tools/heff_center_probe.py C3|C5|C4|L,d,D,M [reps] [groups]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -31,7 +33,8 @@ for _ in range(c):
 shape = eng.get_site_shape(c)[:3]
 x = eng.get_site(c)
 _, flags = eng.heff_apply_center(x)  # warm-up (also builds the cached reduced cores of the edge form)
-print(f"PROBE_BEGIN {name} site {c} shape {shape} flags {flags} reps {reps}", flush=True)
+levels = [2 if flags & hi else 1 if flags & lo else 0 for lo, hi in ((0x100, 0x400), (0x80, 0x200))]
+print(f"PROBE_BEGIN {name} site {c} shape {shape} flags {flags} Strassen levels L {levels[0]} R {levels[1]} reps {reps}", flush=True)
 eng.set_profiling(True)
 for _ in range(groups):
     eng.counters_reset()
