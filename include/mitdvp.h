@@ -260,6 +260,42 @@ int mitdvp_batch_jump_counts(mitdvp_batch* b, long long* counts);
 int mitdvp_batch_set_pair_channel(mitdvp_batch* b, int site, int kind, const double* ops_reim, int nops, int d0, int d1);
 int mitdvp_batch_pair_jump_counts(mitdvp_batch* b, long long* counts);
 int mitdvp_batch_discarded_weight(mitdvp_batch* b, double* weights);
+/* Cross overlaps and one-site matrix elements between two states of a batch (k_batch_cross: one workgroup per PAIR, the
+ * pair index is the workgroup index, ONE launch forms every requested pair; k_batch_mean averages them on the device,
+ * pair after pair in index order).  A state index 0 .. n-1 names replica i as it is now, n + r names the snapshot of
+ * replica r.  An entry (bra, ket, site, O) has the value <psi_bra| O_site |psi_ket>; site = -1 is the plain overlap
+ * <psi_bra|psi_ket>.  The walk runs over all nsite sites (two different states share no canonical form): the transfer
+ * matrix T (index order (bra bond, ket bond)) starts as 1, U = T K with the ket tensor K, the operator acts on the
+ * physical index of U at the entry's site, T' = sum conj(Bra) U, and the value is the 1 x 1 T after the last site.  It
+ * depends on its two states and its operator only: not on the number of pairs, its place in the list, n or the compute
+ * unit.  The replicas are only read; T and U live in a buffer of the batch indexed by pair.  A pair that names a
+ * replica that failed in the same call is zeros.
+ *   mitdvp_batch_snapshot: ONE launch (k_batch_snapshot) copies every site tensor of every replica into the batch's
+ *       snapshot buffer; one host wait.  The centre may be at site 0 or at site nsite-1 (where a batch call leaves it):
+ *       overlaps do not depend on the gauge.  Shapes never change in a batch, so a snapshot stays valid until the next.
+ *   mitdvp_batch_set_cross: registers npairs entries: bra[], ket[], site[] (npairs each); the entries with site >= 0
+ *       take, in list order, the matrices of ops_reim (row-major [out][in], interleaved re / im, one after the other)
+ *       whose orders are op_dims[].  npairs = 0 removes the request.  No launch, no wait.  MITDVP_EINVAL when an index is
+ *       outside 0 .. 2n-1, a snapshot index is used before any snapshot exists, a site is outside -1 .. nsite-1, an
+ *       operator's order is not that site's physical dimension, or there are more than 65536 pairs.
+ *   mitdvp_batch_cross: the request on the current state: TWO launches (k_batch_cross, k_batch_mean), one host wait.
+ *       weights: npairs doubles or NULL (1 / npairs each); values[npairs][2] and mean[2] may each be NULL.
+ *   While a request is set, every record of mitdvp_batch_run / _run_keys and every call of mitdvp_batch_observe /
+ *       _observe_keys records the request too: ONE more launch per record and ONE more k_batch_mean launch per call
+ *       (mitdvp_batch_run: 2 nsteps + 2 records + 2), no further host wait; `what` may then be 0 with out pointing at a
+ *       mitdvp_batch_out of NULLs: the request alone is recorded, by 2 nsteps + records + 1 launches.  With no request set
+ *       nothing changes: the same launches, the same bits, the same refusals.
+ *   mitdvp_batch_cross_records: what the last such call recorded: values[records][npairs][2], mean[records][2],
+ *       counts = {records, npairs}; each may be NULL.  weights NULL: the means under 1 / npairs, formed by that call, no
+ *       launch and no wait here; weights given (npairs doubles): ONE k_batch_mean launch over the records, which are
+ *       still on the device, and one host wait.  A new request or no recording call yet: records = 0.
+ * Every refusal is MITDVP_EINVAL with a message in mitdvp_last_error(NULL) that names the entry point and the limit, and
+ * leaves the request, the snapshot, the records and every engine as they were. */
+int mitdvp_batch_snapshot(mitdvp_batch* b);
+int mitdvp_batch_set_cross(mitdvp_batch* b, int npairs, const int* bra, const int* ket, const int* site, const double* ops_reim,
+                           const int* op_dims);
+int mitdvp_batch_cross(mitdvp_batch* b, const double* weights, double* values, double* mean);
+int mitdvp_batch_cross_records(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[2]);
 /* propagate_along_sweep (_mps_cls.py:798-1014), one direction only. */
 int mitdvp_sweep(mitdvp_engine* h, double dt_au, int forward);
 /* The same half-sweep in parts: the next `nsites` local updates of the half-sweep in progress (one is started when none

@@ -263,6 +263,10 @@ def load() -> C.CDLL:
         "mitdvp_batch_set_pair_channel": (i, [vp, i, i, dp, i, i, i]),
         "mitdvp_batch_pair_jump_counts": (i, [vp, C.POINTER(C.c_longlong)]),
         "mitdvp_batch_discarded_weight": (i, [vp, dp]),
+        "mitdvp_batch_snapshot": (i, [vp]),
+        "mitdvp_batch_set_cross": (i, [vp, i, ip, ip, ip, dp, ip]),
+        "mitdvp_batch_cross": (i, [vp, dp, dp, dp]),
+        "mitdvp_batch_cross_records": (i, [vp, dp, dp, dp, C.POINTER(C.c_size_t)]),
         "mitdvp_cu_mask_probe": (i, [i, C.POINTER(C.c_uint), i, i, C.c_size_t, i, ip]),
     }
     for name, (res, args) in sig.items():

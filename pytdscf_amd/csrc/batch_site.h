@@ -170,4 +170,34 @@ struct BatchDensArgs {
 // batch_observe_launch and behind it when both write one record (k_batch_observe zeroes the whole record first).
 void batch_density_launch(hipStream_t st, const BatchDensArgs& a, int nrep);
 
+// ---- cross overlaps and one-site matrix elements between replicas (k_batch_cross, k_batch_snapshot) ----
+// A state index 0 .. B-1 names a replica, B .. 2B-1 the snapshot of replica (index - B): the copy of all its site tensors
+// that the last batch_snapshot_launch left in the batch's snapshot buffer, [B][sum of site sizes], site after site.
+constexpr int BATCH_CROSS_MAX_PAIRS = 65536;
+struct BatchCrossPair {
+  int bra, ket;   // state indices
+  int site;       // site of the operator, -1: the plain overlap <bra | ket>
+  int pad;
+  long long off;  // the operator in BatchCrossArgs::ops, complex elements: d_site x d_site, row-major [out][in]
+};
+struct BatchCrossArgs {
+  int L, nrep;                 // nrep = B: where the snapshot indices start
+  const BatchShape* shp;       // [L], device
+  void* const* ptrs;           // the pointer table of BatchArgs (only its site tensors are read)
+  int ptr_stride;
+  const int* status;           // [B]: a pair that names a replica whose word is set writes zeros
+  const zc* snap;              // [B][snap_len], null while no snapshot was taken (no pair may name one then)
+  size_t snap_len;             // sum of the site sizes, complex elements
+  const BatchCrossPair* pairs; // [P], device
+  const zc* ops;               // device, the operators of all pairs
+  zc* buf;                     // [P][buf_len]: T, its successor and U of each pair
+  size_t o_t2, o_u, buf_len;   // T at 0, its successor at o_t2 (max_bond each), U at o_u (max_site)
+  double* rec;                 // [P][2]: (re, im) of each pair's value
+};
+// one launch: grid = npairs workgroups, replicas and snapshots are only read
+void batch_cross_launch(hipStream_t st, const BatchCrossArgs& a, int npairs);
+// one launch: grid = (nrep, L), site p of replica r copied to snap[r][offset of site p]
+void batch_snapshot_launch(hipStream_t st, const BatchShape* shp, void* const* ptrs, int ptr_stride, zc* snap, size_t snap_len, int L,
+                           int nrep);
+
 }  // namespace mitdvp

@@ -1,7 +1,9 @@
 // batch_site.hip -- batched trajectories: k_batch_sweep, ONE workgroup per replica, a whole half-sweep per launch.
 // (Further down: k_batch_observe / k_batch_mean, the observables of every replica and their ensemble means, one launch each;
 // k_batch_channel, one-site gates and quantum-jump channels between the two half-sweeps of a time step, one launch;
-// k_batch_pair, the same walk with nearest-neighbour gates and jump channels: merge, apply, truncated re-split.)
+// k_batch_pair, the same walk with nearest-neighbour gates and jump channels: merge, apply, truncated re-split;
+// k_batch_cross / k_batch_snapshot, overlaps and one-site matrix elements between two replicas or their snapshots, one
+// workgroup per pair.)
 //
 // At trajectory shapes (d = 2..4, D <= 32, M <= 16) a local problem is a few tens of kilobytes, so one workgroup can own
 // one replica completely: the replica index is blockIdx.x, nothing is exchanged between workgroups, and therefore there is
@@ -1474,7 +1476,115 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_pair(BatchPairArgs gp) {
   if (rc != SS_OK && tid == 0) g.status[r] = rc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Cross overlaps and one-site matrix elements between two states of a batch: k_batch_cross, ONE workgroup per PAIR (the
+// pair index is blockIdx.x), every requested pair in one launch.  A state is a replica or the snapshot of one
+// (BatchCrossPair in batch_site.h).  Two different states share no canonical form, so the walk runs over all L sites:
+//   T (dl x dl, index order (bra bond, ket bond)) starts as 1
+//   U[a'][(j,s)] = sum_a T[a'][a] K[a][(j,s)]                                  K: the ket tensor
+//   at the pair's site the T' product reads  sum_j O[i][j] U[a'][(j,s)]  in the place of U[a'][(i,s)]  (the arithmetic
+//     of bc_apply: j ascending, fused multiply-adds; formed in the operand fetch, so U needs no second buffer)
+//   T'[s'][s] = sum_(a',j) conj(Bra[a'][j][s']) U[a'][j][s]
+// and the value is the 1 x 1 T after site L-1.  The products are wg_gemm, as in the autocorrelation pass of
+// k_batch_observe, which this walk equals when bra = conj(ket).
+// What is resident where: LDS holds the two operand tiles of wg_gemm (16 896 bytes); T, its successor and U live in
+// the batch's own buffer, indexed by PAIR -- several pairs may read one replica at the same time, so nothing of a walk
+// may sit in a replica's scratch area -- written and re-read by this workgroup only and ordered by workgroup barriers.
+// Replicas, snapshots and operators are only read.  Every element has one owner thread and every sum one order: a value
+// depends on its two states and its operator only, not on the number of pairs, its place in the list, B or the compute
+// unit.  No atomics, nothing waits for another workgroup, every loop is bounded by the shapes.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 86 VGPRs, 76 SGPRs, no vector
+// or scalar register spills, NO private memory (0 bytes per lane: nothing is called out of line, so no access to it can
+// sit inside a product loop), 16 896 bytes of LDS; occupancy 5 waves per SIMD, i.e. TWO workgroups (pairs) per compute
+// unit where k_batch_observe (194 VGPRs through bt_heff) has one.  k_batch_snapshot, one workgroup of 256 threads per
+// (replica, site): 10 VGPRs, no LDS, no private memory.
+__global__ __launch_bounds__(256) void k_batch_snapshot(const BatchShape* __restrict__ shp, void* const* __restrict__ ptrs, int ptr_stride,
+                                                        zc* __restrict__ snap, size_t snap_len) {
+  const int r = blockIdx.x, p = blockIdx.y;
+  size_t off = 0;
+  for (int k = 0; k < p; ++k) off += (size_t)shp[k].dl * shp[k].d * shp[k].dr;
+  const long N = (long)shp[p].dl * shp[p].d * shp[p].dr;
+  const zc* src = reinterpret_cast<const zc*>(ptrs[(size_t)r * ptr_stride + p]);
+  zc* dst = snap + (size_t)r * snap_len + off;
+  for (long e = threadIdx.x; e < N; e += 256) dst[e] = src[e];
+}
+
+__global__ __launch_bounds__(SS_THREADS) void k_batch_cross(BatchCrossArgs g) {
+  __shared__ __attribute__((aligned(16))) zc tiles[2 * BT_TK * BT_LD];
+  const int q = blockIdx.x, tid = threadIdx.x, L = g.L, B = g.nrep;
+  const BatchCrossPair pr = g.pairs[q];
+  double* rec = g.rec + 2 * (size_t)q;
+  const bool dead = (pr.bra < B && g.status[pr.bra] != SS_OK) || (pr.ket < B && g.status[pr.ket] != SS_OK);
+  if (dead) {  // the same decision in every thread of the workgroup
+    if (tid == 0) { rec[0] = 0.0; rec[1] = 0.0; }
+    return;
+  }
+  // a replica's tensors come through its row of the pointer table, a snapshot's lie site after site in the batch's buffer
+  const zc* const* braTab = pr.bra < B ? reinterpret_cast<const zc* const*>(g.ptrs + (size_t)pr.bra * g.ptr_stride) : nullptr;
+  const zc* const* ketTab = pr.ket < B ? reinterpret_cast<const zc* const*>(g.ptrs + (size_t)pr.ket * g.ptr_stride) : nullptr;
+  const zc* braSnap = pr.bra < B ? nullptr : g.snap + (size_t)(pr.bra - B) * g.snap_len;
+  const zc* ketSnap = pr.ket < B ? nullptr : g.snap + (size_t)(pr.ket - B) * g.snap_len;
+  const zc* O = g.ops + pr.off;
+  zc* T = g.buf + (size_t)q * g.buf_len;
+  zc* T2 = T + g.o_t2;
+  zc* U = T + g.o_u;
+
+  if (tid == 0) T[0] = make_double2(1.0, 0.0);
+  __syncthreads();
+  size_t soff = 0;
+  for (int p = 0; p < L; ++p) {
+    const BatchShape s = g.shp[p];
+    const int dl = s.dl, d = s.d, dr = s.dr, ddr = d * dr;
+    const zc* Kt = ketTab ? ketTab[p] : ketSnap + soff;
+    const zc* Bt = braTab ? braTab[p] : braSnap + soff;
+    // U[m][(j,s)] = sum_n T[m][n] K[n][(j,s)]
+    wg_gemm<true, false>(dl, ddr, dl, tiles,
+        [&](int m, int kk) { return T[(long)m * dl + kk]; },
+        [&](int kk, int n) { return Kt[(long)kk * ddr + n]; },
+        [&](int m, int n, zc z) { U[(long)m * ddr + n] = z; });
+    // T'[i][j] = sum_(m,s) conj(Bra[(m,s)][i]) U[(m,s)][j], U with the operator on its physical index at the pair's site
+    if (p == pr.site)
+      wg_gemm<false, false>(dr, dr, dl * d, tiles,
+          [&](int m, int kk) { const zc z = Bt[(long)kk * dr + m]; return make_double2(z.x, -z.y); },
+          [&](int kk, int n) {
+            const int a = kk / d, i = kk - a * d;
+            const zc* col = U + (long)a * ddr + n;
+            const zc* row = O + (long)i * d;
+            double re = 0.0, im = 0.0;
+            for (int j = 0; j < d; ++j) {
+              const zc b = row[j], c = col[(long)j * dr];
+              re = fma(b.x, c.x, re); re = fma(-b.y, c.y, re);
+              im = fma(b.x, c.y, im); im = fma(b.y, c.x, im);
+            }
+            return make_double2(re, im);
+          },
+          [&](int m, int n, zc z) { T2[(long)m * dr + n] = z; });
+    else
+      wg_gemm<false, false>(dr, dr, dl * d, tiles,
+          [&](int m, int kk) { const zc z = Bt[(long)kk * dr + m]; return make_double2(z.x, -z.y); },
+          [&](int kk, int n) { return U[(long)kk * dr + n]; },
+          [&](int m, int n, zc z) { T2[(long)m * dr + n] = z; });
+    zc* t = T; T = T2; T2 = t;
+    soff += (size_t)dl * ddr;
+  }
+  if (tid == 0) { const zc z = T[0]; rec[0] = z.x; rec[1] = z.y; }
+}
+
 }  // namespace
+
+void batch_cross_launch(hipStream_t st, const BatchCrossArgs& a, int npairs) {
+  if (npairs < 1 || npairs > BATCH_CROSS_MAX_PAIRS || a.L < 1 || a.nrep < 1) throw ArgError("batch: no cross pair to observe");
+  if (!a.pairs || !a.buf || !a.rec || !a.ops) throw ArgError("batch: the cross request has no buffers");
+  hipLaunchKernelGGL(k_batch_cross, dim3(npairs), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
+
+void batch_snapshot_launch(hipStream_t st, const BatchShape* shp, void* const* ptrs, int ptr_stride, zc* snap, size_t snap_len, int L,
+                           int nrep) {
+  if (nrep < 1 || L < 1 || !snap) throw ArgError("batch: nothing to snapshot");
+  hipLaunchKernelGGL(k_batch_snapshot, dim3(nrep, L), dim3(256), 0, st, shp, ptrs, ptr_stride, snap, snap_len);
+  HIP_CHECK(hipGetLastError());
+}
 
 bool batch_pair_fits(const BatchShape* shp, int L, const BatchPlan& plan, int q, std::string& why) {
   const std::string at = "batch: pair channel on bond (" + std::to_string(q) + ", " + std::to_string(q + 1) + "): ";

@@ -73,6 +73,29 @@ class Batch {
            int* statuses) {
     run(dt, nsteps, every, sites, nsites, what, weights, out, statuses, DensOut());
   }
+  // ---- cross overlaps and one-site matrix elements between replicas (k_batch_cross, k_batch_snapshot) ----
+  // A state index 0 .. B-1 names replica i, B + r the snapshot of replica r.  Every refusal is an ArgError that names the
+  // entry point and the limit and leaves the request, the snapshot and every engine as they were.
+  // snapshot: ONE launch copies every site tensor of every replica into the batch's snapshot buffer; one host wait.  The
+  // centre may be at site 0 or at site L-1 (where a batch call leaves it).
+  void snapshot();
+  // set_cross: registers npairs entries (bra, ket, site, operator); site -1 is the plain overlap, otherwise the entry
+  // takes the next matrix of ops_reim (row-major [out][in], interleaved re / im) whose order is the next of op_dims.
+  // npairs = 0 removes the request.  Refused: an index outside 0 .. 2B-1, a snapshot index before any snapshot, a site
+  // outside -1 .. L-1, an order that is not the site's d, more than BATCH_CROSS_MAX_PAIRS pairs.  No launch, no wait.
+  void set_cross(int npairs, const int* bra, const int* ket, const int* site, const double* ops_reim, const int* op_dims);
+  bool has_cross() const { return !cross_.empty(); }
+  // cross: the request on the current state: k_batch_cross and k_batch_mean, TWO launches, one host wait.  weights:
+  // npairs doubles or null (1 / npairs); values [npairs][2] and mean [2] may each be null.
+  void cross(const double* weights, double* values, double* mean);
+  // While a request is set every record of run() records it too: ONE more launch per record (k_batch_cross behind the
+  // record's other launches) and ONE more k_batch_mean launch per call (weights 1 / npairs); values and means are copied
+  // with the rest, no further host wait.  cross_records returns what the last run() recorded: values
+  // [records][npairs][2], mean [records][2], counts {records, npairs}; each may be null.  weights null: the means of the
+  // run, no launch and no wait; weights given (npairs doubles): ONE k_batch_mean launch over the records, which are still
+  // on the device, and one host wait.
+  void cross_records(const double* weights, double* values, double* mean, size_t* counts);
+
   std::string status_message(int code) const;
   int size() const { return (int)eng_.size(); }
   int device() const { return device_; }
@@ -144,6 +167,27 @@ class Batch {
   BatchChanSite* d_pair_ = nullptr;
   long long* d_pcounts_ = nullptr;
   double* d_disc_ = nullptr;
+
+  // cross request: the pairs and their operators (host copies and device images), the transfer buffers [P][buf_len] of
+  // k_batch_cross, the records [nrec + 1][P][2] (the slot behind a run's records is cross()'s own) and their means, the
+  // snapshot [B][snap_len]
+  std::vector<BatchCrossPair> cross_;
+  std::vector<zc> cross_ops_;
+  bool cross_dirty_ = false, has_snap_ = false;
+  BatchCrossPair* d_cross_pairs_ = nullptr;
+  zc *d_cross_ops_ = nullptr, *d_cross_buf_ = nullptr, *d_snap_ = nullptr;
+  double *d_cross_rec_ = nullptr, *d_cross_mean_ = nullptr, *d_cross_w_ = nullptr;
+  size_t cross_pairs_elems_ = 0, cross_ops_elems_ = 0, cross_buf_elems_ = 0, cross_rec_slots_ = 0,
+         cross_mean_slots_ = 0, snap_elems_ = 0;  // cross_rec_slots_ / cross_mean_slots_: doubles
+  long cross_nrec_ = 0;  // records of the last run() held in d_cross_rec_ / h_cross_rec_
+  std::vector<double> h_cross_rec_, h_cross_mean_, h_cross_w_, h_cross_now_;
+  size_t snap_len() const;
+  size_t cross_buf_len() const { return 2 * (size_t)plan_.max_bond + (size_t)plan_.max_site; }
+  void check_cross(const char* entry) const;  // the request against the shapes and the snapshot as they are now
+  void prepare_observing();                   // prepare() for a call that only reads the state: centre at 0 or at L-1
+  void upload_cross(long nrec);               // device images of the request, room for nrec records and cross()'s slot
+  void launch_cross(long record);
+  void cross_weights(const double* weights);
 
   static std::vector<BatchShape> shapes_of(Engine& e);
   void check_channels() const;

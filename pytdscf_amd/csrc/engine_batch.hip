@@ -88,6 +88,7 @@ void Batch::validate() {
   if (s0.size() != shp_.size() || std::memcmp(s0.data(), shp_.data(), s0.size() * sizeof(BatchShape)) != 0) {
     shp_ = s0;
     shapes_dirty_ = true;
+    has_snap_ = false;  // a snapshot of other shapes names nothing any more
   }
   plan_ = pl;
   batch_observe_plan(plan_, obs_plan_);
@@ -152,6 +153,13 @@ Batch::~Batch() {
   if (d_disc_) (void)hipFree(d_disc_);
   if (d_legs_) (void)hipFree(d_legs_);
   if (d_tbuf_) (void)hipFree(d_tbuf_);
+  if (d_cross_pairs_) (void)hipFree(d_cross_pairs_);
+  if (d_cross_ops_) (void)hipFree(d_cross_ops_);
+  if (d_cross_buf_) (void)hipFree(d_cross_buf_);
+  if (d_cross_rec_) (void)hipFree(d_cross_rec_);
+  if (d_cross_mean_) (void)hipFree(d_cross_mean_);
+  if (d_cross_w_) (void)hipFree(d_cross_w_);
+  if (d_snap_) (void)hipFree(d_snap_);
   if (st_) (void)hipStreamDestroy(st_);
 }
 
@@ -598,8 +606,11 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   if (nsteps % every != 0) throw ArgError("batch: nsteps must be a multiple of every");
   HIP_CHECK(hipSetDevice(device_));
   const int nkeys = dens.nkeys;
-  const long nrdm = observe_sizes(sites, nsites, what, nkeys > 0);
+  const bool cx = has_cross();  // a cross request rides on every record; it may be all that is recorded
+  const long nrdm = observe_sizes(sites, nsites, what, nkeys > 0 || cx);
   const long ndens = density_sizes(dens.legs, nkeys, nrdm);
+  if (cx) check_cross("mitdvp_batch_run");
+  const bool own = what != 0 || nkeys > 0;  // false: only the cross request is recorded, no record of the replicas
   const size_t n = eng_.size();
   const long nrec = nsteps / every + 1, dens_off = BOBS_HEAD + 2 * nrdm, rec_len = dens_off + 2 * ndens;
   const int per_rec = (what ? 1 : 0) + (nkeys ? 1 : 0);  // launches per record
@@ -607,6 +618,7 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   if (chan) check_channels();
   prepare(true, nsteps > 0 || (what & BOBS_ENERGY));
   if (chan) upload_channels();
+  if (cx) upload_cross(nrec);
   // buffers of the records and their means (grow only), the site list and the weights
   const size_t need_rec = (size_t)nrec * n * rec_len, need_mean = (size_t)nrec * rec_len;
   const size_t need_legs = (size_t)nkeys * L_, need_tbuf = nkeys ? n * 2 * dens_plan_.need : 0;
@@ -649,6 +661,7 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   auto record = [&](long q) {
     if (what) launch_observe(what, nsites, q, rec_len);
     if (nkeys) launch_density(nkeys, what == 0, q, rec_len, dens_off);
+    if (cx) launch_cross(q);
   };
 
   record(0);
@@ -658,18 +671,34 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
     launch(dt, false);
     if ((s + 1) % every == 0) record((s + 1) / every);
   }
-  batch_mean_launch(st_, d_rec_, d_w_, d_mean_, (int)n, rec_len, nrec);
-  n_launch_ += 1;
-  const bool per_replica = out.norm || out.autocorr || out.energy || out.rdm || dens.density;
-  h_mean_.resize(need_mean);
-  HIP_CHECK(hipMemcpyAsync(h_mean_.data(), d_mean_, need_mean * sizeof(double), hipMemcpyDeviceToHost, st_));
+  if (own) {
+    batch_mean_launch(st_, d_rec_, d_w_, d_mean_, (int)n, rec_len, nrec);
+    n_launch_ += 1;
+  }
+  const bool per_replica = own && (out.norm || out.autocorr || out.energy || out.rdm || dens.density);
+  h_mean_.assign(need_mean, 0.0);
+  if (own) HIP_CHECK(hipMemcpyAsync(h_mean_.data(), d_mean_, need_mean * sizeof(double), hipMemcpyDeviceToHost, st_));
+  int cross_launches = 0;
+  if (cx) {  // the request's values and their means (weights 1 / npairs) come back with the rest
+    const size_t np = cross_.size();
+    cross_weights(nullptr);
+    batch_mean_launch(st_, d_cross_rec_, d_cross_w_, d_cross_mean_, (int)np, 2, nrec);
+    n_launch_ += 1;
+    cross_launches = (int)nrec + 1;
+    h_cross_rec_.resize((size_t)nrec * np * 2);
+    h_cross_mean_.resize((size_t)nrec * 2);
+    HIP_CHECK(hipMemcpyAsync(h_cross_rec_.data(), d_cross_rec_, h_cross_rec_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipMemcpyAsync(h_cross_mean_.data(), d_cross_mean_, h_cross_mean_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
+    cross_nrec_ = nrec;
+  }
   if (per_replica) {
     h_rec_.resize(need_rec);
     HIP_CHECK(hipMemcpyAsync(h_rec_.data(), d_rec_, need_rec * sizeof(double), hipMemcpyDeviceToHost, st_));
   }
   steps_done_ += nsteps;
-  if (nsteps > 0) finish(false, nsteps * 2, statuses, (int)nrec * per_rec + 1, chan ? nsteps : 0);
-  else finish_observe((int)nrec * per_rec + 1, statuses);
+  const int other = (int)nrec * per_rec + (own ? 1 : 0) + cross_launches;
+  if (nsteps > 0) finish(false, nsteps * 2, statuses, other, chan ? nsteps : 0);
+  else finish_observe(other, statuses);
 
   for (long q = 0; q < nrec; ++q) {
     const double* m = h_mean_.data() + (size_t)q * rec_len;
@@ -688,6 +717,201 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
       if (dens.density && ndens) std::memcpy(dens.density + at * 2 * ndens, r + dens_off, (size_t)2 * ndens * sizeof(double));
     }
   }
+}
+
+// ---- cross overlaps and one-site matrix elements between replicas (k_batch_cross, k_batch_snapshot) ----
+size_t Batch::snap_len() const {
+  size_t len = 0;
+  for (const BatchShape& s : shp_) len += (size_t)s.dl * s.d * s.dr;
+  return len;
+}
+
+void Batch::prepare_observing() {
+  const bool at_end = L_ > 1 && eng_[0]->center_ == L_ - 1;  // where a forward half-sweep leaves the centre
+  prepare(!at_end, false);
+}
+
+void Batch::snapshot() {
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  prepare_observing();
+  const size_t need = eng_.size() * snap_len();
+  if (need > snap_elems_) {
+    HIP_CHECK(hipStreamSynchronize(st_));
+    if (d_snap_) (void)hipFree(d_snap_);
+    d_snap_ = nullptr;
+    dev_alloc(d_snap_, need);
+    snap_elems_ = need;
+  }
+  batch_snapshot_launch(st_, d_shp_, d_ptrs_, (int)ptrs_per_replica(), d_snap_, snap_len(), L_, (int)eng_.size());
+  n_launch_ += 1;
+  finish_observe(1, nullptr);
+  has_snap_ = true;
+}
+
+void Batch::set_cross(int npairs, const int* bra, const int* ket, const int* site, const double* ops_reim, const int* op_dims) {
+  const std::string at = "mitdvp_batch_set_cross: ";
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  const int B = (int)eng_.size();
+  if (npairs < 0) throw ArgError(at + "npairs must be >= 0");
+  if (npairs > BATCH_CROSS_MAX_PAIRS)
+    throw ArgError(at + std::to_string(npairs) + " pairs, a request takes at most " + std::to_string(BATCH_CROSS_MAX_PAIRS));
+  if (npairs > 0 && (!bra || !ket || !site)) throw ArgError(at + "null list of bra, ket or site indices");
+  std::vector<BatchCrossPair> pairs((size_t)npairs);
+  std::vector<zc> ops;
+  int nop = 0;
+  for (int q = 0; q < npairs; ++q) {
+    const std::string who = at + "pair " + std::to_string(q) + ": ";
+    const int idx[2] = {bra[q], ket[q]};
+    for (int k = 0; k < 2; ++k) {
+      const std::string name = std::string(k ? "ket" : "bra") + " index " + std::to_string(idx[k]);
+      if (idx[k] < 0 || idx[k] >= 2 * B)
+        throw ArgError(who + name + " is outside 0 .. " + std::to_string(2 * B - 1) + " (the batch has " + std::to_string(B) +
+                       " replicas; " + std::to_string(B) + " + r names the snapshot of replica r)");
+      if (idx[k] >= B && !has_snap_)
+        throw ArgError(who + name + " names the snapshot of replica " + std::to_string(idx[k] - B) +
+                       ", and no snapshot was taken yet (mitdvp_batch_snapshot)");
+    }
+    if (site[q] < -1 || site[q] >= L_)
+      throw ArgError(who + "site " + std::to_string(site[q]) + " is out of range (-1: the plain overlap, or 0 .. " + std::to_string(L_ - 1) + ")");
+    pairs[q] = BatchCrossPair{bra[q], ket[q], site[q], 0, 0};
+    if (site[q] < 0) continue;
+    if (!ops_reim || !op_dims) throw ArgError(who + "it has an operator on site " + std::to_string(site[q]) + ", and ops_reim or op_dims is null");
+    const int d = op_dims[nop++];
+    if (d != shp_[site[q]].d)
+      throw ArgError(who + "the operator is " + std::to_string(d) + " x " + std::to_string(d) + ", the physical dimension of site " +
+                     std::to_string(site[q]) + " is " + std::to_string(shp_[site[q]].d));
+    pairs[q].off = (long long)ops.size();
+    const size_t ne = (size_t)d * d;
+    for (size_t e = 0; e < ne; ++e) ops.push_back(make_double2(ops_reim[2 * e], ops_reim[2 * e + 1]));
+    ops_reim += 2 * ne;
+  }
+  cross_ = std::move(pairs);
+  cross_ops_ = std::move(ops);
+  cross_dirty_ = true;
+  cross_nrec_ = 0;  // records of another request are not this one's
+}
+
+void Batch::check_cross(const char* entry) const {
+  const std::string at = std::string(entry) + ": ";
+  if (cross_.empty()) throw ArgError(at + "no cross request is set (mitdvp_batch_set_cross)");
+  const int B = (int)eng_.size();
+  for (size_t q = 0; q < cross_.size(); ++q) {
+    const BatchCrossPair& c = cross_[q];
+    if ((c.bra >= B || c.ket >= B) && !has_snap_)
+      throw ArgError(at + "pair " + std::to_string(q) + " of the cross request names a snapshot, and the shapes changed since it was taken");
+    if (c.site < 0) continue;
+    // the operators lie in list order: this one ends where the next one starts, or at the end of the array
+    size_t end = cross_ops_.size();
+    for (size_t k = q + 1; k < cross_.size(); ++k)
+      if (cross_[k].site >= 0) { end = (size_t)cross_[k].off; break; }
+    if (end - (size_t)c.off != (size_t)shp_[c.site].d * shp_[c.site].d)
+      throw ArgError(at + "pair " + std::to_string(q) + " of the cross request: the operator no longer matches the physical dimension " +
+                     std::to_string(shp_[c.site].d) + " of site " + std::to_string(c.site));
+  }
+}
+
+void Batch::upload_cross(long nrec) {
+  const size_t np = cross_.size(), need_buf = np * cross_buf_len(), slots = (size_t)nrec + 1;
+  if (np > cross_pairs_elems_ || cross_ops_.size() > cross_ops_elems_ || need_buf > cross_buf_elems_ || slots * np * 2 > cross_rec_slots_ ||
+      4 * slots > cross_mean_slots_ || !d_cross_ops_) {
+    HIP_CHECK(hipStreamSynchronize(st_));
+    auto grow = [&](auto*& p, size_t& have, size_t need) {
+      if (p && need <= have) return;
+      if (p) (void)hipFree(p);
+      p = nullptr;
+      dev_alloc(p, need);
+      have = need;
+    };
+    const bool more_pairs = np > cross_pairs_elems_;
+    grow(d_cross_pairs_, cross_pairs_elems_, np);
+    grow(d_cross_ops_, cross_ops_elems_, cross_ops_.size());
+    grow(d_cross_buf_, cross_buf_elems_, need_buf);
+    if (more_pairs) {
+      if (d_cross_w_) (void)hipFree(d_cross_w_);
+      d_cross_w_ = nullptr;
+      dev_alloc(d_cross_w_, np);
+    }
+    // these two grow only with a new request or in run(): no record of the last run is lost
+    grow(d_cross_rec_, cross_rec_slots_, slots * np * 2);
+    // the means of the records, the one of cross(), and the records' means under the weights of cross_records
+    grow(d_cross_mean_, cross_mean_slots_, 2 * slots * 2);
+  }
+  if (cross_dirty_) {
+    HIP_CHECK(hipMemcpyAsync(d_cross_pairs_, cross_.data(), np * sizeof(BatchCrossPair), hipMemcpyHostToDevice, st_));
+    if (!cross_ops_.empty())
+      HIP_CHECK(hipMemcpyAsync(d_cross_ops_, cross_ops_.data(), cross_ops_.size() * sizeof(zc), hipMemcpyHostToDevice, st_));
+    cross_dirty_ = false;
+  }
+}
+
+void Batch::launch_cross(long record) {
+  BatchCrossArgs a{};
+  a.L = L_;
+  a.nrep = (int)eng_.size();
+  a.shp = d_shp_;
+  a.ptrs = d_ptrs_;
+  a.ptr_stride = (int)ptrs_per_replica();
+  a.status = d_status_;
+  a.snap = has_snap_ ? d_snap_ : nullptr;
+  a.snap_len = snap_len();
+  a.pairs = d_cross_pairs_;
+  a.ops = d_cross_ops_;
+  a.buf = d_cross_buf_;
+  a.o_t2 = (size_t)plan_.max_bond;
+  a.o_u = 2 * (size_t)plan_.max_bond;
+  a.buf_len = cross_buf_len();
+  a.rec = d_cross_rec_ + (size_t)record * cross_.size() * 2;
+  batch_cross_launch(st_, a, (int)cross_.size());
+  n_launch_ += 1;
+}
+
+void Batch::cross_weights(const double* weights) {
+  const size_t np = cross_.size();
+  h_cross_w_.assign(np, 1.0 / (double)np);
+  if (weights) h_cross_w_.assign(weights, weights + np);
+  HIP_CHECK(hipMemcpyAsync(d_cross_w_, h_cross_w_.data(), np * sizeof(double), hipMemcpyHostToDevice, st_));
+}
+
+void Batch::cross(const double* weights, double* values, double* mean) {
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  check_cross("mitdvp_batch_cross");
+  prepare_observing();
+  upload_cross(cross_nrec_);
+  const size_t np = cross_.size();
+  const long slot = cross_nrec_;  // behind the records of the last run, which stay
+  cross_weights(weights);
+  launch_cross(slot);
+  batch_mean_launch(st_, d_cross_rec_ + (size_t)slot * np * 2, d_cross_w_, d_cross_mean_ + (size_t)slot * 2, (int)np, 2, 1);
+  n_launch_ += 1;
+  h_cross_now_.resize(np * 2 + 2);
+  HIP_CHECK(hipMemcpyAsync(h_cross_now_.data(), d_cross_rec_ + (size_t)slot * np * 2, np * 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipMemcpyAsync(h_cross_now_.data() + np * 2, d_cross_mean_ + (size_t)slot * 2, 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
+  finish_observe(2, nullptr);
+  if (values) std::memcpy(values, h_cross_now_.data(), np * 2 * sizeof(double));
+  if (mean) std::memcpy(mean, h_cross_now_.data() + np * 2, 2 * sizeof(double));
+}
+
+void Batch::cross_records(const double* weights, double* values, double* mean, size_t* counts) {
+  const size_t np = cross_.size(), nrec = (size_t)cross_nrec_;
+  if (counts) { counts[0] = nrec; counts[1] = np; }
+  if (nrec == 0 || (!values && !mean)) return;
+  if (values) std::memcpy(values, h_cross_rec_.data(), nrec * np * 2 * sizeof(double));
+  if (!mean) return;
+  if (!weights) {
+    std::memcpy(mean, h_cross_mean_.data(), nrec * 2 * sizeof(double));
+    return;
+  }
+  HIP_CHECK(hipSetDevice(device_));
+  cross_weights(weights);
+  // behind the slots of the records' own means and of cross(): the means of the run stay as they are
+  double* dst = d_cross_mean_ + (nrec + 1) * 2;
+  batch_mean_launch(st_, d_cross_rec_, d_cross_w_, dst, (int)np, 2, (long)nrec);
+  n_launch_ += 1;
+  HIP_CHECK(hipMemcpyAsync(mean, dst, nrec * 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
+  finish_observe(1, nullptr);
 }
 
 std::string Batch::status_message(int code) const {

@@ -860,6 +860,7 @@ class TDVPBatch:
         self.records = {}
         self._channels = {}
         self._seed = None
+        self._cross = None
         self._lib = _lib.load()
         try:
             for _ in range(n_replicas):
@@ -883,6 +884,7 @@ class TDVPBatch:
         self.records = {}
         self._channels = {}
         self._seed = None
+        self._cross = None
         self._lib = _lib.load()
         return self
 
@@ -916,6 +918,8 @@ class TDVPBatch:
                         raise ValueError(f"the batch has {n} replicas now, trajectory_ids were given for {len(ids)}: "
                                          "call set_jumps again")
                     self._push_seed(seed, ids)
+                if self._cross is not None:  # the new handle has no snapshot: a request that names one is refused here
+                    self._push_cross(self._cross)
             except Exception:
                 self._drop()
                 raise
@@ -1062,6 +1066,82 @@ class TDVPBatch:
         _lib.check(self._lib.mitdvp_batch_discarded_weight(self._handle(), _dp(out)))
         return out
 
+    # ---- cross overlaps and one-site matrix elements between replicas (mitdvp_batch_set_cross / _cross) ----
+    def snap(self, r: int) -> int:
+        """the state index of the snapshot of replica ``r``, for ``set_cross``"""
+        n = len(self.engines)
+        if not 0 <= int(r) < n:
+            raise ValueError(f"snap: replica {r} is out of range (the batch has {n})")
+        return n + int(r)
+
+    def snapshot(self):
+        """Copies every site tensor of every replica into a device buffer of the batch by ONE launch
+        (``mitdvp_batch_snapshot``); ``snap(r)`` then names that copy of replica ``r`` in ``set_cross``.  The centre may be
+        at site 0 or at the last site.  A snapshot stays until the next one; it is lost, with the library's batch object,
+        when the list ``engines`` is changed."""
+        _lib.check(self._lib.mitdvp_batch_snapshot(self._handle()))
+
+    def _push_cross(self, packed):
+        bra, ket, site, ops, dims = packed
+        n = len(bra)
+        ia = lambda v: (C.c_int * max(len(v), 1))(*v)
+        _lib.check(self._lib.mitdvp_batch_set_cross(self._b, n, ia(bra), ia(ket), ia(site), _dp(ops) if ops.size else None, ia(dims)))
+
+    def set_cross(self, entries):
+        """Registers the pairs that ``cross`` and recorded runs evaluate: an entry is ``(bra, ket)`` -- the overlap
+        ``<psi_bra|psi_ket>`` -- or ``(bra, ket, site, O)`` -- ``<psi_bra| O_site |psi_ket>`` with ``O`` a ``(d, d)``
+        matrix, need not be Hermitian.  ``bra`` / ``ket`` are replica indices or ``snap(r)``.  An empty list removes the
+        request.  The library validates (indices, a snapshot that exists, the site, the operator's order, at most 65536
+        pairs) and a refused request leaves the one before in place."""
+        bra, ket, site, ops, dims = [], [], [], [], []
+        for k, e in enumerate(entries):
+            e = tuple(e)
+            if len(e) == 2:
+                e = (e[0], e[1], -1, None)
+            if len(e) != 4 or (e[3] is None) != (int(e[2]) == -1):
+                raise ValueError(f"set_cross: entry {k} must be (bra, ket) or (bra, ket, site, O)")
+            bra.append(int(e[0])); ket.append(int(e[1])); site.append(int(e[2]))
+            if e[3] is not None:
+                O = _c128(e[3])
+                if O.ndim != 2 or O.shape[0] != O.shape[1]:
+                    raise ValueError(f"set_cross: entry {k}: the operator must be a square matrix, got shape {O.shape}")
+                ops.append(O.ravel())
+                dims.append(O.shape[0])
+        packed = (bra, ket, site, np.ascontiguousarray(np.concatenate(ops)) if ops else np.zeros(0, dtype=np.complex128), dims)
+        self._handle()
+        self._push_cross(packed)
+        self._cross = packed if bra else None
+
+    def _cross_weights(self, weights):
+        if self._cross is None:
+            raise ValueError("no cross request is set (set_cross)")
+        if weights is None:
+            return None
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+        if w.shape != (len(self._cross[0]),):
+            raise ValueError(f"cross weights must be {len(self._cross[0])} numbers, one per pair (got shape {w.shape})")
+        return w
+
+    def cross(self, weights=None):
+        """The request of ``set_cross`` on the current state of the replicas: one launch for all pairs, a second one for
+        their weighted sum (``mitdvp_batch_cross``).  Returns ``{"values": (P,) complex, "mean": complex}``; ``weights``:
+        P numbers, default 1 / P each."""
+        w = self._cross_weights(weights)
+        vals = np.zeros(len(self._cross[0]), dtype=np.complex128)
+        mean = np.zeros(1, dtype=np.complex128)
+        _lib.check(self._lib.mitdvp_batch_cross(self._handle(), None if w is None else _dp(w), _dp(vals), _dp(mean)))
+        return {"values": vals, "mean": complex(mean[0])}
+
+    def _cross_records(self, weights):
+        w = self._cross_weights(weights)
+        cnt = (C.c_size_t * 2)()
+        _lib.check(self._lib.mitdvp_batch_cross_records(self._b, None, None, None, cnt))
+        nrec, npairs = int(cnt[0]), int(cnt[1])
+        vals = np.zeros((nrec, npairs), dtype=np.complex128)
+        mean = np.zeros(nrec, dtype=np.complex128)
+        _lib.check(self._lib.mitdvp_batch_cross_records(self._b, None if w is None else _dp(w), _dp(vals), _dp(mean), cnt))
+        return vals, mean
+
     def launches(self) -> int:
         """kernel launches counted so far on replica 0, where the batch's launches are counted once"""
         return int(self.engines[0].counters()["n_launch"])
@@ -1086,7 +1166,9 @@ class TDVPBatch:
         returns with a leading record axis of ``nsteps // every + 1``.  ``observe`` may also carry ``keys=[...]``, keys as
         ``densities`` takes them: they are recorded in the same run by one more launch per record (``k_batch_density``) and
         come back as ``mean_density`` / ``density``, record axis first; the other entries are bitwise what they are
-        without ``keys``."""
+        without ``keys``.  ``cross=True`` adds the request of ``set_cross``, which every record of a run evaluates while
+        it is set (one more launch per record): ``cross`` of shape ``(nrec, P)`` and ``mean_cross`` ``(nrec,)``, the
+        weighted sum over the pairs with ``cross_weights`` (P numbers, default 1 / P each)."""
         if observe is None:
             self._run(lambda b, st: self._lib.mitdvp_batch_step(b, float(dt_au), int(nsteps), st))
             return None
@@ -1119,8 +1201,10 @@ class TDVPBatch:
         return {k: [x[0] for x in v] for k, v in rec.items()}
 
     def _observed(self, dt_au, nsteps, every, sites=(), norm=True, autocorr=False, energy=False, weights=None, per_replica=True,
-                  keys=()):
+                  keys=(), cross=False, cross_weights=None):
         n = len(self.engines)
+        if cross:
+            self._cross_weights(cross_weights)  # no request, or weights of the wrong length: raised before any library call
         nsite = self.engines[0].nsite
         legs = [density_key_legs(k, nsite) for k in keys]  # a malformed key raises here, before any library call
         sites = [int(p) for p in sites]
@@ -1179,6 +1263,8 @@ class TDVPBatch:
             self._run(lambda bb, st: call(bb, C.byref(out), st))
         finally:
             self.records = self._split(keep, sites, legs)  # a replica that did not converge raises; what was recorded stays readable here
+            if cross:
+                self.records["cross"], self.records["mean_cross"] = self._cross_records(cross_weights)
         return self.records
 
     def _split(self, keep, sites, legs=()):

@@ -7,6 +7,9 @@ trajectories at Hilbert-space cost) act between the two half-sweeps of every ste
 so do sampled nearest-neighbour channels (``jumps={(q, q + 1): B}``: incoherent hopping, correlated decay), which the batch
 applies to the merged two-site tensor and splits again at the bond's dimension (``k_batch_pair``).
 
+``correlation_function`` relates two states of the batch to each other: the autocorrelation function without the t/2
+trick and ``<psi| A(t) B |psi>``, contracted for all trajectories by one launch per record (``k_batch_cross``).
+
 Nothing falls back: a model the batched kernels do not take raises with the library's message."""
 
 from __future__ import annotations
@@ -87,6 +90,106 @@ def _one_site_keys(keys, nsite):
             raise ValueError(f"reduced_density key {k}: site out of range")
         sites.append(s)
     return sites
+
+
+def _site_operator(name, op, dims):
+    site, mat = op
+    site = int(site)
+    if not 0 <= site < len(dims):
+        raise ValueError(f"correlation_function: {name} acts on site {site}, the chain has sites 0 .. {len(dims) - 1}")
+    mat = np.asarray(mat, dtype=np.complex128)
+    if mat.shape != (dims[site], dims[site]):
+        raise ValueError(f"correlation_function: {name} has shape {mat.shape}, site {site} takes ({dims[site]}, {dims[site]})")
+    return site, mat
+
+
+def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every=1, weights=None, integrator="arnoldi",
+                         conserve_norm=False, thresh_sil=1.0e-09, per_trajectory=False, device=0):
+    """Two-time correlation functions of an ensemble of Hartree products in ONE batch, contracted and averaged on the device
+    (``k_batch_cross``, ``mitdvp_batch_run``): no t/2 trick, so complex starts and Hamiltonians that are not complex
+    symmetric are fine.
+
+    ``A`` and ``B`` are ``(site, matrix)``.  With both, every start ``s`` gives two replicas, ``psi_s(0)`` = the start and
+    ``phi_s(0) = B psi_s(0)`` -- still a Hartree product: ``B`` acts on that site's vector, and the product is set with
+    its own norm ``|B psi_s(0)|`` -- and the value is ``C(t) = sum_s w_s <psi_s(t)| A |phi_s(t)>``, i.e.
+    ``<psi| A(t) B |psi>`` for a Hamiltonian that generates a unitary propagation.  With both ``None`` there is one
+    replica per start and a snapshot at t = 0: ``C(t) = sum_s w_s <psi_s(0)|psi_s(t)>``, the autocorrelation function.
+    ``weights``: one number per start, default equal weights.
+
+    ``model``, ``starts``, ``stepsize`` (fs) and the observation convention are those of ``propagate_trajectories``: the
+    states are observed BEFORE steps 0, every, 2 every, ... < ``maxstep``; steps after the last observation are not run.
+    ``model.one_gate_to_apply`` (one-site gates) acts on both replicas of a start.  The defaults differ on purpose:
+    ``conserve_norm=False`` because ``phi`` carries the norm of ``B psi`` and an absorbing Hamiltonian must be allowed to
+    shrink both, and ``integrator="arnoldi"`` because a product state padded to the bond dimension has a null space that
+    Lanczos' three-term recurrence does not keep out of the Krylov vectors.
+
+    Returns ``{"time": (nrec,) in fs, "mean": (nrec,) complex}`` and, with ``per_trajectory``, ``"trajectories"``
+    ``(nrec, len(starts))``.
+
+    There is no ``jumps`` argument: under sampled jump channels ``psi`` and ``phi`` would have to jump together with
+    probabilities of the pair, which is a different scheme from the independent sampling of ``propagate_trajectories``.
+    A model the batched kernels do not take raises with the library's message; nothing falls back."""
+    if integrator not in ("lanczos", "arnoldi"):
+        raise ValueError(f"Invalid integrator: {integrator}")
+    every = int(every)
+    if every < 1 or maxstep < 1:
+        raise ValueError("maxstep and every must be >= 1")
+    if (A is None) != (B is None):
+        raise ValueError("correlation_function: give both A and B, or neither (the autocorrelation function)")
+    if model.nstate != 1 or model.space != "hilbert":
+        raise NotImplementedError("correlation_function: one electronic state in Hilbert space")
+    if model.kraus_op:
+        raise NotImplementedError("correlation_function: kraus_op means a purified state (a Kraus leg that grows)")
+    dims = list(model.dims)
+    nsite = len(dims)
+    if A is not None:
+        A, B = _site_operator("A", A, dims), _site_operator("B", B, dims)
+    starts = [list(s) for s in starts]
+    if not starts:
+        raise ValueError("no start states")
+    ns = len(starts)
+    w = np.full(ns, 1.0 / ns) if weights is None else np.asarray(weights, dtype=np.float64)
+    if w.shape != (ns,):
+        raise ValueError(f"weights must be {ns} numbers, one per start (got shape {w.shape})")
+    # replica 2 s is psi_s, replica 2 s + 1 is phi_s = B psi_s with its norm
+    states, scales = [], []
+    for k, s in enumerate(starts):
+        states.append(s)
+        scales.append(1.0)
+        if B is not None:
+            v = np.asarray(s[B[0]], dtype=np.complex128)
+            if v.ndim != 1:
+                raise ValueError("correlation_function: B acts on a start given as per-site vectors")
+            bv = B[1] @ (v / np.linalg.norm(v))
+            if np.linalg.norm(bv) == 0.0:
+                raise ValueError(f"correlation_function: B annihilates start {k}")
+            states.append(s[:B[0]] + [bv] + s[B[0] + 1:])
+            scales.append(float(np.linalg.norm(bv)))
+    gates = model.one_gate_to_apply.one_site_gates(model.dims) if model.one_gate_to_apply is not None else {}
+    dt_au = stepsize / units.au_in_fs
+    nsteps = (maxstep - 1) // every * every
+    D = model.m_aux_max if model.m_aux_max is not None else 10**9
+    mpo = model.project_mpo(model.hamiltonian.as_mpo(model.dims))
+    bt = TDVPBatch(len(states), nsite, device=device, integrator=integrator, conserve_norm=conserve_norm, thresh=thresh_sil)
+    try:
+        for e, s, scale in zip(bt.engines, states, scales):
+            e.set_mpo(mpo, 0, shift=model.hamiltonian.coupleJ[0][0])
+            e.set_mps(product_state_cores(s, D, space=model.space), canonicalize=True, scale=scale)
+        if gates:
+            bt.set_gates(gates)
+        if B is not None:
+            bt.set_cross([(2 * k, 2 * k + 1, A[0], A[1]) for k in range(ns)])
+        else:
+            bt.snapshot()
+            bt.set_cross([(bt.snap(k), k) for k in range(ns)])
+        rec = bt.propagate(dt_au, nsteps, observe=dict(norm=False, per_replica=False, cross=True, cross_weights=w), every=every)
+    finally:
+        bt.close()
+    nrec = nsteps // every + 1
+    out = {"time": np.arange(nrec) * every * dt_au * units.au_in_fs, "mean": rec["mean_cross"]}
+    if per_trajectory:
+        out["trajectories"] = rec["cross"]
+    return out
 
 
 def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, weights=None, integrator="lanczos",
