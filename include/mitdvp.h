@@ -621,6 +621,8 @@ typedef struct {
                                  applied by the reader): with heff_stage_ms the roofline of each stage's kernel */
   double n_env_fold;       /* environment updates that took the structured form (Gram matrix of the site tensor + folded
                               operator of the general MPO-bond states) instead of the M-fold chain */
+  double n_env_reuse;      /* those of them that took the general states' operator from the Strassen factors the local
+                              solve had packed, instead of building it again and applying it as one plain product */
 } mitdvp_counters;
 int mitdvp_counters_get(mitdvp_engine* h, mitdvp_counters* out);
 int mitdvp_counters_reset(mitdvp_engine* h);

@@ -67,6 +67,7 @@ class Counters(C.Structure):
         ("n_heff_edge", C.c_double),
         ("heff_stage_flops", C.c_double * 3),
         ("n_env_fold", C.c_double),
+        ("n_env_reuse", C.c_double),
     ]
 
     def as_dict(self):

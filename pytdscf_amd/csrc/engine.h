@@ -103,7 +103,15 @@ struct MpoSite {
   //   ws[i][j][out]        = sum_{in in the identity set} (multiple of in) W[in, i, j, out]   (all out states)
   //   wg[k][i][in][j]      = W[in, i, j, t0[k]] for in NOT in the identity set, else 0        (unweighted)
   // t0 = the out states fed by a general in state (one "all applied" state per summand of a finite-state-machine MPO).
-  struct EnvFold { std::vector<int> t0; DevBuf ws, wg; };
+  // Reuse of the local solve's operator (decided by EdgeCache::rebuild from the index sets; Engine::env_update_fold runs it
+  // when the solve packed that side's Strassen factors).  With a single t0 the general states' operator of the update is
+  // the solve's folded operator up to a factor:
+  //   ->  the solve's GL = sum_{c not in S} sum_{t in E} mu_t W[c,i,j,t] L_c = mu_t0 GL_t0: reuse_alpha = 1 / mu_t0, ws as it is;
+  //   <-  the solve's GR = sum_{c in S} lam_c sum_t W[c,i,j,t] R_t, all t.  With t0 = {c0} and c0 the only state of S with a
+  //       block in the core, GR / lam_c0 = the update's operator + sum_{t in E} mu_t W[c0,i,j,t] (x) 1, and that term is
+  //       column c0 of ws: reuse_alpha = 1 / lam_c0, and the Gram core runs with ws_reuse = ws with column c0 zero.
+  // Several general out states, another identity state of S with blocks, or a zero multiple: reuse = false.
+  struct EnvFold { std::vector<int> t0; DevBuf ws, wg; bool reuse = false; hzc reuse_alpha; DevBuf ws_reuse; };
   // what the local solves find out about the site and keep from sweep to sweep: written through the const core
   struct EdgeCache {
     bool valid = false;  // the cores below correspond to (s, e, lam, mu)
@@ -232,11 +240,15 @@ class Engine {
   // W2 ((d*mout) x (min*d)) -> env_out (dout, mout, dout)
   // w2e: the small-site form of the same core (MpoSite::w2el / w2er), nullptr = general path only
   // the structured form of the update (Gram matrix of the site tensor + folded operator of the general states)
-  bool env_fold_ok(const zc* env_in, int din, int min_, int d, int dout, int mout, const MpoSite* sp, int sp_side);
+  // *reuse_level: the Strassen level of the solve's packed operator the update may take (0: build its own)
+  bool env_fold_ok(const zc* env_in, int din, int min_, int d, int dout, int mout, const MpoSite* sp, int sp_side,
+                   int* reuse_level);
   void env_update_fold(const zc* env_in, const zc* T, zc* env_out, int din, int min_, int d, int dout, int mout,
-                       const MpoSite::EnvFold& f);
+                       const MpoSite::EnvFold& f, int sp_side, int reuse_level, const zc* T_plain);
+  // T_plain (sp_side == 1 only): the unmirrored tensor (dout, d, din) of which T is the mirror image, where the caller has
+  // it; without it a backward update cannot reuse the solve's operator
   void env_update(const zc* env_in, const zc* T, const zc* w2, zc* env_out, int din, int min_, int d, int dout,
-                  int mout, const zc* w2e = nullptr, const MpoSite* sp = nullptr, int sp_side = 0);
+                  int mout, const zc* w2e = nullptr, const MpoSite* sp = nullptr, int sp_side = 0, const zc* T_plain = nullptr);
   // x <- exp(scale * Op) x ; returns Krylov dimension used.  The Ritz step and the convergence test run on the device
   // (krylov_dev.h)
   template <class MV>
@@ -338,6 +350,10 @@ class Engine {
   // allocated the first time a side takes the form and grow only; a side whose buffers cannot be allocated drops a level.
   int strassen_mode_ = -1;
   bool strassen_batched_ = true;  // MITDVP_STRASSEN_BATCH=0: 7 / 49 launches instead of one batched launch (A/B testing)
+  // a level-2 L side packs the vector's 49 factors and combines the 49 products in one launch each (strassen_operands2 /
+  // strassen_combine2: the same bits, no level-1 areas in str_v_ / str_m_); MITDVP_STRASSEN_FUSE=0: the two-pass kernels,
+  // which the R side keeps (its gain did not clear the project's ten-spreads rule: profiles/env_reuse_ab.txt)
+  bool strassen_fuse_ = true;
   DevBuf str_l_, str_r_, str_v_, str_m_;
   static bool try_reserve(DevBuf& b, size_t elems);
   void strassen_side(const zc* fixed, bool fixed_is_a, const zc* psi, long ldpsi, zc* out, long hm, long hn, long hk, bool accumulate,
@@ -347,7 +363,12 @@ class Engine {
   // blocks of this site: env_chk_, set there and nowhere else.  It outlives the call (in segment mode site_exp and
   // split_center are separate library calls), but one update may use it and any update takes it away
   int fold_env_mode_ = -1;
-  struct EnvChecked { const MpoSite* w = nullptr; const zc* blk[2] = {nullptr, nullptr}; int n[2] = {0, 0}; } env_chk_;
+  // lvl: the Strassen level at which that solve packed the side's operator (0: L side, str_l_; 1: R side, str_r_; 0 = not
+  // packed).  MITDVP_FOLD_ENV_REUSE=0: the update never takes those factors (env_reuse_).  Only str_l_ / str_r_ are reused,
+  // which nothing but choose_apply_forms writes -- and that clears this record first; X_ / Y_ are not (the update itself
+  // overwrites them: its Gram matrix lives in Y_)
+  bool env_reuse_ = true;
+  struct EnvChecked { const MpoSite* w = nullptr; const zc* blk[2] = {nullptr, nullptr}; int n[2] = {0, 0}; int lvl[2] = {0, 0}; } env_chk_;
   EnvChecked take_env_checked() { const EnvChecked c = env_chk_; env_chk_ = EnvChecked{}; return c; }
   // One look at the MPO-bond states of the two blocks around a site or bond (identity_sets): per state its deviation from
   // a multiple of the identity and that multiple, [0, 64) the left block's states, [64, 128) the right block's

@@ -31,7 +31,9 @@ Engine::Engine(const mitdvp_config& c) : cfg(c), L_(c.nsite) {
   if (const char* e = std::getenv("MITDVP_FOLD_APPLY")) fold_mode_ = std::atoi(e);
   if (const char* e = std::getenv("MITDVP_FOLD_STRASSEN")) strassen_mode_ = std::atoi(e);
   if (const char* e = std::getenv("MITDVP_STRASSEN_BATCH")) strassen_batched_ = std::atoi(e) != 0;
+  if (const char* e = std::getenv("MITDVP_STRASSEN_FUSE")) strassen_fuse_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_FOLD_ENV")) fold_env_mode_ = std::atoi(e);
+  if (const char* e = std::getenv("MITDVP_FOLD_ENV_REUSE")) env_reuse_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_QR_GAUGE_FREE")) qr_gauge_free_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_KEFF_IDENT")) keff_ident_ = std::atoi(e) != 0;
   int ndev = 0;
@@ -357,6 +359,7 @@ void Engine::set_mpo_core(int op_id, int isite, const double* reim, int ml, int 
 void Engine::set_shift(int op_id, double re, double im) { op(op_id).shift = hzc(re, im); }
 
 void Engine::invalidate_env() {
+  (void)take_env_checked();  // the blocks a check described go back to the pool: their addresses may come back with other contents
   for (int b = 1; b < L_; ++b) {
     envL_ok_[b] = 0; envR_ok_[b] = 0;
     pool_put(std::move(envL_[b]));
@@ -791,7 +794,7 @@ int Engine::sweep_part(double dt, bool forward, int nsites) {
       std::swap(site_[p], spare);
       gauge_[p] = MITDVP_GAUGE_B;
       envR_[p] = pool_get((size_t)dl * w.ml * dl);
-      env_update(envR_[p + 1].p, tmp2_.p, w.w2r.p, envR_[p].p, dr, w.mr, d, dl, w.ml, w.w2er.p, &w, 1);
+      env_update(envR_[p + 1].p, tmp2_.p, w.w2r.p, envR_[p].p, dr, w.mr, d, dl, w.ml, w.w2er.p, &w, 1, site_[p].p);
       envR_ok_[p] = 1;
       const zc* Lb = envL_[p].p;
       const zc* Rb = envR_[p].p;

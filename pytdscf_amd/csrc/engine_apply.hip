@@ -126,21 +126,32 @@ bool Engine::try_reserve(DevBuf& b, size_t elems) {
 // (k1, k2) at (7 k1 + k2) quarter-size matrices; psi's seven level-1 factors go to the head of str_v_ and their 49 factors
 // behind them (one batched packing launch over the seven); the 49 products go behind the level-1 area of str_m_, one batched
 // pass combines them into the seven half-size products at its head (written, never added to), and the level-1 pass ends.
+// That is the two-pass form (the R side; MITDVP_STRASSEN_FUSE=0).  By default a level-2 L side packs psi's 49 factors in one launch from
+// psi's 16 blocks (strassen_operands2) and combines the 49 products into out in one launch (strassen_combine2), both with
+// the sums of the two passes in their order (the same bits): neither the seven factors nor the seven products are written.
 void Engine::strassen_side(const zc* fixed, bool fixed_is_a, const zc* psi, long ldpsi, zc* out, long hm, long hn, long hk,
                            bool accumulate, int level) {
   const long vr = fixed_is_a ? hk : hm, vc = fixed_is_a ? hn : hk;  // psi's level-1 factors: vr x vc
   const int vset = fixed_is_a ? STRASSEN_B : STRASSEN_A;
-  strassen_operands(st_, psi, ldpsi, vr, vc, str_v_.p, vset);
+  // (the L side only: measured on the R side, the one-pass kernels' gain stayed under ten spreads of repeated groups --
+  // profiles/env_reuse_ab.txt -- so that side keeps the two passes)
+  const bool fused = level == 2 && strassen_fuse_ && fixed_is_a;
   int np = 7;
   long pm = hm, pn = hn, pk = hk;
   const zc* V = str_v_.p;
   zc* Mp = str_m_.p;
-  if (level == 2) {
-    zc* v2 = str_v_.p + 7 * vr * vc;
-    strassen_operands(st_, str_v_.p, vc, vr / 2, vc / 2, v2, vset, 7, vr * vc, 7 * (vr / 2) * (vc / 2));
+  if (fused) {  // psi's 49 straight from its 16 blocks, the products at the head of str_m_: no level-1 area in either buffer
+    strassen_operands2(st_, psi, ldpsi, vr / 2, vc / 2, str_v_.p, vset);
     np = 49; pm = hm / 2; pn = hn / 2; pk = hk / 2;
-    V = v2;
-    Mp = str_m_.p + 7 * hm * hn;
+  } else {
+    strassen_operands(st_, psi, ldpsi, vr, vc, str_v_.p, vset);
+    if (level == 2) {
+      zc* v2 = str_v_.p + 7 * vr * vc;
+      strassen_operands(st_, str_v_.p, vc, vr / 2, vc / 2, v2, vset, 7, vr * vc, 7 * (vr / 2) * (vc / 2));
+      np = 49; pm = hm / 2; pn = hn / 2; pk = hk / 2;
+      V = v2;
+      Mp = str_m_.p + 7 * hm * hn;
+    }
   }
   const zc* A = fixed_is_a ? fixed : V;
   const zc* B = fixed_is_a ? V : fixed;
@@ -156,9 +167,13 @@ void Engine::strassen_side(const zc* fixed, bool fixed_is_a, const zc* psi, long
       zgemm(st_, h);
     }
   }
-  if (level == 2) strassen_combine(st_, Mp, pm, pn, str_m_.p, hn, false, 7, 7 * pm * pn, hm * hn);
-  strassen_combine(st_, str_m_.p, hm, hn, out, ldpsi, accumulate);
-  cnt_.n_launch += (level == 2 ? 4 : 2) + (strassen_batched_ ? 1 : np);
+  if (fused) {
+    strassen_combine2(st_, Mp, pm, pn, out, ldpsi, accumulate);
+  } else {
+    if (level == 2) strassen_combine(st_, Mp, pm, pn, str_m_.p, hn, false, 7, 7 * pm * pn, hm * hn);
+    strassen_combine(st_, str_m_.p, hm, hn, out, ldpsi, accumulate);
+  }
+  cnt_.n_launch += (fused ? 2 : level == 2 ? 4 : 2) + (strassen_batched_ ? 1 : np);
 }
 
 // The apply for an edge-structured core between canonical environments (MpoSite::EdgeCache; L[:, 0, :] = R[:, mr-1, :] = 1,
@@ -345,6 +360,28 @@ void MpoSite::EdgeCache::rebuild(hipStream_t st, const MpoSite& w, unsigned long
     f.wg.reserve(wg.size());
     HIP_CHECK(hipMemcpyAsync(f.ws.p, ws.data(), ws.size() * sizeof(zc), hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(f.wg.p, wg.data(), wg.size() * sizeof(zc), hipMemcpyHostToDevice, st));
+    // whether the update may take the general states' operator from the solve's packed factors (EnvFold, engine.h).  The
+    // directions differ because every block out of a state of S went to the R-side core wr above, whatever its out state
+    f.reuse = false;
+    std::vector<hzc> ws2;
+    if (f.t0.size() == 1) {
+      const int o = f.t0[0];
+      const hzc wo = side == 0 ? mu[o] : lam[o];
+      bool ok = (((side == 0 ? E : S) >> o) & 1ull) && wo != hzc(0.0, 0.0);
+      if (side == 1)  // no other state of S may have put a block into GR (a zero multiple put none)
+        for (int c = 0; c < ml && ok; ++c) {
+          if (c == o || !((S >> c) & 1ull) || lam[c] == hzc(0.0, 0.0)) continue;
+          for (int t = 0; t < mr && ok; ++t) if (w.nzblk[(size_t)c * mr + t]) ok = false;
+        }
+      if (ok) {
+        f.reuse = true;
+        f.reuse_alpha = hzc(1.0, 0.0) / wo;
+        ws2 = ws;
+        if (side == 1) for (int ij = 0; ij < d * d; ++ij) ws2[(size_t)ij * mo + o] = hzc(0.0, 0.0);
+        f.ws_reuse.reserve(ws2.size());
+        HIP_CHECK(hipMemcpyAsync(f.ws_reuse.p, ws2.data(), ws2.size() * sizeof(zc), hipMemcpyHostToDevice, st));
+      }
+    }
     HIP_CHECK(hipStreamSynchronize(st));  // the host vectors go out of scope
   }
   HIP_CHECK(hipStreamSynchronize(st));
@@ -441,7 +478,8 @@ ApplyPlan Engine::choose_apply_forms(const zc* Lb, const MpoSite& w, const zc* R
     auto pack = [&](const zc* op, long n, DevBuf& f, int which, int want) {  // the n x n operator's factors, 49 or seven, in f
       const long h = n / 2, q = n / 4;
       // (the contents of str_v_ / str_m_ are per-apply scratch: growing them here loses nothing)
-      const size_t two = 7 * quarter + 49 * (quarter / 4);
+      // (a fused side -- the L side, strassen_side -- has no level-1 area)
+      const size_t two = (strassen_fuse_ && which == STRASSEN_A ? 0 : 7 * quarter) + 49 * (quarter / 4);
       if (want == 2 && try_reserve(f, 49 * (size_t)q * q) && try_reserve(str_v_, two) && try_reserve(str_m_, two)) {
         strassen_operands2(st_, op, n, q, q, f.p, which);  // the 49 straight from the operator's 16 blocks
         cnt_.n_launch += 1;
@@ -455,6 +493,8 @@ ApplyPlan Engine::choose_apply_forms(const zc* Lb, const MpoSite& w, const zc* R
     };
     if (plan.fold_r) plan.strassen_r = pack(Y_.p, (long)d * dr, str_r_, STRASSEN_BT, level_of(dl, (long)d * dr, (long)d * dr));
     if (plan.fold_l) plan.strassen_l = pack(X_.p, (long)dl * d, str_l_, STRASSEN_A, level_of((long)dl * d, dr, (long)dl * d));
+    env_chk_.lvl[0] = plan.strassen_l;  // what str_l_ / str_r_ hold of these blocks until the next call of this function
+    env_chk_.lvl[1] = plan.strassen_r;
     timer_end();
     cnt_.n_launch += (plan.fold_r ? 1 : 0) + (plan.fold_l ? 1 : 0);
     if (std::getenv("MITDVP_EDGE_TRACE"))
@@ -634,8 +674,10 @@ void Engine::env_update_rect(const zc* env_in, const zc* Tk, const zc* Tb, const
 //                env_out[:, t0, :] += T^H (GL_t0 T): d^2 D^3 + d D^3 products.
 // (d (d + 1) / 2 + |t0| d^2) D^3 + |t0| d D^3 products against the chain's 2 M d D^3.  The Gram matrix and then GL_t0 T live in Y_,
 // GL_t0 in X_: the chain's own workspaces, (d D)^2 <= D M d D whenever d <= M; nothing is allocated.
-bool Engine::env_fold_ok(const zc* env_in, int din, int min_, int d, int dout, int mout, const MpoSite* sp, int sp_side) {
+bool Engine::env_fold_ok(const zc* env_in, int din, int min_, int d, int dout, int mout, const MpoSite* sp, int sp_side,
+                         int* reuse_level) {
   const EnvChecked chk = take_env_checked();  // whatever this update does, the sets have had their one use
+  *reuse_level = 0;
   int a0, a1;
   if (fold_env_mode_ == 0 || !sp || adaptive_ || shard_range(din, a0, a1)) return false;
   if (chk.w != sp || chk.blk[sp_side] != env_in || chk.n[sp_side] != din || !sp->edge.valid || sp->d != d) return false;
@@ -644,6 +686,9 @@ bool Engine::env_fold_ok(const zc* env_in, int din, int min_, int d, int dout, i
   const MpoSite::EnvFold& f = sp->edge.envf[sp_side];
   const double nt = (double)f.t0.size();
   if ((size_t)d * dout * d * dout > Y_.n || (size_t)din * d * dout > Y_.n || (nt > 0 && (size_t)din * d * din * d > X_.n)) return false;
+  // the solve behind this record packed the consumed side's operator (the record matches block, width and site): the one
+  // general out state's operator is that one up to a factor
+  if (env_reuse_ && f.reuse) *reuse_level = chk.lvl[sp_side];
   if (fold_env_mode_ > 0) return true;
   // the rule: the consumed side's MPO bond wider than d (as for the folded apply), and at most three quarters of the
   // chain's products left (one general out state always passes; a direct sum with several is taken while it pays)
@@ -652,8 +697,17 @@ bool Engine::env_fold_ok(const zc* env_in, int din, int min_, int d, int dout, i
   return min_ > d && 4.0 * fresh <= 3.0 * chain;
 }
 
+// The structured update itself (the formulas: above env_fold_ok).
+// reuse_level >= 1 (one t0; EnvFold::reuse and the record of the solve agree): the operator of the general states is the one
+// the solve packed into str_l_ / str_r_, up to the factor 1 / reuse_alpha.  fold_env_core is skipped and the product with
+// it runs as the solve's applies do (strassen_side; str_v_ / str_m_ are idle between applies), into Y_:
+//   ->  Z[(a,i)][r] = GL T, closed by T^H Z as below;
+//   <-  the R-side product takes the unmirrored tensor B[a][(j,s)] (T_plain; T is its mirror image) and gives
+//       Z'[a][(i,r)] = B GR^T; block c0 += conj(B)[a'][(i,r)] Z'[a][(i,r)], a conjugated, untransposed A against a transposed B.
+//       GR also holds the identity states' blocks out of c0, so the Gram core ran without them (ws_reuse).
 void Engine::env_update_fold(const zc* env_in, const zc* T, zc* env_out, int din, int min_, int d, int dout, int mout,
-                             const MpoSite::EnvFold& f) {
+                             const MpoSite::EnvFold& f, int sp_side, int reuse_level, const zc* T_plain) {
+  const bool reuse = reuse_level >= 1;
   timer_begin(1);
   // G[(i,a')][(j,r)] = conj(T)[a][(i,a')] T[a][(j,r)] is Hermitian: block row i of the product is formed from its diagonal
   // block on (j >= i: d (d + 1) / 2 of the d^2 blocks, the diagonal ones whole), the blocks below the diagonal are the
@@ -666,8 +720,20 @@ void Engine::env_update_fold(const zc* env_in, const zc* T, zc* env_out, int din
     zgemm(st_, g);
   }
   gram_mirror_lower(st_, Y_.p, dout, d);
-  gram_env_core(st_, Y_.p, f.ws.p, env_out, dout, mout, d);
-  for (size_t k = 0; k < f.t0.size(); ++k) {
+  gram_env_core(st_, Y_.p, reuse ? f.ws_reuse.p : f.ws.p, env_out, dout, mout, d);
+  const zc alpha = make_double2(f.reuse_alpha.real(), f.reuse_alpha.imag());
+  if (reuse && sp_side == 0) {
+    strassen_side(str_l_.p, true, T, dout, Y_.p, (long)din * d / 2, dout / 2, (long)din * d / 2, false, reuse_level);
+    ZgemmDesc h = zgemm_desc(T, Y_.p, env_out + (size_t)f.t0[0] * dout, dout, dout, din * d);
+    h.transA = 1; h.conjA = 1; h.lda = dout; h.ldc = (long)mout * dout; h.alpha = alpha; h.beta = make_double2(1.0, 0.0);
+    zgemm(st_, h);
+  } else if (reuse) {
+    strassen_side(str_r_.p, false, T_plain, (long)d * din, Y_.p, dout / 2, (long)d * din / 2, (long)d * din / 2, false, reuse_level);
+    ZgemmDesc h = zgemm_desc(T_plain, Y_.p, env_out + (size_t)f.t0[0] * dout, dout, dout, d * din);
+    h.conjA = 1; h.transB = 1; h.ldb = (long)d * din; h.ldc = (long)mout * dout; h.alpha = alpha; h.beta = make_double2(1.0, 0.0);
+    zgemm(st_, h);
+  }
+  for (size_t k = 0; !reuse && k < f.t0.size(); ++k) {
     // GL[(a,i)][(b,j)] (in X_), Z[(a,i)][r] = GL T[(b,j)][r] (in Y_: the Gram matrix has been consumed), block t0 += T^H Z
     fold_env_core(st_, env_in, f.wg.p + k * (size_t)d * min_ * d, X_.p, din, min_, d, (long)min_ * d, 1, d, (long)din * d,
                   (long)d * din * d, 1, d);
@@ -678,16 +744,18 @@ void Engine::env_update_fold(const zc* env_in, const zc* T, zc* env_out, int din
     zgemm(st_, h);
   }
   timer_end();
-  cnt_.n_launch += d + (d > 1 ? 1 : 0) + 1 + 3 * (long long)f.t0.size();
+  // (strassen_side counts its own launches: the packing, the products and the combining)
+  cnt_.n_launch += d + (d > 1 ? 1 : 0) + 1 + (reuse ? 1 : 3 * (long long)f.t0.size());
   cnt_.n_env += 1;
   cnt_.n_env_fold += 1;
+  if (reuse) cnt_.n_env_reuse += 1;
   // (algorithmic count, as heff_flops: the chain's)
   cnt_.env_flops += 8.0 * ((double)din * din * min_ * d * dout + (double)din * dout * min_ * mout * d * d +
                            (double)din * dout * dout * mout * d);
 }
 
 void Engine::env_update(const zc* env_in, const zc* T, const zc* w2, zc* env_out, int din, int min_, int d, int dout,
-                        int mout, const zc* w2e, const MpoSite* sp, int sp_side) {
+                        int mout, const zc* w2e, const MpoSite* sp, int sp_side, const zc* T_plain) {
   SmallChain sc;
   if (w2e && small_ok() && chain_env(sc, T, w2e, din, min_, d, dout, mout)) {
     timer_begin(1);
@@ -700,8 +768,10 @@ void Engine::env_update(const zc* env_in, const zc* T, const zc* w2, zc* env_out
     (void)take_env_checked();
     return;
   }
-  if (env_fold_ok(env_in, din, min_, d, dout, mout, sp, sp_side)) {
-    env_update_fold(env_in, T, env_out, din, min_, d, dout, mout, sp->edge.envf[sp_side]);
+  int reuse_level = 0;
+  if (env_fold_ok(env_in, din, min_, d, dout, mout, sp, sp_side, &reuse_level)) {
+    if (sp_side == 1 && !T_plain) reuse_level = 0;
+    env_update_fold(env_in, T, env_out, din, min_, d, dout, mout, sp->edge.envf[sp_side], sp_side, reuse_level, T_plain);
     return;
   }
   env_update_rect(env_in, T, T, w2, env_out, din, din, min_, d, dout, dout, mout, sp, sp_side);

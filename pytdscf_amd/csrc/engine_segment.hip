@@ -158,7 +158,7 @@ void Engine::split_center(bool forward) {
     gauge_[p] = MITDVP_GAUGE_B;
     pool_put(std::move(envR_[p]));
     envR_[p] = pool_get((size_t)dl * w.ml * dl);
-    env_update(envR_[p + 1].p, tmp2_.p, w.w2r.p, envR_[p].p, dr, w.mr, d, dl, w.ml, w.w2er.p, &w, 1);
+    env_update(envR_[p + 1].p, tmp2_.p, w.w2r.p, envR_[p].p, dr, w.mr, d, dl, w.ml, w.w2er.p, &w, 1, site_[p].p);
     envR_ok_[p] = 1;
     bond_ = p; bond_dim_ = dl;
   }

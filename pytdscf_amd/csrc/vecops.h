@@ -82,6 +82,11 @@ void strassen_operands2(hipStream_t st, const zc* src, long ld, long qr, long qc
 // batch > 1: batch sets of seven products mstride apart into batch outputs ostride apart.
 void strassen_combine(hipStream_t st, const zc* M, long hr, long hc, zc* out, long ldo, bool accumulate, int batch = 1,
                       long mstride = 0, long ostride = 0);
+// Both levels' combines in one pass: out (4 qr) x (4 qc), leading dimension ldo >= 4 qc, from the 49 quarter-size products
+// M (product (k1, k2) a qr x qc matrix at M + (7 k1 + k2) * qr * qc).  Each level-1 product's four quadrants are summed first,
+// then the four level-1 sums, both in the order above: the bits of strassen_combine with batch = 7 followed by
+// strassen_combine, accumulate applying to the final write only.  M and out must not overlap.
+void strassen_combine2(hipStream_t st, const zc* M, long qr, long qc, zc* out, long ldo, bool accumulate);
 void copy2d(hipStream_t st, zc* dst, long ldd, const zc* src, long lds, long rows, int cols, int zero_to, zc a,
             bool accumulate);
 // Block lists of the K_eff apply with identity states skipped (Engine::keff_prepare): up to 64 blocks, scalars by value.

@@ -1144,6 +1144,47 @@ __global__ __launch_bounds__(256) void k_strassen_combine(const zc* __restrict__
     }
   }
 }
+// Both combining levels in one pass (strassen_combine2): the 16 output blocks from the 49 quarter-size products, product
+// (k1, k2) at 7 k1 + k2.  A thread holds one level at a time: the four quadrants of each of the seven level-1 products (28
+// values, each formed from its seven products as k_strassen_combine forms it), then, quadrant by quadrant, the four level-1
+// sums in the same order: the bits of the two passes, without the seven half-size products being written and read again.
+__global__ __launch_bounds__(256) void k_strassen_combine2(const zc* __restrict__ M, long qr, long qc, zc* __restrict__ out,
+                                                           long ldo, int acc) {
+  const long c = (long)blockIdx.x * 256 + threadIdx.x;
+  if (c >= qc) return;
+  const long blk = qr * qc;
+  for (long r = blockIdx.y; r < qr; r += gridDim.y) {
+    zc h[7][4];  // quadrant u of level-1 product k1
+#pragma unroll
+    for (int k1 = 0; k1 < 7; ++k1) {
+      zc m[7];
+      // the seven of this k1 from a base of its own, kept in vector registers: the seven uniform offsets k * blk serve every
+      // k1 (49 uniform bases would not fit the scalar registers)
+      const zc* mk = M + 7 * k1 * blk + r * qc + c;
+      asm volatile("" : "+v"(mk));
+#pragma unroll
+      for (int k = 0; k < 7; ++k) m[k] = mk[k * blk];
+      h[k1][0] = make_double2(((m[0].x + m[3].x) - m[4].x) + m[6].x, ((m[0].y + m[3].y) - m[4].y) + m[6].y);
+      h[k1][1] = make_double2(m[2].x + m[4].x, m[2].y + m[4].y);
+      h[k1][2] = make_double2(m[1].x + m[3].x, m[1].y + m[3].y);
+      h[k1][3] = make_double2(((m[0].x - m[1].x) + m[2].x) + m[5].x, ((m[0].y - m[1].y) + m[2].y) + m[5].y);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {  // element (r, c) of quadrant u of every level-1 product -> block (2 U + u) of the output
+      zc o[4];
+      o[0] = make_double2(((h[0][u].x + h[3][u].x) - h[4][u].x) + h[6][u].x, ((h[0][u].y + h[3][u].y) - h[4][u].y) + h[6][u].y);
+      o[1] = make_double2(h[2][u].x + h[4][u].x, h[2][u].y + h[4][u].y);
+      o[2] = make_double2(h[1][u].x + h[3][u].x, h[1][u].y + h[3][u].y);
+      o[3] = make_double2(((h[0][u].x - h[1][u].x) + h[2][u].x) + h[5][u].x, ((h[0][u].y - h[1][u].y) + h[2][u].y) + h[5][u].y);
+#pragma unroll
+      for (int U = 0; U < 4; ++U) {
+        zc* p = out + ((2 * (U >> 1) + (u >> 1)) * qr + r) * ldo + (2 * (U & 1) + (u & 1)) * qc + c;
+        if (acc) { const zc v = *p; o[U].x += v.x; o[U].y += v.y; }
+        *p = o[U];
+      }
+    }
+  }
+}
 void strassen_operands(hipStream_t st, const zc* src, long ld, long hr, long hc, zc* dst, int which, int batch, long sstride,
                        long dstride) {
   if (hr < 1 || hc < 1 || batch < 1) return;
@@ -1175,6 +1216,13 @@ void strassen_combine(hipStream_t st, const zc* M, long hr, long hc, zc* out, lo
   if (batch > 65535) throw ArgError("strassen_combine: batch above 65535");
   const dim3 grid((unsigned)((hc + 255) / 256), (unsigned)std::min<long>(hr, 32768), (unsigned)batch);
   hipLaunchKernelGGL(k_strassen_combine, grid, dim3(256), 0, st, M, hr, hc, out, ldo, accumulate ? 1 : 0, mstride, ostride);
+  HIP_CHECK(hipGetLastError());
+}
+void strassen_combine2(hipStream_t st, const zc* M, long qr, long qc, zc* out, long ldo, bool accumulate) {
+  if (qr < 1 || qc < 1) return;
+  if (ldo < 4 * qc) throw ArgError("strassen_combine2: leading dimension below the matrix width");
+  const dim3 grid((unsigned)((qc + 255) / 256), (unsigned)std::min<long>(qr, 32768));
+  hipLaunchKernelGGL(k_strassen_combine2, grid, dim3(256), 0, st, M, qr, qc, out, ldo, accumulate ? 1 : 0);
   HIP_CHECK(hipGetLastError());
 }
 
