@@ -296,6 +296,44 @@ int mitdvp_batch_set_cross(mitdvp_batch* b, int npairs, const int* bra, const in
                            const int* op_dims);
 int mitdvp_batch_cross(mitdvp_batch* b, const double* weights, double* values, double* mean);
 int mitdvp_batch_cross_records(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[2]);
+/* Bond spectra and entanglement entropies of a batch (k_batch_spectra: one workgroup per replica, ONE launch forms every
+ * requested bond of every replica; k_batch_mean averages the records on the device, replica after replica in index
+ * order).  Bond q, 0 <= q <= nsite-2, lies between sites q and q+1 and has dimension chi_q.  With the centre at site 0
+ * and sites 1 .. nsite-1 right-canonical (the state mitdvp_batch_step leaves) the walk runs on work buffers only: X is
+ * the centre tensor; for q = 0 .. the highest requested bond, X seen as (dl d) x dr is QR-factorised (Householder, inside
+ * the workgroup), the rows of R are made mutually orthogonal by one-sided Jacobi rotations -- their squared norms are the
+ * squared Schmidt values sigma^2 of bond q -- and X <- R' B_{q+1} with the rotated R'.  No U and no V is formed; sites
+ * right of the last requested bond are not touched; the replicas are only read.  A replica's record holds, for every
+ * requested bond in list order, 4 + chi_q doubles: W = sum sigma^2 (the replica's squared norm; summed in descending
+ * order), S1 = -sum p ln p with p = sigma^2 / W (the von Neumann entropy, natural logarithm; a term with p <= 0 counts
+ * as 0), S2 = -ln sum p^2 (the second Renyi entropy), pmin = the smallest p (how close the bond is to being too narrow),
+ * then the chi_q values sigma^2, descending, not normalised.  rec_len is the sum of 4 + chi_q over the requested bonds.  A
+ * record depends on its replica only: not on n, its place in the batch or the compute unit.  A replica that failed in
+ * the same call is zeros.
+ *   mitdvp_batch_set_spectra: registers the strictly ascending list bonds[nbonds]; nbonds = 0 removes the request.  No
+ *       launch, no wait.  MITDVP_EINVAL when a bond is outside 0 .. nsite-2, the list is not strictly ascending, or
+ *       rec_len exceeds 65536 doubles.
+ *   mitdvp_batch_spectra: the request on the current state: TWO launches (k_batch_spectra, k_batch_mean), one host wait.
+ *       weights: n doubles or NULL (1 / n each); values[n][rec_len], mean[rec_len]; counts (may be NULL) receives {n,
+ *       rec_len}; with values == NULL && mean == NULL the call only returns the counts.  MITDVP_EINVAL without a request
+ *       or when a replica's centre is not at site 0.
+ *   While a request is set, every record of mitdvp_batch_run / _run_keys and every call of mitdvp_batch_observe /
+ *       _observe_keys records the request too: ONE more launch per record and ONE more k_batch_mean launch per call
+ *       (weights 1 / n), no further host wait; `what` may then be 0 with out pointing at a mitdvp_batch_out of NULLs: the
+ *       request alone is recorded, by 2 nsteps + records + 1 launches.  A cross request that is set as well adds its own
+ *       launches.  With no request set nothing changes: the same launches, the same bits, the same refusals.
+ *   mitdvp_batch_spectra_records: what the last such call recorded: values[records][n][rec_len], mean[records][rec_len],
+ *       counts = {records, n, rec_len}; each may be NULL.  weights NULL: the means under 1 / n, formed by that call, no
+ *       launch and no wait here; weights given (n doubles): ONE k_batch_mean launch over the records, which are still on
+ *       the device, and one host wait.  A new request or no recording call yet: records = 0.
+ * Jacobi sweeps that do not converge within 30 sweeps zero that replica's record; its status and its tensors stay as
+ * they are (an observation never changes a replica), and the call returns MITDVP_ENOTCONV with a message in
+ * mitdvp_last_error(NULL) naming the replica and the bond.  Every refusal is MITDVP_EINVAL with a message in
+ * mitdvp_last_error(NULL) that names the entry point and the limit, and leaves the request, the records and every engine
+ * as they were. */
+int mitdvp_batch_set_spectra(mitdvp_batch* b, const int* bonds, int nbonds);
+int mitdvp_batch_spectra(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[2]);
+int mitdvp_batch_spectra_records(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[3]);
 /* propagate_along_sweep (_mps_cls.py:798-1014), one direction only. */
 int mitdvp_sweep(mitdvp_engine* h, double dt_au, int forward);
 /* The same half-sweep in parts: the next `nsites` local updates of the half-sweep in progress (one is started when none

@@ -200,4 +200,28 @@ void batch_cross_launch(hipStream_t st, const BatchCrossArgs& a, int npairs);
 void batch_snapshot_launch(hipStream_t st, const BatchShape* shp, void* const* ptrs, int ptr_stride, zc* snap, size_t snap_len, int L,
                            int nrep);
 
+// ---- bond spectra and entanglement entropies (k_batch_spectra) ----
+// The request is a strictly ascending list of bonds q in 0 .. L-2; bond q lies between sites q and q+1 (named by its left
+// site, as the pair channels are) and has dimension chi_q = dr of site q.  One replica's record, in doubles, for every
+// listed bond in list order: [0] W = sum sigma^2 (summed in descending order of sigma^2; the replica's norm^2), [1] S1 =
+// -sum p ln p with p = sigma^2 / W (a term with p <= 0 counts as 0), [2] S2 = -ln sum p^2, [3] pmin = the smallest p, then
+// the chi_q values sigma^2, descending, not normalised.  W == 0 gives S1 = S2 = pmin = 0.
+constexpr int BSPEC_HEAD = 4;
+struct BatchSpecArgs {
+  int L, nbonds;
+  const BatchShape* shp;    // [L], device
+  void* const* ptrs;        // the pointer table of BatchArgs (only its site tensors are read)
+  int ptr_stride;
+  const int* status;        // [B]: a replica whose word is set does no work, its record is zeros
+  const int* bonds;         // [nbonds], device, strictly ascending
+  zc* buf;                  // [B][buf_len]: the walk's tensor X, the QR work matrix and R of each replica
+  size_t o_work, o_r, buf_len;  // X at 0 and the work matrix at o_work (max_site each), R at o_r (max_bond)
+  int* fail;                // [B]: 1 + the bond whose Jacobi sweeps did not converge; the kernel only ever sets it
+  double* rec;              // [B][rec_len]: this observation's records
+  long rec_len;             // sum over the listed bonds of BSPEC_HEAD + chi_q
+};
+// one launch: grid = nrep workgroups, the replicas are only read.  Precondition: centre at site 0, sites 1 .. L-1 in
+// gauge B.
+void batch_spectra_launch(hipStream_t st, const BatchSpecArgs& a, int nrep);
+
 }  // namespace mitdvp

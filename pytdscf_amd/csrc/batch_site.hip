@@ -1570,7 +1570,129 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_cross(BatchCrossArgs g) {
   if (tid == 0) { const zc z = T[0]; rec[0] = z.x; rec[1] = z.y; }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Bond spectra and entanglement entropies: k_batch_spectra, ONE workgroup per replica as above, every requested bond of
+// every replica in one launch (BatchSpecArgs in batch_site.h has the record's layout).  The state is k_batch_observe's:
+// centre at site 0, sites 1 .. L-1 right-canonical, so the Schmidt values of bond q are the singular values of the
+// centre tensor once the centre stands at site q.  The walk moves the centre on WORK BUFFERS only:
+//   X = C_0 (read in place)
+//   q = 0 .. the highest requested bond:
+//     X seen as (dl d) x dr  ->  R (dr x dr) by bt_qr, the sweep's Householder QR (its Q goes to X, which is free by then)
+//     bp_jacobi on the rows of R: afterwards they are mutually orthogonal, |row i|^2 are the sigma^2 of bond q
+//     a requested bond: its record from the row norms (bs_record)
+//     q below the last: X = R' B_{q+1} with the rotated R' (bp_merge); R' is R up to a unitary on the left index, which
+//       no later spectrum sees.  No U and no V is formed; sites right of the last requested bond are not touched.
+// The record of a bond (bs_record): the squared row norms ranked by counting as bp_select does (ties: the lower index
+// first) and stored in descending order; W, S1, S2 and pmin formed by ONE thread in that order.
+// A Jacobi that does not converge zeroes the replica's record and sets the request's own word fail[replica]; the
+// replica's status word is not touched -- an observation never changes a replica.
+// What is resident where: LDS holds the two operand tiles of wg_gemm, the Householder scalars, the rotation scalars of a
+// Jacobi round, the row norms, their ranks, the sorted weights and the reduction partials (22 376 bytes); X, the QR work
+// matrix and R live in the request's own buffer [B][buf_len] (global memory, L2-resident), written and re-read by this
+// workgroup only between workgroup barriers.  The replicas are only read.  Every element has one owner thread and every
+// sum one order: a record depends neither on B nor on the replica's place in the batch nor on the compute unit.  No
+// atomics, nothing waits for another workgroup, every loop is bounded by the shapes and BATCH_PAIR_MAX_SWEEPS.
+__device__ __noinline__ void bs_record(int chi, const BpSh& ps, double* srt, double* out) {
+  const int tid = threadIdx.x;
+  if (tid < chi) srt[tid] = 0.0;  // every slot is defined whatever the norms are (NaN compares false everywhere)
+  __syncthreads();
+  if (tid < chi) {
+    const double mine = ps.nrm[tid];
+    int rk = 0;
+    for (int j = 0; j < chi; ++j) {
+      const double v = ps.nrm[j];
+      rk += (v > mine || (v == mine && j < tid)) ? 1 : 0;
+    }
+    ps.rank[tid] = rk;
+    srt[rk] = mine;
+  }
+  __syncthreads();
+  if (tid < chi) out[BSPEC_HEAD + tid] = srt[tid];
+  if (tid == 0) {
+    double W = 0.0;
+    for (int k = 0; k < chi; ++k) W += srt[k];
+    double s1 = 0.0, s2 = 0.0, pmin = 0.0;
+    if (W > 0.0) {
+      double p2 = 0.0;
+      for (int k = 0; k < chi; ++k) {
+        const double p = srt[k] / W;
+        if (p > 0.0) s1 -= p * log(p);
+        p2 += p * p;
+      }
+      s2 = -log(p2);
+      pmin = srt[chi - 1] / W;
+    }
+    out[0] = W; out[1] = s1; out[2] = s2; out[3] = pmin;
+  }
+  __syncthreads();
+}
+
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 136 VGPRs -- those of the
+// non-inlined stage functions it shares with k_batch_pair (bt_qr, bp_jacobi, bp_merge) -- 106 SGPRs, no vector or scalar
+// register spills, 224 bytes of private memory per lane (the argument blocks of the calls of the stage functions, none of
+// it inside a QR, Jacobi or product loop), 22 376 bytes of LDS; occupancy 3 waves per SIMD, i.e. one workgroup per
+// compute unit.  The other batch kernels compile to what they compiled to before.  DESIGN.md section 7.3.
+__global__ __launch_bounds__(SS_THREADS) void k_batch_spectra(BatchSpecArgs g) {
+  __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
+  __shared__ zc s_z[2 * BATCH_MAX_BOND];
+  __shared__ double s_d[SS_WAVES * 8 + 8 + BATCH_MAX_BOND + 2 * BATCH_MAX_BOND + BATCH_MAX_BOND + BATCH_MAX_BOND + 3];
+  __shared__ int s_i[BATCH_MAX_BOND + 2];
+  BtSh sh{};
+  sh.mats = s_tiles;
+  sh.udiag = s_z; sh.rdiag = s_z + BATCH_MAX_BOND;
+  sh.wsh = s_d; sh.red = sh.wsh + SS_WAVES * 8; sh.gam = sh.red + 8;
+  BpSh ps{};  // what bp_jacobi uses of it, sized for BATCH_MAX_BOND rows: the rotations of a round, the row norms, the scale
+  ps.rot = sh.gam + BATCH_MAX_BOND; ps.nrm = ps.rot + 2 * BATCH_MAX_BOND;
+  double* srt = ps.nrm + BATCH_MAX_BOND;  // [BATCH_MAX_BOND] the weights of a bond in descending order
+  ps.scal = srt + BATCH_MAX_BOND;         // [3]
+  ps.rank = s_i; ps.flag = s_i + BATCH_MAX_BOND;
+  zc* tiles = s_tiles;
+
+  const int r = blockIdx.x, tid = threadIdx.x;
+  double* rec = g.rec + (size_t)r * g.rec_len;
+  for (long e = tid; e < g.rec_len; e += SS_THREADS) rec[e] = 0.0;
+  __syncthreads();
+  if (g.status[r] != SS_OK) return;  // a replica that failed: zeros
+  const zc* const* site = reinterpret_cast<const zc* const*>(g.ptrs + (size_t)r * g.ptr_stride);
+  zc* X = g.buf + (size_t)r * g.buf_len;
+  zc* work = X + g.o_work;
+  zc* R = X + g.o_r;
+
+  const int last = g.bonds[g.nbonds - 1];
+  int k = 0, rc = SS_OK, q = 0;
+  long off = 0;
+  for (; q <= last; ++q) {
+    const BatchShape s = g.shp[q];
+    const int m = s.dl * s.d, n = s.dr;
+    bt_qr(q == 0 ? site[0] : X, X, n, 1, R, n, 1, m, n, work, sh);
+    rc = bp_jacobi(R, n, n, ps, sh);
+    if (rc != SS_OK) break;  // the same decision in every thread of the workgroup
+    if (g.bonds[k] == q) {
+      bs_record(n, ps, srt, rec + off);
+      off += BSPEC_HEAD + n;
+      ++k;
+    }
+    if (q < last) {
+      const BatchShape t = g.shp[q + 1];
+      bp_merge(R, site[q + 1], X, n, t.d * t.dr, n, tiles);
+    }
+  }
+  if (rc != SS_OK) {
+    __syncthreads();
+    for (long e = tid; e < g.rec_len; e += SS_THREADS) rec[e] = 0.0;
+    if (tid == 0) g.fail[r] = q + 1;
+  }
+}
+
 }  // namespace
+
+void batch_spectra_launch(hipStream_t st, const BatchSpecArgs& a, int nrep) {
+  if (nrep < 1 || a.L < 2) throw ArgError("batch: nothing to launch");
+  if (a.nbonds < 1 || a.nbonds > a.L - 1 || !a.bonds || !a.buf || !a.fail || !a.rec || a.rec_len < 1)
+    throw ArgError("batch: no bond spectrum to observe");
+  hipLaunchKernelGGL(k_batch_spectra, dim3(nrep), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
 
 void batch_cross_launch(hipStream_t st, const BatchCrossArgs& a, int npairs) {
   if (npairs < 1 || npairs > BATCH_CROSS_MAX_PAIRS || a.L < 1 || a.nrep < 1) throw ArgError("batch: no cross pair to observe");

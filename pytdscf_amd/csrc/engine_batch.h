@@ -96,6 +96,27 @@ class Batch {
   // on the device, and one host wait.
   void cross_records(const double* weights, double* values, double* mean, size_t* counts);
 
+  // ---- bond spectra and entanglement entropies (k_batch_spectra) ----
+  // The request is a strictly ascending list of bonds q in 0 .. L-2 (bond q lies between sites q and q+1); a replica's
+  // record is, per listed bond, BSPEC_HEAD + chi_q doubles (batch_site.h).  Every refusal is an ArgError that names the
+  // entry point and the limit and leaves the request, the records and every engine as they were.
+  // set_spectra: nbonds = 0 removes the request.  Refused: a bond outside 0 .. L-2, a list that is not strictly ascending,
+  // a record of more than BATCH_OBS_MAX_RDM doubles.  No launch, no wait.
+  void set_spectra(const int* bonds, int nbonds);
+  bool has_spectra() const { return !spec_bonds_.empty(); }
+  // spectra: the request on the current state (centre at site 0): k_batch_spectra and k_batch_mean, TWO launches, one host
+  // wait.  weights: B doubles or null (1 / B); values [B][rec_len] and mean [rec_len] may each be null; counts {B,
+  // rec_len}; with all outputs null only the counts are returned.  NotConverged, naming the replica and the bond, when a
+  // Jacobi sweep did not converge (that replica's record is zeros; its status word and its tensors stay as they are).
+  void spectra(const double* weights, double* values, double* mean, size_t* counts);
+  // While a request is set every record of run() records it too: ONE more launch per record (k_batch_spectra behind the
+  // record's other launches) and ONE more k_batch_mean launch per call (weights 1 / B); values and means are copied with
+  // the rest, no further host wait.  spectra_records returns what the last run() recorded: values
+  // [records][B][rec_len], mean [records][rec_len], counts {records, B, rec_len}; each may be null.  weights null: the
+  // means of the run, no launch and no wait; weights given (B doubles): ONE k_batch_mean launch over the records, which
+  // are still on the device, and one host wait.
+  void spectra_records(const double* weights, double* values, double* mean, size_t* counts);
+
   std::string status_message(int code) const;
   int size() const { return (int)eng_.size(); }
   int device() const { return device_; }
@@ -188,6 +209,26 @@ class Batch {
   void upload_cross(long nrec);               // device images of the request, room for nrec records and cross()'s slot
   void launch_cross(long record);
   void cross_weights(const double* weights);
+
+  // spectra request: the bonds (host copy and device image), the walk's buffers [B][buf_len], the word per replica that a
+  // Jacobi sweep without convergence sets, the records [nrec + 1][B][rec_len] (the slot behind a run's records is
+  // spectra()'s own) and their means
+  std::vector<int> spec_bonds_;
+  bool spec_dirty_ = false;
+  int *d_spec_bonds_ = nullptr, *d_spec_fail_ = nullptr;
+  zc* d_spec_buf_ = nullptr;
+  double *d_spec_rec_ = nullptr, *d_spec_mean_ = nullptr, *d_spec_w_ = nullptr;
+  size_t spec_buf_elems_ = 0, spec_rec_slots_ = 0, spec_mean_slots_ = 0;  // the last two: doubles
+  long spec_nrec_ = 0;  // records of the last run() held in d_spec_rec_ / h_spec_rec_
+  std::vector<double> h_spec_rec_, h_spec_mean_, h_spec_w_, h_spec_now_;
+  std::vector<int> h_spec_fail_;
+  long spec_rec_len() const;
+  size_t spec_buf_len() const { return 2 * (size_t)plan_.max_site + (size_t)plan_.max_bond; }
+  void check_spectra(const char* entry) const;  // the request against the shapes as they are now
+  void upload_spectra(long nrec);               // device image of the request, room for nrec records and spectra()'s slot
+  void launch_spectra(long record);
+  void spectra_weights(const double* weights);
+  void spectra_failed(const char* entry) const;  // NotConverged when h_spec_fail_ names a replica
 
   static std::vector<BatchShape> shapes_of(Engine& e);
   void check_channels() const;

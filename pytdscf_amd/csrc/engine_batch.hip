@@ -89,6 +89,7 @@ void Batch::validate() {
     shp_ = s0;
     shapes_dirty_ = true;
     has_snap_ = false;  // a snapshot of other shapes names nothing any more
+    spec_nrec_ = 0;     // nor do spectra records of other bond dimensions
   }
   plan_ = pl;
   batch_observe_plan(plan_, obs_plan_);
@@ -121,6 +122,9 @@ Batch::Batch(const std::vector<Engine*>& engines) : eng_(engines) {
   dev_alloc(d_pair_, (size_t)L_);
   dev_alloc(d_pcounts_, n * L_ * BATCH_MAX_JUMP);
   dev_alloc(d_disc_, n);
+  dev_alloc(d_spec_bonds_, (size_t)L_);
+  dev_alloc(d_spec_fail_, n);
+  dev_alloc(d_spec_w_, n);
   chan_.assign((size_t)L_, BatchChanSite{BCH_NONE, 0, 0});
   chan_ops_.assign((size_t)L_, {});
   pair_.assign((size_t)L_, BatchChanSite{BCH_NONE, 0, 0});
@@ -160,6 +164,12 @@ Batch::~Batch() {
   if (d_cross_mean_) (void)hipFree(d_cross_mean_);
   if (d_cross_w_) (void)hipFree(d_cross_w_);
   if (d_snap_) (void)hipFree(d_snap_);
+  if (d_spec_bonds_) (void)hipFree(d_spec_bonds_);
+  if (d_spec_fail_) (void)hipFree(d_spec_fail_);
+  if (d_spec_w_) (void)hipFree(d_spec_w_);
+  if (d_spec_buf_) (void)hipFree(d_spec_buf_);
+  if (d_spec_rec_) (void)hipFree(d_spec_rec_);
+  if (d_spec_mean_) (void)hipFree(d_spec_mean_);
   if (st_) (void)hipStreamDestroy(st_);
 }
 
@@ -607,9 +617,11 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   HIP_CHECK(hipSetDevice(device_));
   const int nkeys = dens.nkeys;
   const bool cx = has_cross();  // a cross request rides on every record; it may be all that is recorded
-  const long nrdm = observe_sizes(sites, nsites, what, nkeys > 0 || cx);
+  const bool sp = has_spectra();  // so does a spectra request
+  const long nrdm = observe_sizes(sites, nsites, what, nkeys > 0 || cx || sp);
   const long ndens = density_sizes(dens.legs, nkeys, nrdm);
   if (cx) check_cross("mitdvp_batch_run");
+  if (sp) check_spectra("mitdvp_batch_run");
   const bool own = what != 0 || nkeys > 0;  // false: only the cross request is recorded, no record of the replicas
   const size_t n = eng_.size();
   const long nrec = nsteps / every + 1, dens_off = BOBS_HEAD + 2 * nrdm, rec_len = dens_off + 2 * ndens;
@@ -619,6 +631,7 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   prepare(true, nsteps > 0 || (what & BOBS_ENERGY));
   if (chan) upload_channels();
   if (cx) upload_cross(nrec);
+  if (sp) upload_spectra(nrec);
   // buffers of the records and their means (grow only), the site list and the weights
   const size_t need_rec = (size_t)nrec * n * rec_len, need_mean = (size_t)nrec * rec_len;
   const size_t need_legs = (size_t)nkeys * L_, need_tbuf = nkeys ? n * 2 * dens_plan_.need : 0;
@@ -662,6 +675,7 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
     if (what) launch_observe(what, nsites, q, rec_len);
     if (nkeys) launch_density(nkeys, what == 0, q, rec_len, dens_off);
     if (cx) launch_cross(q);
+    if (sp) launch_spectra(q);
   };
 
   record(0);
@@ -691,12 +705,26 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
     HIP_CHECK(hipMemcpyAsync(h_cross_mean_.data(), d_cross_mean_, h_cross_mean_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
     cross_nrec_ = nrec;
   }
+  int spec_launches = 0;
+  if (sp) {  // the same for the spectra request (weights 1 / B)
+    const size_t len = (size_t)spec_rec_len();
+    spectra_weights(nullptr);
+    batch_mean_launch(st_, d_spec_rec_, d_spec_w_, d_spec_mean_, (int)n, (long)len, nrec);
+    n_launch_ += 1;
+    spec_launches = (int)nrec + 1;
+    h_spec_rec_.resize((size_t)nrec * n * len);
+    h_spec_mean_.resize((size_t)nrec * len);
+    HIP_CHECK(hipMemcpyAsync(h_spec_rec_.data(), d_spec_rec_, h_spec_rec_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipMemcpyAsync(h_spec_mean_.data(), d_spec_mean_, h_spec_mean_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipMemcpyAsync(h_spec_fail_.data(), d_spec_fail_, n * sizeof(int), hipMemcpyDeviceToHost, st_));
+    spec_nrec_ = nrec;
+  }
   if (per_replica) {
     h_rec_.resize(need_rec);
     HIP_CHECK(hipMemcpyAsync(h_rec_.data(), d_rec_, need_rec * sizeof(double), hipMemcpyDeviceToHost, st_));
   }
   steps_done_ += nsteps;
-  const int other = (int)nrec * per_rec + (own ? 1 : 0) + cross_launches;
+  const int other = (int)nrec * per_rec + (own ? 1 : 0) + cross_launches + spec_launches;
   if (nsteps > 0) finish(false, nsteps * 2, statuses, other, chan ? nsteps : 0);
   else finish_observe(other, statuses);
 
@@ -717,6 +745,7 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
       if (dens.density && ndens) std::memcpy(dens.density + at * 2 * ndens, r + dens_off, (size_t)2 * ndens * sizeof(double));
     }
   }
+  if (sp) spectra_failed("mitdvp_batch_run");
 }
 
 // ---- cross overlaps and one-site matrix elements between replicas (k_batch_cross, k_batch_snapshot) ----
@@ -911,6 +940,156 @@ void Batch::cross_records(const double* weights, double* values, double* mean, s
   batch_mean_launch(st_, d_cross_rec_, d_cross_w_, dst, (int)np, 2, (long)nrec);
   n_launch_ += 1;
   HIP_CHECK(hipMemcpyAsync(mean, dst, nrec * 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
+  finish_observe(1, nullptr);
+}
+
+// ---- bond spectra and entanglement entropies (k_batch_spectra) ----
+long Batch::spec_rec_len() const {
+  long len = 0;
+  for (int q : spec_bonds_) len += BSPEC_HEAD + shp_[q].dr;
+  return len;
+}
+
+void Batch::set_spectra(const int* bonds, int nbonds) {
+  const std::string at = "mitdvp_batch_set_spectra: ";
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  if (nbonds < 0 || (nbonds > 0 && !bonds)) throw ArgError(at + "bad list of bonds (nbonds must be >= 0, and the list not null)");
+  long len = 0;
+  for (int k = 0; k < nbonds; ++k) {
+    if (bonds[k] < 0 || bonds[k] > L_ - 2)
+      throw ArgError(at + "bond " + std::to_string(bonds[k]) + " is out of range (the chain has " + std::to_string(L_) + " sites, bonds 0 .. " +
+                     std::to_string(L_ - 2) + "; bond q lies between sites q and q + 1)");
+    if (k > 0 && bonds[k] <= bonds[k - 1])
+      throw ArgError(at + "the bonds must be strictly ascending (bond " + std::to_string(bonds[k]) + " follows bond " + std::to_string(bonds[k - 1]) + ")");
+    len += BSPEC_HEAD + shp_[bonds[k]].dr;
+  }
+  if (len > BATCH_OBS_MAX_RDM)
+    throw ArgError(at + "a replica's record would have " + std::to_string(len) + " doubles (4 + the bond's dimension per bond), a request takes at most " +
+                   std::to_string(BATCH_OBS_MAX_RDM));
+  spec_bonds_.assign(bonds, bonds + nbonds);
+  spec_dirty_ = true;
+  spec_nrec_ = 0;  // records of another request are not this one's
+}
+
+void Batch::check_spectra(const char* entry) const {
+  const std::string at = std::string(entry) + ": ";
+  if (spec_bonds_.empty()) throw ArgError(at + "no spectra request is set (mitdvp_batch_set_spectra)");
+  if (spec_bonds_.back() > L_ - 2) throw ArgError(at + "the spectra request names bond " + std::to_string(spec_bonds_.back()) + ", which the chain no longer has");
+  if (spec_rec_len() > BATCH_OBS_MAX_RDM)
+    throw ArgError(at + "a replica's spectra record has " + std::to_string(spec_rec_len()) + " doubles at the bond dimensions as they are now, a request takes at most " +
+                   std::to_string(BATCH_OBS_MAX_RDM));
+}
+
+void Batch::upload_spectra(long nrec) {
+  const size_t n = eng_.size(), len = (size_t)spec_rec_len(), slots = (size_t)nrec + 1;
+  const size_t need_buf = n * spec_buf_len(), need_rec = slots * n * len, need_mean = 2 * slots * len;
+  if (need_buf > spec_buf_elems_ || need_rec > spec_rec_slots_ || need_mean > spec_mean_slots_) {
+    HIP_CHECK(hipStreamSynchronize(st_));
+    auto grow = [&](auto*& p, size_t& have, size_t need) {
+      if (p && need <= have) return;
+      if (p) (void)hipFree(p);
+      p = nullptr;
+      dev_alloc(p, need);
+      have = need;
+    };
+    grow(d_spec_buf_, spec_buf_elems_, need_buf);
+    // these two grow only with a new request or in run(): no record of the last run is lost
+    grow(d_spec_rec_, spec_rec_slots_, need_rec);
+    // the means of the records, the one of spectra(), and the records' means under the weights of spectra_records
+    grow(d_spec_mean_, spec_mean_slots_, need_mean);
+  }
+  if (spec_dirty_) {
+    HIP_CHECK(hipMemcpyAsync(d_spec_bonds_, spec_bonds_.data(), spec_bonds_.size() * sizeof(int), hipMemcpyHostToDevice, st_));
+    spec_dirty_ = false;
+  }
+  h_spec_fail_.assign(n, 0);
+  HIP_CHECK(hipMemsetAsync(d_spec_fail_, 0, n * sizeof(int), st_));
+}
+
+void Batch::launch_spectra(long record) {
+  BatchSpecArgs a{};
+  a.L = L_;
+  a.nbonds = (int)spec_bonds_.size();
+  a.shp = d_shp_;
+  a.ptrs = d_ptrs_;
+  a.ptr_stride = (int)ptrs_per_replica();
+  a.status = d_status_;
+  a.bonds = d_spec_bonds_;
+  a.buf = d_spec_buf_;
+  a.o_work = (size_t)plan_.max_site;
+  a.o_r = 2 * (size_t)plan_.max_site;
+  a.buf_len = spec_buf_len();
+  a.fail = d_spec_fail_;
+  a.rec_len = spec_rec_len();
+  a.rec = d_spec_rec_ + (size_t)record * eng_.size() * (size_t)a.rec_len;
+  batch_spectra_launch(st_, a, (int)eng_.size());
+  n_launch_ += 1;
+}
+
+void Batch::spectra_weights(const double* weights) {
+  const size_t n = eng_.size();
+  h_spec_w_.assign(n, 1.0 / (double)n);
+  if (weights) h_spec_w_.assign(weights, weights + n);
+  HIP_CHECK(hipMemcpyAsync(d_spec_w_, h_spec_w_.data(), n * sizeof(double), hipMemcpyHostToDevice, st_));
+}
+
+void Batch::spectra_failed(const char* entry) const {
+  for (size_t i = 0; i < h_spec_fail_.size(); ++i)
+    if (h_spec_fail_[i] != 0) {
+      const int q = h_spec_fail_[i] - 1;
+      throw NotConverged(std::string(entry) + ": replica " + std::to_string(i) + ": the Jacobi rotations of bond " + std::to_string(q) + " (between sites " +
+                         std::to_string(q) + " and " + std::to_string(q + 1) + ") are not converged in " + std::to_string(BATCH_PAIR_MAX_SWEEPS) +
+                         " sweeps; its spectra record is zeros, the replica itself is as it was");
+    }
+}
+
+void Batch::spectra(const double* weights, double* values, double* mean, size_t* counts) {
+  const std::string at = "mitdvp_batch_spectra: ";
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  check_spectra("mitdvp_batch_spectra");
+  const size_t n = eng_.size(), len = (size_t)spec_rec_len();
+  if (counts) { counts[0] = n; counts[1] = len; }
+  if (!values && !mean) return;
+  for (size_t i = 0; i < n; ++i)
+    if (eng_[i]->center_ != 0)
+      throw ArgError(at + "replica " + std::to_string(i) + " has its centre at site " + std::to_string(eng_[i]->center_) +
+                     "; the walk starts from the centre at site 0 (the state a batch step leaves)");
+  prepare(true, false);
+  upload_spectra(spec_nrec_);
+  const size_t slot = (size_t)spec_nrec_;  // behind the records of the last run, which stay
+  spectra_weights(weights);
+  launch_spectra((long)slot);
+  batch_mean_launch(st_, d_spec_rec_ + slot * n * len, d_spec_w_, d_spec_mean_ + slot * len, (int)n, (long)len, 1);
+  n_launch_ += 1;
+  h_spec_now_.resize(n * len + len);
+  HIP_CHECK(hipMemcpyAsync(h_spec_now_.data(), d_spec_rec_ + slot * n * len, n * len * sizeof(double), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipMemcpyAsync(h_spec_now_.data() + n * len, d_spec_mean_ + slot * len, len * sizeof(double), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipMemcpyAsync(h_spec_fail_.data(), d_spec_fail_, n * sizeof(int), hipMemcpyDeviceToHost, st_));
+  finish_observe(2, nullptr);
+  if (values) std::memcpy(values, h_spec_now_.data(), n * len * sizeof(double));
+  if (mean) std::memcpy(mean, h_spec_now_.data() + n * len, len * sizeof(double));
+  spectra_failed("mitdvp_batch_spectra");
+}
+
+void Batch::spectra_records(const double* weights, double* values, double* mean, size_t* counts) {
+  const size_t n = eng_.size(), nrec = (size_t)spec_nrec_, len = spec_bonds_.empty() ? 0 : (size_t)spec_rec_len();
+  if (counts) { counts[0] = nrec; counts[1] = n; counts[2] = len; }
+  if (nrec == 0 || (!values && !mean)) return;
+  if (values) std::memcpy(values, h_spec_rec_.data(), nrec * n * len * sizeof(double));
+  if (!mean) return;
+  if (!weights) {
+    std::memcpy(mean, h_spec_mean_.data(), nrec * len * sizeof(double));
+    return;
+  }
+  HIP_CHECK(hipSetDevice(device_));
+  spectra_weights(weights);
+  // behind the slots of the records' own means and of spectra(): the means of the run stay as they are
+  double* dst = d_spec_mean_ + (nrec + 1) * len;
+  batch_mean_launch(st_, d_spec_rec_, d_spec_w_, dst, (int)n, (long)len, (long)nrec);
+  n_launch_ += 1;
+  HIP_CHECK(hipMemcpyAsync(mean, dst, nrec * len * sizeof(double), hipMemcpyDeviceToHost, st_));
   finish_observe(1, nullptr);
 }
 

@@ -835,6 +835,28 @@ def pair_key(key, nsite: int) -> tuple[int, int]:
     return k
 
 
+def spectra_bonds(bonds, nsite: int) -> list[int]:
+    """The bond list of a spectra request as plain integers: an iterable of whole numbers (a single number is a list of
+    one).  ``ValueError`` for anything that is not a whole number or does not fit the library's ``int``; range and order
+    are the library's to check (``mitdvp_batch_set_spectra``), whose message names the limit.  Pure Python."""
+    import numbers
+
+    if isinstance(bonds, numbers.Integral):
+        bonds = [bonds]
+    try:
+        items = list(bonds)
+    except TypeError:
+        raise ValueError(f"spectra bonds {bonds!r}: a list of bonds q, 0 <= q <= {nsite - 2}") from None
+    out = []
+    for q in items:
+        if isinstance(q, bool) or not isinstance(q, (numbers.Integral, np.integer)):
+            raise ValueError(f"spectra bonds {items!r}: bond {q!r} is not a whole number (bond q lies between sites q and q + 1)")
+        if not -2**31 <= int(q) < 2**31:
+            raise ValueError(f"spectra bonds {items!r}: bond {q!r} does not fit an int")
+        out.append(int(q))
+    return out
+
+
 class TDVPBatch:
     """B independent trajectories (replicas) of one chain shape on ONE GPU, any B: one kernel launch per half-sweep for the
     whole batch (``mitdvp_batch_step`` / ``k_batch_sweep``: one workgroup owns one replica, the replica index is the
@@ -861,6 +883,7 @@ class TDVPBatch:
         self._channels = {}
         self._seed = None
         self._cross = None
+        self._spectra = None
         self._lib = _lib.load()
         try:
             for _ in range(n_replicas):
@@ -885,6 +908,7 @@ class TDVPBatch:
         self._channels = {}
         self._seed = None
         self._cross = None
+        self._spectra = None
         self._lib = _lib.load()
         return self
 
@@ -920,6 +944,8 @@ class TDVPBatch:
                     self._push_seed(seed, ids)
                 if self._cross is not None:  # the new handle has no snapshot: a request that names one is refused here
                     self._push_cross(self._cross)
+                if self._spectra is not None:
+                    self._push_spectra(self._spectra)
             except Exception:
                 self._drop()
                 raise
@@ -1142,6 +1168,79 @@ class TDVPBatch:
         _lib.check(self._lib.mitdvp_batch_cross_records(self._b, None if w is None else _dp(w), _dp(vals), _dp(mean), cnt))
         return vals, mean
 
+    # ---- bond spectra and entanglement entropies (mitdvp_batch_set_spectra / _spectra) ----
+    def _push_spectra(self, bonds):
+        arr = (C.c_int * max(len(bonds), 1))(*bonds)
+        _lib.check(self._lib.mitdvp_batch_set_spectra(self._b, arr, len(bonds)))
+
+    def set_spectra(self, bonds):
+        """Registers the bonds whose Schmidt spectra ``spectra`` and recorded runs evaluate: a strictly ascending list of
+        bonds ``q`` in ``0 .. L-2``; bond ``q`` lies between sites ``q`` and ``q + 1``.  An empty list removes the
+        request.  The library validates (range, order, the record's size) and a refused request leaves the one before
+        in place."""
+        bonds = spectra_bonds(bonds, self.engines[0].nsite)
+        self._handle()
+        self._push_spectra(bonds)
+        self._spectra = bonds if bonds else None
+
+    def _spectra_weights(self, weights):
+        if self._spectra is None:
+            raise ValueError("no spectra request is set (set_spectra)")
+        if weights is None:
+            return None
+        n = len(self.engines)
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+        if w.shape != (n,):
+            raise ValueError(f"spectra weights must be {n} numbers, one per replica (got shape {w.shape})")
+        return w
+
+    def _split_spectra(self, values, mean, per_replica=True):
+        """the flat records cut by bond: W, S1, S2, pmin and the chi weights of every requested bond"""
+        chis = [self.engines[0].get_site_shape(q)[2] for q in self._spectra]
+        res = {}
+        for prefix, flat in (("mean_", mean), ("", values)):
+            if flat is None or (not prefix and not per_replica):
+                continue
+            head, wts, at = [], [], 0
+            for chi in chis:
+                head.append(flat[..., at:at + 4])
+                wts.append(np.ascontiguousarray(flat[..., at + 4:at + 4 + chi]))
+                at += 4 + chi
+            head = np.stack(head, axis=-2)  # (..., nb, 4)
+            for k, name in enumerate(("norm2", "entropy", "renyi2", "min_weight")):
+                res[prefix + name] = np.ascontiguousarray(head[..., k])
+            res[prefix + "weights"] = wts
+        return res
+
+    def spectra(self, weights=None, per_replica: bool = True):
+        """The Schmidt spectrum of every bond of ``set_spectra`` for every replica by ONE launch (``k_batch_spectra``), the
+        ensemble means by a second one (``mitdvp_batch_spectra``); all replicas must have their centre at site 0 and are
+        only read.  Returns, with ``nb`` the number of requested bonds: ``mean_entropy`` (von Neumann, natural
+        logarithm), ``mean_renyi2``, ``mean_min_weight`` (the smallest normalised Schmidt weight: how close the bond is
+        to being too narrow), ``mean_norm2``, each ``(nb,)``; ``mean_weights``, a list of ``(chi_q,)`` arrays of squared
+        Schmidt values, descending, not normalised; and, with ``per_replica``, the same names without ``mean_`` and with
+        a leading B axis.  The entropies are those of each trajectory, THEN averaged: they are not functions of the
+        averaged densities.  ``weights``: B numbers, default 1 / B each."""
+        w = self._spectra_weights(weights)
+        b = self._handle()
+        cnt = (C.c_size_t * 2)()
+        _lib.check(self._lib.mitdvp_batch_spectra(b, None, None, None, cnt))
+        n, rec_len = int(cnt[0]), int(cnt[1])
+        vals = np.zeros((n, rec_len), dtype=np.float64)
+        mean = np.zeros(rec_len, dtype=np.float64)
+        _lib.check(self._lib.mitdvp_batch_spectra(b, None if w is None else _dp(w), _dp(vals), _dp(mean), cnt))
+        return self._split_spectra(vals, mean, per_replica)
+
+    def _spectra_records(self, weights, per_replica=True):
+        w = self._spectra_weights(weights)
+        cnt = (C.c_size_t * 3)()
+        _lib.check(self._lib.mitdvp_batch_spectra_records(self._b, None, None, None, cnt))
+        nrec, n, rec_len = (int(c) for c in cnt)
+        vals = np.zeros((nrec, n, rec_len), dtype=np.float64)
+        mean = np.zeros((nrec, rec_len), dtype=np.float64)
+        _lib.check(self._lib.mitdvp_batch_spectra_records(self._b, None if w is None else _dp(w), _dp(vals), _dp(mean), cnt))
+        return self._split_spectra(vals, mean, per_replica)
+
     def launches(self) -> int:
         """kernel launches counted so far on replica 0, where the batch's launches are counted once"""
         return int(self.engines[0].counters()["n_launch"])
@@ -1168,7 +1267,11 @@ class TDVPBatch:
         come back as ``mean_density`` / ``density``, record axis first; the other entries are bitwise what they are
         without ``keys``.  ``cross=True`` adds the request of ``set_cross``, which every record of a run evaluates while
         it is set (one more launch per record): ``cross`` of shape ``(nrec, P)`` and ``mean_cross`` ``(nrec,)``, the
-        weighted sum over the pairs with ``cross_weights`` (P numbers, default 1 / P each)."""
+        weighted sum over the pairs with ``cross_weights`` (P numbers, default 1 / P each).  ``spectra=True`` adds the
+        request of ``set_spectra`` in the same way (``k_batch_spectra``, one more launch per record): the entries of
+        ``spectra()`` with a leading record axis, averaged with ``spectra_weights`` (B numbers, default 1 / B each).  With
+        ``norm=True`` the entry ``mean_norm2`` stays the observation's ``(nrec,)`` array, which every bond's sum of
+        weights equals."""
         if observe is None:
             self._run(lambda b, st: self._lib.mitdvp_batch_step(b, float(dt_au), int(nsteps), st))
             return None
@@ -1201,10 +1304,12 @@ class TDVPBatch:
         return {k: [x[0] for x in v] for k, v in rec.items()}
 
     def _observed(self, dt_au, nsteps, every, sites=(), norm=True, autocorr=False, energy=False, weights=None, per_replica=True,
-                  keys=(), cross=False, cross_weights=None):
+                  keys=(), cross=False, cross_weights=None, spectra=False, spectra_weights=None):
         n = len(self.engines)
         if cross:
             self._cross_weights(cross_weights)  # no request, or weights of the wrong length: raised before any library call
+        if spectra:
+            self._spectra_weights(spectra_weights)
         nsite = self.engines[0].nsite
         legs = [density_key_legs(k, nsite) for k in keys]  # a malformed key raises here, before any library call
         sites = [int(p) for p in sites]
@@ -1265,6 +1370,9 @@ class TDVPBatch:
             self.records = self._split(keep, sites, legs)  # a replica that did not converge raises; what was recorded stays readable here
             if cross:
                 self.records["cross"], self.records["mean_cross"] = self._cross_records(cross_weights)
+            if spectra:
+                for k, v in self._spectra_records(spectra_weights, per_replica).items():
+                    self.records.setdefault(k, v)  # norm=True owns mean_norm2: every bond's W is that very number
         return self.records
 
     def _split(self, keep, sites, legs=()):

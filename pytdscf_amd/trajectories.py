@@ -17,7 +17,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import units
-from .engine import TDVPBatch, density_key_legs, pair_key
+from .engine import TDVPBatch, density_key_legs, pair_key, spectra_bonds
 from .mps import product_state_cores
 
 
@@ -194,7 +194,7 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
 
 def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, weights=None, integrator="lanczos",
                            conserve_norm=True, per_trajectory=False, thresh_sil=1.0e-09, device=0, jumps=None, seed=0,
-                           replicas_per_start=1, first_trajectory=0, densities=None):
+                           replicas_per_start=1, first_trajectory=0, densities=None, entanglement=None):
     """Propagate every Hartree product of ``starts`` under ``model`` and average their reduced densities.
 
     ``model``: a ``Model`` as the shell takes it (one electronic state, Hilbert space); its ``one_gate_to_apply``
@@ -223,7 +223,15 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
     over the two physical indices) or ``(K, d_q, d_{q+1}, d_q, d_{q+1})``: a nearest-neighbour Kraus channel, sampled by the
     same rule with the uniform ``jump_uniform(seed, trajectory, step, nsite + q)``; the bond keeps its dimension, so what
     the re-split truncates is lost (``TDVPBatch.discarded_weight``).  A key that is not an ascending pair of neighbours is
-    a ``ValueError`` naming it.  ``model.one_gate_to_apply`` stays one-site."""
+    a ``ValueError`` naming it.  ``model.one_gate_to_apply`` stays one-site.
+
+    ``entanglement``: a strictly ascending list of bonds ``q`` (bond ``q`` lies between sites ``q`` and ``q + 1``).  The
+    Schmidt spectrum of each is formed for every trajectory at the interval of ``reduced_density`` in the same run
+    (``k_batch_spectra``, one more launch per record), and the result gains ``"entropy"`` of shape ``(nrec, nb)`` -- the
+    weighted mean over the trajectories of each trajectory's von Neumann entropy (natural logarithm), which no averaged
+    density gives -- and ``"min_weight"`` ``(nrec, nb)``, the mean of the smallest normalised Schmidt weight: the check
+    that the bond dimension is wide enough.  With ``per_trajectory`` also ``"entropy_trajectories"`` ``(nrec, ntraj, nb)``.
+    The default ``None`` leaves the result as it is without the keyword."""
     if integrator not in ("lanczos", "arnoldi"):
         raise ValueError(f"Invalid integrator: {integrator}")
     keys, every = reduced_density
@@ -233,6 +241,9 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
         raise ValueError("maxstep and the reduced-density interval must be >= 1")
     nsite = len(model.dims)
     key_sites = _one_site_keys(keys, nsite)
+    bonds = spectra_bonds(entanglement, nsite) if entanglement is not None else []
+    if entanglement is not None and not bonds:
+        raise ValueError("entanglement names no bond")
     dens_keys = [tuple(k) for k in densities] if densities is not None else []
     for k in dens_keys:
         density_key_legs(k, nsite)  # a malformed key raises here, before any engine exists
@@ -276,6 +287,9 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
         req = dict(sites=sites, norm=False, weights=weights, per_replica=per_trajectory)
         if dens_keys:
             req["keys"] = dens_keys
+        if bonds:
+            bt.set_spectra(bonds)
+            req.update(spectra=True, spectra_weights=weights)
         rec = bt.propagate(dt_au, nsteps, observe=req, every=every)
     finally:
         bt.close()
@@ -288,4 +302,8 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
         out["mean"][k] = rec["mean_density"][i]
         if per_trajectory:
             out["trajectories"][k] = rec["density"][i]
+    if bonds:
+        out["entropy"], out["min_weight"] = rec["mean_entropy"], rec["mean_min_weight"]
+        if per_trajectory:
+            out["entropy_trajectories"] = rec["entropy"]
     return out
