@@ -111,7 +111,12 @@ struct MpoSite {
   //       block in the core, GR / lam_c0 = the update's operator + sum_{t in E} mu_t W[c0,i,j,t] (x) 1, and that term is
   //       column c0 of ws: reuse_alpha = 1 / lam_c0, and the Gram core runs with ws_reuse = ws with column c0 zero.
   // Several general out states, another identity state of S with blocks, or a zero multiple: reuse = false.
-  struct EnvFold { std::vector<int> t0; DevBuf ws, wg; bool reuse = false; hzc reuse_alpha; DevBuf ws_reuse; };
+  // ws_list / ws_reuse_list: the Gram lists of ws / ws_reuse; wg_list: the fold lists of wg[k], wg_list_stride elements apart
+  // (core_lists.h; written and valid with the cores they are made from)
+  struct EnvFold {
+    std::vector<int> t0; DevBuf ws, wg; bool reuse = false; hzc reuse_alpha; DevBuf ws_reuse;
+    DevBuf ws_list, ws_reuse_list, wg_list; size_t wg_list_stride = 0;
+  };
   // what the local solves find out about the site and keep from sweep to sweep: written through the const core
   struct EdgeCache {
     bool valid = false;  // the cores below correspond to (s, e, lam, mu)
@@ -120,6 +125,7 @@ struct MpoSite {
     bool has_l = false, has_r = false;
     int skip = 0;        // local solves for which the (failed) structure check is not repeated
     DevBuf w_l, w_r;
+    DevBuf w_l_list, w_r_list;  // their fold lists, for the strides choose_apply_forms folds them with (core_lists.h)
     DevBuf w_lf, w_rf;   // the same cores in the epilogue's fragment order (zgemm_reduce_pack_core)
     bool lf_ok = false, rf_ok = false;
     EnvFold envf[2];
@@ -368,6 +374,9 @@ class Engine {
   // which nothing but choose_apply_forms writes -- and that clears this record first; X_ / Y_ are not (the update itself
   // overwrites them: its Gram matrix lives in Y_)
   bool env_reuse_ = true;
+  // MITDVP_CORE_LISTS=0: fold_env_core and gram_env_core read the dense cores themselves instead of the lists uploaded
+  // beside them (core_lists.h; the same bits, kept for A/B runs)
+  bool core_lists_ = true;
   struct EnvChecked { const MpoSite* w = nullptr; const zc* blk[2] = {nullptr, nullptr}; int n[2] = {0, 0}; int lvl[2] = {0, 0}; } env_chk_;
   EnvChecked take_env_checked() { const EnvChecked c = env_chk_; env_chk_ = EnvChecked{}; return c; }
   // One look at the MPO-bond states of the two blocks around a site or bond (identity_sets): per state its deviation from

@@ -34,6 +34,7 @@ Engine::Engine(const mitdvp_config& c) : cfg(c), L_(c.nsite) {
   if (const char* e = std::getenv("MITDVP_STRASSEN_FUSE")) strassen_fuse_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_FOLD_ENV")) fold_env_mode_ = std::atoi(e);
   if (const char* e = std::getenv("MITDVP_FOLD_ENV_REUSE")) env_reuse_ = std::atoi(e) != 0;
+  if (const char* e = std::getenv("MITDVP_CORE_LISTS")) core_lists_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_QR_GAUGE_FREE")) qr_gauge_free_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("MITDVP_KEFF_IDENT")) keff_ident_ = std::atoi(e) != 0;
   int ndev = 0;

@@ -1,6 +1,7 @@
 // engine_apply.hip -- the contractions of the large-bond hot path: H_eff / K_eff applies in all their forms, the
 // environment update, and the identity checks of the environment blocks that choose between the forms.
 #include "engine_internal.h"
+#include "core_lists.h"
 
 namespace mitdvp {
 
@@ -322,6 +323,20 @@ void MpoSite::EdgeCache::rebuild(hipStream_t st, const MpoSite& w, unsigned long
   w_r.reserve(wr.size());
   HIP_CHECK(hipMemcpyAsync(w_l.p, wl.data(), wl.size() * sizeof(zc), hipMemcpyHostToDevice, st));
   HIP_CHECK(hipMemcpyAsync(w_r.p, wr.data(), wr.size() * sizeof(zc), hipMemcpyHostToDevice, st));
+  // the lists of the same cores (core_lists.h), for the strides choose_apply_forms folds them with; they live and die with
+  // the cores.  (the blobs are whole 16-byte words; each copy is waited for: its host blob goes out of scope)
+  auto upload_list = [&](DevBuf& b, const std::vector<unsigned char>& blob, size_t at = 0) {
+    HIP_CHECK(hipMemcpyAsync(reinterpret_cast<unsigned char*>(b.p) + at, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  };
+  {
+    const std::vector<unsigned char> ll = build_fold_list(wl.data(), d, ml, (long)ml * d, 1, d);
+    const std::vector<unsigned char> lr = build_fold_list(wr.data(), d, mr, (long)d * mr, mr, 1);
+    w_l_list.reserve(ll.size() / sizeof(zc));
+    w_r_list.reserve(lr.size() / sizeof(zc));
+    upload_list(w_l_list, ll);
+    upload_list(w_r_list, lr);
+  }
   w_lf.reserve(wl.size());
   w_rf.reserve(wr.size());
   lf_ok = zgemm_reduce_pack_core(st, w_l.p, (long)ml * d, d, ml * d, w_lf.p);
@@ -360,6 +375,17 @@ void MpoSite::EdgeCache::rebuild(hipStream_t st, const MpoSite& w, unsigned long
     f.wg.reserve(wg.size());
     HIP_CHECK(hipMemcpyAsync(f.ws.p, ws.data(), ws.size() * sizeof(zc), hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(f.wg.p, wg.data(), wg.size() * sizeof(zc), hipMemcpyHostToDevice, st));
+    {
+      const std::vector<unsigned char> gl = build_gram_list(ws.data(), d, mo, gram_list_tu(mo));
+      f.ws_list.reserve(gl.size() / sizeof(zc));
+      upload_list(f.ws_list, gl);
+      // a dense wg[k] bounds every list: one stride for all k
+      f.wg_list_stride = (fold_list_head(d) + (size_t)d * ((d + 3) / 4) * mi * sizeof(FoldEntry)) / sizeof(zc);
+      f.wg_list.reserve(std::max<size_t>(f.t0.size(), 1) * f.wg_list_stride);
+      for (size_t k = 0; k < f.t0.size(); ++k)
+        upload_list(f.wg_list, build_fold_list(wg.data() + k * (size_t)d * mi * d, d, mi, (long)mi * d, 1, d),
+                    k * f.wg_list_stride * sizeof(zc));
+    }
     // whether the update may take the general states' operator from the solve's packed factors (EnvFold, engine.h).  The
     // directions differ because every block out of a state of S went to the R-side core wr above, whatever its out state
     f.reuse = false;
@@ -380,6 +406,9 @@ void MpoSite::EdgeCache::rebuild(hipStream_t st, const MpoSite& w, unsigned long
         if (side == 1) for (int ij = 0; ij < d * d; ++ij) ws2[(size_t)ij * mo + o] = hzc(0.0, 0.0);
         f.ws_reuse.reserve(ws2.size());
         HIP_CHECK(hipMemcpyAsync(f.ws_reuse.p, ws2.data(), ws2.size() * sizeof(zc), hipMemcpyHostToDevice, st));
+        const std::vector<unsigned char> gl2 = build_gram_list(ws2.data(), d, mo, gram_list_tu(mo));
+        f.ws_reuse_list.reserve(gl2.size() / sizeof(zc));
+        upload_list(f.ws_reuse_list, gl2);
       }
     }
     HIP_CHECK(hipStreamSynchronize(st));  // the host vectors go out of scope
@@ -457,8 +486,12 @@ ApplyPlan Engine::choose_apply_forms(const zc* Lb, const MpoSite& w, const zc* R
   plan.fold_l = w.edge.has_l && can_fold_l;
   if (plan.fold_r || plan.fold_l) {  // once per local solve, on the stream, no synchronisation
     timer_begin(11);
-    if (plan.fold_r) fold_env_core(st_, Rb, w.edge.w_r.p, Y_.p, dr, mr, d, (long)d * mr, mr, 1, (long)dr * d * dr, (long)d * dr, dr, 1);
-    if (plan.fold_l) fold_env_core(st_, Lb, w.edge.w_l.p, X_.p, dl, ml, d, (long)ml * d, 1, d, (long)dl * d, (long)d * dl * d, 1, d);
+    if (plan.fold_r)
+      fold_env_core(st_, Rb, w.edge.w_r.p, Y_.p, dr, mr, d, (long)d * mr, mr, 1, (long)dr * d * dr, (long)d * dr, dr, 1,
+                    core_lists_ ? w.edge.w_r_list.p : nullptr);
+    if (plan.fold_l)
+      fold_env_core(st_, Lb, w.edge.w_l.p, X_.p, dl, ml, d, (long)ml * d, 1, d, (long)dl * d, (long)d * dl * d, 1, d,
+                    core_lists_ ? w.edge.w_l_list.p : nullptr);
     // Strassen levels over a folded side.  One level: its rows, columns and contraction length even, and (the rule) the
     // half-size products still at least one whole round of 64 x 64 tiles on the device -- STRASSEN_MIN_TILES per product,
     // measured: profiles/fold_strassen_ab.txt.  Two levels: all three divisible by 4 and the same of the quarter-size
@@ -720,7 +753,8 @@ void Engine::env_update_fold(const zc* env_in, const zc* T, zc* env_out, int din
     zgemm(st_, g);
   }
   gram_mirror_lower(st_, Y_.p, dout, d);
-  gram_env_core(st_, Y_.p, reuse ? f.ws_reuse.p : f.ws.p, env_out, dout, mout, d);
+  gram_env_core(st_, Y_.p, reuse ? f.ws_reuse.p : f.ws.p, env_out, dout, mout, d,
+                !core_lists_ ? nullptr : reuse ? f.ws_reuse_list.p : f.ws_list.p);
   const zc alpha = make_double2(f.reuse_alpha.real(), f.reuse_alpha.imag());
   if (reuse && sp_side == 0) {
     strassen_side(str_l_.p, true, T, dout, Y_.p, (long)din * d / 2, dout / 2, (long)din * d / 2, false, reuse_level);
@@ -736,7 +770,7 @@ void Engine::env_update_fold(const zc* env_in, const zc* T, zc* env_out, int din
   for (size_t k = 0; !reuse && k < f.t0.size(); ++k) {
     // GL[(a,i)][(b,j)] (in X_), Z[(a,i)][r] = GL T[(b,j)][r] (in Y_: the Gram matrix has been consumed), block t0 += T^H Z
     fold_env_core(st_, env_in, f.wg.p + k * (size_t)d * min_ * d, X_.p, din, min_, d, (long)min_ * d, 1, d, (long)din * d,
-                  (long)d * din * d, 1, d);
+                  (long)d * din * d, 1, d, core_lists_ ? f.wg_list.p + k * f.wg_list_stride : nullptr);
     ZgemmDesc g = zgemm_desc(X_.p, T, Y_.p, din * d, dout, din * d);
     zgemm(st_, g);
     ZgemmDesc h = zgemm_desc(T, Y_.p, env_out + (size_t)f.t0[k] * dout, dout, dout, din * d);

@@ -50,12 +50,15 @@ void ident_deviation_multi(hipStream_t st, const zc* base, int nblk, long blk_st
 // An environment block env (n, m, n) with a reduced MPO core folded in (the folded variant of the edge form,
 // Engine::heff_apply_edge): G[i * gi + p * gp + j * gj + q * gq] = sum_c w[i * wi + j * wj + c * wm] * env[p][c][q],
 // i, j < d, m <= 64.  The caller's strides must address d * d * n * n distinct elements of G.
+// list: the device copy of the core's fold list for (w, d, m, wi, wj, wm) (core_lists.h), whose coefficients then reach the
+// products as scalar operands; null: the dense kernel, which reads w itself.  The same sums in the same order either way.
 void fold_env_core(hipStream_t st, const zc* env, const zc* w, zc* G, int n, int m, int d, long wi, long wj, long wm, long gi,
-                   long gp, long gj, long gq);
+                   long gp, long gj, long gq, const void* list = nullptr);
 // The Gram matrix G ((d n) x (d n), rows (i, p), columns (j, q)) of a site tensor contracted with a reduced core
 // (the structured environment update, Engine::env_update_fold): out[p][t][q] = sum_{i, j} ws[(i * d + j) * m + t] *
 // G[(i, p)][(j, q)], all m <= 64 blocks of the (n, m, n) block, which is overwritten.
-void gram_env_core(hipStream_t st, const zc* G, const zc* ws, zc* out, int n, int m, int d);
+// list: the device copy of the Gram list of ws (core_lists.h), or null for the dense kernels; the same bits either way.
+void gram_env_core(hipStream_t st, const zc* G, const zc* ws, zc* out, int n, int m, int d, const void* list = nullptr);
 // The lower block half of that Gram matrix from its upper one, in place: blocks (i, j), i > j, become the conjugate
 // transposes of the blocks (j, i) (n x n each); blocks i <= j are only read.  d <= 64.
 void gram_mirror_lower(hipStream_t st, zc* G, int n, int d);

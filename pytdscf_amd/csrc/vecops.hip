@@ -7,6 +7,7 @@
 // the kernels of one Krylov iteration (the reference syncs twice per iteration,
 // _integrator.py:553-554).
 #include "vecops.h"
+#include "core_lists.h"
 #include "krylov_dev.h"
 
 #include <algorithm>
@@ -945,13 +946,70 @@ __global__ __launch_bounds__(256) void k_fold_env_core(const zc* __restrict__ en
         if (j0 + u < d) G[i * gi + p * gp + (j0 + u) * gj + q * gq] = acc[u];
   }
 }
+// The same contraction with the core's coefficients taken from its fold list (core_lists.h: per item the bond states c with
+// a non-zero among the four coefficients, ascending, and the four coefficients).  The item and the entry index are
+// wave-uniform, so an entry arrives through scalar loads and its coefficients are the FMAs' scalar operands: per entry one
+// LDS read and the dense kernel's 16 FMAs, in its order -- the same bits.  An item without entries stores zeros.
+// (fold_list_entries: N consecutive entries of one item, fetched together, multiplied out one after the other)
+template <int N>
+__device__ __forceinline__ void fold_list_entries(const FoldEntry* __restrict__ ent, const zc* es, int lane, zc (&acc)[4]) {
+  zc e[N];
+#pragma unroll
+  for (int r = 0; r < N; ++r) e[r] = es[ent[r].c * 64 + lane];
+#pragma unroll
+  for (int r = 0; r < N; ++r)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const double fx = ent[r].f[2 * u], fy = ent[r].f[2 * u + 1];
+      acc[u].x = fma(-fy, e[r].y, fma(fx, e[r].x, acc[u].x));
+      acc[u].y = fma(fy, e[r].x, fma(fx, e[r].y, acc[u].y));
+    }
+}
+__global__ __launch_bounds__(256) void k_fold_env_core_list(const zc* __restrict__ env, const int* __restrict__ off,
+                                                            const FoldEntry* __restrict__ ent, zc* __restrict__ G, int n, int m,
+                                                            int d, long gi, long gp, long gj, long gq) {
+  extern __shared__ __attribute__((aligned(16))) char fold_raw[];
+  zc* es = reinterpret_cast<zc*>(fold_raw);
+  const int p = blockIdx.y, q0 = blockIdx.x * 64;
+  for (int e = threadIdx.x; e < m * 64; e += 256) {
+    const int c = e >> 6, q = q0 + (e & 63);
+    es[e] = q < n ? env[((long)p * m + c) * n + q] : make_double2(0.0, 0.0);
+  }
+  __syncthreads();
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int q = q0 + lane;
+  const int njb = (d + 3) / 4;
+  for (int item = wave; item < d * njb; item += 4) {
+    const int i = item / njb, j0 = (item % njb) * 4;
+    const int k1 = off[item + 1];
+    zc acc[4] = {};
+    int k = off[item];
+    // four entries at a time, then two, then one: the scalar loads and the LDS reads of a group are issued together and
+    // waited for once (an entry is a miss of the scalar cache more often than not: the list is streamed by every wave),
+    // the products then run entry by entry in the list's order
+    for (; k + 4 <= k1; k += 4) fold_list_entries<4>(ent + k, es, lane, acc);
+    if (k + 2 <= k1) { fold_list_entries<2>(ent + k, es, lane, acc); k += 2; }
+    if (k < k1) fold_list_entries<1>(ent + k, es, lane, acc);
+    if (q < n)
+      for (int u = 0; u < 4; ++u)
+        if (j0 + u < d) G[i * gi + p * gp + (j0 + u) * gj + q * gq] = acc[u];
+  }
+}
 // G[i * gi + p * gp + j * gj + q * gq] = sum_c w[i * wi + j * wj + c * wm] * env[p][c][q]   (env: n x m x n, i, j < d)
+// list: the core's fold list for these strides (build_fold_list), or null for the dense kernel
 void fold_env_core(hipStream_t st, const zc* env, const zc* w, zc* G, int n, int m, int d, long wi, long wj, long wm, long gi,
-                   long gp, long gj, long gq) {
+                   long gp, long gj, long gq, const void* list) {
   if (n < 1 || d < 1) return;
   if (m < 1 || m > 64 || n > 65535) throw ArgError("fold_env_core: MPO bond in [1, 64] and bond dimension <= 65535");
-  hipLaunchKernelGGL(k_fold_env_core, dim3((n + 63) / 64, n), dim3(256), (size_t)m * 64 * sizeof(zc), st, env, w, G, n, m, d,
-                     wi, wj, wm, gi, gp, gj, gq);
+  const dim3 grid((n + 63) / 64, n);
+  const size_t lds = (size_t)m * 64 * sizeof(zc);
+  if (list) {
+    const char* b = static_cast<const char*>(list);
+    hipLaunchKernelGGL(k_fold_env_core_list, grid, dim3(256), lds, st, env, reinterpret_cast<const int*>(b),
+                       reinterpret_cast<const FoldEntry*>(b + fold_list_head(d)), G, n, m, d, gi, gp, gj, gq);
+  } else {
+    hipLaunchKernelGGL(k_fold_env_core, grid, dim3(256), lds, st, env, w, G, n, m, d, wi, wj, wm, gi, gp, gj, gq);
+  }
   HIP_CHECK(hipGetLastError());
 }
 
@@ -999,6 +1057,68 @@ __global__ __launch_bounds__(256) void k_gram_env_core(const zc* __restrict__ G,
           if (f[u].x == 0.0 && f[u].y == 0.0) continue;
           acc[u0 + u].x = fma(-f[u].y, e.y, fma(f[u].x, e.x, acc[u0 + u].x));
           acc[u0 + u].y = fma(f[u].y, e.x, fma(f[u].x, e.y, acc[u0 + u].y));
+        }
+      }
+    }
+  }
+  if (q < n) {
+#pragma unroll
+    for (int u = 0; u < TU; ++u) {
+      const int t = wave + 4 * u;
+      if (t < m) out[((long)p * m + t) * n + q] = acc[u];
+    }
+  }
+}
+// The same contraction with the core's coefficients taken from its Gram list (core_lists.h: per (i, j, wave, chunk) a mask of
+// the non-zero coefficients and the UC coefficients, in the order t = v + 4 (u0 + u)).  The record's address is
+// wave-uniform: mask and coefficients arrive through scalar loads, a zero mask skips the LDS read, and bit u decides
+// statically unrolled whether acc[u0 + u] takes its product -- the dense kernel's FMAs in its order, the same bits.
+template <int TU>
+__global__ __launch_bounds__(256) void k_gram_env_core_list(const zc* __restrict__ G, const unsigned* __restrict__ mask,
+                                                            const zc* __restrict__ cf, zc* __restrict__ out, int n, int m, int d) {
+  extern __shared__ __attribute__((aligned(16))) char gram_raw[];
+  zc* es = reinterpret_cast<zc*>(gram_raw);
+  const int p = blockIdx.y, q0 = blockIdx.x * 64;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int q = q0 + lane;
+  const long ldg = (long)d * n;
+  constexpr int UC = TU < 8 ? TU : 8, NCH = TU / UC;
+  zc acc[TU] = {};
+  for (int i = 0; i < d; ++i) {
+    __syncthreads();  // the previous slab has been read by every wave
+    for (int e = threadIdx.x; e < d * 64; e += 256) {
+      const int j = e >> 6, qq = q0 + (e & 63);
+      es[e] = qq < n ? G[((long)i * n + p) * ldg + (long)j * n + qq] : make_double2(0.0, 0.0);
+    }
+    __syncthreads();
+    for (int j = 0; j < d; ++j) {
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch) {
+        const int rec = ((i * 4 + wave) * d + j) * NCH + ch;  // a wave walks its records front to back
+        const unsigned mk = mask[rec];
+        if (!mk) continue;
+        const zc e = es[j * 64 + lane];
+        // all UC coefficients in one batch of scalar loads, pinned above the first test by an empty statement that names
+        // them (it emits nothing): left alone, the compiler moves each load into the branch that uses it, where it is waited
+        // for -- UC latencies in a row
+        const zc* f = cf + (long)rec * UC;
+        double fxs[UC], fys[UC];
+#pragma unroll
+        for (int u = 0; u < UC; ++u) {
+          fxs[u] = f[u].x;
+          fys[u] = f[u].y;
+        }
+#pragma unroll
+        for (int u = 0; u < UC; ++u) asm volatile("" : : "s"(fxs[u]), "s"(fys[u]));
+#pragma unroll
+        for (int u = 0; u < UC; ++u) {
+          if (!((mk >> u) & 1u)) continue;
+          // (emits nothing; it keeps this a branch: as selects, the skipped products would all be formed and every
+          // accumulator pay two moves per coefficient on the same pipe as the products)
+          __builtin_amdgcn_sched_barrier(0);
+          const double fx = fxs[u], fy = fys[u];
+          acc[ch * UC + u].x = fma(-fy, e.y, fma(fx, e.x, acc[ch * UC + u].x));
+          acc[ch * UC + u].y = fma(fy, e.x, fma(fx, e.y, acc[ch * UC + u].y));
         }
       }
     }
@@ -1227,14 +1347,26 @@ void strassen_combine2(hipStream_t st, const zc* M, long qr, long qc, zc* out, l
 }
 
 // out[p][t][q] = sum_{i, j} ws[(i * d + j) * m + t] * G[(i, p)][(j, q)]   (G: (d n) x (d n) row-major; out: n x m x n)
-void gram_env_core(hipStream_t st, const zc* G, const zc* ws, zc* out, int n, int m, int d) {
-  if (n < 1 || d < 1) return;
-  if (m < 1 || m > 64 || n > 65535 || d > 64) throw ArgError("gram_env_core: MPO bond in [1, 64], d <= 64 and bond dimension <= 65535");
+// list: the core's Gram list for gram_list_tu(m) (build_gram_list), or null for the dense kernels
+template <int TU>
+static void gram_env_core_launch(hipStream_t st, const zc* G, const zc* ws, zc* out, int n, int m, int d, const void* list) {
   const dim3 grid((n + 63) / 64, n), block(256);
   const size_t lds = (size_t)d * 64 * sizeof(zc);
-  if (m <= 16) hipLaunchKernelGGL(k_gram_env_core<4>, grid, block, lds, st, G, ws, out, n, m, d);
-  else if (m <= 32) hipLaunchKernelGGL(k_gram_env_core<8>, grid, block, lds, st, G, ws, out, n, m, d);
-  else hipLaunchKernelGGL(k_gram_env_core<16>, grid, block, lds, st, G, ws, out, n, m, d);
+  if (list) {
+    const char* b = static_cast<const char*>(list);
+    hipLaunchKernelGGL(k_gram_env_core_list<TU>, grid, block, lds, st, G, reinterpret_cast<const unsigned*>(b),
+                       reinterpret_cast<const zc*>(b + gram_list_head(d, TU)), out, n, m, d);
+  } else {
+    hipLaunchKernelGGL(k_gram_env_core<TU>, grid, block, lds, st, G, ws, out, n, m, d);
+  }
+}
+void gram_env_core(hipStream_t st, const zc* G, const zc* ws, zc* out, int n, int m, int d, const void* list) {
+  if (n < 1 || d < 1) return;
+  if (m < 1 || m > 64 || n > 65535 || d > 64) throw ArgError("gram_env_core: MPO bond in [1, 64], d <= 64 and bond dimension <= 65535");
+  const int tu = gram_list_tu(m);
+  if (tu == 4) gram_env_core_launch<4>(st, G, ws, out, n, m, d, list);
+  else if (tu == 8) gram_env_core_launch<8>(st, G, ws, out, n, m, d, list);
+  else gram_env_core_launch<16>(st, G, ws, out, n, m, d, list);
   HIP_CHECK(hipGetLastError());
 }
 
