@@ -726,6 +726,30 @@ typedef struct mitdvp_zgemm_args {
 } mitdvp_zgemm_args;
 int mitdvp_zgemm_desc(int device, const mitdvp_zgemm_args* a, const double* A, size_t nA, const double* B, size_t nB,
                       double* C, size_t nC, const int* klist, size_t nklist);
+/* The same kernel with its REDUCING epilogue (the call each side of the edge form of an H_eff apply makes), one call:
+ *   C[offC + u*su + v*sv + i*si] (+)= sum_{x < xm, y < yn} W[offW + i*ldw + x*yn + y] * T[u*xm + x][v*yn + y],  i < di,
+ *   T = A * op(B)  (m x n, never stored),  u < m / xm,  v < n / yn;  acc = 1 adds to C, acc = 0 overwrites it.
+ * A (m x k, rows lda apart), B (transB = 0: k x n, 1: n x k; rows ldb apart), W and C are WHOLE buffers of nA, nB, nW,
+ * nC complex elements: all are copied to the device, the product runs once, all of C comes back.  The fragment-ordered
+ * copy of the core is built as the engine builds it whenever the shape runs the unguarded epilogue.
+ *   epi_b4 / epi_full: -1 = as the library decides, 0 = the 4 x 4 x 4 form / its unguarded variant off for this call
+ *   (1 is refused: a form cannot be forced on);  the timing bits of MITDVP_ZGEMM_TUNE are not honoured.
+ *   variant_out (may be NULL): the epilogue body the call ran, 1..13 (numbering: csrc/zgemm_reduce_args_check.h).
+ * Before any HIP call MITDVP_EINVAL is returned if the last element of A, B, W ((di-1)*ldw + xm*yn - 1) or C
+ * ((m/xm-1)*su + (n/yn-1)*sv + (di-1)*si) falls outside its buffer, a stride or offset is negative, m % xm or n % yn is
+ * non-zero, k < 1, the kernel does not serve (xm, yn, di), or epi_b4 / epi_full is 1.  m or n of 0: success, C unchanged. */
+typedef struct mitdvp_zgemm_reduce_args {
+  int m, n, k;                 /* m = nu * xm, n = nv * yn */
+  int transB;                  /* 0: NN (the L side's form), 1: NT (the R side's) */
+  long lda, ldb, offA, offB;
+  int xm, yn, di, acc;
+  long ldw, offW;              /* w[i * ldw + x * yn + y] */
+  long su, sv, si, offC;
+  int mode3m;                  /* -1 library default, 0 = 4M, 1 = 3M */
+  int epi_b4, epi_full;        /* -1 = as the library decides; 0 = off */
+} mitdvp_zgemm_reduce_args;
+int mitdvp_zgemm_reduce(int device, const mitdvp_zgemm_reduce_args* a, const double* A, size_t nA, const double* B, size_t nB,
+                        const double* W, size_t nW, double* C, size_t nC, int* variant_out);
 /* Complex-product form of the MFMA zgemm kernel for everything that follows:
  * 0 = "4M" (textbook, 4 real MFMA products), 1 = "3M" (Karatsuba, 3 products,
  * normwise stable); the library default is 1 unless MITDVP_ZGEMM=4m is set. */

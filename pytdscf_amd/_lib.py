@@ -103,6 +103,21 @@ class ZgemmArgs(C.Structure):
     ]
 
 
+class ZgemmReduceArgs(C.Structure):
+    """mitdvp_zgemm_reduce_args: the descriptor of one reducing product of mitdvp_zgemm_reduce"""
+
+    _fields_ = [
+        ("m", C.c_int), ("n", C.c_int), ("k", C.c_int),
+        ("transB", C.c_int),
+        ("lda", C.c_long), ("ldb", C.c_long), ("offA", C.c_long), ("offB", C.c_long),
+        ("xm", C.c_int), ("yn", C.c_int), ("di", C.c_int), ("acc", C.c_int),
+        ("ldw", C.c_long), ("offW", C.c_long),
+        ("su", C.c_long), ("sv", C.c_long), ("si", C.c_long), ("offC", C.c_long),
+        ("mode3m", C.c_int),
+        ("epi_b4", C.c_int), ("epi_full", C.c_int),
+    ]
+
+
 OBS_NORM, OBS_AUTOCORR, OBS_ENERGY, OBS_RDM = 1, 2, 4, 8
 CHANNEL_GATE, CHANNEL_JUMP = 1, 2
 MAX_JUMP = 16  # operators of one jump channel (BATCH_MAX_JUMP)
@@ -217,6 +232,7 @@ def load() -> C.CDLL:
         "mitdvp_expm_dense_counted": (i, [i, i, i, i, dp, i, dp, d, d, d, i, dp, ip, C.POINTER(Counters)]),
         "mitdvp_zgemm": (i, [i, i, i, i, i, i, i, i, dp, dp, dp, dp, dp, i, i, dp]),
         "mitdvp_zgemm_desc": (i, [i, C.POINTER(ZgemmArgs), dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, ip, C.c_size_t]),
+        "mitdvp_zgemm_reduce": (i, [i, C.POINTER(ZgemmReduceArgs), dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, ip]),
         "mitdvp_bench_heff": (i, [i, i, i, i, i, i, i, i, dp]),
         "mitdvp_heff_selfcheck": (i, [i, i, i, i, i, i, dp]),
         "mitdvp_set_gemm_mode": (i, [i]),

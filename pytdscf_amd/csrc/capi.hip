@@ -8,6 +8,7 @@
 #include "engine_internal.h"
 #include "engine_krylov.inc"
 #include "zgemm_args_check.h"
+#include "zgemm_reduce_args_check.h"
 
 namespace {
 thread_local std::string g_err;
@@ -774,6 +775,45 @@ int mitdvp_zgemm_desc(int device, const mitdvp_zgemm_args* a, const double* A, s
       zgemm(st, g);
       if (nC) to_host(st, C, dC.p(), nC);
       else HIP_CHECK(hipStreamSynchronize(st));
+    }
+    zgemm_release_stream(st);
+    HIP_CHECK(hipStreamDestroy(st));
+  });
+}
+
+// one reducing product (zgemm_reduce) on the caller's whole buffers, as a side of the edge apply issues it: the core also in
+// fragment order whenever the shape runs the unguarded epilogue; zgemm_reduce_args_check.h refuses, before any HIP call,
+// whatever would leave a buffer.  The timing bits of MITDVP_ZGEMM_TUNE are not honoured (tune = 0).
+int mitdvp_zgemm_reduce(int device, const mitdvp_zgemm_reduce_args* a, const double* A, size_t nA, const double* B, size_t nB,
+                        const double* W, size_t nW, double* C, size_t nC, int* variant_out) {
+  return guard(nullptr, [&] {
+    using namespace mitdvp;
+    if (const char* bad = zgemm_reduce_args_check(a, A, nA, B, nB, W, nW, C, nC)) throw ArgError(bad);
+    if (a->m == 0 || a->n == 0) {  // nothing to do: C stays as it is, no device is touched
+      if (variant_out) *variant_out = 0;
+      return;
+    }
+    HIP_CHECK(hipSetDevice(device));
+    hipStream_t st;
+    HIP_CHECK(hipStreamCreate(&st));
+    {
+      const int kp = a->xm * a->yn;
+      Dev dA(st, A, nA), dB(st, B, nB), dW(st, W, nW), dC(st, C, nC), dWf((size_t)a->di * kp);
+      const int b4 = a->epi_b4 != 0 && zgemm_reduce_b4_available(st) != 0;
+      // the engine's rule (MpoSite::EdgeCache::rebuild, heff_apply_edge): zgemm_reduce_full_ok decides, zgemm_reduce_pack_core packs
+      const bool wf = b4 && a->epi_full != 0 && zgemm_reduce_full_ok(st, a->xm, a->yn, a->di) &&
+                      zgemm_reduce_pack_core(st, dW.p() + a->offW, a->ldw, a->di, kp, dWf.p());
+      ZgemmDesc g = zgemm_desc(dA.p() + a->offA, dB.p() + a->offB, dC.p() + a->offC, a->m, a->n, a->k);
+      g.transB = a->transB;
+      g.lda = a->lda; g.ldb = a->ldb;
+      g.mode3m = a->mode3m;
+      g.tune = 0;
+      g.epi_w = dW.p() + a->offW; g.epi_ldw = a->ldw; g.epi_xm = a->xm; g.epi_yn = a->yn; g.epi_di = a->di;
+      g.epi_wf = wf ? dWf.p() : nullptr;
+      g.epi_su = a->su; g.epi_sv = a->sv; g.epi_si = a->si; g.epi_acc = a->acc;
+      zgemm_reduce(st, g, a->epi_b4, a->epi_full);
+      to_host(st, C, dC.p(), nC);
+      if (variant_out) *variant_out = zgemm_reduce_variant(a->xm, a->yn, a->di, b4, wf ? 1 : 0);
     }
     zgemm_release_stream(st);
     HIP_CHECK(hipStreamDestroy(st));

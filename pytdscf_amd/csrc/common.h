@@ -163,6 +163,9 @@ int zgemm_reduce_b4_available(hipStream_t st);
 bool zgemm_reduce_full_ok(hipStream_t st, int xm, int yn, int di);
 bool zgemm_reduce_pack_core(hipStream_t st, const zc* w, long ldw, int di, int kp, zc* wf);
 void zgemm_reduce(hipStream_t st, const ZgemmDesc& d);
+// the same for one call with the 4 x 4 x 4 form (b4) or its unguarded variant (full) switched off: -1 = as the process-wide
+// switches decide, 0 = off; nothing can be forced on (the test hook mitdvp_zgemm_reduce)
+void zgemm_reduce(hipStream_t st, const ZgemmDesc& d, int b4, int full);
 int zgemm_default_mode();
 void zgemm_set_default_mode(int m);
 double mfma_peak_probe(hipStream_t st);

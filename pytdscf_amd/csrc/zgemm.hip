@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "zgemm_reduce_args_check.h"
 
 #include <map>
 #include <mutex>
@@ -439,6 +440,7 @@ __global__ __launch_bounds__(256, (WM * WN <= 4 ? 2 : 1)) void zgemm_kernel(Zgem
     // four blocks of outputs: one block per wave over the whole contraction (no partials to exchange); fewer: the
     // contraction split over the waves
     const int npair_ = (BM / d.epi_xm) * (BN / d.epi_yn);
+    // (which body runs is restated on the host as zgemm_reduce_variant, zgemm_reduce_args_check.h: keep the two alike)
     if (d.epi_b4 && !(d.epi_di <= 4 && npair_ <= 64) && npair_ <= 8 && d.epi_di <= 32) {
       // few (u, v) pairs per tile (d M = 512: eight): 4 x 4 x 4 products in four independent blocks per instruction
       // instead of 16 x 16 x 4 products half of whose columns are padding.  (It stores the tile itself, after its first
@@ -1298,12 +1300,7 @@ static int zgemm_tune_default() {
 
 int zgemm_cd_mode(hipStream_t st);
 
-bool zgemm_reduce_ok(int xm, int yn, int di) {
-  if (xm < 1 || yn < 1 || di < 1 || xm > 64 || yn > 64 || di > 64) return false;
-  const int rb = (di + 15) / 16, cb = ((64 / xm) * (64 / yn) + 15) / 16;
-  // the block shapes reduce_epilogue is instantiated for (3 row blocks run as 4, 3 column blocks as 4)
-  return (cb == 1) || (cb == 2 && rb <= 2) || (cb <= 4 && rb == 1);
-}
+bool zgemm_reduce_ok(int xm, int yn, int di) { return zgemm_reduce_shape_ok(xm, yn, di); }
 
 // v_mfma_f64_4x4x4_4b_f64 with the lane maps reduce_epilogue_b4 assumes, against the products formed on the host (small
 // integers: exact).  Once per process; a mismatch only switches the 4 x 4 x 4 epilogue off (the 16 x 16 form stays).
@@ -1353,11 +1350,9 @@ __global__ __launch_bounds__(256) void k_pack_core(const zc* __restrict__ w, lon
 }
 // whether a reducing product of this shape runs the unguarded 4 x 4 x 4 epilogue (the condition of zgemm_kernel's EPI branch)
 bool zgemm_reduce_full_ok(hipStream_t st, int xm, int yn, int di) {
-  if (!zgemm_reduce_b4_available(st) || xm < 1 || yn < 1 || xm > 64 || yn > 64) return false;
+  if (!zgemm_reduce_b4_available(st)) return false;
   static const bool on = !(std::getenv("MITDVP_EPI_FULL") && std::getenv("MITDVP_EPI_FULL")[0] == '0');
-  const int kp = xm * yn, npair = (64 / xm) * (64 / yn);
-  return on && (di == 16 || di == 32) && npair == 8 && yn % 4 == 0 && kp % 128 == 0 && !(xm & (xm - 1)) && !(yn & (yn - 1)) &&
-         8 * (kp + 4) <= 2 * (64 * 17 + 16 * 64);
+  return on && zgemm_reduce_full_shape(xm, yn, di);  // (which body a shape runs altogether: zgemm_reduce_variant, same header)
 }
 bool zgemm_reduce_pack_core(hipStream_t st, const zc* w, long ldw, int di, int kp, zc* wf) {
   if (di % 16 || kp % 4 || di < 16 || !zgemm_reduce_b4_available(st)) return false;
@@ -1367,11 +1362,13 @@ bool zgemm_reduce_pack_core(hipStream_t st, const zc* w, long ldw, int di, int k
   return true;
 }
 
-void zgemm_reduce(hipStream_t st, const ZgemmDesc& d0) {
+void zgemm_reduce(hipStream_t st, const ZgemmDesc& d0) { zgemm_reduce(st, d0, -1, -1); }
+
+void zgemm_reduce(hipStream_t st, const ZgemmDesc& d0, int b4, int full) {
   ZgemmDesc d = d0;
-  d.epi_b4 = b4_layout_ok(st);
+  d.epi_b4 = b4 == 0 ? 0 : b4_layout_ok(st);
   static const int epi_full = [] { const char* e = std::getenv("MITDVP_EPI_FULL"); return (e && e[0] == '0') ? 0 : 1; }();
-  d.epi_full = epi_full;
+  d.epi_full = full == 0 ? 0 : epi_full;
   if (d.tune < 0) d.tune = zgemm_tune_default();
   if (d.M <= 0 || d.N <= 0) return;
   if (!zgemm_reduce_ok(d.epi_xm, d.epi_yn, d.epi_di) || !d.epi_w) throw ArgError("zgemm_reduce: shape outside the reducing epilogue's range");

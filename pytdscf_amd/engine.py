@@ -703,6 +703,34 @@ def zgemm_desc(args: dict, A, B, Cbuf, klist=None, device=0) -> np.ndarray:
     return out
 
 
+ZGEMM_REDUCE_DEFAULTS = dict(
+    m=0, n=0, k=0, transB=0, lda=0, ldb=0, offA=0, offB=0, xm=0, yn=0, di=0, acc=0, ldw=0, offW=0, su=0, sv=0, si=0, offC=0,
+    mode3m=-1, epi_b4=-1, epi_full=-1)
+
+
+def zgemm_reduce(args: dict, A, B, W, Cbuf, device=0):
+    """One product of the MFMA kernel with its reducing epilogue (``mitdvp_zgemm_reduce``), as a side of the edge form of
+    an H_eff apply issues it: ``args`` holds the fields of ``mitdvp_zgemm_reduce_args`` (missing ones as in
+    ``ZGEMM_REDUCE_DEFAULTS``); ``A``, ``B``, ``W``, ``Cbuf`` are whole flat buffers.  Returns ``(C_out, variant)``: the whole
+    C buffer after the product (``Cbuf`` is not modified) and the number, 1..13, of the epilogue body that ran.  A
+    descriptor that leaves a buffer, or that the kernel does not serve, raises ValueError before the GPU is touched."""
+    unknown = set(args) - set(ZGEMM_REDUCE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"zgemm_reduce: unknown descriptor fields {sorted(unknown)}")
+    a = _lib.ZgemmReduceArgs()
+    for name, val in dict(ZGEMM_REDUCE_DEFAULTS, **args).items():
+        setattr(a, name, int(val))
+    A, B, W = _c128(A).reshape(-1), _c128(B).reshape(-1), _c128(W).reshape(-1)
+    out = _c128(Cbuf).reshape(-1).copy()
+    variant = C.c_int(0)
+    _lib.check(
+        _lib.load().mitdvp_zgemm_reduce(
+            device, C.byref(a), _dp(A), A.size, _dp(B), B.size, _dp(W), W.size, _dp(out), out.size, C.byref(variant)
+        )
+    )
+    return out, variant.value
+
+
 def thin_to_full(site, gauge: str, delta_rank: int, device=0) -> np.ndarray:
     """``SiteCoef.thin_to_full``: widen an "A" (or "B") isometry by ``delta_rank``
     orthonormal columns (rows) of its orthogonal complement (capped at its dimension)."""
