@@ -334,6 +334,44 @@ int mitdvp_batch_cross_records(mitdvp_batch* b, const double* weights, double* v
 int mitdvp_batch_set_spectra(mitdvp_batch* b, const int* bonds, int nbonds);
 int mitdvp_batch_spectra(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[2]);
 int mitdvp_batch_spectra_records(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[3]);
+/* Sampled configurations of a batch (k_batch_sample: one workgroup per replica, ONE launch draws nshots configurations of
+ * every replica; k_batch_mean averages the frequencies on the device, replica after replica in index order).  A
+ * configuration is one basis index per site, drawn with probability |<j_0 .. j_{nsite-1}|psi>|^2 / <psi|psi>.  With the
+ * centre at site 0 and sites 1 .. nsite-1 right-canonical (the state mitdvp_batch_step leaves) shot t of replica r walks
+ * the chain once from left to right, on work buffers only: v = [1]; at site p, w[j][s] = sum_a v[a] C_p[a][j][s] and
+ * g_j = sum_s |w[j][s]|^2; the outcome is picked by the rule of the jump channels -- G = sum_j g_j in index order, the
+ * smallest j whose running sum exceeds u G, else the last j with g_j > 0 -- then v <- w[j][:] / sqrt(g_j) and
+ * prob <- prob g_j / G.  The uniform is counter-based, u = (key >> 11) 2^-53 with
+ * key = mix(mix(mix(mix(seed ^ trajectory_id) + step) + site) + shot): mix, trajectory_id and step are those of the jump
+ * channels (mitdvp_batch_set_seed; step counts the batch's completed time steps), seed is the request's own.  A shot
+ * therefore depends on (state, seed, id, step, shot) only: not on n, the replica's place in the batch, nshots or the
+ * compute unit.  G == 0 at a site gives that shot -1 from that site on and prob = 0; a replica that failed in the same
+ * call writes -1 everywhere and zeros.  The replicas are only read.  Per replica: configs[nshots][nsite] (int),
+ * prob[nshots] (the product of the conditionals), freq[F] with F = sum_p d_p, entry (p, j) = count / nshots of outcome j
+ * at site p; mean_freq[F] is the weighted sum of freq over the replicas.
+ *   mitdvp_batch_set_samples: registers the request; nshots = 0 removes it.  No launch, no wait.  MITDVP_EINVAL when
+ *       nshots is outside 0 .. 65536 or nshots * nsite exceeds 2^22.
+ *   mitdvp_batch_samples: the request on the current state: TWO launches (k_batch_sample, k_batch_mean), one host wait.
+ *       weights: n doubles or NULL (1 / n each); configs[n][nshots][nsite], prob[n][nshots], freq[n][F], mean_freq[F], each
+ *       may be NULL; counts (may be NULL) receives {n, nshots, nsite, F}; with all four NULL the call only returns the
+ *       counts.  MITDVP_EINVAL without a request or when a replica's centre is not at site 0.
+ *   While a request is set, every record of mitdvp_batch_run / _run_keys and every call of mitdvp_batch_observe /
+ *       _observe_keys records the request too: ONE more launch per record and ONE more k_batch_mean launch per call
+ *       (weights 1 / n), no further host wait; `what` may then be 0 with out pointing at a mitdvp_batch_out of NULLs: the
+ *       request alone is recorded, by 2 nsteps + records + 1 launches.  With no request set nothing changes: the same
+ *       launches, the same bits, the same refusals.
+ *   mitdvp_batch_samples_records: what the last such call recorded, the arrays of mitdvp_batch_samples with a leading
+ *       record axis; counts = {records, n, nshots, nsite, F}; each may be NULL.  weights NULL: the means under 1 / n,
+ *       formed by that call, no launch and no wait here; weights given (n doubles): ONE k_batch_mean launch over the
+ *       records, which are still on the device, and one host wait.  A new request, other shapes or no recording call
+ *       yet: records = 0.
+ * Every refusal is MITDVP_EINVAL with a message in mitdvp_last_error(NULL) that names the entry point and the limit, and
+ * leaves the request, the records and every engine as they were. */
+int mitdvp_batch_set_samples(mitdvp_batch* b, int nshots, unsigned long long seed);
+int mitdvp_batch_samples(mitdvp_batch* b, const double* weights, int* configs, double* prob, double* freq, double* mean_freq,
+                         size_t counts[4]);
+int mitdvp_batch_samples_records(mitdvp_batch* b, const double* weights, int* configs, double* prob, double* freq,
+                                 double* mean_freq, size_t counts[5]);
 /* propagate_along_sweep (_mps_cls.py:798-1014), one direction only. */
 int mitdvp_sweep(mitdvp_engine* h, double dt_au, int forward);
 /* The same half-sweep in parts: the next `nsites` local updates of the half-sweep in progress (one is started when none

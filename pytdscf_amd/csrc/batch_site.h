@@ -224,4 +224,34 @@ struct BatchSpecArgs {
 // gauge B.
 void batch_spectra_launch(hipStream_t st, const BatchSpecArgs& a, int nrep);
 
+// ---- sampled configurations (k_batch_sample) ----
+// A configuration is one basis index per site, drawn with probability |<j_0 .. j_{L-1}|psi>|^2 / <psi|psi>.  Shot t of a
+// replica walks the chain once, left to right: v = [1]; at site p, w[j][s] = sum_a v[a] C_p[a][j][s], g_j = sum_s
+// |w[j][s]|^2, the outcome j by the selection rule of the jump channels (bc_pick) on the uniform of (seed, trajectory id,
+// step, site, shot), v <- w[j][:] / sqrt(g_j), prob <- prob g_j / G.  G == 0 gives -1 from that site on and prob = 0.
+// Shots are processed BATCH_SAMPLE_CHUNK at a time; a shot's bits depend neither on the chunk it fell into nor on nshots.
+constexpr int BATCH_SAMPLE_CHUNK = 64;
+constexpr int BATCH_SAMPLE_MAX_SHOTS = 65536;     // shots of one request
+constexpr long BATCH_SAMPLE_MAX_CONFIG = 1L << 22;  // nshots * L, the int32 entries of one replica's configurations
+constexpr int BATCH_SAMPLE_LDS_D = 16;  // up to this physical dimension (that of the channels' operators) a chunk's weights live in LDS
+struct BatchSampleArgs {
+  int L, nshots;
+  const BatchShape* shp;    // [L], device
+  void* const* ptrs;        // the pointer table of BatchArgs (only its site tensors are read)
+  int ptr_stride;
+  const int* status;        // [B]: a replica whose word is set writes -1 and zeros
+  unsigned long long seed;  // the request's own seed
+  long long step;           // completed time steps of the batch since the seed was set (the jump channels' counter)
+  const unsigned long long* ids;  // [B] trajectory ids
+  zc* buf;                  // [B][buf_len]: V (chunk x widest bond), W (chunk x widest d dr), then a chunk's weights
+  size_t o_w, o_g, buf_len; // V at 0, W at o_w, the weights (doubles, chunk x widest d) at o_g; complex elements
+  int* configs;             // [B][nshots][L]
+  double* prob;             // [B][nshots]
+  double* freq;             // [B][F], F = sum d_p: entry (p, j) is count / nshots
+  long F;
+};
+// one launch: grid = nrep workgroups, the replicas are only read.  Precondition: centre at site 0, sites 1 .. L-1 in
+// gauge B.
+void batch_sample_launch(hipStream_t st, const BatchSampleArgs& a, int nrep);
+
 }  // namespace mitdvp

@@ -3,7 +3,8 @@
 // k_batch_channel, one-site gates and quantum-jump channels between the two half-sweeps of a time step, one launch;
 // k_batch_pair, the same walk with nearest-neighbour gates and jump channels: merge, apply, truncated re-split;
 // k_batch_cross / k_batch_snapshot, overlaps and one-site matrix elements between two replicas or their snapshots, one
-// workgroup per pair.)
+// workgroup per pair; k_batch_spectra, the Schmidt spectra of the requested bonds; k_batch_sample, configurations drawn
+// from every replica's state, one workgroup per replica.)
 //
 // At trajectory shapes (d = 2..4, D <= 32, M <= 16) a local problem is a few tens of kilobytes, so one workgroup can own
 // one replica completely: the replica index is blockIdx.x, nothing is exchanged between workgroups, and therefore there is
@@ -1684,7 +1685,150 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_spectra(BatchSpecArgs g) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Sampled configurations: k_batch_sample, ONE workgroup per replica, nshots configurations of every replica in one launch
+// (BatchSampleArgs in batch_site.h has the arithmetic).  The state is k_batch_observe's: centre at site 0, sites 1 .. L-1
+// right-canonical, so the weight of outcome j at site p given the outcomes left of it is |v C_p[:, j, :]|^2 with v the
+// normalised left boundary vector of the shot: one walk from left to right, no environment.  Shots go through the walk
+// BATCH_SAMPLE_CHUNK at a time; per site of a chunk:
+//   product    W (chunk x d dr) = V (chunk x dl) C_p (dl x d dr): ONE wg_gemm
+//   weights    g[t][j] = sum_s |W[t][j dr + s]|^2: (shot, outcome) q of a round of 64 belongs to lanes 8 (q % 64) ..
+//              8 (q % 64) + 7; lane l of them adds s = l, l + 8, .. in that order, then a three-level xor tree over the 8
+//   selection  thread t owns shot t of the chunk: G in index order, bc_pick on the shot's uniform, the int32 outcome and
+//              the running probability
+//   normalise  V[t][s] = W[t][j_t dr + s] / sqrt(g[t][j_t]), element e by thread e % 512
+// A row of the product takes its K terms in the order of wg_gemm whatever the other rows are, so a shot's bits depend on
+// (replica state, seed, id, step, shot) only: not on the chunk, nshots, B or the compute unit.  The frequencies are counted
+// at the end over the replica's finished configurations, (site, outcome) f by thread f % 512.
+// What is resident where: LDS holds the two operand tiles of wg_gemm, a chunk's weights while d <= BATCH_SAMPLE_LDS_D
+// (otherwise they go to the request's buffer), and per shot of the chunk the running probability, the outcome and
+// sqrt(g); V and W live in the request's own buffer [B][buf_len] (global memory, L2-resident), written and re-read by
+// this workgroup only between workgroup barriers.  The replicas are only read.  No atomics, nothing waits for another
+// workgroup, every loop is bounded by the shapes and nshots.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 110 VGPRs, 82 SGPRs, no vector
+// or scalar register spills, no private memory (wg_gemm is inlined: there is no call and no argument block), 26 368 bytes
+// of LDS; occupancy 4 waves per SIMD, i.e. two workgroups per compute unit.  The other batch kernels compile to what they
+// compiled to before.  DESIGN.md section 7.3.
+__device__ __forceinline__ double bsm_uniform(unsigned long long base, unsigned long long site, unsigned long long shot) {
+  // base = mix(mix(seed ^ trajectory) + step): key = mix(mix(base + site) + shot)
+  const unsigned long long key = bc_mix(bc_mix(base + site) + shot);
+  return (double)(key >> 11) * 0x1.0p-53;
+}
+
+__global__ __launch_bounds__(SS_THREADS) void k_batch_sample(BatchSampleArgs g) {
+  __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
+  __shared__ double s_g[BATCH_SAMPLE_CHUNK * BATCH_SAMPLE_LDS_D];
+  __shared__ double s_prob[BATCH_SAMPLE_CHUNK], s_nrm[BATCH_SAMPLE_CHUNK];
+  __shared__ int s_pick[BATCH_SAMPLE_CHUNK];
+  zc* tiles = s_tiles;
+
+  const int r = blockIdx.x, tid = threadIdx.x, L = g.L, nshots = g.nshots;
+  int* cfg = g.configs + (size_t)r * nshots * L;
+  double* prob = g.prob + (size_t)r * nshots;
+  double* freq = g.freq + (size_t)r * g.F;
+  if (g.status[r] != SS_OK) {  // a replica that failed: -1 everywhere and zeros
+    for (long e = tid; e < (long)nshots * L; e += SS_THREADS) cfg[e] = -1;
+    for (long e = tid; e < nshots; e += SS_THREADS) prob[e] = 0.0;
+    for (long e = tid; e < g.F; e += SS_THREADS) freq[e] = 0.0;
+    return;
+  }
+  const zc* const* site = reinterpret_cast<const zc* const*>(g.ptrs + (size_t)r * g.ptr_stride);
+  zc* V = g.buf + (size_t)r * g.buf_len;
+  zc* W = V + g.o_w;
+  double* gbuf = reinterpret_cast<double*>(V + g.o_g);
+  const unsigned long long base = bc_mix(bc_mix(g.seed ^ g.ids[r]) + (unsigned long long)g.step);
+  const int sub = tid & 7, grp = tid >> 3;
+
+  for (int c0 = 0; c0 < nshots; c0 += BATCH_SAMPLE_CHUNK) {
+    const int nc = min(BATCH_SAMPLE_CHUNK, nshots - c0);
+    if (tid < nc) {
+      V[tid] = make_double2(1.0, 0.0);
+      s_prob[tid] = 1.0;
+      s_pick[tid] = 0;
+    }
+    __syncthreads();
+    for (int p = 0; p < L; ++p) {
+      const BatchShape s = g.shp[p];
+      const int dl = s.dl, d = s.d, dr = s.dr, ddr = d * dr;
+      const zc* C = site[p];
+      wg_gemm<true, false>(nc, ddr, dl, tiles,
+                           [&](int m, int k) { return V[m * dl + k]; },
+                           [&](int k, int n) { return C[(long)k * ddr + n]; },
+                           [&](int m, int n, zc z) { W[m * ddr + n] = z; });
+      double* gw = d <= BATCH_SAMPLE_LDS_D ? s_g : gbuf;
+      const int total = nc * d;
+      for (int q0 = 0; q0 < total; q0 += SS_THREADS / 8) {
+        const int q = q0 + grp;
+        double acc = 0.0;
+        if (q < total) {
+          const int t = q / d, j = q - t * d;
+          const zc* row = W + t * ddr + j * dr;
+          for (int k = sub; k < dr; k += 8) {
+            const zc z = row[k];
+            acc = fma(z.x, z.x, acc); acc = fma(z.y, z.y, acc);
+          }
+        }
+        acc += __shfl_xor(acc, 4, 64);
+        acc += __shfl_xor(acc, 2, 64);
+        acc += __shfl_xor(acc, 1, 64);
+        if (q < total && sub == 0) gw[q] = acc;
+      }
+      __syncthreads();
+      if (tid < nc) {
+        int pick = -1;
+        double nrm = 1.0;
+        if (s_pick[tid] >= 0) {  // a shot that met G == 0 stays at -1
+          const double* w = gw + tid * d;
+          pick = bc_pick(w, d, bsm_uniform(base, (unsigned long long)p, (unsigned long long)(c0 + tid)));
+          if (pick >= 0) {
+            double G = 0.0;
+            for (int j = 0; j < d; ++j) G += w[j];
+            s_prob[tid] *= w[pick] / G;
+            nrm = sqrt(w[pick]);
+          } else {
+            s_prob[tid] = 0.0;
+          }
+        }
+        s_pick[tid] = pick;
+        s_nrm[tid] = nrm;
+        cfg[(size_t)(c0 + tid) * L + p] = pick;
+      }
+      __syncthreads();
+      for (int e = tid; e < nc * dr; e += SS_THREADS) {
+        const int t = e / dr, k = e - t * dr, pk = s_pick[t];
+        zc z = make_double2(0.0, 0.0);
+        if (pk >= 0) {
+          const zc w = W[t * ddr + pk * dr + k];
+          const double nr = s_nrm[t];
+          z = make_double2(w.x / nr, w.y / nr);
+        }
+        V[e] = z;
+      }
+      __syncthreads();
+    }
+    if (tid < nc) prob[c0 + tid] = s_prob[tid];
+    __syncthreads();
+  }
+  for (long f = tid; f < g.F; f += SS_THREADS) {
+    int p = 0;
+    long j = f;
+    while (j >= g.shp[p].d) { j -= g.shp[p].d; ++p; }  // f < F = sum d_p: p stays below L
+    long cnt = 0;
+    for (int t = 0; t < nshots; ++t) cnt += cfg[(size_t)t * L + p] == (int)j ? 1 : 0;
+    freq[f] = (double)cnt / (double)nshots;
+  }
+}
+
 }  // namespace
+
+void batch_sample_launch(hipStream_t st, const BatchSampleArgs& a, int nrep) {
+  if (nrep < 1 || a.L < 1) throw ArgError("batch: nothing to launch");
+  if (a.nshots < 1 || a.nshots > BATCH_SAMPLE_MAX_SHOTS || (long)a.nshots * a.L > BATCH_SAMPLE_MAX_CONFIG || !a.buf || !a.configs || !a.prob ||
+      !a.freq || !a.ids || a.F < a.L)
+    throw ArgError("batch: no configurations to sample");
+  hipLaunchKernelGGL(k_batch_sample, dim3(nrep), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
 
 void batch_spectra_launch(hipStream_t st, const BatchSpecArgs& a, int nrep) {
   if (nrep < 1 || a.L < 2) throw ArgError("batch: nothing to launch");

@@ -117,6 +117,26 @@ class Batch {
   // are still on the device, and one host wait.
   void spectra_records(const double* weights, double* values, double* mean, size_t* counts);
 
+  // ---- sampled configurations (k_batch_sample) ----
+  // The request is a number of shots and a seed of its own; a replica's record is configs [nshots][L] (int32), prob
+  // [nshots] and freq [F], F = sum d_p (batch_site.h).  Every refusal is an ArgError that names the entry point and the
+  // limit and leaves the request, the records and every engine as they were.
+  // set_samples: nshots = 0 removes the request.  Refused: nshots outside 0 .. BATCH_SAMPLE_MAX_SHOTS, nshots * L above
+  // BATCH_SAMPLE_MAX_CONFIG.  No launch, no wait.
+  void set_samples(int nshots, unsigned long long seed);
+  bool has_samples() const { return smp_nshots_ > 0; }
+  // samples: the request on the current state (centre at site 0): k_batch_sample and k_batch_mean, TWO launches, one host
+  // wait.  weights: B doubles or null (1 / B); configs [B][nshots][L], prob [B][nshots], freq [B][F] and mean_freq [F]
+  // may each be null; counts {B, nshots, L, F}; with all outputs null only the counts are returned.
+  void samples(const double* weights, int* configs, double* prob, double* freq, double* mean_freq, size_t* counts);
+  // While a request is set every record of run() records it too: ONE more launch per record (k_batch_sample behind the
+  // record's other launches) and ONE more k_batch_mean launch per call (weights 1 / B); values and means are copied with
+  // the rest, no further host wait.  samples_records returns what the last run() recorded, the arrays of samples() with a
+  // leading record axis, counts {records, B, nshots, L, F}; each may be null.  weights null: the means of the run, no
+  // launch and no wait; weights given (B doubles): ONE k_batch_mean launch over the records, which are still on the
+  // device, and one host wait.
+  void samples_records(const double* weights, int* configs, double* prob, double* freq, double* mean_freq, size_t* counts);
+
   std::string status_message(int code) const;
   int size() const { return (int)eng_.size(); }
   int device() const { return device_; }
@@ -229,6 +249,26 @@ class Batch {
   void launch_spectra(long record);
   void spectra_weights(const double* weights);
   void spectra_failed(const char* entry) const;  // NotConverged when h_spec_fail_ names a replica
+
+  // samples request: shots and seed, the walk's buffers [B][buf_len], the records [nrec + 1] of configurations,
+  // probabilities and frequencies (the slot behind a run's records is samples()'s own) and the frequencies' means
+  int smp_nshots_ = 0;
+  unsigned long long smp_seed_ = 0;
+  zc* d_smp_buf_ = nullptr;
+  int* d_smp_cfg_ = nullptr;
+  double *d_smp_prob_ = nullptr, *d_smp_freq_ = nullptr, *d_smp_mean_ = nullptr, *d_smp_w_ = nullptr;
+  size_t smp_buf_elems_ = 0, smp_cfg_slots_ = 0, smp_prob_slots_ = 0, smp_freq_slots_ = 0, smp_mean_slots_ = 0;
+  long smp_nrec_ = 0;  // records of the last run() held in d_smp_* / h_smp_*
+  std::vector<int> h_smp_cfg_, h_smp_cfg_now_;
+  std::vector<double> h_smp_prob_, h_smp_freq_, h_smp_mean_, h_smp_w_, h_smp_now_;
+  long smp_F() const;           // sum of the physical dimensions
+  size_t smp_o_w() const;       // offsets of W and of the weights in a replica's part of d_smp_buf_, and its length
+  size_t smp_o_g() const;
+  size_t smp_buf_len() const;
+  void check_samples(const char* entry) const;  // the request against the shapes as they are now
+  void upload_samples(long nrec);               // room for nrec records and samples()'s slot
+  void launch_samples(long record, long long step);
+  void samples_weights(const double* weights);
 
   static std::vector<BatchShape> shapes_of(Engine& e);
   void check_channels() const;

@@ -90,6 +90,7 @@ void Batch::validate() {
     shapes_dirty_ = true;
     has_snap_ = false;  // a snapshot of other shapes names nothing any more
     spec_nrec_ = 0;     // nor do spectra records of other bond dimensions
+    smp_nrec_ = 0;      // nor sampled configurations of other shapes
   }
   plan_ = pl;
   batch_observe_plan(plan_, obs_plan_);
@@ -125,6 +126,7 @@ Batch::Batch(const std::vector<Engine*>& engines) : eng_(engines) {
   dev_alloc(d_spec_bonds_, (size_t)L_);
   dev_alloc(d_spec_fail_, n);
   dev_alloc(d_spec_w_, n);
+  dev_alloc(d_smp_w_, n);
   chan_.assign((size_t)L_, BatchChanSite{BCH_NONE, 0, 0});
   chan_ops_.assign((size_t)L_, {});
   pair_.assign((size_t)L_, BatchChanSite{BCH_NONE, 0, 0});
@@ -170,6 +172,12 @@ Batch::~Batch() {
   if (d_spec_buf_) (void)hipFree(d_spec_buf_);
   if (d_spec_rec_) (void)hipFree(d_spec_rec_);
   if (d_spec_mean_) (void)hipFree(d_spec_mean_);
+  if (d_smp_w_) (void)hipFree(d_smp_w_);
+  if (d_smp_buf_) (void)hipFree(d_smp_buf_);
+  if (d_smp_cfg_) (void)hipFree(d_smp_cfg_);
+  if (d_smp_prob_) (void)hipFree(d_smp_prob_);
+  if (d_smp_freq_) (void)hipFree(d_smp_freq_);
+  if (d_smp_mean_) (void)hipFree(d_smp_mean_);
   if (st_) (void)hipStreamDestroy(st_);
 }
 
@@ -618,10 +626,12 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   const int nkeys = dens.nkeys;
   const bool cx = has_cross();  // a cross request rides on every record; it may be all that is recorded
   const bool sp = has_spectra();  // so does a spectra request
-  const long nrdm = observe_sizes(sites, nsites, what, nkeys > 0 || cx || sp);
+  const bool sm = has_samples();  // and a samples request
+  const long nrdm = observe_sizes(sites, nsites, what, nkeys > 0 || cx || sp || sm);
   const long ndens = density_sizes(dens.legs, nkeys, nrdm);
   if (cx) check_cross("mitdvp_batch_run");
   if (sp) check_spectra("mitdvp_batch_run");
+  if (sm) check_samples("mitdvp_batch_run");
   const bool own = what != 0 || nkeys > 0;  // false: only the cross request is recorded, no record of the replicas
   const size_t n = eng_.size();
   const long nrec = nsteps / every + 1, dens_off = BOBS_HEAD + 2 * nrdm, rec_len = dens_off + 2 * ndens;
@@ -632,6 +642,7 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   if (chan) upload_channels();
   if (cx) upload_cross(nrec);
   if (sp) upload_spectra(nrec);
+  if (sm) upload_samples(nrec);
   // buffers of the records and their means (grow only), the site list and the weights
   const size_t need_rec = (size_t)nrec * n * rec_len, need_mean = (size_t)nrec * rec_len;
   const size_t need_legs = (size_t)nkeys * L_, need_tbuf = nkeys ? n * 2 * dens_plan_.need : 0;
@@ -671,19 +682,20 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
     h_legs_.assign(dens.legs, dens.legs + need_legs);
     HIP_CHECK(hipMemcpyAsync(d_legs_, h_legs_.data(), need_legs * sizeof(int), hipMemcpyHostToDevice, st_));
   }
-  auto record = [&](long q) {
+  auto record = [&](long q, long long step) {
     if (what) launch_observe(what, nsites, q, rec_len);
     if (nkeys) launch_density(nkeys, what == 0, q, rec_len, dens_off);
     if (cx) launch_cross(q);
     if (sp) launch_spectra(q);
+    if (sm) launch_samples(q, step);
   };
 
-  record(0);
+  record(0, steps_done_);
   for (int s = 0; s < nsteps; ++s) {
     launch(dt, true);
     if (chan) launch_channel(steps_done_ + s);
     launch(dt, false);
-    if ((s + 1) % every == 0) record((s + 1) / every);
+    if ((s + 1) % every == 0) record((s + 1) / every, steps_done_ + s + 1);
   }
   if (own) {
     batch_mean_launch(st_, d_rec_, d_w_, d_mean_, (int)n, rec_len, nrec);
@@ -719,12 +731,29 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
     HIP_CHECK(hipMemcpyAsync(h_spec_fail_.data(), d_spec_fail_, n * sizeof(int), hipMemcpyDeviceToHost, st_));
     spec_nrec_ = nrec;
   }
+  int smp_launches = 0;
+  if (sm) {  // and for the samples request: the frequencies' means under 1 / B
+    const size_t ns = (size_t)smp_nshots_, F = (size_t)smp_F();
+    samples_weights(nullptr);
+    batch_mean_launch(st_, d_smp_freq_, d_smp_w_, d_smp_mean_, (int)n, (long)F, nrec);
+    n_launch_ += 1;
+    smp_launches = (int)nrec + 1;
+    h_smp_cfg_.resize((size_t)nrec * n * ns * L_);
+    h_smp_prob_.resize((size_t)nrec * n * ns);
+    h_smp_freq_.resize((size_t)nrec * n * F);
+    h_smp_mean_.resize((size_t)nrec * F);
+    HIP_CHECK(hipMemcpyAsync(h_smp_cfg_.data(), d_smp_cfg_, h_smp_cfg_.size() * sizeof(int), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipMemcpyAsync(h_smp_prob_.data(), d_smp_prob_, h_smp_prob_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipMemcpyAsync(h_smp_freq_.data(), d_smp_freq_, h_smp_freq_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipMemcpyAsync(h_smp_mean_.data(), d_smp_mean_, h_smp_mean_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
+    smp_nrec_ = nrec;
+  }
   if (per_replica) {
     h_rec_.resize(need_rec);
     HIP_CHECK(hipMemcpyAsync(h_rec_.data(), d_rec_, need_rec * sizeof(double), hipMemcpyDeviceToHost, st_));
   }
   steps_done_ += nsteps;
-  const int other = (int)nrec * per_rec + (own ? 1 : 0) + cross_launches + spec_launches;
+  const int other = (int)nrec * per_rec + (own ? 1 : 0) + cross_launches + spec_launches + smp_launches;
   if (nsteps > 0) finish(false, nsteps * 2, statuses, other, chan ? nsteps : 0);
   else finish_observe(other, statuses);
 
@@ -1090,6 +1119,163 @@ void Batch::spectra_records(const double* weights, double* values, double* mean,
   batch_mean_launch(st_, d_spec_rec_, d_spec_w_, dst, (int)n, (long)len, (long)nrec);
   n_launch_ += 1;
   HIP_CHECK(hipMemcpyAsync(mean, dst, nrec * len * sizeof(double), hipMemcpyDeviceToHost, st_));
+  finish_observe(1, nullptr);
+}
+
+// ---- sampled configurations (k_batch_sample) ----
+long Batch::smp_F() const {
+  long F = 0;
+  for (const BatchShape& s : shp_) F += s.d;
+  return F;
+}
+
+size_t Batch::smp_o_w() const {
+  int b = 1;
+  for (const BatchShape& s : shp_) b = std::max(b, std::max(s.dl, s.dr));
+  return (size_t)BATCH_SAMPLE_CHUNK * b;
+}
+
+size_t Batch::smp_o_g() const {
+  long ddr = 1;
+  for (const BatchShape& s : shp_) ddr = std::max(ddr, (long)s.d * s.dr);
+  return smp_o_w() + (size_t)BATCH_SAMPLE_CHUNK * ddr;
+}
+
+size_t Batch::smp_buf_len() const {
+  int d = 1;
+  for (const BatchShape& s : shp_) d = std::max(d, s.d);
+  return smp_o_g() + ((size_t)BATCH_SAMPLE_CHUNK * d + 1) / 2;  // the weights are doubles: two to a complex element
+}
+
+void Batch::set_samples(int nshots, unsigned long long seed) {
+  const std::string at = "mitdvp_batch_set_samples: ";
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  if (nshots < 0 || nshots > BATCH_SAMPLE_MAX_SHOTS)
+    throw ArgError(at + "nshots = " + std::to_string(nshots) + " is outside 0 .. " + std::to_string(BATCH_SAMPLE_MAX_SHOTS) + " (0 removes the request)");
+  if ((long)nshots * L_ > BATCH_SAMPLE_MAX_CONFIG)
+    throw ArgError(at + std::to_string(nshots) + " shots of " + std::to_string(L_) + " sites are " + std::to_string((long)nshots * L_) +
+                   " outcomes per replica, a request takes at most " + std::to_string(BATCH_SAMPLE_MAX_CONFIG));
+  smp_nshots_ = nshots;
+  smp_seed_ = seed;
+  smp_nrec_ = 0;  // records of another request are not this one's
+}
+
+void Batch::check_samples(const char* entry) const {
+  const std::string at = std::string(entry) + ": ";
+  if (smp_nshots_ < 1) throw ArgError(at + "no samples request is set (mitdvp_batch_set_samples)");
+  if ((long)smp_nshots_ * L_ > BATCH_SAMPLE_MAX_CONFIG)
+    throw ArgError(at + "the samples request has " + std::to_string((long)smp_nshots_ * L_) + " outcomes per replica, a request takes at most " +
+                   std::to_string(BATCH_SAMPLE_MAX_CONFIG));
+}
+
+void Batch::upload_samples(long nrec) {
+  const size_t n = eng_.size(), ns = (size_t)smp_nshots_, F = (size_t)smp_F(), slots = (size_t)nrec + 1;
+  const size_t need_buf = n * smp_buf_len(), need_cfg = slots * n * ns * L_, need_prob = slots * n * ns, need_freq = slots * n * F,
+               need_mean = 2 * slots * F;
+  if (need_buf > smp_buf_elems_ || need_cfg > smp_cfg_slots_ || need_prob > smp_prob_slots_ || need_freq > smp_freq_slots_ ||
+      need_mean > smp_mean_slots_) {
+    HIP_CHECK(hipStreamSynchronize(st_));
+    auto grow = [&](auto*& p, size_t& have, size_t need) {
+      if (p && need <= have) return;
+      if (p) (void)hipFree(p);
+      p = nullptr;
+      dev_alloc(p, need);
+      have = need;
+    };
+    grow(d_smp_buf_, smp_buf_elems_, need_buf);
+    // these grow only with a new request, other shapes or in run(): no record of the last run is lost
+    grow(d_smp_cfg_, smp_cfg_slots_, need_cfg);
+    grow(d_smp_prob_, smp_prob_slots_, need_prob);
+    grow(d_smp_freq_, smp_freq_slots_, need_freq);
+    // the means of the records, the one of samples(), and the records' means under the weights of samples_records
+    grow(d_smp_mean_, smp_mean_slots_, need_mean);
+  }
+}
+
+void Batch::launch_samples(long record, long long step) {
+  const size_t n = eng_.size(), ns = (size_t)smp_nshots_;
+  BatchSampleArgs a{};
+  a.L = L_;
+  a.nshots = smp_nshots_;
+  a.shp = d_shp_;
+  a.ptrs = d_ptrs_;
+  a.ptr_stride = (int)ptrs_per_replica();
+  a.status = d_status_;
+  a.seed = smp_seed_;
+  a.step = step;
+  a.ids = d_ids_;
+  a.buf = d_smp_buf_;
+  a.o_w = smp_o_w();
+  a.o_g = smp_o_g();
+  a.buf_len = smp_buf_len();
+  a.F = smp_F();
+  a.configs = d_smp_cfg_ + (size_t)record * n * ns * L_;
+  a.prob = d_smp_prob_ + (size_t)record * n * ns;
+  a.freq = d_smp_freq_ + (size_t)record * n * (size_t)a.F;
+  batch_sample_launch(st_, a, (int)n);
+  n_launch_ += 1;
+}
+
+void Batch::samples_weights(const double* weights) {
+  const size_t n = eng_.size();
+  h_smp_w_.assign(n, 1.0 / (double)n);
+  if (weights) h_smp_w_.assign(weights, weights + n);
+  HIP_CHECK(hipMemcpyAsync(d_smp_w_, h_smp_w_.data(), n * sizeof(double), hipMemcpyHostToDevice, st_));
+}
+
+void Batch::samples(const double* weights, int* configs, double* prob, double* freq, double* mean_freq, size_t* counts) {
+  const std::string at = "mitdvp_batch_samples: ";
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  check_samples("mitdvp_batch_samples");
+  const size_t n = eng_.size(), ns = (size_t)smp_nshots_, F = (size_t)smp_F();
+  if (counts) { counts[0] = n; counts[1] = ns; counts[2] = (size_t)L_; counts[3] = F; }
+  if (!configs && !prob && !freq && !mean_freq) return;
+  for (size_t i = 0; i < n; ++i)
+    if (eng_[i]->center_ != 0)
+      throw ArgError(at + "replica " + std::to_string(i) + " has its centre at site " + std::to_string(eng_[i]->center_) +
+                     "; the walk starts from the centre at site 0 (the state a batch step leaves)");
+  prepare(true, false);
+  upload_samples(smp_nrec_);
+  const size_t slot = (size_t)smp_nrec_;  // behind the records of the last run, which stay
+  samples_weights(weights);
+  launch_samples((long)slot, steps_done_);
+  batch_mean_launch(st_, d_smp_freq_ + slot * n * F, d_smp_w_, d_smp_mean_ + slot * F, (int)n, (long)F, 1);
+  n_launch_ += 1;
+  h_smp_cfg_now_.resize(n * ns * L_);
+  h_smp_now_.resize(n * ns + n * F + F);
+  double* hp = h_smp_now_.data();
+  if (configs) HIP_CHECK(hipMemcpyAsync(h_smp_cfg_now_.data(), d_smp_cfg_ + slot * n * ns * L_, n * ns * L_ * sizeof(int), hipMemcpyDeviceToHost, st_));
+  if (prob) HIP_CHECK(hipMemcpyAsync(hp, d_smp_prob_ + slot * n * ns, n * ns * sizeof(double), hipMemcpyDeviceToHost, st_));
+  if (freq) HIP_CHECK(hipMemcpyAsync(hp + n * ns, d_smp_freq_ + slot * n * F, n * F * sizeof(double), hipMemcpyDeviceToHost, st_));
+  if (mean_freq) HIP_CHECK(hipMemcpyAsync(hp + n * ns + n * F, d_smp_mean_ + slot * F, F * sizeof(double), hipMemcpyDeviceToHost, st_));
+  finish_observe(2, nullptr);
+  if (configs) std::memcpy(configs, h_smp_cfg_now_.data(), n * ns * L_ * sizeof(int));
+  if (prob) std::memcpy(prob, hp, n * ns * sizeof(double));
+  if (freq) std::memcpy(freq, hp + n * ns, n * F * sizeof(double));
+  if (mean_freq) std::memcpy(mean_freq, hp + n * ns + n * F, F * sizeof(double));
+}
+
+void Batch::samples_records(const double* weights, int* configs, double* prob, double* freq, double* mean_freq, size_t* counts) {
+  const size_t n = eng_.size(), nrec = (size_t)smp_nrec_, ns = (size_t)smp_nshots_, F = smp_nshots_ > 0 ? (size_t)smp_F() : 0;
+  if (counts) { counts[0] = nrec; counts[1] = n; counts[2] = ns; counts[3] = (size_t)L_; counts[4] = F; }
+  if (nrec == 0 || (!configs && !prob && !freq && !mean_freq)) return;
+  if (configs) std::memcpy(configs, h_smp_cfg_.data(), nrec * n * ns * L_ * sizeof(int));
+  if (prob) std::memcpy(prob, h_smp_prob_.data(), nrec * n * ns * sizeof(double));
+  if (freq) std::memcpy(freq, h_smp_freq_.data(), nrec * n * F * sizeof(double));
+  if (!mean_freq) return;
+  if (!weights) {
+    std::memcpy(mean_freq, h_smp_mean_.data(), nrec * F * sizeof(double));
+    return;
+  }
+  HIP_CHECK(hipSetDevice(device_));
+  samples_weights(weights);
+  // behind the slots of the records' own means and of samples(): the means of the run stay as they are
+  double* dst = d_smp_mean_ + (nrec + 1) * F;
+  batch_mean_launch(st_, d_smp_freq_, d_smp_w_, dst, (int)n, (long)F, (long)nrec);
+  n_launch_ += 1;
+  HIP_CHECK(hipMemcpyAsync(mean_freq, dst, nrec * F * sizeof(double), hipMemcpyDeviceToHost, st_));
   finish_observe(1, nullptr);
 }
 

@@ -885,6 +885,22 @@ def spectra_bonds(bonds, nsite: int) -> list[int]:
     return out
 
 
+def sample_request(nshots, seed=0) -> tuple[int, int]:
+    """``nshots`` and ``seed`` of a samples request as plain integers.  ``ValueError`` for anything that is not a whole
+    number or does not fit the library's ``int`` / 64-bit unsigned seed; the range of ``nshots`` is the library's to check
+    (``mitdvp_batch_set_samples``), whose message names the limit.  Pure Python."""
+    import numbers
+
+    for name, x in (("nshots", nshots), ("seed", seed)):
+        if isinstance(x, bool) or not isinstance(x, (numbers.Integral, np.integer)):
+            raise ValueError(f"samples request: {name} = {x!r} is not a whole number")
+    if not -2**31 <= int(nshots) < 2**31:
+        raise ValueError(f"samples request: nshots = {nshots!r} does not fit an int")
+    if not 0 <= int(seed) < 2**64:
+        raise ValueError(f"samples request: seed = {seed!r} is not a 64-bit unsigned number")
+    return int(nshots), int(seed)
+
+
 class TDVPBatch:
     """B independent trajectories (replicas) of one chain shape on ONE GPU, any B: one kernel launch per half-sweep for the
     whole batch (``mitdvp_batch_step`` / ``k_batch_sweep``: one workgroup owns one replica, the replica index is the
@@ -912,6 +928,7 @@ class TDVPBatch:
         self._seed = None
         self._cross = None
         self._spectra = None
+        self._samples = None
         self._lib = _lib.load()
         try:
             for _ in range(n_replicas):
@@ -937,6 +954,7 @@ class TDVPBatch:
         self._seed = None
         self._cross = None
         self._spectra = None
+        self._samples = None
         self._lib = _lib.load()
         return self
 
@@ -974,6 +992,8 @@ class TDVPBatch:
                     self._push_cross(self._cross)
                 if self._spectra is not None:
                     self._push_spectra(self._spectra)
+                if self._samples is not None:
+                    self._push_samples(*self._samples)
             except Exception:
                 self._drop()
                 raise
@@ -1269,6 +1289,74 @@ class TDVPBatch:
         _lib.check(self._lib.mitdvp_batch_spectra_records(self._b, None if w is None else _dp(w), _dp(vals), _dp(mean), cnt))
         return self._split_spectra(vals, mean, per_replica)
 
+    # ---- sampled configurations (mitdvp_batch_set_samples / _samples) ----
+    def _push_samples(self, nshots, seed):
+        _lib.check(self._lib.mitdvp_batch_set_samples(self._b, nshots, C.c_ulonglong(seed)))
+
+    def set_samples(self, nshots, seed=0):
+        """Registers the request that ``samples`` and recorded runs evaluate: ``nshots`` configurations of every replica,
+        drawn with the counter-based uniforms ``trajectories.sample_uniform(seed, trajectory_id, step, site, shot)``;
+        ``nshots = 0`` removes the request.  The library validates the range (at most 65 536 shots, ``nshots * L`` at most
+        2^22) and a refused request leaves the one before in place."""
+        nshots, seed = sample_request(nshots, seed)
+        self._handle()
+        self._push_samples(nshots, seed)
+        self._samples = (nshots, seed) if nshots else None
+
+    def _samples_weights(self, weights):
+        if self._samples is None:
+            raise ValueError("no samples request is set (set_samples)")
+        if weights is None:
+            return None
+        n = len(self.engines)
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+        if w.shape != (n,):
+            raise ValueError(f"samples weights must be {n} numbers, one per replica (got shape {w.shape})")
+        return w
+
+    def _split_samples(self, configs, prob, freq, mean, per_replica=True):
+        """the flat frequency axis cut by site: one (.., d_p) array per site"""
+        dims = [self.engines[0].get_site_shape(p)[1] for p in range(self.engines[0].nsite)]
+        cut = lambda flat: [np.ascontiguousarray(flat[..., at - d:at]) for d, at in zip(dims, np.cumsum(dims))]
+        res = {"mean_freq": cut(mean)}
+        if per_replica:
+            res.update(configs=configs, prob=prob, freq=cut(freq))
+        return res
+
+    def _samples_call(self, fn, w, nlead, per_replica):
+        """the size query, the arrays and the call of ``mitdvp_batch_samples`` (``nlead`` = 0) or ``_samples_records``
+        (``nlead`` = 1: a leading record axis, counts one entry longer)"""
+        ip = C.POINTER(C.c_int)
+        cnt = (C.c_size_t * (4 + nlead))()
+        _lib.check(fn(self._b, None, None, None, None, None, cnt))
+        shape = tuple(int(c) for c in cnt)
+        lead, (n, nshots, nsite, F) = shape[:nlead], shape[nlead:]
+        mean = np.zeros(lead + (F,), dtype=np.float64)
+        configs = prob = freq = None
+        if per_replica:
+            configs = np.full(lead + (n, nshots, nsite), -1, dtype=np.int32)
+            prob = np.zeros(lead + (n, nshots), dtype=np.float64)
+            freq = np.zeros(lead + (n, F), dtype=np.float64)
+        _lib.check(fn(self._b, None if w is None else _dp(w), None if configs is None else configs.ctypes.data_as(ip),
+                      None if prob is None else _dp(prob), None if freq is None else _dp(freq), _dp(mean), cnt))
+        return self._split_samples(configs, prob, freq, mean, per_replica)
+
+    def samples(self, weights=None, per_replica: bool = True):
+        """``nshots`` configurations of every replica's current state by ONE launch (``k_batch_sample``), the ensemble
+        means of their one-site frequencies by a second one (``mitdvp_batch_samples``); all replicas must have their
+        centre at site 0 and are only read.  Returns ``mean_freq``, a list of ``(d_p,)`` arrays -- the weighted sum over
+        the replicas of the fraction of shots that gave outcome ``j`` at site ``p`` -- and, with ``per_replica``,
+        ``configs`` ``(B, nshots, L)`` int32 (one basis index per site; -1 from the site on at which a zero state left no
+        weight), ``prob`` ``(B, nshots)`` (``|<config|psi>|^2 / <psi|psi>``) and ``freq``, a list of ``(B, d_p)`` arrays.
+        ``weights``: B numbers, default 1 / B each."""
+        w = self._samples_weights(weights)
+        self._handle()
+        return self._samples_call(self._lib.mitdvp_batch_samples, w, 0, per_replica)
+
+    def _samples_records(self, weights, per_replica=True):
+        w = self._samples_weights(weights)
+        return self._samples_call(self._lib.mitdvp_batch_samples_records, w, 1, per_replica)
+
     def launches(self) -> int:
         """kernel launches counted so far on replica 0, where the batch's launches are counted once"""
         return int(self.engines[0].counters()["n_launch"])
@@ -1299,7 +1387,9 @@ class TDVPBatch:
         request of ``set_spectra`` in the same way (``k_batch_spectra``, one more launch per record): the entries of
         ``spectra()`` with a leading record axis, averaged with ``spectra_weights`` (B numbers, default 1 / B each).  With
         ``norm=True`` the entry ``mean_norm2`` stays the observation's ``(nrec,)`` array, which every bond's sum of
-        weights equals."""
+        weights equals.  ``samples=True`` adds the request of ``set_samples`` (``k_batch_sample``, one more launch per
+        record; a record draws with the batch's step counter as it stands at that record): the entries of ``samples()``
+        with a leading record axis, ``mean_freq`` formed with ``samples_weights`` (B numbers, default 1 / B each)."""
         if observe is None:
             self._run(lambda b, st: self._lib.mitdvp_batch_step(b, float(dt_au), int(nsteps), st))
             return None
@@ -1332,12 +1422,15 @@ class TDVPBatch:
         return {k: [x[0] for x in v] for k, v in rec.items()}
 
     def _observed(self, dt_au, nsteps, every, sites=(), norm=True, autocorr=False, energy=False, weights=None, per_replica=True,
-                  keys=(), cross=False, cross_weights=None, spectra=False, spectra_weights=None):
+                  keys=(), cross=False, cross_weights=None, spectra=False, spectra_weights=None, samples=False,
+                  samples_weights=None):
         n = len(self.engines)
         if cross:
             self._cross_weights(cross_weights)  # no request, or weights of the wrong length: raised before any library call
         if spectra:
             self._spectra_weights(spectra_weights)
+        if samples:
+            self._samples_weights(samples_weights)
         nsite = self.engines[0].nsite
         legs = [density_key_legs(k, nsite) for k in keys]  # a malformed key raises here, before any library call
         sites = [int(p) for p in sites]
@@ -1401,6 +1494,8 @@ class TDVPBatch:
             if spectra:
                 for k, v in self._spectra_records(spectra_weights, per_replica).items():
                     self.records.setdefault(k, v)  # norm=True owns mean_norm2: every bond's W is that very number
+            if samples:
+                self.records.update(self._samples_records(samples_weights, per_replica))
         return self.records
 
     def _split(self, keep, sites, legs=()):

@@ -17,7 +17,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import units
-from .engine import TDVPBatch, density_key_legs, pair_key, spectra_bonds
+from .engine import TDVPBatch, density_key_legs, pair_key, sample_request, spectra_bonds
 from .mps import product_state_cores
 
 
@@ -39,6 +39,16 @@ def jump_uniform(seed: int, trajectory_id: int, step: int, site: int) -> float:
     ``key = mix(mix(mix(seed ^ trajectory_id) + step) + site)``, ``u = (key >> 11) * 2**-53`` on 64-bit unsigned integers."""
     seed, trajectory_id, step, site = (int(x) & _M64 for x in (seed, trajectory_id, step, site))
     key = _mix((_mix((_mix(seed ^ trajectory_id) + step) & _M64) + site) & _M64)
+    return (key >> 11) * 2.0 ** -53
+
+
+def sample_uniform(seed: int, trajectory_id: int, step: int, site: int, shot: int) -> float:
+    """The uniform in [0, 1) that ``k_batch_sample`` draws at ``site`` for shot ``shot`` of trajectory ``trajectory_id``
+    when the batch has completed ``step`` time steps since the seed was set: one more level of ``jump_uniform``'s counter
+    scheme, with the samples request's own ``seed`` --
+    ``key = mix(mix(mix(mix(seed ^ trajectory_id) + step) + site) + shot)``, ``u = (key >> 11) * 2**-53``."""
+    seed, trajectory_id, step, site, shot = (int(x) & _M64 for x in (seed, trajectory_id, step, site, shot))
+    key = _mix((_mix((_mix((_mix(seed ^ trajectory_id) + step) & _M64) + site) & _M64) + shot) & _M64)
     return (key >> 11) * 2.0 ** -53
 
 
@@ -194,7 +204,8 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
 
 def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, weights=None, integrator="lanczos",
                            conserve_norm=True, per_trajectory=False, thresh_sil=1.0e-09, device=0, jumps=None, seed=0,
-                           replicas_per_start=1, first_trajectory=0, densities=None, entanglement=None):
+                           replicas_per_start=1, first_trajectory=0, densities=None, entanglement=None, shots=None,
+                           shot_seed=0):
     """Propagate every Hartree product of ``starts`` under ``model`` and average their reduced densities.
 
     ``model``: a ``Model`` as the shell takes it (one electronic state, Hilbert space); its ``one_gate_to_apply``
@@ -231,9 +242,22 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
     weighted mean over the trajectories of each trajectory's von Neumann entropy (natural logarithm), which no averaged
     density gives -- and ``"min_weight"`` ``(nrec, nb)``, the mean of the smallest normalised Schmidt weight: the check
     that the bond dimension is wide enough.  With ``per_trajectory`` also ``"entropy_trajectories"`` ``(nrec, ntraj, nb)``.
-    The default ``None`` leaves the result as it is without the keyword."""
+    The default ``None`` leaves the result as it is without the keyword.
+
+    ``shots``: a number of configurations -- one basis index per site, drawn from every trajectory's state with
+    probability ``|<j_0 .. j_{L-1}|psi>|^2 / <psi|psi>`` -- sampled at the interval of ``reduced_density`` in the same run
+    (``k_batch_sample``, one more launch per record), trajectory i of the expanded list drawing
+    ``sample_uniform(shot_seed, first_trajectory + i, step, site, shot)``.  The result gains ``"configurations"`` of shape
+    ``(nrec, ntraj, shots, L)`` (int32): the joint distribution of the site occupations, diagonal correlators of any
+    order and full counting statistics are histograms of it; and ``"frequencies"``, a list of ``(nrec, d_p)`` arrays, the
+    weighted mean over the trajectories of the fraction of shots with outcome j at site p.  The default ``None`` leaves
+    the result as it is without the keyword."""
     if integrator not in ("lanczos", "arnoldi"):
         raise ValueError(f"Invalid integrator: {integrator}")
+    if shots is not None:
+        shots, shot_seed = sample_request(shots, shot_seed)
+        if shots < 1:
+            raise ValueError("shots must be >= 1")
     keys, every = reduced_density
     keys = [tuple(k) for k in keys]
     every = int(every)
@@ -290,7 +314,14 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
         if bonds:
             bt.set_spectra(bonds)
             req.update(spectra=True, spectra_weights=weights)
+        if shots is not None:
+            if not jump_table:  # the ids of the draws; with jumps set_jumps has registered these very ids
+                bt.set_jumps({}, seed=seed, trajectory_ids=range(first_trajectory, first_trajectory + nrep))
+            bt.set_samples(shots, shot_seed)
+            req.update(samples=True, samples_weights=weights)
         rec = bt.propagate(dt_au, nsteps, observe=req, every=every)
+        if shots is not None and not per_trajectory:  # the configurations are per trajectory by nature
+            rec = dict(rec, configs=bt._samples_records(None, True)["configs"])  # handed out from the host copy: no launch
     finally:
         bt.close()
     nrec = nsteps // every + 1
@@ -306,4 +337,6 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
         out["entropy"], out["min_weight"] = rec["mean_entropy"], rec["mean_min_weight"]
         if per_trajectory:
             out["entropy_trajectories"] = rec["entropy"]
+    if shots is not None:
+        out["configurations"], out["frequencies"] = rec["configs"], rec["mean_freq"]
     return out
