@@ -372,6 +372,42 @@ int mitdvp_batch_samples(mitdvp_batch* b, const double* weights, int* configs, d
                          size_t counts[4]);
 int mitdvp_batch_samples_records(mitdvp_batch* b, const double* weights, int* configs, double* prob, double* freq,
                                  double* mean_freq, size_t counts[5]);
+/* Expectation values of MPO observables of a batch (k_batch_expect: one workgroup per (replica, operator) pair, ONE
+ * launch walks every listed operator over every replica; k_batch_mean averages the records on the device, replica after
+ * replica in index order).  An operator is named by the op_id under which mitdvp_set_mpo_core gave its cores to every
+ * replica (and mitdvp_set_shift its scalar term): total dipole, site-energy sums, currents, bath energies, any sum of
+ * products over the chain.  With the centre at site 0 and sites 1 .. nsite-1 right-canonical (the state mitdvp_batch_step
+ * leaves) the value of (replica r, operator k) is what mitdvp_expect(engine r, k) returns, <psi | O_k | psi> + shift_k
+ * <psi | psi>, not normalised, by the same arithmetic: the right blocks of O_k are walked afresh from the right boundary
+ * to bond 1 on work buffers of the request, then one H_eff apply at site 0.  op_id 0 is allowed and gives the energy by a
+ * fresh walk, whether or not the sweep's right blocks are valid.  The replicas may carry different cores under one
+ * op_id, of equal shapes.  A replica's record holds (re, im) of every listed operator in list order.  A value depends
+ * on its replica and its operator only: not on n, nops, the operator's place in the list or the compute unit.  A
+ * replica that failed in the same call is zeros.  Replicas, operators and status words are only read.
+ *   mitdvp_batch_set_expect: registers the list op_ids[nops]; nops = 0 removes the request.  No launch, no wait.
+ *       MITDVP_EINVAL when nops is outside 0 .. 64, an op_id is negative or listed twice, a replica has no core of a
+ *       listed operator at some site, the core shapes differ between replicas or their physical dimension is not the
+ *       site's, an MPO bond exceeds 16, neighbouring cores do not fit, or the outer MPO bonds are not 1.
+ *   mitdvp_batch_expect: the request on the current state: TWO launches (k_batch_expect, k_batch_mean), one host wait.
+ *       weights: n doubles or NULL (1 / n each); values[n][nops][2], mean[nops][2]; counts (may be NULL) receives {n,
+ *       nops}; with values == NULL && mean == NULL the call only returns the counts.  MITDVP_EINVAL without a request,
+ *       when the cores the replicas carry now are refused as above, or when a replica's centre is not at site 0 (the
+ *       message names the replica).
+ *   While a request is set, every record of mitdvp_batch_run / _run_keys and every call of mitdvp_batch_observe /
+ *       _observe_keys records the request too: ONE more launch per record and ONE more k_batch_mean launch per call
+ *       (weights 1 / n), no further host wait; `what` may then be 0 with out pointing at a mitdvp_batch_out of NULLs: the
+ *       request alone is recorded, by 2 nsteps + records + 1 launches.  With no request set nothing changes: the same
+ *       launches, the same bits, the same refusals.
+ *   mitdvp_batch_expect_records: what the last such call recorded: values[records][n][nops][2], mean[records][nops][2],
+ *       counts = {records, n, nops}; each may be NULL.  weights NULL: the means under 1 / n, formed by that call, no
+ *       launch and no wait here; weights given (n doubles): ONE k_batch_mean launch over the records, which are still on
+ *       the device, and one host wait.  A new request, other shapes of the chain or of the cores, or no recording call
+ *       yet: records = 0.
+ * Every refusal is MITDVP_EINVAL with a message in mitdvp_last_error(NULL) that names the entry point, the operator, the
+ * site and the limit, and leaves the request, the records and every engine as they were. */
+int mitdvp_batch_set_expect(mitdvp_batch* b, const int* op_ids, int nops);
+int mitdvp_batch_expect(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[2]);
+int mitdvp_batch_expect_records(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[3]);
 /* propagate_along_sweep (_mps_cls.py:798-1014), one direction only. */
 int mitdvp_sweep(mitdvp_engine* h, double dt_au, int forward);
 /* The same half-sweep in parts: the next `nsites` local updates of the half-sweep in progress (one is started when none

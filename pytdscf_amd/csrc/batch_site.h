@@ -254,4 +254,37 @@ struct BatchSampleArgs {
 // gauge B.
 void batch_sample_launch(hipStream_t st, const BatchSampleArgs& a, int nrep);
 
+// ---- expectation values of MPO observables (k_batch_expect) ----
+// The request is a list of operator ids; every replica carries each of them as a whole MPO (Engine::set_mpo_core packs
+// w2l / w2el / w2er for every id).  The value of (replica r, operator k) is <psi_r | O_k | psi_r> + shift_k <psi_r | psi_r>,
+// not normalised, by the arithmetic of Engine::expect: a fresh walk of the right blocks of O_k from the right boundary to
+// bond 1 and one H_eff apply at site 0.  One replica's record, in doubles: (re, im) of every listed operator in list order.
+constexpr int BATCH_EXPECT_MAX_OPS = 64;
+// One (replica, operator) pair's carve of the request's buffer, offsets in complex elements: the two right blocks the
+// walk writes alternately (E0 at 0, E1 at o_e1: the largest dl * ml_k * dl of sites 1 .. L-1 each), X and Y (the largest
+// either bt_env or the site-0 bt_heff needs) and H C (the site-0 tensor).  The maxima run over all listed operators: every
+// pair has the same carve.
+struct BatchExpectPlan {
+  size_t o_e1 = 0, o_x = 0, o_y = 0, o_h = 0, total = 0;
+};
+// shp: [nops][L], the site shapes with operator k's MPO bonds; op_ids: [nops], the names of the operators.  false + a
+// message naming the operator, the site and the limit when an MPO bond is outside 1 .. BATCH_MAX_MPO, the bonds of
+// neighbouring cores differ or the outer ones are not 1.
+bool batch_expect_plan(const BatchShape* shp, const int* op_ids, int L, int nops, BatchExpectPlan& plan, std::string& why);
+struct BatchExpectArgs {
+  int L, nops;
+  const BatchShape* shp;    // [nops][L], device: operator k's ml / mr at every site
+  void* const* ptrs;        // the pointer table of BatchArgs (its site tensors, left block 0 and right block L are read)
+  int ptr_stride;
+  void* const* ops;         // [B][nops][3 L], device: w2l, w2el (not read), w2er of operator k of replica r
+  const zc* shift;          // [B][nops]
+  const int* status;        // [B]: a replica whose word is set does no work, its values are zeros
+  zc* buf;                  // [B][nops][plan.total]
+  BatchExpectPlan plan;
+  double* rec;              // [B][2 nops]: this observation's records
+};
+// one launch: grid = nrep * nops workgroups, workgroup r * nops + k; replicas and operators are only read.  Precondition:
+// centre at site 0, sites 1 .. L-1 in gauge B.
+void batch_expect_launch(hipStream_t st, const BatchExpectArgs& a, int nrep);
+
 }  // namespace mitdvp

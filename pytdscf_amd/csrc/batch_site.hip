@@ -4,7 +4,8 @@
 // k_batch_pair, the same walk with nearest-neighbour gates and jump channels: merge, apply, truncated re-split;
 // k_batch_cross / k_batch_snapshot, overlaps and one-site matrix elements between two replicas or their snapshots, one
 // workgroup per pair; k_batch_spectra, the Schmidt spectra of the requested bonds; k_batch_sample, configurations drawn
-// from every replica's state, one workgroup per replica.)
+// from every replica's state, one workgroup per replica; k_batch_expect, expectation values of MPO observables, one
+// workgroup per replica and operator.)
 //
 // At trajectory shapes (d = 2..4, D <= 32, M <= 16) a local problem is a few tens of kilobytes, so one workgroup can own
 // one replica completely: the replica index is blockIdx.x, nothing is exchanged between workgroups, and therefore there is
@@ -1819,7 +1820,136 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_sample(BatchSampleArgs g) 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Expectation values of MPO observables: k_batch_expect, ONE workgroup per (replica, operator) pair, workgroup index
+// r * nops + k, every listed operator of every replica in one launch (BatchExpectArgs in batch_site.h).  The state is
+// k_batch_observe's: centre at site 0, sites 1 .. L-1 right-canonical.  The walk is the arithmetic of Engine::expect for an
+// operator whose right blocks nobody has cached:
+//   E = the right boundary block (1 x 1 x 1, the engine's own)
+//   p = L-1 .. 1:  E <- bt_env(E, site p in its mirror-image strides, w2er of operator k at p), the form k_batch_sweep
+//                  uses on its way back, with operator k's ml / mr; written alternately into the pair's two blocks
+//   H = bt_heff(left block 0, w2l of operator k at site 0, E, C_0)
+//   value = <C_0 | H> + shift_k <C_0 | C_0>, not normalised: the three sums split over the 512 threads in one fixed order
+//           and finished by wg_reduce, as the energy of k_batch_observe
+// L = 1 skips the walk.  What is resident where: LDS holds the two operand tiles of wg_gemm and the reduction partials
+// (17 472 bytes); the two blocks, X, Y and H C live in the pair's carve of the request's own buffer [B][nops][carve]
+// (global memory, L2-resident), written and re-read by this workgroup only between workgroup barriers.  Replicas, operators
+// and status words are only read.  Every element has one owner thread and every sum one order: a value depends on its
+// replica and its operator only, not on B, nops, the operator's place in the list or the compute unit.  No atomics, nothing
+// waits for another workgroup, every loop is bounded by the shapes.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 200 VGPRs -- those of the
+// non-inlined product functions bt_env / bt_heff it shares with k_batch_sweep and k_batch_observe -- 105 SGPRs, no vector or
+// scalar register spills, 32 bytes of private memory per lane (the shape block bt_heff takes by reference, none of it
+// inside a product loop), 17 472 bytes of LDS; occupancy 2 waves per SIMD, i.e. one workgroup per compute unit.  The other
+// batch kernels compile to what they compiled to before.  DESIGN.md section 7.3.
+__global__ __launch_bounds__(SS_THREADS) void k_batch_expect(BatchExpectArgs g) {
+  __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
+  __shared__ double s_d[SS_WAVES * 8 + 8];
+  BtSh sh{};
+  sh.mats = s_tiles;
+  sh.wsh = s_d;
+  sh.red = s_d + SS_WAVES * 8;
+  zc* tiles = s_tiles;
+
+  const int wg = blockIdx.x, tid = threadIdx.x, L = g.L;
+  const int r = wg / g.nops, k = wg - r * g.nops;
+  double* rec = g.rec + (size_t)wg * 2;
+  if (g.status[r] != SS_OK) {  // a replica that failed: zeros
+    if (tid < 2) rec[tid] = 0.0;
+    return;
+  }
+  void* const* tab = g.ptrs + (size_t)r * g.ptr_stride;
+  const zc* const* site = reinterpret_cast<const zc* const*>(tab);
+  const zc* envL0 = reinterpret_cast<const zc*>(tab[L]);
+  const zc* cur = reinterpret_cast<const zc*>(tab[3 * L + 1]);  // right block L, the boundary
+  const zc* const* w2l = reinterpret_cast<const zc* const*>(g.ops + (size_t)wg * 3 * L);
+  const zc* const* w2er = w2l + 2 * L;
+  const BatchShape* shp = g.shp + (size_t)k * L;
+  zc* buf = g.buf + (size_t)wg * g.plan.total;
+  zc* Ea = buf;
+  zc* Eb = buf + g.plan.o_e1;
+  zc* X = buf + g.plan.o_x;
+  zc* Y = buf + g.plan.o_y;
+  zc* H = buf + g.plan.o_h;
+
+  for (int p = L - 1; p >= 1; --p) {
+    const BatchShape s = shp[p];
+    bt_env(cur, site[p], 1, s.dr, (long)s.d * s.dr, w2er[p], s.dr, s.mr, s.d, s.dl, s.ml, X, Y, Ea, tiles);
+    cur = Ea;
+    zc* t = Ea; Ea = Eb; Eb = t;
+  }
+  const BatchShape s0 = shp[0];
+  const long N0 = (long)s0.dl * s0.d * s0.dr;
+  const zc* C = site[0];
+  bt_heff(s0, envL0, w2l[0], cur, C, 1.0, X, Y, H, tiles);
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (long e = tid; e < N0; e += SS_THREADS) {
+    const zc c = C[e], h = H[e];
+    acc[0] += c.x * h.x + c.y * h.y;  // conj(c) h
+    acc[1] += c.x * h.y - c.y * h.x;
+    acc[2] += c.x * c.x + c.y * c.y;
+  }
+  wg_reduce(acc, sh);
+  if (tid == 0) {
+    const zc sft = g.shift[wg];
+    const double n2 = sh.red[2];
+    rec[0] = sh.red[0] + sft.x * n2;
+    rec[1] = sh.red[1] + sft.y * n2;
+  }
+}
+
 }  // namespace
+
+bool batch_expect_plan(const BatchShape* shp, const int* op_ids, int L, int nops, BatchExpectPlan& plan, std::string& why) {
+  plan = BatchExpectPlan{};
+  size_t ne = 1, nx = 1, ny = 1, nh = 1;
+  for (int k = 0; k < nops; ++k) {
+    const BatchShape* s = shp + (size_t)k * L;
+    for (int p = 0; p < L; ++p) {
+      const std::string at = "operator " + std::to_string(op_ids[k]) + ", site " + std::to_string(p) + ": MPO bonds (" +
+                             std::to_string(s[p].ml) + ", " + std::to_string(s[p].mr) + "): ";
+      if (s[p].ml < 1 || s[p].mr < 1 || s[p].ml > BATCH_MAX_MPO || s[p].mr > BATCH_MAX_MPO) {
+        why = at + "the batched kernel takes MPO bonds of 1 to " + std::to_string(BATCH_MAX_MPO);
+        return false;
+      }
+      if (p + 1 < L && s[p].mr != s[p + 1].ml) {
+        why = at + "the core of site " + std::to_string(p + 1) + " has the left MPO bond " + std::to_string(s[p + 1].ml);
+        return false;
+      }
+      const size_t n = (size_t)s[p].dl * s[p].d * s[p].dr;
+      if (p == 0) {  // the H_eff apply: X (dl ml) x (d dr), Y dl x (d mr) x dr, H C
+        nx = std::max(nx, n * s[p].ml);
+        ny = std::max(ny, n * s[p].mr);
+        nh = std::max(nh, n);
+      } else {       // the update of the right block: X (d dl) x (mr dr), Y dl x (ml d) x dr, E (dl, ml, dl)
+        nx = std::max(nx, n * s[p].mr);
+        ny = std::max(ny, n * s[p].ml);
+        ne = std::max(ne, (size_t)s[p].dl * s[p].ml * s[p].dl);
+      }
+    }
+    if (s[0].ml != 1 || s[L - 1].mr != 1) {
+      why = "operator " + std::to_string(op_ids[k]) + ": the outer MPO bonds are (" + std::to_string(s[0].ml) + ", " +
+            std::to_string(s[L - 1].mr) + "), they must be 1";
+      return false;
+    }
+  }
+  size_t o = 0;
+  o += ne;
+  plan.o_e1 = o; o += ne;
+  plan.o_x = o; o += nx;
+  plan.o_y = o; o += ny;
+  plan.o_h = o; o += nh;
+  plan.total = (o + 15) / 16 * 16;
+  return true;
+}
+
+void batch_expect_launch(hipStream_t st, const BatchExpectArgs& a, int nrep) {
+  if (nrep < 1 || a.L < 1) throw ArgError("batch: nothing to launch");
+  if (a.nops < 1 || a.nops > BATCH_EXPECT_MAX_OPS || !a.shp || !a.ops || !a.shift || !a.buf || !a.rec || a.plan.total < 1)
+    throw ArgError("batch: no operator to take the expectation value of");
+  hipLaunchKernelGGL(k_batch_expect, dim3((unsigned)nrep * (unsigned)a.nops), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
 
 void batch_sample_launch(hipStream_t st, const BatchSampleArgs& a, int nrep) {
   if (nrep < 1 || a.L < 1) throw ArgError("batch: nothing to launch");

@@ -244,7 +244,8 @@ int mitdvp_batch_run_keys(mitdvp_batch* b, double dt_au, int nsteps, int every, 
       throw mitdvp::ArgError("batch: nsteps must be >= 0 and a multiple of every >= 1");
     if (nkeys < 0 || (nkeys > 0 && !remain_nleg)) throw mitdvp::ArgError("batch: bad list of density keys");
     HIP_CHECK(hipSetDevice(b->b->device()));
-    const long nrdm = b->b->observe_sizes(sites, nsites, what, nkeys > 0 || b->b->has_cross() || b->b->has_spectra() || b->b->has_samples());
+    const long nrdm = b->b->observe_sizes(sites, nsites, what, nkeys > 0 || b->b->has_cross() || b->b->has_spectra() || b->b->has_samples() ||
+                                                                         b->b->has_expect());
     const long ndens = b->b->density_sizes(remain_nleg, nkeys, nrdm);
     if (counts) {
       counts[0] = (size_t)(nsteps / every + 1); counts[1] = (size_t)b->b->size(); counts[2] = (size_t)nrdm; counts[3] = (size_t)ndens;
@@ -345,6 +346,18 @@ int mitdvp_batch_samples_records(mitdvp_batch* b, const double* weights, int* co
                                  size_t counts[5]) {
   if (!b || !b->b) { g_err = "mitdvp_batch_samples_records: null handle"; return MITDVP_EINVAL; }
   return guard(nullptr, [&] { b->b->samples_records(weights, configs, prob, freq, mean_freq, counts); });
+}
+int mitdvp_batch_set_expect(mitdvp_batch* b, const int* op_ids, int nops) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_set_expect: null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->set_expect(op_ids, nops); });
+}
+int mitdvp_batch_expect(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[2]) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_expect: null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->expect(weights, values, mean, counts); });
+}
+int mitdvp_batch_expect_records(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[3]) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_expect_records: null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->expect_records(weights, values, mean, counts); });
 }
 void mitdvp_batch_destroy(mitdvp_batch* b) { delete b; }
 int mitdvp_invalidate_env(mitdvp_engine* h) { ENG_CALL(h, h->e->invalidate_env()); }

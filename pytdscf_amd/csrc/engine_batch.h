@@ -137,6 +137,28 @@ class Batch {
   // device, and one host wait.
   void samples_records(const double* weights, int* configs, double* prob, double* freq, double* mean_freq, size_t* counts);
 
+  // ---- expectation values of MPO observables (k_batch_expect) ----
+  // The request is a list of operator ids that every replica carries at every site (Engine::set_mpo_core); a replica's
+  // record is 2 nops doubles, (re, im) of <psi | O_k | psi> + shift_k <psi | psi> in list order, not normalised.  Every
+  // refusal is an ArgError that names the entry point, the operator, the site and the limit and leaves the request, the
+  // records and every engine as they were.
+  // set_expect: nops = 0 removes the request.  Refused: nops outside 0 .. BATCH_EXPECT_MAX_OPS, a repeated or negative id,
+  // an operator that a replica does not carry at every site, core shapes that differ between replicas or whose physical
+  // dimension is not the site's, MPO bonds above BATCH_MAX_MPO, outer MPO bonds that are not 1.  No launch, no wait.
+  void set_expect(const int* op_ids, int nops);
+  bool has_expect() const { return !exp_ops_.empty(); }
+  // expect: the request on the current state (centre at site 0): k_batch_expect and k_batch_mean, TWO launches, one host
+  // wait.  weights: B doubles or null (1 / B); values [B][nops][2] and mean [nops][2] may each be null; counts {B, nops};
+  // with all outputs null only the counts are returned.
+  void expect(const double* weights, double* values, double* mean, size_t* counts);
+  // While a request is set every record of run() records it too: ONE more launch per record (k_batch_expect behind the
+  // record's other launches) and ONE more k_batch_mean launch per call (weights 1 / B); values and means are copied with
+  // the rest, no further host wait.  expect_records returns what the last run() recorded: values [records][B][nops][2],
+  // mean [records][nops][2], counts {records, B, nops}; each may be null.  weights null: the means of the run, no launch
+  // and no wait; weights given (B doubles): ONE k_batch_mean launch over the records, which are still on the device, and
+  // one host wait.
+  void expect_records(const double* weights, double* values, double* mean, size_t* counts);
+
   std::string status_message(int code) const;
   int size() const { return (int)eng_.size(); }
   int device() const { return device_; }
@@ -269,6 +291,31 @@ class Batch {
   void upload_samples(long nrec);               // room for nrec records and samples()'s slot
   void launch_samples(long record, long long step);
   void samples_weights(const double* weights);
+
+  // expect request: the operator ids, the shapes [nops][L] with each operator's MPO bonds and the carve they give, the
+  // device tables (operator blocks [B][nops][3 L], shapes, shifts [B][nops]; refreshed with the batch's own tables, since
+  // engines may be given new cores between calls), the walk's buffer [B][nops][carve], the records [nrec + 1][B][2 nops]
+  // (the slot behind a run's records is expect()'s own) and their means
+  std::vector<int> exp_ops_;
+  std::vector<BatchShape> exp_shp_;
+  BatchExpectPlan exp_plan_;
+  bool exp_shp_dirty_ = false;
+  void** d_exp_ptrs_ = nullptr;
+  BatchShape* d_exp_shp_ = nullptr;
+  zc *d_exp_shift_ = nullptr, *d_exp_buf_ = nullptr;
+  double *d_exp_rec_ = nullptr, *d_exp_mean_ = nullptr, *d_exp_w_ = nullptr;
+  size_t exp_ptrs_elems_ = 0, exp_shp_elems_ = 0, exp_shift_elems_ = 0, exp_buf_elems_ = 0, exp_rec_slots_ = 0,
+         exp_mean_slots_ = 0;  // the last two: doubles
+  long exp_nrec_ = 0;  // records of the last run() held in d_exp_rec_ / h_exp_rec_
+  std::vector<void*> h_exp_ptrs_;
+  std::vector<zc> h_exp_shift_;
+  std::vector<double> h_exp_rec_, h_exp_mean_, h_exp_w_, h_exp_now_;
+  // the shapes of the listed operators on the engines as they are now; ArgError naming the entry point otherwise
+  void expect_shapes(const char* entry, const int* op_ids, int nops, std::vector<BatchShape>& shp, BatchExpectPlan& plan) const;
+  void check_expect(const char* entry);  // the request against the engines as they are now; new shapes drop the records
+  void upload_expect(long nrec);         // the device tables, room for nrec records and expect()'s slot
+  void launch_expect(long record);
+  void expect_weights(const double* weights);
 
   static std::vector<BatchShape> shapes_of(Engine& e);
   void check_channels() const;

@@ -91,6 +91,7 @@ void Batch::validate() {
     has_snap_ = false;  // a snapshot of other shapes names nothing any more
     spec_nrec_ = 0;     // nor do spectra records of other bond dimensions
     smp_nrec_ = 0;      // nor sampled configurations of other shapes
+    exp_nrec_ = 0;      // nor expectation values walked over other bonds
   }
   plan_ = pl;
   batch_observe_plan(plan_, obs_plan_);
@@ -127,6 +128,7 @@ Batch::Batch(const std::vector<Engine*>& engines) : eng_(engines) {
   dev_alloc(d_spec_fail_, n);
   dev_alloc(d_spec_w_, n);
   dev_alloc(d_smp_w_, n);
+  dev_alloc(d_exp_w_, n);
   chan_.assign((size_t)L_, BatchChanSite{BCH_NONE, 0, 0});
   chan_ops_.assign((size_t)L_, {});
   pair_.assign((size_t)L_, BatchChanSite{BCH_NONE, 0, 0});
@@ -178,6 +180,13 @@ Batch::~Batch() {
   if (d_smp_prob_) (void)hipFree(d_smp_prob_);
   if (d_smp_freq_) (void)hipFree(d_smp_freq_);
   if (d_smp_mean_) (void)hipFree(d_smp_mean_);
+  if (d_exp_w_) (void)hipFree(d_exp_w_);
+  if (d_exp_ptrs_) (void)hipFree(d_exp_ptrs_);
+  if (d_exp_shp_) (void)hipFree(d_exp_shp_);
+  if (d_exp_shift_) (void)hipFree(d_exp_shift_);
+  if (d_exp_buf_) (void)hipFree(d_exp_buf_);
+  if (d_exp_rec_) (void)hipFree(d_exp_rec_);
+  if (d_exp_mean_) (void)hipFree(d_exp_mean_);
   if (st_) (void)hipStreamDestroy(st_);
 }
 
@@ -627,11 +636,13 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   const bool cx = has_cross();  // a cross request rides on every record; it may be all that is recorded
   const bool sp = has_spectra();  // so does a spectra request
   const bool sm = has_samples();  // and a samples request
-  const long nrdm = observe_sizes(sites, nsites, what, nkeys > 0 || cx || sp || sm);
+  const bool ex = has_expect();   // and an expect request
+  const long nrdm = observe_sizes(sites, nsites, what, nkeys > 0 || cx || sp || sm || ex);
   const long ndens = density_sizes(dens.legs, nkeys, nrdm);
   if (cx) check_cross("mitdvp_batch_run");
   if (sp) check_spectra("mitdvp_batch_run");
   if (sm) check_samples("mitdvp_batch_run");
+  if (ex) check_expect("mitdvp_batch_run");
   const bool own = what != 0 || nkeys > 0;  // false: only the cross request is recorded, no record of the replicas
   const size_t n = eng_.size();
   const long nrec = nsteps / every + 1, dens_off = BOBS_HEAD + 2 * nrdm, rec_len = dens_off + 2 * ndens;
@@ -643,6 +654,7 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   if (cx) upload_cross(nrec);
   if (sp) upload_spectra(nrec);
   if (sm) upload_samples(nrec);
+  if (ex) upload_expect(nrec);
   // buffers of the records and their means (grow only), the site list and the weights
   const size_t need_rec = (size_t)nrec * n * rec_len, need_mean = (size_t)nrec * rec_len;
   const size_t need_legs = (size_t)nkeys * L_, need_tbuf = nkeys ? n * 2 * dens_plan_.need : 0;
@@ -688,6 +700,7 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
     if (cx) launch_cross(q);
     if (sp) launch_spectra(q);
     if (sm) launch_samples(q, step);
+    if (ex) launch_expect(q);
   };
 
   record(0, steps_done_);
@@ -748,12 +761,25 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
     HIP_CHECK(hipMemcpyAsync(h_smp_mean_.data(), d_smp_mean_, h_smp_mean_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
     smp_nrec_ = nrec;
   }
+  int exp_launches = 0;
+  if (ex) {  // and for the expect request (weights 1 / B)
+    const size_t len = 2 * exp_ops_.size();
+    expect_weights(nullptr);
+    batch_mean_launch(st_, d_exp_rec_, d_exp_w_, d_exp_mean_, (int)n, (long)len, nrec);
+    n_launch_ += 1;
+    exp_launches = (int)nrec + 1;
+    h_exp_rec_.resize((size_t)nrec * n * len);
+    h_exp_mean_.resize((size_t)nrec * len);
+    HIP_CHECK(hipMemcpyAsync(h_exp_rec_.data(), d_exp_rec_, h_exp_rec_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipMemcpyAsync(h_exp_mean_.data(), d_exp_mean_, h_exp_mean_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
+    exp_nrec_ = nrec;
+  }
   if (per_replica) {
     h_rec_.resize(need_rec);
     HIP_CHECK(hipMemcpyAsync(h_rec_.data(), d_rec_, need_rec * sizeof(double), hipMemcpyDeviceToHost, st_));
   }
   steps_done_ += nsteps;
-  const int other = (int)nrec * per_rec + (own ? 1 : 0) + cross_launches + spec_launches + smp_launches;
+  const int other = (int)nrec * per_rec + (own ? 1 : 0) + cross_launches + spec_launches + smp_launches + exp_launches;
   if (nsteps > 0) finish(false, nsteps * 2, statuses, other, chan ? nsteps : 0);
   else finish_observe(other, statuses);
 
@@ -1276,6 +1302,193 @@ void Batch::samples_records(const double* weights, int* configs, double* prob, d
   batch_mean_launch(st_, d_smp_freq_, d_smp_w_, dst, (int)n, (long)F, (long)nrec);
   n_launch_ += 1;
   HIP_CHECK(hipMemcpyAsync(mean_freq, dst, nrec * F * sizeof(double), hipMemcpyDeviceToHost, st_));
+  finish_observe(1, nullptr);
+}
+
+// ---- expectation values of MPO observables (k_batch_expect) ----
+void Batch::expect_shapes(const char* entry, const int* op_ids, int nops, std::vector<BatchShape>& shp, BatchExpectPlan& plan) const {
+  const std::string at = std::string(entry) + ": ";
+  shp.assign((size_t)nops * L_, BatchShape{});
+  for (int k = 0; k < nops; ++k) {
+    const std::string op = "operator " + std::to_string(op_ids[k]) + " ";
+    for (size_t i = 0; i < eng_.size(); ++i) {
+      const Engine& e = *eng_[i];
+      auto it = e.ops_.find(op_ids[k]);
+      for (int p = 0; p < L_; ++p) {
+        if (it == e.ops_.end() || !it->second.sites[p].set)
+          throw ArgError(at + op + "has no core at site " + std::to_string(p) + " of replica " + std::to_string(i) +
+                         " (every replica must carry every listed operator at all " + std::to_string(L_) + " sites)");
+        const MpoSite& w = it->second.sites[p];
+        if (w.d != shp_[p].d)
+          throw ArgError(at + op + "has physical dimension " + std::to_string(w.d) + " at site " + std::to_string(p) + " of replica " +
+                         std::to_string(i) + ", the site's is " + std::to_string(shp_[p].d));
+        BatchShape& s = shp[(size_t)k * L_ + p];
+        if (i == 0) s = BatchShape{shp_[p].dl, shp_[p].d, shp_[p].dr, w.ml, w.mr};
+        else if (w.ml != s.ml || w.mr != s.mr)
+          throw ArgError(at + op + "has MPO bonds (" + std::to_string(w.ml) + ", " + std::to_string(w.mr) + ") at site " + std::to_string(p) +
+                         " of replica " + std::to_string(i) + ", replica 0 has (" + std::to_string(s.ml) + ", " + std::to_string(s.mr) +
+                         "): the core shapes must be equal across the replicas");
+      }
+    }
+  }
+  std::string why;
+  if (!batch_expect_plan(shp.data(), op_ids, L_, nops, plan, why)) throw ArgError(at + why);
+}
+
+void Batch::set_expect(const int* op_ids, int nops) {
+  const std::string at = "mitdvp_batch_set_expect: ";
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  if (nops < 0 || nops > BATCH_EXPECT_MAX_OPS || (nops > 0 && !op_ids))
+    throw ArgError(at + "bad list of operators (" + std::to_string(nops) + " given; a request takes 0 to " + std::to_string(BATCH_EXPECT_MAX_OPS) +
+                   ", and the list must not be null)");
+  for (int k = 0; k < nops; ++k) {
+    if (op_ids[k] < 0) throw ArgError(at + "operator " + std::to_string(op_ids[k]) + " is negative (operator ids are >= 0)");
+    for (int j = 0; j < k; ++j)
+      if (op_ids[j] == op_ids[k]) throw ArgError(at + "operator " + std::to_string(op_ids[k]) + " is listed twice");
+  }
+  std::vector<BatchShape> shp;
+  BatchExpectPlan plan;
+  expect_shapes("mitdvp_batch_set_expect", op_ids, nops, shp, plan);
+  exp_ops_.assign(op_ids, op_ids + nops);
+  exp_shp_ = std::move(shp);
+  exp_plan_ = plan;
+  exp_shp_dirty_ = true;
+  h_exp_ptrs_.clear();
+  exp_nrec_ = 0;  // records of another request are not this one's
+}
+
+void Batch::check_expect(const char* entry) {
+  if (exp_ops_.empty()) throw ArgError(std::string(entry) + ": no expect request is set (mitdvp_batch_set_expect)");
+  std::vector<BatchShape> shp;
+  BatchExpectPlan plan;
+  expect_shapes(entry, exp_ops_.data(), (int)exp_ops_.size(), shp, plan);
+  if (shp.size() != exp_shp_.size() || std::memcmp(shp.data(), exp_shp_.data(), shp.size() * sizeof(BatchShape)) != 0) {
+    exp_shp_ = std::move(shp);
+    exp_shp_dirty_ = true;
+    exp_nrec_ = 0;  // the engines were given cores of other shapes: records walked over the old ones are dropped
+  }
+  exp_plan_ = plan;
+}
+
+void Batch::upload_expect(long nrec) {
+  const size_t n = eng_.size(), nops = exp_ops_.size(), len = 2 * nops, slots = (size_t)nrec + 1;
+  const size_t need_ptrs = n * nops * 3 * L_, need_shp = nops * L_, need_shift = n * nops;
+  const size_t need_buf = n * nops * exp_plan_.total, need_rec = slots * n * len, need_mean = 2 * slots * len;
+  if (need_ptrs > exp_ptrs_elems_ || need_shp > exp_shp_elems_ || need_shift > exp_shift_elems_ || need_buf > exp_buf_elems_ ||
+      need_rec > exp_rec_slots_ || need_mean > exp_mean_slots_) {
+    HIP_CHECK(hipStreamSynchronize(st_));
+    auto grow = [&](auto*& p, size_t& have, size_t need) {
+      if (p && need <= have) return;
+      if (p) (void)hipFree(p);
+      p = nullptr;
+      dev_alloc(p, need);
+      have = need;
+    };
+    if (need_ptrs > exp_ptrs_elems_) h_exp_ptrs_.clear();
+    if (need_shp > exp_shp_elems_) exp_shp_dirty_ = true;
+    grow(d_exp_ptrs_, exp_ptrs_elems_, need_ptrs);
+    grow(d_exp_shp_, exp_shp_elems_, need_shp);
+    grow(d_exp_shift_, exp_shift_elems_, need_shift);
+    grow(d_exp_buf_, exp_buf_elems_, need_buf);
+    // these two grow only with a new request or in run(): no record of the last run is lost
+    grow(d_exp_rec_, exp_rec_slots_, need_rec);
+    // the means of the records, the one of expect(), and the records' means under the weights of expect_records
+    grow(d_exp_mean_, exp_mean_slots_, need_mean);
+  }
+  // tables: [w2l L][w2el L][w2er L] per (replica, operator); the engines may have been given new cores since the last call
+  std::vector<void*> h(need_ptrs);
+  h_exp_shift_.resize(need_shift);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t k = 0; k < nops; ++k) {
+      const Operator& o = eng_[i]->ops_.find(exp_ops_[k])->second;
+      void** q = h.data() + (i * nops + k) * 3 * L_;
+      for (int p = 0; p < L_; ++p) {
+        q[p] = o.sites[p].w2l.p;
+        q[L_ + p] = o.sites[p].w2el.p;
+        q[2 * L_ + p] = o.sites[p].w2er.p;
+      }
+      h_exp_shift_[i * nops + k] = make_double2(o.shift.real(), o.shift.imag());
+    }
+  if (h != h_exp_ptrs_) {
+    h_exp_ptrs_ = h;
+    HIP_CHECK(hipMemcpyAsync(d_exp_ptrs_, h_exp_ptrs_.data(), need_ptrs * sizeof(void*), hipMemcpyHostToDevice, st_));
+  }
+  if (exp_shp_dirty_) {
+    HIP_CHECK(hipMemcpyAsync(d_exp_shp_, exp_shp_.data(), need_shp * sizeof(BatchShape), hipMemcpyHostToDevice, st_));
+    exp_shp_dirty_ = false;
+  }
+  HIP_CHECK(hipMemcpyAsync(d_exp_shift_, h_exp_shift_.data(), need_shift * sizeof(zc), hipMemcpyHostToDevice, st_));
+}
+
+void Batch::launch_expect(long record) {
+  BatchExpectArgs a{};
+  a.L = L_;
+  a.nops = (int)exp_ops_.size();
+  a.shp = d_exp_shp_;
+  a.ptrs = d_ptrs_;
+  a.ptr_stride = (int)ptrs_per_replica();
+  a.ops = d_exp_ptrs_;
+  a.shift = d_exp_shift_;
+  a.status = d_status_;
+  a.buf = d_exp_buf_;
+  a.plan = exp_plan_;
+  a.rec = d_exp_rec_ + (size_t)record * eng_.size() * 2 * exp_ops_.size();
+  batch_expect_launch(st_, a, (int)eng_.size());
+  n_launch_ += 1;
+}
+
+void Batch::expect_weights(const double* weights) {
+  const size_t n = eng_.size();
+  h_exp_w_.assign(n, 1.0 / (double)n);
+  if (weights) h_exp_w_.assign(weights, weights + n);
+  HIP_CHECK(hipMemcpyAsync(d_exp_w_, h_exp_w_.data(), n * sizeof(double), hipMemcpyHostToDevice, st_));
+}
+
+void Batch::expect(const double* weights, double* values, double* mean, size_t* counts) {
+  const std::string at = "mitdvp_batch_expect: ";
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  check_expect("mitdvp_batch_expect");
+  const size_t n = eng_.size(), len = 2 * exp_ops_.size();
+  if (counts) { counts[0] = n; counts[1] = exp_ops_.size(); }
+  if (!values && !mean) return;
+  for (size_t i = 0; i < n; ++i)
+    if (eng_[i]->center_ != 0)
+      throw ArgError(at + "replica " + std::to_string(i) + " has its centre at site " + std::to_string(eng_[i]->center_) +
+                     "; the walk ends at the centre at site 0 (the state a batch step leaves)");
+  prepare(true, false);
+  upload_expect(exp_nrec_);
+  const size_t slot = (size_t)exp_nrec_;  // behind the records of the last run, which stay
+  expect_weights(weights);
+  launch_expect((long)slot);
+  batch_mean_launch(st_, d_exp_rec_ + slot * n * len, d_exp_w_, d_exp_mean_ + slot * len, (int)n, (long)len, 1);
+  n_launch_ += 1;
+  h_exp_now_.resize(n * len + len);
+  HIP_CHECK(hipMemcpyAsync(h_exp_now_.data(), d_exp_rec_ + slot * n * len, n * len * sizeof(double), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipMemcpyAsync(h_exp_now_.data() + n * len, d_exp_mean_ + slot * len, len * sizeof(double), hipMemcpyDeviceToHost, st_));
+  finish_observe(2, nullptr);
+  if (values) std::memcpy(values, h_exp_now_.data(), n * len * sizeof(double));
+  if (mean) std::memcpy(mean, h_exp_now_.data() + n * len, len * sizeof(double));
+}
+
+void Batch::expect_records(const double* weights, double* values, double* mean, size_t* counts) {
+  const size_t n = eng_.size(), nrec = (size_t)exp_nrec_, len = 2 * exp_ops_.size();
+  if (counts) { counts[0] = nrec; counts[1] = n; counts[2] = exp_ops_.size(); }
+  if (nrec == 0 || (!values && !mean)) return;
+  if (values) std::memcpy(values, h_exp_rec_.data(), nrec * n * len * sizeof(double));
+  if (!mean) return;
+  if (!weights) {
+    std::memcpy(mean, h_exp_mean_.data(), nrec * len * sizeof(double));
+    return;
+  }
+  HIP_CHECK(hipSetDevice(device_));
+  expect_weights(weights);
+  // behind the slots of the records' own means and of expect(): the means of the run stay as they are
+  double* dst = d_exp_mean_ + (nrec + 1) * len;
+  batch_mean_launch(st_, d_exp_rec_, d_exp_w_, dst, (int)n, (long)len, (long)nrec);
+  n_launch_ += 1;
+  HIP_CHECK(hipMemcpyAsync(mean, dst, nrec * len * sizeof(double), hipMemcpyDeviceToHost, st_));
   finish_observe(1, nullptr);
 }
 

@@ -885,6 +885,34 @@ def spectra_bonds(bonds, nsite: int) -> list[int]:
     return out
 
 
+def expect_ops(op_ids) -> list[int]:
+    """The operator list of an expect request as plain integers: an iterable of whole numbers (a single number is a list
+    of one).  ``ValueError`` for anything that is not a whole number, is negative, does not fit the library's ``int`` or
+    is listed twice, and for more than 64 operators; whether every replica carries the operators, and their shapes, are the
+    library's to check (``mitdvp_batch_set_expect``), whose message names the operator, the site and the limit.  Pure
+    Python."""
+    import numbers
+
+    if isinstance(op_ids, numbers.Integral) and not isinstance(op_ids, bool):
+        op_ids = [op_ids]
+    try:
+        items = list(op_ids)
+    except TypeError:
+        raise ValueError(f"expect operators {op_ids!r}: a list of operator ids (the op_id of set_mpo)") from None
+    out = []
+    for k in items:
+        if isinstance(k, bool) or not isinstance(k, (numbers.Integral, np.integer)):
+            raise ValueError(f"expect operators {items!r}: operator {k!r} is not a whole number")
+        if not 0 <= int(k) < 2**31:
+            raise ValueError(f"expect operators {items!r}: operator {k!r} is negative or does not fit an int")
+        if int(k) in out:
+            raise ValueError(f"expect operators {items!r}: operator {k!r} is listed twice")
+        out.append(int(k))
+    if len(out) > 64:
+        raise ValueError(f"expect operators: {len(out)} operators, a request takes at most 64")
+    return out
+
+
 def sample_request(nshots, seed=0) -> tuple[int, int]:
     """``nshots`` and ``seed`` of a samples request as plain integers.  ``ValueError`` for anything that is not a whole
     number or does not fit the library's ``int`` / 64-bit unsigned seed; the range of ``nshots`` is the library's to check
@@ -929,6 +957,7 @@ class TDVPBatch:
         self._cross = None
         self._spectra = None
         self._samples = None
+        self._expect = None
         self._lib = _lib.load()
         try:
             for _ in range(n_replicas):
@@ -955,6 +984,7 @@ class TDVPBatch:
         self._cross = None
         self._spectra = None
         self._samples = None
+        self._expect = None
         self._lib = _lib.load()
         return self
 
@@ -994,6 +1024,8 @@ class TDVPBatch:
                     self._push_spectra(self._spectra)
                 if self._samples is not None:
                     self._push_samples(*self._samples)
+                if self._expect is not None:
+                    self._push_expect(self._expect)
             except Exception:
                 self._drop()
                 raise
@@ -1357,6 +1389,60 @@ class TDVPBatch:
         w = self._samples_weights(weights)
         return self._samples_call(self._lib.mitdvp_batch_samples_records, w, 1, per_replica)
 
+    # ---- expectation values of MPO observables (mitdvp_batch_set_expect / _expect) ----
+    def _push_expect(self, ops):
+        arr = (C.c_int * max(len(ops), 1))(*ops)
+        _lib.check(self._lib.mitdvp_batch_set_expect(self._b, arr, len(ops)))
+
+    def set_expect(self, op_ids):
+        """Registers the operators whose expectation values ``expect`` and recorded runs evaluate: a list of the
+        ``op_id`` under which ``set_mpo`` gave every replica the operator's cores (``TDVPEngine.set_mpo(..., shift=)`` its
+        scalar term); 0, the
+        Hamiltonian, is allowed.  An empty list removes the request.  The replicas must carry the operators already: the
+        library validates (every site, equal shapes across the replicas, MPO bonds of at most 16, outer bonds 1) and a
+        refused request leaves the one before in place."""
+        ops = expect_ops(op_ids)
+        self._handle()
+        self._push_expect(ops)
+        self._expect = ops if ops else None
+
+    def _expect_weights(self, weights):
+        if self._expect is None:
+            raise ValueError("no expect request is set (set_expect)")
+        if weights is None:
+            return None
+        n = len(self.engines)
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+        if w.shape != (n,):
+            raise ValueError(f"expect weights must be {n} numbers, one per replica (got shape {w.shape})")
+        return w
+
+    def expect(self, weights=None, per_replica: bool = True):
+        """``<psi | O_k | psi> + shift_k <psi | psi>`` (not normalised, as ``TDVPEngine.expectation``) of every operator of
+        ``set_expect`` for every replica by ONE launch (``k_batch_expect``, one workgroup per replica and operator), the
+        ensemble means by a second one (``mitdvp_batch_expect``); all replicas must have their centre at site 0 and are
+        only read.  Returns ``mean`` of shape ``(nops,)`` and, with ``per_replica``, ``values`` ``(B, nops)``, complex, in
+        the order of the request.  ``weights``: B numbers, default 1 / B each."""
+        w = self._expect_weights(weights)
+        b = self._handle()
+        cnt = (C.c_size_t * 2)()
+        _lib.check(self._lib.mitdvp_batch_expect(b, None, None, None, cnt))
+        n, nops = int(cnt[0]), int(cnt[1])
+        vals = np.zeros((n, nops), dtype=np.complex128)
+        mean = np.zeros(nops, dtype=np.complex128)
+        _lib.check(self._lib.mitdvp_batch_expect(b, None if w is None else _dp(w), _dp(vals), _dp(mean), cnt))
+        return {"values": vals, "mean": mean} if per_replica else {"mean": mean}
+
+    def _expect_records(self, weights, per_replica=True):
+        w = self._expect_weights(weights)
+        cnt = (C.c_size_t * 3)()
+        _lib.check(self._lib.mitdvp_batch_expect_records(self._b, None, None, None, cnt))
+        nrec, n, nops = (int(c) for c in cnt)
+        vals = np.zeros((nrec, n, nops), dtype=np.complex128)
+        mean = np.zeros((nrec, nops), dtype=np.complex128)
+        _lib.check(self._lib.mitdvp_batch_expect_records(self._b, None if w is None else _dp(w), _dp(vals), _dp(mean), cnt))
+        return {"expect": vals, "mean_expect": mean} if per_replica else {"mean_expect": mean}
+
     def launches(self) -> int:
         """kernel launches counted so far on replica 0, where the batch's launches are counted once"""
         return int(self.engines[0].counters()["n_launch"])
@@ -1389,7 +1475,10 @@ class TDVPBatch:
         ``norm=True`` the entry ``mean_norm2`` stays the observation's ``(nrec,)`` array, which every bond's sum of
         weights equals.  ``samples=True`` adds the request of ``set_samples`` (``k_batch_sample``, one more launch per
         record; a record draws with the batch's step counter as it stands at that record): the entries of ``samples()``
-        with a leading record axis, ``mean_freq`` formed with ``samples_weights`` (B numbers, default 1 / B each)."""
+        with a leading record axis, ``mean_freq`` formed with ``samples_weights`` (B numbers, default 1 / B each).
+        ``expect=True`` adds the request of ``set_expect`` (``k_batch_expect``, one more launch per record): ``expect`` of
+        shape ``(nrec, B, nops)`` and ``mean_expect`` ``(nrec, nops)``, averaged with ``expect_weights`` (B numbers,
+        default 1 / B each)."""
         if observe is None:
             self._run(lambda b, st: self._lib.mitdvp_batch_step(b, float(dt_au), int(nsteps), st))
             return None
@@ -1423,7 +1512,7 @@ class TDVPBatch:
 
     def _observed(self, dt_au, nsteps, every, sites=(), norm=True, autocorr=False, energy=False, weights=None, per_replica=True,
                   keys=(), cross=False, cross_weights=None, spectra=False, spectra_weights=None, samples=False,
-                  samples_weights=None):
+                  samples_weights=None, expect=False, expect_weights=None):
         n = len(self.engines)
         if cross:
             self._cross_weights(cross_weights)  # no request, or weights of the wrong length: raised before any library call
@@ -1431,6 +1520,8 @@ class TDVPBatch:
             self._spectra_weights(spectra_weights)
         if samples:
             self._samples_weights(samples_weights)
+        if expect:
+            self._expect_weights(expect_weights)
         nsite = self.engines[0].nsite
         legs = [density_key_legs(k, nsite) for k in keys]  # a malformed key raises here, before any library call
         sites = [int(p) for p in sites]
@@ -1496,6 +1587,8 @@ class TDVPBatch:
                     self.records.setdefault(k, v)  # norm=True owns mean_norm2: every bond's W is that very number
             if samples:
                 self.records.update(self._samples_records(samples_weights, per_replica))
+            if expect:
+                self.records.update(self._expect_records(expect_weights, per_replica))
         return self.records
 
     def _split(self, keep, sites, legs=()):

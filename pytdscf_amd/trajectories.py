@@ -202,10 +202,36 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
     return out
 
 
+def observable_names(model, observables) -> list[str]:
+    """The names of ``propagate_trajectories(observables=...)``: ``None`` or ``False`` is none, ``True`` every entry of
+    ``model.observables`` in its order, otherwise a list of names (a single string is a list of one).  ``ValueError``
+    naming a name the model does not have or one listed twice, and for more than 64 names (the request's limit).  Pure
+    Python: raised before any engine exists."""
+    if observables is None or observables is False:
+        return []
+    have = getattr(model, "observables", None) or {}
+    if observables is True:
+        names = list(have)
+        if not names:
+            raise ValueError("observables=True, but model.observables is empty")
+    else:
+        names = [observables] if isinstance(observables, str) else list(observables)
+        if not names:
+            raise ValueError("observables names no observable")
+    for i, name in enumerate(names):
+        if name not in have:
+            raise ValueError(f"observable {name!r} is not in model.observables (it has {sorted(have)})")
+        if name in names[:i]:
+            raise ValueError(f"observable {name!r} is listed twice")
+    if len(names) > 64:
+        raise ValueError(f"{len(names)} observables, one run takes at most 64")
+    return names
+
+
 def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, weights=None, integrator="lanczos",
                            conserve_norm=True, per_trajectory=False, thresh_sil=1.0e-09, device=0, jumps=None, seed=0,
                            replicas_per_start=1, first_trajectory=0, densities=None, entanglement=None, shots=None,
-                           shot_seed=0):
+                           shot_seed=0, observables=None):
     """Propagate every Hartree product of ``starts`` under ``model`` and average their reduced densities.
 
     ``model``: a ``Model`` as the shell takes it (one electronic state, Hilbert space); its ``one_gate_to_apply``
@@ -251,9 +277,19 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
     ``(nrec, ntraj, shots, L)`` (int32): the joint distribution of the site occupations, diagonal correlators of any
     order and full counting statistics are histograms of it; and ``"frequencies"``, a list of ``(nrec, d_p)`` arrays, the
     weighted mean over the trajectories of the fraction of shots with outcome j at site p.  The default ``None`` leaves
-    the result as it is without the keyword."""
+    the result as it is without the keyword.
+
+    ``observables``: ``True`` for every entry of ``model.observables``, or a list of their names.  Each is turned into an
+    MPO as ``Simulator.propagate(observables=True)`` prepares it (``op.as_mpo(model.dims)``, no scalar term), given to
+    every trajectory as operator 1, 2, ... and evaluated at the interval of ``reduced_density`` in the same run
+    (``k_batch_expect``, one workgroup per trajectory and observable, one more launch per record).  The result gains
+    ``"expectations"``, ``{name: (nrec,) complex}`` -- the weighted mean over the trajectories of ``<psi|O|psi>``, not
+    normalised, what ``expectations.dat`` holds for one state -- and, with ``per_trajectory``,
+    ``"expectation_trajectories"``, ``{name: (nrec, ntraj)}``.  A name the model does not have is a ``ValueError`` naming
+    it.  The default ``None`` leaves the result as it is without the keyword."""
     if integrator not in ("lanczos", "arnoldi"):
         raise ValueError(f"Invalid integrator: {integrator}")
+    obs_names = observable_names(model, observables)  # an unknown name raises here, before any engine exists
     if shots is not None:
         shots, shot_seed = sample_request(shots, shot_seed)
         if shots < 1:
@@ -295,10 +331,13 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
     nsteps = (maxstep - 1) // every * every
     D = model.m_aux_max if model.m_aux_max is not None else 10**9
     mpo = model.project_mpo(model.hamiltonian.as_mpo(model.dims))
+    obs_mpos = [model.observables[name].as_mpo(model.dims) for name in obs_names]
     bt = TDVPBatch(nrep, nsite, device=device, integrator=integrator, conserve_norm=conserve_norm, thresh=thresh_sil)
     try:
         for i, e in enumerate(bt.engines):
             e.set_mpo(mpo, 0, shift=model.hamiltonian.coupleJ[0][0])
+            for k, cores in enumerate(obs_mpos, start=1):
+                e.set_mpo(cores, k)
             if i % replicas_per_start == 0:  # a start is brought to canonical form once; its repeats get those very tensors
                 e.set_mps(product_state_cores(starts[i // replicas_per_start], D, space=model.space), canonicalize=True, scale=1.0)
                 canonical = e.get_mps()
@@ -319,6 +358,9 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
                 bt.set_jumps({}, seed=seed, trajectory_ids=range(first_trajectory, first_trajectory + nrep))
             bt.set_samples(shots, shot_seed)
             req.update(samples=True, samples_weights=weights)
+        if obs_names:
+            bt.set_expect(range(1, len(obs_names) + 1))
+            req.update(expect=True, expect_weights=weights)
         rec = bt.propagate(dt_au, nsteps, observe=req, every=every)
         if shots is not None and not per_trajectory:  # the configurations are per trajectory by nature
             rec = dict(rec, configs=bt._samples_records(None, True)["configs"])  # handed out from the host copy: no launch
@@ -339,4 +381,8 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
             out["entropy_trajectories"] = rec["entropy"]
     if shots is not None:
         out["configurations"], out["frequencies"] = rec["configs"], rec["mean_freq"]
+    if obs_names:
+        out["expectations"] = {name: np.ascontiguousarray(rec["mean_expect"][:, k]) for k, name in enumerate(obs_names)}
+        if per_trajectory:
+            out["expectation_trajectories"] = {name: np.ascontiguousarray(rec["expect"][:, :, k]) for k, name in enumerate(obs_names)}
     return out
