@@ -408,6 +408,41 @@ int mitdvp_batch_samples_records(mitdvp_batch* b, const double* weights, int* co
 int mitdvp_batch_set_expect(mitdvp_batch* b, const int* op_ids, int nops);
 int mitdvp_batch_expect(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[2]);
 int mitdvp_batch_expect_records(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[3]);
+/* MPO matrix elements between two states of a batch (k_batch_cross_mpo: one workgroup per entry, ONE launch forms every
+ * entry; k_batch_mean sums the values on the device, entry after entry in index order).  An entry is (bra, ket, op_id):
+ * the state indices are those of mitdvp_batch_set_cross (0 .. n-1 a replica, n + r the snapshot of replica r), op_id names
+ * an operator that every replica carries at every site (mitdvp_set_mpo_core, its scalar term from mitdvp_set_shift), as for
+ * mitdvp_batch_set_expect.  The cores and the scalar term used are those of the ket's owner, replica ket mod n.  The value
+ * is <psi_bra | O | psi_ket> + shift <psi_bra | psi_ket>, not normalised.  Two different states share no canonical form, so
+ * the walk runs over all nsite sites, left to right: a left block (bra bond, MPO bond, ket bond) starts as [1] and takes
+ * the three products of the forward environment update at every site, conj of the bra tensor in the first and the ket
+ * tensor in the third; with a non-zero scalar term the same workgroup then walks the plain overlap by the arithmetic of
+ * mitdvp_batch_cross and adds shift times it.  A value depends on its two states and its operator only: not on nentries,
+ * its place in the list, n or the compute unit.  An entry that names a replica which failed in the same call is zeros.
+ * Replicas, snapshots, operators and status words are only read.
+ *   mitdvp_batch_set_cross_mpo: registers nentries entries; nentries = 0 removes the request.  No launch, no wait.
+ *       MITDVP_EINVAL when an index is outside 0 .. 2n-1, a snapshot is named before any was taken, an op_id is negative,
+ *       a replica has no core of a named operator at some site, the core shapes differ between replicas, an MPO bond is
+ *       outside 1 .. 16, neighbouring cores do not fit, the outer MPO bonds are not 1, nentries exceeds 65536, or the
+ *       request's work buffer (nentries x carve x 16 bytes, carve = 2 max chi m chi + max n ml + max n mr complex numbers,
+ *       n = dl d dr) would exceed 2^32 bytes: the message names the figure and the largest nentries that fits.
+ *   mitdvp_batch_cross_mpo: the request on the current state: TWO launches (k_batch_cross_mpo, k_batch_mean), one host
+ *       wait.  The centre may be at site 0 or at site nsite-1.  weights: nentries doubles or NULL (1 / nentries each);
+ *       values[nentries][2], mean[2]; each may be NULL.  MITDVP_EINVAL without a request, or when the cores the replicas
+ *       carry now are refused as above.  Cores may be replaced between calls; cores of other shapes drop the records.
+ *   While a request is set, every record of mitdvp_batch_run / _run_keys and every call of mitdvp_batch_observe /
+ *       _observe_keys records the request too: ONE more launch per record and ONE more k_batch_mean launch per call
+ *       (weights 1 / nentries), no further host wait; the cross and expect requests may be set beside it.  With no request
+ *       set nothing changes: the same launches, the same bits, the same refusals.
+ *   mitdvp_batch_cross_mpo_records: what the last such call recorded: values[records][nentries][2], mean[records][2],
+ *       counts = {records, nentries}; each may be NULL.  weights NULL: the means under 1 / nentries, formed by that call,
+ *       no launch and no wait here; weights given (nentries doubles): ONE k_batch_mean launch over the records, which are
+ *       still on the device, and one host wait.  A new request, other shapes, or no recording call yet: records = 0.
+ * Every refusal is MITDVP_EINVAL with a message in mitdvp_last_error(NULL) that names the entry point, the entry, the
+ * operator, the site and the limit, and leaves the request, the records, the snapshot and every engine as they were. */
+int mitdvp_batch_set_cross_mpo(mitdvp_batch* b, int nentries, const int* bra, const int* ket, const int* op_id);
+int mitdvp_batch_cross_mpo(mitdvp_batch* b, const double* weights, double* values, double* mean);
+int mitdvp_batch_cross_mpo_records(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[2]);
 /* propagate_along_sweep (_mps_cls.py:798-1014), one direction only. */
 int mitdvp_sweep(mitdvp_engine* h, double dt_au, int forward);
 /* The same half-sweep in parts: the next `nsites` local updates of the half-sweep in progress (one is started when none

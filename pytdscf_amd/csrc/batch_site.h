@@ -3,16 +3,12 @@
 #pragma once
 #include <string>
 
+#include "batch_cross_mpo_plan.h"
+#include "batch_shape.h"
 #include "common.h"
 #include "small_site.h"
 
 namespace mitdvp {
-
-// shapes of one site of the chain (identical across the replicas of a batch)
-struct BatchShape {
-  int dl, d, dr;  // site tensor (dl, d, dr)
-  int ml, mr;     // MPO core (ml, d, d, mr)
-};
 
 // Qualifying envelope of k_batch_sweep, decided on the host (the twin of small_chain_plan for this kernel):
 //   * dl * d * dr <= BATCH_MAX_SITE elements per site tensor (the kernel keeps nothing of that size in LDS, so the
@@ -20,9 +16,8 @@ struct BatchShape {
 //   * MPO bonds ml, mr <= BATCH_MAX_MPO,
 //   * bonds dl, dr <= BATCH_MAX_BOND (the Householder scalars of a gauge move live in LDS),
 //   * dl * d >= dr and d * dr >= dl (a thin QR needs at least as many rows as columns; the sweep requires the same).
-constexpr long BATCH_MAX_SITE = 8192;
-constexpr int BATCH_MAX_MPO = 16;
-constexpr int BATCH_MAX_BOND = 64;
+// (the three constants BATCH_MAX_SITE = 8192, BATCH_MAX_MPO = 16, BATCH_MAX_BOND = 64 and BatchShape itself are in
+// batch_shape.h, which needs no HIP)
 
 struct BatchPlan {
   long max_site = 1;  // largest site tensor, elements
@@ -173,7 +168,7 @@ void batch_density_launch(hipStream_t st, const BatchDensArgs& a, int nrep);
 // ---- cross overlaps and one-site matrix elements between replicas (k_batch_cross, k_batch_snapshot) ----
 // A state index 0 .. B-1 names a replica, B .. 2B-1 the snapshot of replica (index - B): the copy of all its site tensors
 // that the last batch_snapshot_launch left in the batch's snapshot buffer, [B][sum of site sizes], site after site.
-constexpr int BATCH_CROSS_MAX_PAIRS = 65536;
+// at most BATCH_CROSS_MAX_PAIRS (batch_shape.h: 65536) pairs in one request
 struct BatchCrossPair {
   int bra, ket;   // state indices
   int site;       // site of the operator, -1: the plain overlap <bra | ket>
@@ -286,5 +281,32 @@ struct BatchExpectArgs {
 // one launch: grid = nrep * nops workgroups, workgroup r * nops + k; replicas and operators are only read.  Precondition:
 // centre at site 0, sites 1 .. L-1 in gauge B.
 void batch_expect_launch(hipStream_t st, const BatchExpectArgs& a, int nrep);
+
+// ---- MPO matrix elements between replicas (k_batch_cross_mpo) ----
+// An entry is (bra, ket, operator): the state indices are BatchCrossPair's (0 .. B-1 a replica, B + r the snapshot of
+// replica r), the operator is an index into the request's list of distinct operator ids, which every replica carries as
+// a whole MPO.  The cores and the scalar term used are those of the ket's owner, replica ket mod B.  The value is
+// <psi_bra | O | psi_ket> + shift <psi_bra | psi_ket>, not normalised: a walk of the left block T (bra bond, MPO bond,
+// ket bond) over all L sites in the three stages of the forward environment update, conj of the bra tensor in stage 1
+// and the ket tensor in stage 3; then, for a non-zero shift, k_batch_cross's plain-overlap walk.
+// BATCH_CROSS_MPO_MAX_BYTES, BatchCrossMpoEntry, BatchCrossMpoPlan, batch_cross_mpo_plan, batch_cross_mpo_fits and the check
+// of a request's entries, batch_cross_mpo_entries_ok: batch_cross_mpo_plan.h, which needs no HIP.
+struct BatchCrossMpoArgs {
+  int L, nrep, nops;                  // nrep = B: where the snapshot indices start; nops distinct operators
+  const BatchShape* shp;              // [nops][L], device: operator k's ml / mr at every site
+  void* const* ptrs;                  // the pointer table of BatchArgs (only its site tensors are read)
+  int ptr_stride;
+  const int* status;                  // [B]: an entry that names a replica whose word is set writes zeros
+  const zc* snap;                     // [B][snap_len], null while no snapshot was taken (no entry may name one then)
+  size_t snap_len;                    // sum of the site sizes, complex elements
+  const BatchCrossMpoEntry* entries;  // [P], device
+  void* const* ops;                   // [B][nops][L], device: w2el of operator k of replica r at every site
+  const zc* shift;                    // [B][nops]
+  zc* buf;                            // [P][plan.total]
+  BatchCrossMpoPlan plan;
+  double* rec;                        // [P][2]: (re, im) of each entry's value
+};
+// one launch: grid = nentries workgroups; replicas, snapshots and operators are only read
+void batch_cross_mpo_launch(hipStream_t st, const BatchCrossMpoArgs& a, int nentries);
 
 }  // namespace mitdvp

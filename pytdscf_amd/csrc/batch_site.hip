@@ -5,7 +5,8 @@
 // k_batch_cross / k_batch_snapshot, overlaps and one-site matrix elements between two replicas or their snapshots, one
 // workgroup per pair; k_batch_spectra, the Schmidt spectra of the requested bonds; k_batch_sample, configurations drawn
 // from every replica's state, one workgroup per replica; k_batch_expect, expectation values of MPO observables, one
-// workgroup per replica and operator.)
+// workgroup per replica and operator; k_batch_cross_mpo, matrix elements of MPOs between two replicas or snapshots, one
+// workgroup per entry.)
 //
 // At trajectory shapes (d = 2..4, D <= 32, M <= 16) a local problem is a few tens of kilobytes, so one workgroup can own
 // one replica completely: the replica index is blockIdx.x, nothing is exchanged between workgroups, and therefore there is
@@ -1898,7 +1899,140 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_expect(BatchExpectArgs g) 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// MPO matrix elements between two states of a batch: k_batch_cross_mpo, ONE workgroup per ENTRY (the entry index is
+// blockIdx.x), every entry of the request in one launch (BatchCrossMpoArgs in batch_site.h).  An entry is (bra, ket,
+// operator); the states are named as in k_batch_cross, the operator's cores and scalar term are those of the ket's owner,
+// replica ket mod B.  Two different states share no canonical form, so the walk runs over all L sites, left to right:
+//   T (bra bond, MPO bond, ket bond) = the 1 x 1 x 1 block [1]
+//   p = 0 .. L-1:  T <- bt_env2(T, Bra_p, Ket_p, w2el of the operator at p): the three products of bt_env in the roles of
+//                  the forward sweep, strides (d dr, dr, 1); stage 1 reads conj of the BRA tensor, stage 3 the KET
+//                  tensor; written alternately into the entry's two blocks
+//   value = the 1 x 1 x 1 block after site L-1, <bra | O | ket>, not normalised
+// With a non-zero scalar term the same workgroup then runs k_batch_cross's plain-overlap walk (site = -1) with that
+// kernel's products and adds shift * <bra | ket>; the decision is the same in every thread.
+// bt_env2 is a product function of its own: bt_env, and with it k_batch_sweep / _channel / _pair / _expect, compile to
+// what they compiled to before.
+// What is resident where: LDS holds the two operand tiles of wg_gemm (16 896 bytes); the two blocks, X and Y live in the
+// ENTRY's carve of the request's own buffer [P][carve] -- several entries may read one replica at the same time, so
+// nothing of a walk may sit in a replica's scratch area -- written and re-read by this workgroup only between workgroup
+// barriers; the overlap walk reuses them (T and its successor in the blocks, U in X).  Replicas, snapshots, operators and
+// status words are only read.  Every element has one owner thread and every sum one order: a value depends on its two
+// states and its operator only, not on the number of entries, its place in the list, B or the compute unit.  No atomics,
+// nothing waits for another workgroup, every loop is bounded by the shapes.
+__device__ __noinline__ void bt_env2(const zc* env, const zc* Tb, const zc* Tk, long sTi, long sTd, long sTo, const zc* W2e, int din,
+                                     int min_, int d, int dout, int mout, zc* X, zc* Y, zc* out, zc* tiles) {
+  const int nx = min_ * din;
+  // X[(c,a)][(p,s)] = sum_b conj(Bra(b,c,a)) env[b][(p,s)]
+  wg_gemm<false, false>(d * dout, nx, din, tiles,
+      [&](int m, int k) { const int c = m / dout, a = m - c * dout; const zc z = Tb[k * sTi + c * sTd + a * sTo]; return make_double2(z.x, -z.y); },
+      [&](int k, int n) { return env[(long)k * nx + n]; },
+      [&](int m, int n, zc z) { X[(long)m * nx + n] = z; });
+  // Y[a][(q,t)][s] = sum_(c,p) W2e[(q,t)][(c,p)] X[c][a][p][s]
+  const int kw = d * min_, mw = mout * d;
+  wg_gemm<true, false>(mw, dout * din, kw, tiles,
+      [&](int m, int k) { return W2e[(long)m * kw + k]; },
+      [&](int k, int n) {
+        const int c = k / min_, p = k - c * min_, a = n / din, ss = n - a * din;
+        return X[(((long)c * dout + a) * min_ + p) * din + ss];
+      },
+      [&](int m, int n, zc z) { const int a = n / din, ss = n - a * din; Y[((long)a * mw + m) * din + ss] = z; });
+  // out[(a,q)][r] = sum_(t,s) Y[(a,q)][(t,s)] Ket(s,t,r)
+  const int kr = d * din;
+  wg_gemm<true, false>(dout * mout, dout, kr, tiles,
+      [&](int m, int k) { return Y[(long)m * kr + k]; },
+      [&](int k, int n) { const int t = k / din, ss = k - t * din; return Tk[ss * sTi + t * sTd + n * sTo]; },
+      [&](int m, int n, zc z) { out[(long)m * dout + n] = z; });
+}
+
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 184 VGPRs -- those of bt_env2 --
+// 82 SGPRs, no vector or scalar register spills, NO private memory (0 bytes per lane: bt_env2 takes its arguments in
+// registers, so no access to private memory can sit inside a product loop), 16 896 bytes of LDS; occupancy 2 waves per
+// SIMD, i.e. one workgroup (entry) per compute unit.  The other batch kernels compile to what they compiled to before.
+__global__ __launch_bounds__(SS_THREADS) void k_batch_cross_mpo(BatchCrossMpoArgs g) {
+  __shared__ __attribute__((aligned(16))) zc tiles[2 * BT_TK * BT_LD];
+  const int q = blockIdx.x, tid = threadIdx.x, L = g.L, B = g.nrep;
+  const BatchCrossMpoEntry en = g.entries[q];
+  double* rec = g.rec + 2 * (size_t)q;
+  const bool dead = (en.bra < B && g.status[en.bra] != SS_OK) || (en.ket < B && g.status[en.ket] != SS_OK);
+  if (dead) {  // the same decision in every thread of the workgroup
+    if (tid == 0) { rec[0] = 0.0; rec[1] = 0.0; }
+    return;
+  }
+  const int owner = en.ket < B ? en.ket : en.ket - B;
+  // a replica's tensors come through its row of the pointer table, a snapshot's lie site after site in the batch's buffer
+  const zc* const* braTab = en.bra < B ? reinterpret_cast<const zc* const*>(g.ptrs + (size_t)en.bra * g.ptr_stride) : nullptr;
+  const zc* const* ketTab = en.ket < B ? reinterpret_cast<const zc* const*>(g.ptrs + (size_t)en.ket * g.ptr_stride) : nullptr;
+  const zc* braSnap = en.bra < B ? nullptr : g.snap + (size_t)(en.bra - B) * g.snap_len;
+  const zc* ketSnap = en.ket < B ? nullptr : g.snap + (size_t)(en.ket - B) * g.snap_len;
+  const zc* const* w2el = reinterpret_cast<const zc* const*>(g.ops + ((size_t)owner * g.nops + en.op) * L);
+  const BatchShape* shp = g.shp + (size_t)en.op * L;
+  const zc sft = g.shift[(size_t)owner * g.nops + en.op];
+  zc* buf = g.buf + (size_t)q * g.plan.total;
+  zc* Ea = buf;
+  zc* Eb = buf + g.plan.o_e1;
+  zc* X = buf + g.plan.o_x;
+  zc* Y = buf + g.plan.o_y;
+
+  if (tid == 0) Ea[0] = make_double2(1.0, 0.0);
+  __syncthreads();
+  size_t soff = 0;
+  for (int p = 0; p < L; ++p) {
+    const BatchShape s = shp[p];
+    const zc* Kt = ketTab ? ketTab[p] : ketSnap + soff;
+    const zc* Bt = braTab ? braTab[p] : braSnap + soff;
+    bt_env2(Ea, Bt, Kt, (long)s.d * s.dr, s.dr, 1, w2el[p], s.dl, s.ml, s.d, s.dr, s.mr, X, Y, Eb, tiles);
+    zc* t = Ea; Ea = Eb; Eb = t;
+    soff += (size_t)s.dl * s.d * s.dr;
+  }
+  const zc val = Ea[0];
+  if (sft.x == 0.0 && sft.y == 0.0) {  // uniform: the scalar term is the entry's
+    if (tid == 0) { rec[0] = val.x; rec[1] = val.y; }
+    return;
+  }
+  __syncthreads();  // every thread has read the value before the blocks are used again
+  // the plain overlap <bra | ket>: the walk and the products of k_batch_cross with site = -1
+  zc* T = Ea;
+  zc* T2 = Eb;
+  zc* U = X;
+  if (tid == 0) T[0] = make_double2(1.0, 0.0);
+  __syncthreads();
+  soff = 0;
+  for (int p = 0; p < L; ++p) {
+    const BatchShape s = shp[p];
+    const int dl = s.dl, d = s.d, dr = s.dr, ddr = d * dr;
+    const zc* Kt = ketTab ? ketTab[p] : ketSnap + soff;
+    const zc* Bt = braTab ? braTab[p] : braSnap + soff;
+    // U[m][(j,s)] = sum_n T[m][n] K[n][(j,s)]
+    wg_gemm<true, false>(dl, ddr, dl, tiles,
+        [&](int m, int kk) { return T[(long)m * dl + kk]; },
+        [&](int kk, int n) { return Kt[(long)kk * ddr + n]; },
+        [&](int m, int n, zc z) { U[(long)m * ddr + n] = z; });
+    // T'[i][j] = sum_(m,s) conj(Bra[(m,s)][i]) U[(m,s)][j]
+    wg_gemm<false, false>(dr, dr, dl * d, tiles,
+        [&](int m, int kk) { const zc z = Bt[(long)kk * dr + m]; return make_double2(z.x, -z.y); },
+        [&](int kk, int n) { return U[(long)kk * dr + n]; },
+        [&](int m, int n, zc z) { T2[(long)m * dr + n] = z; });
+    zc* t = T; T = T2; T2 = t;
+    soff += (size_t)dl * ddr;
+  }
+  if (tid == 0) {
+    const zc ov = T[0];
+    rec[0] = val.x + (sft.x * ov.x - sft.y * ov.y);
+    rec[1] = val.y + (sft.x * ov.y + sft.y * ov.x);
+  }
+}
+
 }  // namespace
+
+void batch_cross_mpo_launch(hipStream_t st, const BatchCrossMpoArgs& a, int nentries) {
+  if (nentries < 1 || nentries > BATCH_CROSS_MAX_PAIRS || a.L < 1 || a.nrep < 1 || a.nops < 1)
+    throw ArgError("batch: no cross entry of an MPO to observe");
+  if (!a.entries || !a.shp || !a.ops || !a.shift || !a.buf || !a.rec || a.plan.total < 1)
+    throw ArgError("batch: the cross request of MPOs has no buffers");
+  hipLaunchKernelGGL(k_batch_cross_mpo, dim3(nentries), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
 
 bool batch_expect_plan(const BatchShape* shp, const int* op_ids, int L, int nops, BatchExpectPlan& plan, std::string& why) {
   plan = BatchExpectPlan{};

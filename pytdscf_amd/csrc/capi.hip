@@ -245,7 +245,7 @@ int mitdvp_batch_run_keys(mitdvp_batch* b, double dt_au, int nsteps, int every, 
     if (nkeys < 0 || (nkeys > 0 && !remain_nleg)) throw mitdvp::ArgError("batch: bad list of density keys");
     HIP_CHECK(hipSetDevice(b->b->device()));
     const long nrdm = b->b->observe_sizes(sites, nsites, what, nkeys > 0 || b->b->has_cross() || b->b->has_spectra() || b->b->has_samples() ||
-                                                                         b->b->has_expect());
+                                                                         b->b->has_expect() || b->b->has_cross_mpo());
     const long ndens = b->b->density_sizes(remain_nleg, nkeys, nrdm);
     if (counts) {
       counts[0] = (size_t)(nsteps / every + 1); counts[1] = (size_t)b->b->size(); counts[2] = (size_t)nrdm; counts[3] = (size_t)ndens;
@@ -358,6 +358,18 @@ int mitdvp_batch_expect(mitdvp_batch* b, const double* weights, double* values, 
 int mitdvp_batch_expect_records(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[3]) {
   if (!b || !b->b) { g_err = "mitdvp_batch_expect_records: null handle"; return MITDVP_EINVAL; }
   return guard(nullptr, [&] { b->b->expect_records(weights, values, mean, counts); });
+}
+int mitdvp_batch_set_cross_mpo(mitdvp_batch* b, int nentries, const int* bra, const int* ket, const int* op_id) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_set_cross_mpo: null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->set_cross_mpo(nentries, bra, ket, op_id); });
+}
+int mitdvp_batch_cross_mpo(mitdvp_batch* b, const double* weights, double* values, double* mean) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_cross_mpo: null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->cross_mpo(weights, values, mean); });
+}
+int mitdvp_batch_cross_mpo_records(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[2]) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_cross_mpo_records: null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->cross_mpo_records(weights, values, mean, counts); });
 }
 void mitdvp_batch_destroy(mitdvp_batch* b) { delete b; }
 int mitdvp_invalidate_env(mitdvp_engine* h) { ENG_CALL(h, h->e->invalidate_env()); }

@@ -159,6 +159,28 @@ class Batch {
   // one host wait.
   void expect_records(const double* weights, double* values, double* mean, size_t* counts);
 
+  // ---- MPO matrix elements between replicas (k_batch_cross_mpo) ----
+  // An entry is (bra, ket, op_id): state indices as for set_cross, op_id an operator every replica carries at every site
+  // (Engine::set_mpo_core); its value is <psi_bra | O | psi_ket> + shift <psi_bra | psi_ket> with the cores and the scalar
+  // term of the ket's owner (replica ket mod B), not normalised.  Every refusal is an ArgError that names the entry point,
+  // the entry, the operator, the site and the limit and leaves the request, the records, the snapshot and every engine as
+  // they were.
+  // set_cross_mpo: nentries = 0 removes the request.  Refused: an index outside 0 .. 2B-1, a snapshot index before any
+  // snapshot, a negative op_id, an operator that a replica does not carry at every site, core shapes that differ between
+  // replicas, MPO bonds outside 1 .. BATCH_MAX_MPO, neighbouring cores that do not fit, outer MPO bonds that are not 1,
+  // more than BATCH_CROSS_MAX_PAIRS entries, a buffer above BATCH_CROSS_MPO_MAX_BYTES.  No launch, no wait.
+  void set_cross_mpo(int nentries, const int* bra, const int* ket, const int* op_id);
+  bool has_cross_mpo() const { return !xm_.empty(); }
+  // cross_mpo: the request on the current state (centre at site 0 or L-1): k_batch_cross_mpo and k_batch_mean, TWO
+  // launches, one host wait.  weights: nentries doubles or null (1 / nentries); values [nentries][2] and mean [2] may each
+  // be null.
+  void cross_mpo(const double* weights, double* values, double* mean);
+  // While a request is set every record of run() records it too: ONE more launch per record and ONE more k_batch_mean
+  // launch per call (weights 1 / nentries), no further host wait.  cross_mpo_records returns what the last run() recorded:
+  // values [records][nentries][2], mean [records][2], counts {records, nentries}; each may be null.  weights null: the
+  // means of the run, no launch and no wait; weights given: ONE k_batch_mean launch over the records and one host wait.
+  void cross_mpo_records(const double* weights, double* values, double* mean, size_t* counts);
+
   std::string status_message(int code) const;
   int size() const { return (int)eng_.size(); }
   int device() const { return device_; }
@@ -316,6 +338,37 @@ class Batch {
   void upload_expect(long nrec);         // the device tables, room for nrec records and expect()'s slot
   void launch_expect(long record);
   void expect_weights(const double* weights);
+  // the shapes [nops][L] of the listed operators on the engines as they are now (the gathering half of expect_shapes);
+  // ArgError naming the entry point, the operator, the site and the replica otherwise
+  void operator_shapes(const char* entry, const int* op_ids, int nops, std::vector<BatchShape>& shp) const;
+
+  // cross request of MPOs: the entries (op = index into xm_ops_, the distinct operator ids in order of first use), the
+  // shapes [nops][L] and the carve they give, the device tables (w2el [B][nops][L], shapes, shifts [B][nops]; refreshed
+  // with the batch's own tables, since engines may be given new cores between calls), the walk's buffer [P][carve], the
+  // records [nrec + 1][P][2] (the slot behind a run's records is cross_mpo()'s own) and their means, the weights [P]
+  std::vector<BatchCrossMpoEntry> xm_;
+  std::vector<int> xm_ops_;
+  std::vector<BatchShape> xm_shp_;
+  BatchCrossMpoPlan xm_plan_;
+  bool xm_dirty_ = false;
+  BatchCrossMpoEntry* d_xm_ent_ = nullptr;
+  void** d_xm_ptrs_ = nullptr;
+  BatchShape* d_xm_shp_ = nullptr;
+  zc *d_xm_shift_ = nullptr, *d_xm_buf_ = nullptr;
+  double *d_xm_rec_ = nullptr, *d_xm_mean_ = nullptr, *d_xm_w_ = nullptr;
+  size_t xm_ent_elems_ = 0, xm_ptrs_elems_ = 0, xm_shp_elems_ = 0, xm_shift_elems_ = 0, xm_buf_elems_ = 0, xm_rec_slots_ = 0,
+         xm_mean_slots_ = 0, xm_w_elems_ = 0;  // xm_rec_slots_ / xm_mean_slots_: doubles
+  long xm_nrec_ = 0;  // records of the last run() held in d_xm_rec_ / h_xm_rec_
+  std::vector<void*> h_xm_ptrs_;
+  std::vector<zc> h_xm_shift_;
+  std::vector<double> h_xm_rec_, h_xm_mean_, h_xm_w_, h_xm_now_;
+  // shapes and carve of the listed operators on the engines as they are now, and the buffer cap for nentries entries
+  void cross_mpo_shapes(const char* entry, const int* op_ids, int nops, size_t nentries, std::vector<BatchShape>& shp,
+                        BatchCrossMpoPlan& plan) const;
+  void check_cross_mpo(const char* entry);  // the request against the engines and the snapshot as they are now
+  void upload_cross_mpo(long nrec);         // the device tables, room for nrec records and cross_mpo()'s slot
+  void launch_cross_mpo(long record);
+  void cross_mpo_weights(const double* weights);
 
   static std::vector<BatchShape> shapes_of(Engine& e);
   void check_channels() const;

@@ -11,6 +11,7 @@
 #include "engine_batch.h"
 #include "capi_internal.h"
 
+#include <map>
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -92,6 +93,7 @@ void Batch::validate() {
     spec_nrec_ = 0;     // nor do spectra records of other bond dimensions
     smp_nrec_ = 0;      // nor sampled configurations of other shapes
     exp_nrec_ = 0;      // nor expectation values walked over other bonds
+    xm_nrec_ = 0;       // nor MPO matrix elements between states of other bonds
   }
   plan_ = pl;
   batch_observe_plan(plan_, obs_plan_);
@@ -187,6 +189,14 @@ Batch::~Batch() {
   if (d_exp_buf_) (void)hipFree(d_exp_buf_);
   if (d_exp_rec_) (void)hipFree(d_exp_rec_);
   if (d_exp_mean_) (void)hipFree(d_exp_mean_);
+  if (d_xm_ent_) (void)hipFree(d_xm_ent_);
+  if (d_xm_ptrs_) (void)hipFree(d_xm_ptrs_);
+  if (d_xm_shp_) (void)hipFree(d_xm_shp_);
+  if (d_xm_shift_) (void)hipFree(d_xm_shift_);
+  if (d_xm_buf_) (void)hipFree(d_xm_buf_);
+  if (d_xm_rec_) (void)hipFree(d_xm_rec_);
+  if (d_xm_mean_) (void)hipFree(d_xm_mean_);
+  if (d_xm_w_) (void)hipFree(d_xm_w_);
   if (st_) (void)hipStreamDestroy(st_);
 }
 
@@ -637,12 +647,14 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   const bool sp = has_spectra();  // so does a spectra request
   const bool sm = has_samples();  // and a samples request
   const bool ex = has_expect();   // and an expect request
-  const long nrdm = observe_sizes(sites, nsites, what, nkeys > 0 || cx || sp || sm || ex);
+  const bool xm = has_cross_mpo();  // and a cross request of MPOs
+  const long nrdm = observe_sizes(sites, nsites, what, nkeys > 0 || cx || sp || sm || ex || xm);
   const long ndens = density_sizes(dens.legs, nkeys, nrdm);
   if (cx) check_cross("mitdvp_batch_run");
   if (sp) check_spectra("mitdvp_batch_run");
   if (sm) check_samples("mitdvp_batch_run");
   if (ex) check_expect("mitdvp_batch_run");
+  if (xm) check_cross_mpo("mitdvp_batch_run");
   const bool own = what != 0 || nkeys > 0;  // false: only the cross request is recorded, no record of the replicas
   const size_t n = eng_.size();
   const long nrec = nsteps / every + 1, dens_off = BOBS_HEAD + 2 * nrdm, rec_len = dens_off + 2 * ndens;
@@ -655,6 +667,7 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   if (sp) upload_spectra(nrec);
   if (sm) upload_samples(nrec);
   if (ex) upload_expect(nrec);
+  if (xm) upload_cross_mpo(nrec);
   // buffers of the records and their means (grow only), the site list and the weights
   const size_t need_rec = (size_t)nrec * n * rec_len, need_mean = (size_t)nrec * rec_len;
   const size_t need_legs = (size_t)nkeys * L_, need_tbuf = nkeys ? n * 2 * dens_plan_.need : 0;
@@ -701,6 +714,7 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
     if (sp) launch_spectra(q);
     if (sm) launch_samples(q, step);
     if (ex) launch_expect(q);
+    if (xm) launch_cross_mpo(q);
   };
 
   record(0, steps_done_);
@@ -774,12 +788,25 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
     HIP_CHECK(hipMemcpyAsync(h_exp_mean_.data(), d_exp_mean_, h_exp_mean_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
     exp_nrec_ = nrec;
   }
+  int xm_launches = 0;
+  if (xm) {  // and for the cross request of MPOs (weights 1 / nentries)
+    const size_t np = xm_.size();
+    cross_mpo_weights(nullptr);
+    batch_mean_launch(st_, d_xm_rec_, d_xm_w_, d_xm_mean_, (int)np, 2, nrec);
+    n_launch_ += 1;
+    xm_launches = (int)nrec + 1;
+    h_xm_rec_.resize((size_t)nrec * np * 2);
+    h_xm_mean_.resize((size_t)nrec * 2);
+    HIP_CHECK(hipMemcpyAsync(h_xm_rec_.data(), d_xm_rec_, h_xm_rec_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipMemcpyAsync(h_xm_mean_.data(), d_xm_mean_, h_xm_mean_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
+    xm_nrec_ = nrec;
+  }
   if (per_replica) {
     h_rec_.resize(need_rec);
     HIP_CHECK(hipMemcpyAsync(h_rec_.data(), d_rec_, need_rec * sizeof(double), hipMemcpyDeviceToHost, st_));
   }
   steps_done_ += nsteps;
-  const int other = (int)nrec * per_rec + (own ? 1 : 0) + cross_launches + spec_launches + smp_launches + exp_launches;
+  const int other = (int)nrec * per_rec + (own ? 1 : 0) + cross_launches + spec_launches + smp_launches + exp_launches + xm_launches;
   if (nsteps > 0) finish(false, nsteps * 2, statuses, other, chan ? nsteps : 0);
   else finish_observe(other, statuses);
 
@@ -1307,6 +1334,12 @@ void Batch::samples_records(const double* weights, int* configs, double* prob, d
 
 // ---- expectation values of MPO observables (k_batch_expect) ----
 void Batch::expect_shapes(const char* entry, const int* op_ids, int nops, std::vector<BatchShape>& shp, BatchExpectPlan& plan) const {
+  operator_shapes(entry, op_ids, nops, shp);
+  std::string why;
+  if (!batch_expect_plan(shp.data(), op_ids, L_, nops, plan, why)) throw ArgError(std::string(entry) + ": " + why);
+}
+
+void Batch::operator_shapes(const char* entry, const int* op_ids, int nops, std::vector<BatchShape>& shp) const {
   const std::string at = std::string(entry) + ": ";
   shp.assign((size_t)nops * L_, BatchShape{});
   for (int k = 0; k < nops; ++k) {
@@ -1331,8 +1364,6 @@ void Batch::expect_shapes(const char* entry, const int* op_ids, int nops, std::v
       }
     }
   }
-  std::string why;
-  if (!batch_expect_plan(shp.data(), op_ids, L_, nops, plan, why)) throw ArgError(at + why);
 }
 
 void Batch::set_expect(const int* op_ids, int nops) {
@@ -1489,6 +1520,180 @@ void Batch::expect_records(const double* weights, double* values, double* mean, 
   batch_mean_launch(st_, d_exp_rec_, d_exp_w_, dst, (int)n, (long)len, (long)nrec);
   n_launch_ += 1;
   HIP_CHECK(hipMemcpyAsync(mean, dst, nrec * len * sizeof(double), hipMemcpyDeviceToHost, st_));
+  finish_observe(1, nullptr);
+}
+
+// ---- MPO matrix elements between replicas (k_batch_cross_mpo) ----
+void Batch::cross_mpo_shapes(const char* entry, const int* op_ids, int nops, size_t nentries, std::vector<BatchShape>& shp,
+                             BatchCrossMpoPlan& plan) const {
+  const std::string at = std::string(entry) + ": ";
+  operator_shapes(entry, op_ids, nops, shp);
+  std::string why;
+  if (!batch_cross_mpo_plan(shp.data(), op_ids, L_, nops, plan, why)) throw ArgError(at + why);
+  if (!batch_cross_mpo_fits(nentries, plan, why)) throw ArgError(at + why);
+}
+
+void Batch::set_cross_mpo(int nentries, const int* bra, const int* ket, const int* op_id) {
+  const std::string at = "mitdvp_batch_set_cross_mpo: ";
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  const int B = (int)eng_.size();
+  std::string bad;
+  if (!batch_cross_mpo_entries_ok(B, has_snap_, nentries, bra, ket, op_id, bad)) throw ArgError(at + bad);
+  std::vector<BatchCrossMpoEntry> ent((size_t)nentries);
+  std::vector<int> ops;  // the distinct operators in order of first use
+  std::map<int, int> slot;
+  for (int q = 0; q < nentries; ++q) {
+    auto it = slot.find(op_id[q]);
+    if (it == slot.end()) {
+      it = slot.emplace(op_id[q], (int)ops.size()).first;
+      ops.push_back(op_id[q]);
+    }
+    ent[q] = BatchCrossMpoEntry{bra[q], ket[q], it->second, 0};
+  }
+  std::vector<BatchShape> shp;
+  BatchCrossMpoPlan plan;
+  cross_mpo_shapes("mitdvp_batch_set_cross_mpo", ops.data(), (int)ops.size(), (size_t)nentries, shp, plan);
+  xm_ = std::move(ent);
+  xm_ops_ = std::move(ops);
+  xm_shp_ = std::move(shp);
+  xm_plan_ = plan;
+  xm_dirty_ = true;
+  h_xm_ptrs_.clear();
+  xm_nrec_ = 0;  // records of another request are not this one's
+}
+
+void Batch::check_cross_mpo(const char* entry) {
+  const std::string at = std::string(entry) + ": ";
+  if (xm_.empty()) throw ArgError(at + "no cross request of MPOs is set (mitdvp_batch_set_cross_mpo)");
+  const int B = (int)eng_.size();
+  for (size_t q = 0; q < xm_.size(); ++q)
+    if ((xm_[q].bra >= B || xm_[q].ket >= B) && !has_snap_)
+      throw ArgError(at + "entry " + std::to_string(q) + " of the cross request of MPOs names a snapshot, and the shapes changed since it was taken");
+  std::vector<BatchShape> shp;
+  BatchCrossMpoPlan plan;
+  cross_mpo_shapes(entry, xm_ops_.data(), (int)xm_ops_.size(), xm_.size(), shp, plan);
+  if (shp.size() != xm_shp_.size() || std::memcmp(shp.data(), xm_shp_.data(), shp.size() * sizeof(BatchShape)) != 0) {
+    xm_shp_ = std::move(shp);
+    xm_dirty_ = true;
+    xm_nrec_ = 0;  // the engines were given cores of other shapes: records walked over the old ones are dropped
+  }
+  xm_plan_ = plan;
+}
+
+void Batch::upload_cross_mpo(long nrec) {
+  const size_t n = eng_.size(), np = xm_.size(), nops = xm_ops_.size(), slots = (size_t)nrec + 1;
+  const size_t need_ptrs = n * nops * L_, need_shp = nops * L_, need_shift = n * nops, need_buf = np * xm_plan_.total;
+  if (np > xm_ent_elems_ || need_ptrs > xm_ptrs_elems_ || need_shp > xm_shp_elems_ || need_shift > xm_shift_elems_ ||
+      need_buf > xm_buf_elems_ || slots * np * 2 > xm_rec_slots_ || 4 * slots > xm_mean_slots_ || np > xm_w_elems_) {
+    HIP_CHECK(hipStreamSynchronize(st_));
+    auto grow = [&](auto*& p, size_t& have, size_t need) {
+      if (p && need <= have) return;
+      if (p) (void)hipFree(p);
+      p = nullptr;
+      dev_alloc(p, need);
+      have = need;
+    };
+    if (np > xm_ent_elems_ || need_shp > xm_shp_elems_) xm_dirty_ = true;
+    if (need_ptrs > xm_ptrs_elems_) h_xm_ptrs_.clear();
+    grow(d_xm_ent_, xm_ent_elems_, np);
+    grow(d_xm_ptrs_, xm_ptrs_elems_, need_ptrs);
+    grow(d_xm_shp_, xm_shp_elems_, need_shp);
+    grow(d_xm_shift_, xm_shift_elems_, need_shift);
+    grow(d_xm_buf_, xm_buf_elems_, need_buf);
+    grow(d_xm_w_, xm_w_elems_, np);
+    // these two grow only with a new request or in run(): no record of the last run is lost
+    grow(d_xm_rec_, xm_rec_slots_, slots * np * 2);
+    // the means of the records, the one of cross_mpo(), and the records' means under the weights of cross_mpo_records
+    grow(d_xm_mean_, xm_mean_slots_, 2 * slots * 2);
+  }
+  // tables: w2el of every site per (replica, operator); the engines may have been given new cores since the last call
+  std::vector<void*> h(need_ptrs);
+  h_xm_shift_.resize(need_shift);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t k = 0; k < nops; ++k) {
+      const Operator& o = eng_[i]->ops_.find(xm_ops_[k])->second;
+      void** q = h.data() + (i * nops + k) * L_;
+      for (int p = 0; p < L_; ++p) q[p] = o.sites[p].w2el.p;
+      h_xm_shift_[i * nops + k] = make_double2(o.shift.real(), o.shift.imag());
+    }
+  if (h != h_xm_ptrs_) {
+    h_xm_ptrs_ = h;
+    HIP_CHECK(hipMemcpyAsync(d_xm_ptrs_, h_xm_ptrs_.data(), need_ptrs * sizeof(void*), hipMemcpyHostToDevice, st_));
+  }
+  if (xm_dirty_) {
+    HIP_CHECK(hipMemcpyAsync(d_xm_ent_, xm_.data(), np * sizeof(BatchCrossMpoEntry), hipMemcpyHostToDevice, st_));
+    HIP_CHECK(hipMemcpyAsync(d_xm_shp_, xm_shp_.data(), need_shp * sizeof(BatchShape), hipMemcpyHostToDevice, st_));
+    xm_dirty_ = false;
+  }
+  HIP_CHECK(hipMemcpyAsync(d_xm_shift_, h_xm_shift_.data(), need_shift * sizeof(zc), hipMemcpyHostToDevice, st_));
+}
+
+void Batch::launch_cross_mpo(long record) {
+  BatchCrossMpoArgs a{};
+  a.L = L_;
+  a.nrep = (int)eng_.size();
+  a.nops = (int)xm_ops_.size();
+  a.shp = d_xm_shp_;
+  a.ptrs = d_ptrs_;
+  a.ptr_stride = (int)ptrs_per_replica();
+  a.status = d_status_;
+  a.snap = has_snap_ ? d_snap_ : nullptr;
+  a.snap_len = snap_len();
+  a.entries = d_xm_ent_;
+  a.ops = d_xm_ptrs_;
+  a.shift = d_xm_shift_;
+  a.buf = d_xm_buf_;
+  a.plan = xm_plan_;
+  a.rec = d_xm_rec_ + (size_t)record * xm_.size() * 2;
+  batch_cross_mpo_launch(st_, a, (int)xm_.size());
+  n_launch_ += 1;
+}
+
+void Batch::cross_mpo_weights(const double* weights) {
+  const size_t np = xm_.size();
+  h_xm_w_.assign(np, 1.0 / (double)np);
+  if (weights) h_xm_w_.assign(weights, weights + np);
+  HIP_CHECK(hipMemcpyAsync(d_xm_w_, h_xm_w_.data(), np * sizeof(double), hipMemcpyHostToDevice, st_));
+}
+
+void Batch::cross_mpo(const double* weights, double* values, double* mean) {
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  check_cross_mpo("mitdvp_batch_cross_mpo");
+  prepare_observing();
+  upload_cross_mpo(xm_nrec_);
+  const size_t np = xm_.size();
+  const long slot = xm_nrec_;  // behind the records of the last run, which stay
+  cross_mpo_weights(weights);
+  launch_cross_mpo(slot);
+  batch_mean_launch(st_, d_xm_rec_ + (size_t)slot * np * 2, d_xm_w_, d_xm_mean_ + (size_t)slot * 2, (int)np, 2, 1);
+  n_launch_ += 1;
+  h_xm_now_.resize(np * 2 + 2);
+  HIP_CHECK(hipMemcpyAsync(h_xm_now_.data(), d_xm_rec_ + (size_t)slot * np * 2, np * 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipMemcpyAsync(h_xm_now_.data() + np * 2, d_xm_mean_ + (size_t)slot * 2, 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
+  finish_observe(2, nullptr);
+  if (values) std::memcpy(values, h_xm_now_.data(), np * 2 * sizeof(double));
+  if (mean) std::memcpy(mean, h_xm_now_.data() + np * 2, 2 * sizeof(double));
+}
+
+void Batch::cross_mpo_records(const double* weights, double* values, double* mean, size_t* counts) {
+  const size_t np = xm_.size(), nrec = (size_t)xm_nrec_;
+  if (counts) { counts[0] = nrec; counts[1] = np; }
+  if (nrec == 0 || (!values && !mean)) return;
+  if (values) std::memcpy(values, h_xm_rec_.data(), nrec * np * 2 * sizeof(double));
+  if (!mean) return;
+  if (!weights) {
+    std::memcpy(mean, h_xm_mean_.data(), nrec * 2 * sizeof(double));
+    return;
+  }
+  HIP_CHECK(hipSetDevice(device_));
+  cross_mpo_weights(weights);
+  // behind the slots of the records' own means and of cross_mpo(): the means of the run stay as they are
+  double* dst = d_xm_mean_ + (nrec + 1) * 2;
+  batch_mean_launch(st_, d_xm_rec_, d_xm_w_, dst, (int)np, 2, (long)nrec);
+  n_launch_ += 1;
+  HIP_CHECK(hipMemcpyAsync(mean, dst, nrec * 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
   finish_observe(1, nullptr);
 }
 

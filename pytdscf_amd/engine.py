@@ -8,6 +8,7 @@ Mirrors what ``WFunc``/``MPSCoefMPO`` expose for the hot path in the reference:
 from __future__ import annotations
 
 import ctypes as C
+import operator
 
 import numpy as np
 
@@ -958,6 +959,7 @@ class TDVPBatch:
         self._spectra = None
         self._samples = None
         self._expect = None
+        self._cross_mpo = None
         self._lib = _lib.load()
         try:
             for _ in range(n_replicas):
@@ -985,6 +987,7 @@ class TDVPBatch:
         self._spectra = None
         self._samples = None
         self._expect = None
+        self._cross_mpo = None
         self._lib = _lib.load()
         return self
 
@@ -1026,6 +1029,8 @@ class TDVPBatch:
                     self._push_samples(*self._samples)
                 if self._expect is not None:
                     self._push_expect(self._expect)
+                if self._cross_mpo is not None:
+                    self._push_cross_mpo(self._cross_mpo)
             except Exception:
                 self._drop()
                 raise
@@ -1443,6 +1448,66 @@ class TDVPBatch:
         _lib.check(self._lib.mitdvp_batch_expect_records(self._b, None if w is None else _dp(w), _dp(vals), _dp(mean), cnt))
         return {"expect": vals, "mean_expect": mean} if per_replica else {"mean_expect": mean}
 
+    # ---- MPO matrix elements between replicas (mitdvp_batch_set_cross_mpo / _cross_mpo) ----
+    def _push_cross_mpo(self, packed):
+        bra, ket, ops = packed
+        ia = lambda v: (C.c_int * max(len(v), 1))(*v)
+        _lib.check(self._lib.mitdvp_batch_set_cross_mpo(self._b, len(bra), ia(bra), ia(ket), ia(ops)))
+
+    def set_cross_mpo(self, entries):
+        """Registers the entries that ``cross_mpo`` and recorded runs evaluate: ``(bra, ket, op_id)`` is
+        ``<psi_bra| O |psi_ket> + shift <psi_bra|psi_ket>``, not normalised, with ``O`` the MPO that every replica carries
+        under ``op_id`` (``set_mpo``) -- the cores and the scalar term of the ket's owner.  ``bra`` / ``ket`` are replica
+        indices or ``snap(r)``.  An empty list removes the request.  The library validates (indices, a snapshot that
+        exists, every site, equal shapes across the replicas, MPO bonds of at most 16, outer bonds 1, at most 65536
+        entries, a work buffer of at most 2**32 bytes) and a refused request leaves the one before in place."""
+        bra, ket, ops = [], [], []
+        for k, e in enumerate(entries):
+            e = tuple(e)
+            if len(e) != 3:
+                raise ValueError(f"set_cross_mpo: entry {k} must be (bra, ket, op_id)")
+            try:
+                e = tuple(operator.index(x) for x in e)
+            except TypeError:
+                raise ValueError(f"set_cross_mpo: entry {k} must be three whole numbers (bra, ket, op_id), got {e!r}") from None
+            if any(not -2**31 <= x < 2**31 for x in e):
+                raise ValueError(f"set_cross_mpo: entry {k}: {e!r} does not fit an int")
+            bra.append(e[0]); ket.append(e[1]); ops.append(e[2])
+        packed = (bra, ket, ops)
+        self._handle()
+        self._push_cross_mpo(packed)
+        self._cross_mpo = packed if bra else None
+
+    def _cross_mpo_weights(self, weights):
+        if self._cross_mpo is None:
+            raise ValueError("no cross request of MPOs is set (set_cross_mpo)")
+        if weights is None:
+            return None
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+        if w.shape != (len(self._cross_mpo[0]),):
+            raise ValueError(f"cross_mpo weights must be {len(self._cross_mpo[0])} numbers, one per entry (got shape {w.shape})")
+        return w
+
+    def cross_mpo(self, weights=None):
+        """The request of ``set_cross_mpo`` on the current state of the replicas: one launch for all entries
+        (``k_batch_cross_mpo``, one workgroup per entry), a second one for their weighted sum (``mitdvp_batch_cross_mpo``).
+        Returns ``{"values": (P,) complex, "mean": complex}``; ``weights``: P numbers, default 1 / P each."""
+        w = self._cross_mpo_weights(weights)
+        vals = np.zeros(len(self._cross_mpo[0]), dtype=np.complex128)
+        mean = np.zeros(1, dtype=np.complex128)
+        _lib.check(self._lib.mitdvp_batch_cross_mpo(self._handle(), None if w is None else _dp(w), _dp(vals), _dp(mean)))
+        return {"values": vals, "mean": complex(mean[0])}
+
+    def _cross_mpo_records(self, weights):
+        w = self._cross_mpo_weights(weights)
+        cnt = (C.c_size_t * 2)()
+        _lib.check(self._lib.mitdvp_batch_cross_mpo_records(self._b, None, None, None, cnt))
+        nrec, np_ = int(cnt[0]), int(cnt[1])
+        vals = np.zeros((nrec, np_), dtype=np.complex128)
+        mean = np.zeros(nrec, dtype=np.complex128)
+        _lib.check(self._lib.mitdvp_batch_cross_mpo_records(self._b, None if w is None else _dp(w), _dp(vals), _dp(mean), cnt))
+        return vals, mean
+
     def launches(self) -> int:
         """kernel launches counted so far on replica 0, where the batch's launches are counted once"""
         return int(self.engines[0].counters()["n_launch"])
@@ -1478,7 +1543,9 @@ class TDVPBatch:
         with a leading record axis, ``mean_freq`` formed with ``samples_weights`` (B numbers, default 1 / B each).
         ``expect=True`` adds the request of ``set_expect`` (``k_batch_expect``, one more launch per record): ``expect`` of
         shape ``(nrec, B, nops)`` and ``mean_expect`` ``(nrec, nops)``, averaged with ``expect_weights`` (B numbers,
-        default 1 / B each)."""
+        default 1 / B each).  ``cross_mpo=True`` adds the request of ``set_cross_mpo`` (``k_batch_cross_mpo``, one more launch
+        per record): ``cross_mpo`` of shape ``(nrec, P)`` and ``mean_cross_mpo`` ``(nrec,)``, the weighted sum over the entries
+        with ``cross_mpo_weights`` (P numbers, default 1 / P each)."""
         if observe is None:
             self._run(lambda b, st: self._lib.mitdvp_batch_step(b, float(dt_au), int(nsteps), st))
             return None
@@ -1512,7 +1579,7 @@ class TDVPBatch:
 
     def _observed(self, dt_au, nsteps, every, sites=(), norm=True, autocorr=False, energy=False, weights=None, per_replica=True,
                   keys=(), cross=False, cross_weights=None, spectra=False, spectra_weights=None, samples=False,
-                  samples_weights=None, expect=False, expect_weights=None):
+                  samples_weights=None, expect=False, expect_weights=None, cross_mpo=False, cross_mpo_weights=None):
         n = len(self.engines)
         if cross:
             self._cross_weights(cross_weights)  # no request, or weights of the wrong length: raised before any library call
@@ -1522,6 +1589,8 @@ class TDVPBatch:
             self._samples_weights(samples_weights)
         if expect:
             self._expect_weights(expect_weights)
+        if cross_mpo:
+            self._cross_mpo_weights(cross_mpo_weights)
         nsite = self.engines[0].nsite
         legs = [density_key_legs(k, nsite) for k in keys]  # a malformed key raises here, before any library call
         sites = [int(p) for p in sites]
@@ -1589,6 +1658,8 @@ class TDVPBatch:
                 self.records.update(self._samples_records(samples_weights, per_replica))
             if expect:
                 self.records.update(self._expect_records(expect_weights, per_replica))
+            if cross_mpo:
+                self.records["cross_mpo"], self.records["mean_cross_mpo"] = self._cross_mpo_records(cross_mpo_weights)
         return self.records
 
     def _split(self, keep, sites, legs=()):

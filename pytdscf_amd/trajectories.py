@@ -8,7 +8,8 @@ so do sampled nearest-neighbour channels (``jumps={(q, q + 1): B}``: incoherent 
 applies to the merged two-site tensor and splits again at the bond's dimension (``k_batch_pair``).
 
 ``correlation_function`` relates two states of the batch to each other: the autocorrelation function without the t/2
-trick and ``<psi| A(t) B |psi>``, contracted for all trajectories by one launch per record (``k_batch_cross``).
+trick and ``<psi| A(t) B |psi>``, contracted for all trajectories by one launch per record (``k_batch_cross``; ``k_batch_cross_mpo``
+when ``A`` is a sum over the chain given as an MPO).
 
 Nothing falls back: a model the batched kernels do not take raises with the library's message."""
 
@@ -18,7 +19,7 @@ import numpy as np
 
 from . import units
 from .engine import TDVPBatch, density_key_legs, pair_key, sample_request, spectra_bonds
-from .mps import product_state_cores
+from .mps import bond_dims, product_state_cores
 
 
 _M64 = (1 << 64) - 1
@@ -113,13 +114,82 @@ def _site_operator(name, op, dims):
     return site, mat
 
 
+def _operator_form(name, op, model, dims):
+    """("site", site, matrix) for ``(site, matrix)``; ("mpo", cores) for the name of an entry of ``model.observables`` or a
+    list of MPO cores (ml, d, d, mr per site).  ``ValueError`` naming what is wrong, before any engine exists."""
+    if isinstance(op, str):
+        have = getattr(model, "observables", None) or {}
+        if op not in have:
+            raise ValueError(f"correlation_function: {name} = {op!r} is not in model.observables (it has {sorted(have)})")
+        cores = have[op].as_mpo(dims)
+    elif (isinstance(op, (tuple, list)) and len(op) == 2 and isinstance(op[0], (int, np.integer)) and not isinstance(op[0], bool)):
+        return ("site",) + _site_operator(name, op, dims)
+    else:
+        try:
+            cores = list(op)
+        except TypeError:
+            raise ValueError(f"correlation_function: {name} must be (site, matrix), the name of an entry of model.observables "
+                             "or a list of MPO cores") from None
+    cores = [np.ascontiguousarray(w, dtype=np.complex128) for w in cores]
+    if len(cores) != len(dims):
+        raise ValueError(f"correlation_function: {name} has {len(cores)} MPO cores, the chain has {len(dims)} sites")
+    left = 1
+    for p, (w, d) in enumerate(zip(cores, dims)):
+        if w.ndim != 4 or w.shape[1] != d or w.shape[2] != d or w.shape[0] != left:
+            raise ValueError(f"correlation_function: {name}: the MPO core of site {p} has shape {w.shape}, expected "
+                             f"({left}, {d}, {d}, m)")
+        left = w.shape[3]
+    if left != 1:
+        raise ValueError(f"correlation_function: {name}: the last MPO core ends in a bond of {left}, it must be 1")
+    return "mpo", cores
+
+
+def check_mpo_fits_bonds(name, cores, dims, D):
+    """``ValueError`` naming the bond and both figures when the MPO is wider somewhere than the state's bond there: the
+    product ``B psi`` is an exact MPS of the MPO's bonds and must fit the bond dimensions of ``model.m_aux_max``."""
+    for q, ((_, dr), w) in enumerate(zip(bond_dims(list(dims), D), cores[:-1])):
+        if w.shape[3] > dr:
+            raise ValueError(f"correlation_function: {name} has MPO bond {w.shape[3]} between sites {q} and {q + 1}, the state's "
+                             f"bond there is {dr} (model.m_aux_max): B psi does not fit")
+
+
+def mpo_on_product(cores, vectors):
+    """The cores of ``B psi`` for the MPO ``cores`` and the Hartree product of ``vectors`` (each normalised first):
+    ``phi_p[c, i, t] = sum_j W_p[c, i, j, t] v_p[j]``, an exact MPS of the MPO's bonds, with the norm of ``B psi``."""
+    out = []
+    for w, v in zip(cores, vectors):
+        v = np.asarray(v, dtype=np.complex128)
+        if v.ndim != 1:
+            raise ValueError("correlation_function: an MPO B acts on a start given as per-site vectors")
+        out.append(np.einsum("cijt,j->cit", w, v / np.linalg.norm(v)))
+    return out
+
+
+def _mps_norm(cores):
+    T = np.ones((1, 1), dtype=np.complex128)
+    for c in cores:
+        T = np.einsum("ab,ajs,bjt->st", T, np.conj(c), c)
+    return float(np.sqrt(abs(T[0, 0])))
+
+
 def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every=1, weights=None, integrator="arnoldi",
                          conserve_norm=False, thresh_sil=1.0e-09, per_trajectory=False, device=0):
     """Two-time correlation functions of an ensemble of Hartree products in ONE batch, contracted and averaged on the device
     (``k_batch_cross``, ``mitdvp_batch_run``): no t/2 trick, so complex starts and Hamiltonians that are not complex
     symmetric are fine.
 
-    ``A`` and ``B`` are ``(site, matrix)``.  With both, every start ``s`` gives two replicas, ``psi_s(0)`` = the start and
+    ``A`` and ``B`` each take one of three forms: ``(site, matrix)``, a one-site operator; the name of an entry of
+    ``model.observables``; or a list of MPO cores ``(ml, d, d, mr)``, one per site.  A named observable is turned into an
+    MPO as ``propagate_trajectories`` prepares it (``op.as_mpo(model.dims)``, no scalar term): the total dipole of an
+    aggregate, a current, the Hamiltonian.  An MPO ``A`` is given to every replica as operator 1 and evaluated by
+    ``k_batch_cross_mpo`` (``TDVPBatch.set_cross_mpo``), one workgroup per start.  An MPO ``B`` is applied to each Hartree
+    product on the host: ``phi_p[c, i, t] = sum_j W_p[c, i, j, t] v_p[j]`` is an exact MPS of the MPO's bonds, zero-padded
+    to the bond dimensions of ``model.m_aux_max`` and set with its own norm ``|B psi|``; an MPO bond wider than the state's
+    bond there is a ``ValueError`` naming the bond and both figures, as are an unknown name and a start that ``B``
+    annihilates, all raised before any engine exists.  The forms may be mixed, and with both
+    ``(site, matrix)`` everything is as it was.
+
+    With both given, every start ``s`` gives two replicas, ``psi_s(0)`` = the start and
     ``phi_s(0) = B psi_s(0)`` -- still a Hartree product: ``B`` acts on that site's vector, and the product is set with
     its own norm ``|B psi_s(0)|`` -- and the value is ``C(t) = sum_s w_s <psi_s(t)| A |phi_s(t)>``, i.e.
     ``<psi| A(t) B |psi>`` for a Hamiltonian that generates a unitary propagation.  With both ``None`` there is one
@@ -152,8 +222,17 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
         raise NotImplementedError("correlation_function: kraus_op means a purified state (a Kraus leg that grows)")
     dims = list(model.dims)
     nsite = len(dims)
+    D = model.m_aux_max if model.m_aux_max is not None else 10**9
+    a_mpo = b_mpo = None
     if A is not None:
-        A, B = _site_operator("A", A, dims), _site_operator("B", B, dims)
+        fa, fb = _operator_form("A", A, model, dims), _operator_form("B", B, model, dims)
+        A = fa[1:] if fa[0] == "site" else None
+        B = fb[1:] if fb[0] == "site" else None
+        a_mpo = fa[1] if fa[0] == "mpo" else None
+        b_mpo = fb[1] if fb[0] == "mpo" else None
+        if b_mpo is not None:
+            check_mpo_fits_bonds("B", b_mpo, dims, D)
+    two = A is not None or a_mpo is not None
     starts = [list(s) for s in starts]
     if not starts:
         raise ValueError("no start states")
@@ -166,7 +245,14 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
     for k, s in enumerate(starts):
         states.append(s)
         scales.append(1.0)
-        if B is not None:
+        if b_mpo is not None:
+            phi = mpo_on_product(b_mpo, s)
+            # |B psi| <= prod_p |W_p|_F for a normalised product: below 1e-14 of that it is rounding of the MPO's cores
+            if _mps_norm(phi) <= 1e-14 * float(np.prod([np.linalg.norm(w) for w in b_mpo])):
+                raise ValueError(f"correlation_function: B annihilates start {k}")
+            states.append(phi)
+            scales.append(None)
+        elif B is not None:
             v = np.asarray(s[B[0]], dtype=np.complex128)
             if v.ndim != 1:
                 raise ValueError("correlation_function: B acts on a start given as per-site vectors")
@@ -178,27 +264,32 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
     gates = model.one_gate_to_apply.one_site_gates(model.dims) if model.one_gate_to_apply is not None else {}
     dt_au = stepsize / units.au_in_fs
     nsteps = (maxstep - 1) // every * every
-    D = model.m_aux_max if model.m_aux_max is not None else 10**9
     mpo = model.project_mpo(model.hamiltonian.as_mpo(model.dims))
     bt = TDVPBatch(len(states), nsite, device=device, integrator=integrator, conserve_norm=conserve_norm, thresh=thresh_sil)
     try:
         for e, s, scale in zip(bt.engines, states, scales):
             e.set_mpo(mpo, 0, shift=model.hamiltonian.coupleJ[0][0])
+            if a_mpo is not None:
+                e.set_mpo(a_mpo, 1)
             e.set_mps(product_state_cores(s, D, space=model.space), canonicalize=True, scale=scale)
         if gates:
             bt.set_gates(gates)
-        if B is not None:
+        key = "cross"
+        if a_mpo is not None:
+            key = "cross_mpo"
+            bt.set_cross_mpo([(2 * k, 2 * k + 1, 1) for k in range(ns)])
+        elif two:
             bt.set_cross([(2 * k, 2 * k + 1, A[0], A[1]) for k in range(ns)])
         else:
             bt.snapshot()
             bt.set_cross([(bt.snap(k), k) for k in range(ns)])
-        rec = bt.propagate(dt_au, nsteps, observe=dict(norm=False, per_replica=False, cross=True, cross_weights=w), every=every)
+        rec = bt.propagate(dt_au, nsteps, observe={"norm": False, "per_replica": False, key: True, key + "_weights": w}, every=every)
     finally:
         bt.close()
     nrec = nsteps // every + 1
-    out = {"time": np.arange(nrec) * every * dt_au * units.au_in_fs, "mean": rec["mean_cross"]}
+    out = {"time": np.arange(nrec) * every * dt_au * units.au_in_fs, "mean": rec["mean_" + key]}
     if per_trajectory:
-        out["trajectories"] = rec["cross"]
+        out["trajectories"] = rec[key]
     return out
 
 
