@@ -443,6 +443,27 @@ int mitdvp_batch_expect_records(mitdvp_batch* b, const double* weights, double* 
 int mitdvp_batch_set_cross_mpo(mitdvp_batch* b, int nentries, const int* bra, const int* ket, const int* op_id);
 int mitdvp_batch_cross_mpo(mitdvp_batch* b, const double* weights, double* values, double* mean);
 int mitdvp_batch_cross_mpo_records(mitdvp_batch* b, const double* weights, double* values, double* mean, size_t counts[2]);
+/* An MPO applied to replicas of a batch (k_batch_operate: one workgroup per selected replica, ONE launch and one host
+ * wait for the whole fit of all of them): mitdvp_operate for every selected replica.  phi ~ O|psi> / |O|psi>| is fitted in
+ * the bond dimensions of psi by up to maxstep double sweeps of mixed-block applies, O the operator the replica carries under
+ * op_id (mitdvp_set_mpo_core; its scalar term, mitdvp_set_shift, goes through the overlap blocks); a replica stops on its
+ * own when |1 - |<phi_i|phi_{i-1}>|| < conv_tol, and reaching maxstep unconverged is not an error.  The fit is exact only
+ * where O psi fits the bonds.  replicas: nsel distinct replica indices, or NULL for all.  The selected replicas are WRITTEN:
+ * on return their tensors are phi, normalised, centre at site 0, gauge Psi B B ..., their blocks invalid.  norms, iters and
+ * statuses (each n entries, indexed by replica, each may be NULL) are written for the selected replicas only: the norm of
+ * the last apply at site 0, the double sweeps run, and MITDVP_OK or MITDVP_EINVAL.  An apply whose norm is not > 0 (the
+ * operator annihilates the state) stops that replica -- norm 0, MITDVP_EINVAL in its status, its message in
+ * mitdvp_last_error(its engine), its chain to be set again -- while the others finish; the call then returns MITDVP_EINVAL.
+ * Krylov memories, the jump generator's step counter and counters, channels, the snapshot, every request and the records
+ * of the last run are untouched; the call is allowed with channels set and in either relax mode.
+ * Refused with MITDVP_EINVAL before the GPU is touched, everything left as it was, the message naming the entry point, the
+ * replica / operator / site and the limit: maxstep < 1; conv_tol negative or not finite; a replica index out of range or
+ * repeated; a selected replica whose centre is not at site 0; an operator that a selected replica does not carry at every
+ * site; core shapes that differ between the selected replicas; MPO bonds outside 1 .. 16; outer MPO bonds that are not 1;
+ * neighbouring cores that do not fit; a work buffer (selected replicas x carve x 16 bytes) above 2^32 bytes: the message
+ * names both figures and the largest number of replicas that fits. */
+int mitdvp_batch_operate(mitdvp_batch* b, int op_id, int maxstep, double conv_tol, const int* replicas, int nsel, double* norms,
+                         int* iters, int* statuses);
 /* propagate_along_sweep (_mps_cls.py:798-1014), one direction only. */
 int mitdvp_sweep(mitdvp_engine* h, double dt_au, int forward);
 /* The same half-sweep in parts: the next `nsites` local updates of the half-sweep in progress (one is started when none

@@ -4,6 +4,7 @@
 #include <string>
 
 #include "batch_cross_mpo_plan.h"
+#include "batch_operate_plan.h"
 #include "batch_shape.h"
 #include "common.h"
 #include "small_site.h"
@@ -308,5 +309,34 @@ struct BatchCrossMpoArgs {
 };
 // one launch: grid = nentries workgroups; replicas, snapshots and operators are only read
 void batch_cross_mpo_launch(hipStream_t st, const BatchCrossMpoArgs& a, int nentries);
+
+// ---- an MPO applied to the replicas: the variational fit of Engine::operate (k_batch_operate) ----
+// phi ~ O|psi> / |O|psi>| in the bond dimensions of psi, for every SELECTED replica, the whole fit in one launch: up to
+// maxstep double sweeps in which every site tensor of the bra (the replica's own tensors) is replaced by the mixed-block
+// apply on the ket (a copy of the replica's tensors in the request's buffer), each replica stopping on its own when
+// |1 - |<phi_i | phi_{i-1}>|| < conv_tol.  The kernel WRITES the replica: on return its tensors are phi, normalised,
+// centre at site 0, sites 1 .. L-1 in gauge B.  BATCH_OPERATE_MAX_BYTES, BatchOperatePlan, batch_operate_plan and
+// batch_operate_fits: batch_operate_plan.h, which needs no HIP.
+struct BatchOperateCarve {  // the offsets of BatchOperatePlan, complex elements
+  size_t o_ket, o_prev, o_mix, o_ov, o_x, o_y, o_work, o_spare, o_h, o_sig, o_t0, o_t1, o_id, total;
+};
+struct BatchOperateArgs {
+  int L, maxstep;
+  double conv_tol;
+  const BatchShape* shp;   // [L], device: the site shapes with the operator's ml / mr
+  void* const* ptrs;       // the pointer table of BatchArgs (only its site tensors are used: read AND written)
+  int ptr_stride;
+  const int* replicas;     // [nsel], device: workgroup j owns replica replicas[j]
+  void* const* ops;        // [nsel][3][L], device: w2l, w2el, w2er of the operator on workgroup j's replica
+  const zc* shift;         // [nsel]: the operator's scalar term
+  const long long* offs;   // [3][L + 1], device: BatchOperatePlan::site, mix, ov
+  zc* buf;                 // [nsel][carve.total]
+  BatchOperateCarve carve;
+  int* status;             // [B], by replica: SS_EZERO when an apply gave a norm that is not > 0
+  double* norms;           // [nsel]: the norm of the last apply at site 0; 0 for a replica that stopped
+  int* iters;              // [nsel]: double sweeps run
+};
+// one launch: grid = nsel workgroups
+void batch_operate_launch(hipStream_t st, const BatchOperateArgs& a, int nsel);
 
 }  // namespace mitdvp

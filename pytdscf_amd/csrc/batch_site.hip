@@ -1380,7 +1380,11 @@ __device__ __noinline__ void bp_cprime(const zc* T, const zc* Bp, zc* Cp, int m,
       [&](int mm, int nn, zc z) { Cp[(long)mm * r + nn] = make_double2(z.x * scl, z.y * scl); });
 }
 
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): see DESIGN.md section 7.3.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 248 VGPRs, 106 SGPRs, no vector
+// register spills, 20 scalar registers spilled around the calls of the stage functions, 384 bytes of private memory per lane
+// (BopCtx, which the stage functions take by reference and read BEFORE their products, and the shape blocks bt_heff takes
+// by reference: none of it inside a product loop), 20 032 bytes of LDS; occupancy 2 waves per SIMD, i.e. one workgroup
+// (replica) per compute unit.  The other batch kernels compile to what they compiled to before.  DESIGN.md section 7.3.
 __global__ __launch_bounds__(SS_THREADS) void k_batch_pair(BatchPairArgs gp) {
   __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
   __shared__ zc s_z[3 * BATCH_MAX_BOND];
@@ -2023,7 +2027,307 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_cross_mpo(BatchCrossMpoArg
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// An MPO applied to the replicas: k_batch_operate, ONE workgroup per SELECTED replica (workgroup j owns replica
+// replicas[j]), the whole variational fit of Engine::operate / oracle.operate in one launch (BatchOperateArgs in
+// batch_site.h): phi ~ O|psi> / |O|psi>| in the bond dimensions of psi.  The bra, phi, lives in the replica's own site
+// tensors, which the kernel WRITES; the ket is a copy of them in the replica's carve of the request's buffer.
+//   setup      ket <- the replica's tensors (centre at site 0); blocks 0 and L of the mixed and of the overlap chain <- [1];
+//              p = L-1 .. 1: block p <- bt_env2(block p+1, bra_p, ket_p, w2er at p) in the mirror-image strides of the
+//              backward sweep (bra = ket here)
+//   double sweep it = 1 .. maxstep:
+//     prev <- bra
+//     p = 0 .. L-1:   bra_p <- bt_heff(block p, w2l at p, block p+1, ket_p)  [+ shift * the same apply of the overlap
+//                     blocks with the identity core]; nrm = |bra_p|; bra_p /= nrm; unless p = L-1: thin QR of bra_p (R
+//                     dropped: the next site is replaced) and of ket_p (R absorbed into ket_{p+1}), block p+1 <-
+//                     bt_env2(block p, bra_p, ket_p, w2el at p)  [and the overlap block with the identity core]
+//     p = L-1 .. 0:   the mirror image: QR of the transposes, R^T absorbed into ket_{p-1}, block p <- bt_env2(block p+1, ..,
+//                     w2er at p)
+//     ov = <bra | prev> by k_batch_cross's plain-overlap walk; stop when |1 - |ov|| < conv_tol
+//   norms[j] = nrm of the last apply at site 0, iters[j] = double sweeps run.  A norm that is not > 0 stops the replica:
+//   SS_EZERO in its status word, norms[j] = 0; the decision is formed from a workgroup reduction, the same in every thread.
+// One array of L + 1 blocks serves both directions: block b is the left block while the centre is at a site >= b and the
+// right block otherwise, and a half-sweep overwrites it exactly when its other role is spent.  The scalar term goes
+// through the overlap blocks as the engine does it: the identity core of MPO bond 1 (written into the carve for the
+// site's d before each use) through the same bt_heff / bt_env2.  L = 1: one apply per half-sweep, no QR.
+// What is resident where: LDS holds the two operand tiles of wg_gemm, the Householder scalars of a gauge move and the
+// reduction partials (20 032 bytes); everything of tensor size lives in the replica's carve of the REQUEST's own buffer
+// (BatchOperatePlan: ket, prev, the blocks, X, Y, the QR work matrix, ...), written and re-read by this workgroup only
+// between workgroup barriers.  Every element has one owner thread and every sum one order: a replica's result depends on
+// its tensors, its operator, maxstep and conv_tol only -- not on the selection, B or the compute unit.  No atomics, nothing
+// waits for another workgroup, every loop is bounded by the shapes and maxstep.  The stages are non-inlined functions that
+// take what they need by value, so that no private-memory access sits inside a product loop.
+struct BopCtx {
+  int L;
+  zc sft;
+  const BatchShape* shp;
+  zc* const* site;
+  const zc* const* w2l;
+  const zc* const* w2el;
+  const zc* const* w2er;
+  const long long *soff, *moff, *voff;
+  zc *ket, *mix, *ov, *X, *Y, *work, *spare, *H, *sig, *Id, *tiles;
+};
+
+// bt_env2's three products under a name of the fit's own: the fit calls them with both stride patterns, and a second
+// caller of bt_env2 itself would make k_batch_cross_mpo, whose strides are constants, compile to something else
+__device__ __noinline__ void bop_env(const zc* env, const zc* Tb, const zc* Tk, long sTi, long sTd, long sTo, const zc* W2e, int din,
+                                     int min_, int d, int dout, int mout, zc* X, zc* Y, zc* out, zc* tiles) {
+  const int nx = min_ * din;
+  // X[(c,a)][(p,s)] = sum_b conj(Bra(b,c,a)) env[b][(p,s)]
+  wg_gemm<false, false>(d * dout, nx, din, tiles,
+      [&](int m, int k) { const int c = m / dout, a = m - c * dout; const zc z = Tb[k * sTi + c * sTd + a * sTo]; return make_double2(z.x, -z.y); },
+      [&](int k, int n) { return env[(long)k * nx + n]; },
+      [&](int m, int n, zc z) { X[(long)m * nx + n] = z; });
+  // Y[a][(q,t)][s] = sum_(c,p) W2e[(q,t)][(c,p)] X[c][a][p][s]
+  const int kw = d * min_, mw = mout * d;
+  wg_gemm<true, false>(mw, dout * din, kw, tiles,
+      [&](int m, int k) { return W2e[(long)m * kw + k]; },
+      [&](int k, int n) {
+        const int c = k / min_, p = k - c * min_, a = n / din, ss = n - a * din;
+        return X[(((long)c * dout + a) * min_ + p) * din + ss];
+      },
+      [&](int m, int n, zc z) { const int a = n / din, ss = n - a * din; Y[((long)a * mw + m) * din + ss] = z; });
+  // out[(a,q)][r] = sum_(t,s) Y[(a,q)][(t,s)] Ket(s,t,r)
+  const int kr = d * din;
+  wg_gemm<true, false>(dout * mout, dout, kr, tiles,
+      [&](int m, int k) { return Y[(long)m * kr + k]; },
+      [&](int k, int n) { const int t = k / din, ss = k - t * din; return Tk[ss * sTi + t * sTd + n * sTo]; },
+      [&](int m, int n, zc z) { out[(long)m * dout + n] = z; });
+}
+
+// bt_matmul likewise: with a further caller of bt_matmul itself k_batch_channel compiles to something else (8 scalar
+// registers fewer, as it happens -- but "as before" is what the other kernels are held to)
+__device__ __noinline__ void bop_matmul(const zc* A, const zc* B, zc* tmp, zc* dst, int M, int N, int K, zc* tiles) {
+  wg_gemm<true, false>(M, N, K, tiles,
+      [&](int m, int k) { return A[(long)m * K + k]; },
+      [&](int k, int n) { return B[(long)k * N + n]; },
+      [&](int m, int n, zc z) { tmp[(long)m * N + n] = z; });
+  for (long e = threadIdx.x; e < (long)M * N; e += SS_THREADS) dst[e] = tmp[e];
+  __syncthreads();
+}
+
+// the d x d identity: the core (1, d, d, 1) of the scalar term's operator in all three of its forms
+__device__ __noinline__ void bop_ident(zc* Id, int d) {
+  for (int e = threadIdx.x; e < d * d; e += SS_THREADS) Id[e] = make_double2(e / d == e % d ? 1.0 : 0.0, 0.0);
+  __syncthreads();
+}
+
+// bra_p <- (mixed blocks) W ket_p [+ shift (overlap blocks) ket_p], normalised; returns the norm, the same bits in every
+// thread; a norm that is not > 0 leaves bra_p unscaled
+__device__ __noinline__ double bop_apply(const BopCtx& c, int p, const BtSh& sh) {
+  const BatchShape s = c.shp[p];
+  const long N = (long)s.dl * s.d * s.dr;
+  const zc* kt = c.ket + c.soff[p];
+  zc* out = c.site[p];
+  zc* X = c.X;
+  zc* Y = c.Y;
+  zc* tiles = c.tiles;
+  bt_heff(s, c.mix + c.moff[p], c.w2l[p], c.mix + c.moff[p + 1], kt, 1.0, X, Y, out, tiles);
+  const zc sft = c.sft;
+  const bool hs = sft.x != 0.0 || sft.y != 0.0;
+  zc* H = c.H;
+  if (hs) {
+    const BatchShape si{s.dl, s.d, s.dr, 1, 1};
+    zc* Id = c.Id;
+    bop_ident(Id, s.d);
+    bt_heff(si, c.ov + c.voff[p], Id, c.ov + c.voff[p + 1], kt, 1.0, X, Y, H, tiles);
+  }
+  double acc[1] = {0.0};
+  for (long e = threadIdx.x; e < N; e += SS_THREADS) {
+    zc z = out[e];
+    if (hs) {
+      const zc h = H[e];
+      z.x += sft.x * h.x - sft.y * h.y;
+      z.y += sft.x * h.y + sft.y * h.x;
+      out[e] = z;
+    }
+    acc[0] += z.x * z.x + z.y * z.y;
+  }
+  wg_reduce(acc, sh);
+  const double nrm = sqrt(sh.red[0]);
+  if (nrm > 0.0)
+    for (long e = threadIdx.x; e < N; e += SS_THREADS) {  // the same thread read or wrote out[e] above
+      zc z = out[e];
+      z.x /= nrm; z.y /= nrm;
+      out[e] = z;
+    }
+  __syncthreads();
+  return nrm;
+}
+
+// the centre of bra and ket moves from site p to p + 1 (fwd) or p - 1, and the block between them is renewed
+__device__ __noinline__ void bop_move(const BopCtx& c, int p, bool fwd, const BtSh& sh) {
+  const BatchShape s = c.shp[p];
+  const int dl = s.dl, d = s.d, dr = s.dr;
+  const bool hs = c.sft.x != 0.0 || c.sft.y != 0.0;
+  zc* bra = c.site[p];
+  zc* kt = c.ket + c.soff[p];
+  zc *X = c.X, *Y = c.Y, *sig = c.sig, *work = c.work, *spare = c.spare, *tiles = c.tiles, *Id = c.Id;
+  if (fwd) {
+    bt_qr(bra, bra, dr, 1, sig, dr, 1, dl * d, dr, work, sh);  // phi: Psi -> A, its R goes into a tensor that is replaced next
+    bt_qr(kt, kt, dr, 1, sig, dr, 1, dl * d, dr, work, sh);    // psi: Psi -> A sigma
+    const BatchShape q = c.shp[p + 1];
+    zc* nxt = c.ket + c.soff[p + 1];
+    bop_matmul(sig, nxt, spare, nxt, dr, q.d * q.dr, dr, tiles);
+    bop_env(c.mix + c.moff[p], bra, kt, (long)d * dr, dr, 1, c.w2el[p], dl, s.ml, d, dr, s.mr, X, Y, c.mix + c.moff[p + 1], tiles);
+    if (hs) {
+      bop_ident(Id, d);
+      bop_env(c.ov + c.voff[p], bra, kt, (long)d * dr, dr, 1, Id, dl, 1, d, dr, 1, X, Y, c.ov + c.voff[p + 1], tiles);
+    }
+  } else {
+    const int mq = d * dr;
+    bt_qr(bra, bra, 1, mq, sig, 1, dl, mq, dl, work, sh);  // Psi^T = Q R: B = Q^T in place
+    bt_qr(kt, kt, 1, mq, sig, 1, dl, mq, dl, work, sh);    // sigma = R^T (dl x dl)
+    const BatchShape q = c.shp[p - 1];
+    zc* prv = c.ket + c.soff[p - 1];
+    bop_matmul(prv, sig, spare, prv, q.dl * q.d, dl, dl, tiles);
+    bop_env(c.mix + c.moff[p + 1], bra, kt, 1, dr, (long)d * dr, c.w2er[p], dr, s.mr, d, dl, s.ml, X, Y, c.mix + c.moff[p], tiles);
+    if (hs) {
+      bop_ident(Id, d);
+      bop_env(c.ov + c.voff[p + 1], bra, kt, 1, dr, (long)d * dr, Id, dr, 1, d, dl, 1, X, Y, c.ov + c.voff[p], tiles);
+    }
+  }
+}
+
+// <bra | prev> over all sites: the walk and the products of k_batch_cross with site = -1; the same bits in every thread
+__device__ __noinline__ zc bop_overlap(int L, const BatchShape* shp, zc* const* site, const zc* prev, const long long* soff, zc* T,
+                                       zc* T2, zc* U, zc* tiles) {
+  if (threadIdx.x == 0) T[0] = make_double2(1.0, 0.0);
+  __syncthreads();
+  for (int p = 0; p < L; ++p) {
+    const BatchShape s = shp[p];
+    const int dl = s.dl, d = s.d, dr = s.dr, ddr = d * dr;
+    const zc* Kt = prev + soff[p];
+    const zc* Bt = site[p];
+    // U[m][(j,s)] = sum_n T[m][n] K[n][(j,s)]
+    wg_gemm<true, false>(dl, ddr, dl, tiles,
+        [&](int m, int kk) { return T[(long)m * dl + kk]; },
+        [&](int kk, int n) { return Kt[(long)kk * ddr + n]; },
+        [&](int m, int n, zc z) { U[(long)m * ddr + n] = z; });
+    // T'[i][j] = sum_(m,s) conj(Bra[(m,s)][i]) U[(m,s)][j]
+    wg_gemm<false, false>(dr, dr, dl * d, tiles,
+        [&](int m, int kk) { const zc z = Bt[(long)kk * dr + m]; return make_double2(z.x, -z.y); },
+        [&](int kk, int n) { return U[(long)kk * dr + n]; },
+        [&](int m, int n, zc z) { T2[(long)m * dr + n] = z; });
+    zc* t = T; T = T2; T2 = t;
+  }
+  const zc ov = T[0];
+  __syncthreads();  // every thread has read the value before the blocks are used again
+  return ov;
+}
+
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): see DESIGN.md section 7.3.
+__global__ __launch_bounds__(SS_THREADS) void k_batch_operate(BatchOperateArgs g) {
+  __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
+  __shared__ zc s_z[2 * BATCH_MAX_BOND];
+  __shared__ double s_d[SS_WAVES * 8 + 8 + BATCH_MAX_BOND];
+  BtSh sh{};
+  sh.mats = s_tiles;
+  sh.wsh = s_d;
+  sh.red = s_d + SS_WAVES * 8;
+  sh.gam = sh.red + 8;
+  sh.udiag = s_z;
+  sh.rdiag = s_z + BATCH_MAX_BOND;
+
+  const int j = blockIdx.x, tid = threadIdx.x, L = g.L;
+  const int r = g.replicas[j];
+  zc* buf = g.buf + (size_t)j * g.carve.total;
+  BopCtx c;
+  c.L = L;
+  c.sft = g.shift[j];
+  c.shp = g.shp;
+  c.site = reinterpret_cast<zc* const*>(g.ptrs + (size_t)r * g.ptr_stride);
+  c.w2l = reinterpret_cast<const zc* const*>(g.ops + (size_t)j * 3 * L);
+  c.w2el = c.w2l + L;
+  c.w2er = c.w2l + 2 * L;
+  c.soff = g.offs;
+  c.moff = g.offs + (L + 1);
+  c.voff = g.offs + 2 * (L + 1);
+  c.ket = buf + g.carve.o_ket;
+  c.mix = buf + g.carve.o_mix;
+  c.ov = buf + g.carve.o_ov;
+  c.X = buf + g.carve.o_x;
+  c.Y = buf + g.carve.o_y;
+  c.work = buf + g.carve.o_work;
+  c.spare = buf + g.carve.o_spare;
+  c.H = buf + g.carve.o_h;
+  c.sig = buf + g.carve.o_sig;
+  c.Id = buf + g.carve.o_id;
+  c.tiles = s_tiles;
+  zc* prev = buf + g.carve.o_prev;
+  zc* T0 = buf + g.carve.o_t0;
+  zc* T1 = buf + g.carve.o_t1;
+  const bool hs = c.sft.x != 0.0 || c.sft.y != 0.0;  // uniform: the scalar term is the replica's
+
+  // setup: the ket, the boundary blocks, the right blocks of the initial bra = ket pair
+  for (int p = 0; p < L; ++p) {
+    const long N = c.soff[p + 1] - c.soff[p];
+    const zc* src = c.site[p];
+    zc* dst = c.ket + c.soff[p];
+    for (long e = tid; e < N; e += SS_THREADS) dst[e] = src[e];
+  }
+  if (tid == 0) {
+    const zc one = make_double2(1.0, 0.0);
+    c.mix[c.moff[0]] = one; c.mix[c.moff[L]] = one;
+    c.ov[c.voff[0]] = one; c.ov[c.voff[L]] = one;
+  }
+  __syncthreads();
+  for (int p = L - 1; p >= 1; --p) {
+    const BatchShape s = c.shp[p];
+    const zc* kt = c.ket + c.soff[p];
+    bop_env(c.mix + c.moff[p + 1], c.site[p], kt, 1, s.dr, (long)s.d * s.dr, c.w2er[p], s.dr, s.mr, s.d, s.dl, s.ml, c.X, c.Y,
+            c.mix + c.moff[p], c.tiles);
+    if (hs) {
+      bop_ident(c.Id, s.d);
+      bop_env(c.ov + c.voff[p + 1], c.site[p], kt, 1, s.dr, (long)s.d * s.dr, c.Id, s.dr, 1, s.d, s.dl, 1, c.X, c.Y, c.ov + c.voff[p],
+              c.tiles);
+    }
+  }
+
+  double nrm = 0.0;
+  bool dead = false;
+  int it = 1;
+  for (; it <= g.maxstep; ++it) {
+    for (int p = 0; p < L; ++p) {
+      const long N = c.soff[p + 1] - c.soff[p];
+      const zc* src = c.site[p];
+      zc* dst = prev + c.soff[p];
+      for (long e = tid; e < N; e += SS_THREADS) dst[e] = src[e];
+    }
+    __syncthreads();
+    for (int p = 0; p < L && !dead; ++p) {  // ->
+      nrm = bop_apply(c, p, sh);
+      dead = !(nrm > 0.0);
+      if (!dead && p < L - 1) bop_move(c, p, true, sh);
+    }
+    for (int p = L - 1; p >= 0 && !dead; --p) {  // <-
+      nrm = bop_apply(c, p, sh);
+      dead = !(nrm > 0.0);
+      if (!dead && p > 0) bop_move(c, p, false, sh);
+    }
+    if (dead) break;
+    const zc ov = bop_overlap(L, c.shp, c.site, prev, c.soff, T0, T1, c.X, c.tiles);
+    // _is_converged: |1 - |<phi_i | phi_{i-1}>|| < conv_tol
+    if (fabs(1.0 - sqrt(ov.x * ov.x + ov.y * ov.y)) < g.conv_tol || it == g.maxstep) break;
+  }
+  if (tid == 0) {
+    if (dead) g.status[r] = SS_EZERO;
+    g.norms[j] = dead ? 0.0 : nrm;
+    g.iters[j] = it;
+  }
+}
+
 }  // namespace
+
+void batch_operate_launch(hipStream_t st, const BatchOperateArgs& a, int nsel) {
+  if (nsel < 1 || a.L < 1 || a.maxstep < 1) throw ArgError("batch: no replica to apply the operator to");
+  if (!a.shp || !a.ptrs || !a.replicas || !a.ops || !a.shift || !a.offs || !a.buf || !a.status || !a.norms || !a.iters ||
+      a.carve.total < 1)
+    throw ArgError("batch: the operator application has no buffers");
+  hipLaunchKernelGGL(k_batch_operate, dim3(nsel), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
 
 void batch_cross_mpo_launch(hipStream_t st, const BatchCrossMpoArgs& a, int nentries) {
   if (nentries < 1 || nentries > BATCH_CROSS_MAX_PAIRS || a.L < 1 || a.nrep < 1 || a.nops < 1)

@@ -371,6 +371,27 @@ int mitdvp_batch_cross_mpo_records(mitdvp_batch* b, const double* weights, doubl
   if (!b || !b->b) { g_err = "mitdvp_batch_cross_mpo_records: null handle"; return MITDVP_EINVAL; }
   return guard(nullptr, [&] { b->b->cross_mpo_records(weights, values, mean, counts); });
 }
+int mitdvp_batch_operate(mitdvp_batch* b, int op_id, int maxstep, double conv_tol, const int* replicas, int nsel, double* norms,
+                         int* iters, int* statuses) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_operate: null handle"; return MITDVP_EINVAL; }
+  const size_t n = (size_t)b->b->size();
+  std::vector<int> st(n, -1);  // -1: not selected, left as given
+  const int rc = guard(nullptr, [&] { b->b->operate(op_id, maxstep, conv_tol, replicas, nsel, norms, iters, st.data()); });
+  if (rc != MITDVP_OK) return rc;
+  int first = MITDVP_OK;
+  for (size_t i = 0; i < n; ++i) {
+    if (st[i] < 0) continue;
+    int code = MITDVP_OK;
+    if (st[i] != mitdvp::SS_OK) {
+      code = MITDVP_EINVAL;
+      b->hs[i]->err = "mitdvp_batch_operate: the operator annihilates the state of replica " + std::to_string(i) +
+                      " (an apply gave a norm that is not > 0)";
+      if (first == MITDVP_OK) first = code;
+    }
+    if (statuses) statuses[i] = code;
+  }
+  return first;
+}
 void mitdvp_batch_destroy(mitdvp_batch* b) { delete b; }
 int mitdvp_invalidate_env(mitdvp_engine* h) { ENG_CALL(h, h->e->invalidate_env()); }
 int mitdvp_replace_site(mitdvp_engine* h, int isite, const double* reim, int gauge) {

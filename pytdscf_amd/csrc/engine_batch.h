@@ -181,6 +181,24 @@ class Batch {
   // means of the run, no launch and no wait; weights given: ONE k_batch_mean launch over the records and one host wait.
   void cross_mpo_records(const double* weights, double* values, double* mean, size_t* counts);
 
+  // ---- an MPO applied to the replicas (k_batch_operate) ----
+  // Engine::operate for every selected replica in ONE launch and one host wait: phi ~ O|psi> / |O|psi>| in the bond
+  // dimensions of psi, O the operator every selected replica carries under op_id (its scalar term included), up to maxstep
+  // double sweeps, each replica stopping on its own when |1 - |<phi_i | phi_{i-1}>|| < conv_tol; reaching maxstep is not
+  // an error.  replicas: nsel distinct replica indices, null: all of them.  The selected replicas are WRITTEN: on return
+  // their tensors are phi, normalised, centre at site 0, gauge Psi B B ..., every block invalid.  norms [B], iters [B] and
+  // statuses [B] are indexed by replica and may each be null; entries of replicas that are not selected are left as given.
+  // norms[r]: the norm of the last apply at site 0; iters[r]: double sweeps run; statuses[r]: SS_OK, or SS_EZERO when an
+  // apply gave a norm that is not > 0 -- that replica stops (norms[r] = 0, gauge C, centre -1, as a replica that stopped in
+  // a step), the others finish.  Krylov memories, the jump generator, channels, the snapshot, every request and the records
+  // of the last run() are untouched.  Refused before the GPU is touched, with an ArgError that names the entry point, the
+  // replica / operator / site and the limit and leaves everything as it was: maxstep < 1, conv_tol negative or not finite,
+  // a replica index out of range or repeated, a selected replica whose centre is not at site 0, an operator that a selected
+  // replica does not carry at every site, core shapes that differ between the selected replicas, MPO bonds outside
+  // 1 .. BATCH_MAX_MPO, outer MPO bonds that are not 1, neighbouring cores that do not fit, a buffer (selected replicas x
+  // carve x 16 bytes, batch_operate_plan.h) above BATCH_OPERATE_MAX_BYTES.
+  void operate(int op_id, int maxstep, double conv_tol, const int* replicas, int nsel, double* norms, int* iters, int* statuses);
+
   std::string status_message(int code) const;
   int size() const { return (int)eng_.size(); }
   int device() const { return device_; }
@@ -340,7 +358,22 @@ class Batch {
   void expect_weights(const double* weights);
   // the shapes [nops][L] of the listed operators on the engines as they are now (the gathering half of expect_shapes);
   // ArgError naming the entry point, the operator, the site and the replica otherwise
-  void operator_shapes(const char* entry, const int* op_ids, int nops, std::vector<BatchShape>& shp) const;
+  // only: the replicas to look at (nonly of them), null: all
+  void operator_shapes(const char* entry, const int* op_ids, int nops, std::vector<BatchShape>& shp, const int* only = nullptr,
+                       int nonly = 0) const;
+
+  // operate(): the tables of one call (grow only): the selected replicas [nsel], w2l / w2el / w2er of the operator
+  // [nsel][3][L], its scalar terms [nsel], the shapes [L] with its MPO bonds, the carve's prefix sums [3][L + 1], the
+  // carves [nsel][total], the norms and sweep counts [nsel]
+  int* d_op_rep_ = nullptr;
+  void** d_op_ptrs_ = nullptr;
+  zc *d_op_shift_ = nullptr, *d_op_buf_ = nullptr;
+  BatchShape* d_op_shp_ = nullptr;
+  long long* d_op_offs_ = nullptr;
+  double* d_op_norms_ = nullptr;
+  int* d_op_iters_ = nullptr;
+  size_t op_rep_elems_ = 0, op_ptrs_elems_ = 0, op_shift_elems_ = 0, op_buf_elems_ = 0, op_shp_elems_ = 0, op_offs_elems_ = 0,
+         op_norms_elems_ = 0, op_iters_elems_ = 0;
 
   // cross request of MPOs: the entries (op = index into xm_ops_, the distinct operator ids in order of first use), the
   // shapes [nops][L] and the carve they give, the device tables (w2el [B][nops][L], shapes, shifts [B][nops]; refreshed

@@ -197,6 +197,14 @@ Batch::~Batch() {
   if (d_xm_rec_) (void)hipFree(d_xm_rec_);
   if (d_xm_mean_) (void)hipFree(d_xm_mean_);
   if (d_xm_w_) (void)hipFree(d_xm_w_);
+  if (d_op_rep_) (void)hipFree(d_op_rep_);
+  if (d_op_ptrs_) (void)hipFree(d_op_ptrs_);
+  if (d_op_shift_) (void)hipFree(d_op_shift_);
+  if (d_op_buf_) (void)hipFree(d_op_buf_);
+  if (d_op_shp_) (void)hipFree(d_op_shp_);
+  if (d_op_offs_) (void)hipFree(d_op_offs_);
+  if (d_op_norms_) (void)hipFree(d_op_norms_);
+  if (d_op_iters_) (void)hipFree(d_op_iters_);
   if (st_) (void)hipStreamDestroy(st_);
 }
 
@@ -1339,12 +1347,16 @@ void Batch::expect_shapes(const char* entry, const int* op_ids, int nops, std::v
   if (!batch_expect_plan(shp.data(), op_ids, L_, nops, plan, why)) throw ArgError(std::string(entry) + ": " + why);
 }
 
-void Batch::operator_shapes(const char* entry, const int* op_ids, int nops, std::vector<BatchShape>& shp) const {
+void Batch::operator_shapes(const char* entry, const int* op_ids, int nops, std::vector<BatchShape>& shp, const int* only,
+                            int nonly) const {
   const std::string at = std::string(entry) + ": ";
   shp.assign((size_t)nops * L_, BatchShape{});
+  const size_t nlook = only ? (size_t)nonly : eng_.size();
+  const size_t first = only && nonly > 0 ? (size_t)only[0] : 0;
   for (int k = 0; k < nops; ++k) {
     const std::string op = "operator " + std::to_string(op_ids[k]) + " ";
-    for (size_t i = 0; i < eng_.size(); ++i) {
+    for (size_t ii = 0; ii < nlook; ++ii) {
+      const size_t i = only ? (size_t)only[ii] : ii;
       const Engine& e = *eng_[i];
       auto it = e.ops_.find(op_ids[k]);
       for (int p = 0; p < L_; ++p) {
@@ -1356,10 +1368,10 @@ void Batch::operator_shapes(const char* entry, const int* op_ids, int nops, std:
           throw ArgError(at + op + "has physical dimension " + std::to_string(w.d) + " at site " + std::to_string(p) + " of replica " +
                          std::to_string(i) + ", the site's is " + std::to_string(shp_[p].d));
         BatchShape& s = shp[(size_t)k * L_ + p];
-        if (i == 0) s = BatchShape{shp_[p].dl, shp_[p].d, shp_[p].dr, w.ml, w.mr};
+        if (ii == 0) s = BatchShape{shp_[p].dl, shp_[p].d, shp_[p].dr, w.ml, w.mr};
         else if (w.ml != s.ml || w.mr != s.mr)
           throw ArgError(at + op + "has MPO bonds (" + std::to_string(w.ml) + ", " + std::to_string(w.mr) + ") at site " + std::to_string(p) +
-                         " of replica " + std::to_string(i) + ", replica 0 has (" + std::to_string(s.ml) + ", " + std::to_string(s.mr) +
+                         " of replica " + std::to_string(i) + ", replica " + std::to_string(first) + " has (" + std::to_string(s.ml) + ", " + std::to_string(s.mr) +
                          "): the core shapes must be equal across the replicas");
       }
     }
@@ -1695,6 +1707,132 @@ void Batch::cross_mpo_records(const double* weights, double* values, double* mea
   n_launch_ += 1;
   HIP_CHECK(hipMemcpyAsync(mean, dst, nrec * 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
   finish_observe(1, nullptr);
+}
+
+// ---- an MPO applied to the replicas (k_batch_operate) ----
+void Batch::operate(int op_id, int maxstep, double conv_tol, const int* replicas, int nsel, double* norms, int* iters, int* statuses) {
+  const std::string at = "mitdvp_batch_operate: ";
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  const int B = (int)eng_.size();
+  if (maxstep < 1) throw ArgError(at + "maxstep = " + std::to_string(maxstep) + ", it must be >= 1");
+  if (!(conv_tol >= 0.0) || !std::isfinite(conv_tol))
+    throw ArgError(at + "conv_tol = " + std::to_string(conv_tol) + ", it must be finite and >= 0");
+  if (op_id < 0) throw ArgError(at + "operator " + std::to_string(op_id) + " is negative (operator ids are >= 0)");
+  std::vector<int> sel;
+  if (replicas) {
+    if (nsel < 1) throw ArgError(at + "the list of replicas is empty (null selects all " + std::to_string(B) + ")");
+    std::vector<char> seen((size_t)B, 0);
+    for (int k = 0; k < nsel; ++k) {
+      const int r = replicas[k];
+      if (r < 0 || r >= B)
+        throw ArgError(at + "replica " + std::to_string(r) + " (entry " + std::to_string(k) + " of the list) is outside 0 .. " +
+                       std::to_string(B - 1));
+      if (seen[(size_t)r]) throw ArgError(at + "replica " + std::to_string(r) + " is listed twice (entry " + std::to_string(k) + ")");
+      seen[(size_t)r] = 1;
+    }
+    sel.assign(replicas, replicas + nsel);
+  } else {
+    sel.resize((size_t)B);
+    for (int r = 0; r < B; ++r) sel[(size_t)r] = r;
+  }
+  const size_t ns = sel.size();
+  for (int r : sel)
+    if (eng_[(size_t)r]->center_ != 0)
+      throw ArgError(at + "replica " + std::to_string(r) + " has its centre at site " + std::to_string(eng_[(size_t)r]->center_) +
+                     "; the fit starts from the centre at site 0 (the state a batch step leaves)");
+  std::vector<BatchShape> shp;
+  operator_shapes("mitdvp_batch_operate", &op_id, 1, shp, sel.data(), (int)ns);
+  BatchOperatePlan plan;
+  std::string why;
+  if (!batch_operate_plan(shp.data(), op_id, L_, plan, why)) throw ArgError(at + why);
+  if (!batch_operate_fits(ns, plan, why)) throw ArgError(at + why);
+
+  prepare(true, false);  // canonical chains around site 0; the pointer table, zeroed status words, the engines' streams
+  const size_t need_ptrs = ns * 3 * L_, need_offs = (size_t)3 * (L_ + 1), need_buf = ns * plan.total;
+  if (ns > op_rep_elems_ || need_ptrs > op_ptrs_elems_ || ns > op_shift_elems_ || need_buf > op_buf_elems_ ||
+      (size_t)L_ > op_shp_elems_ || need_offs > op_offs_elems_ || ns > op_norms_elems_ || ns > op_iters_elems_) {
+    HIP_CHECK(hipStreamSynchronize(st_));
+    auto grow = [&](auto*& p, size_t& have, size_t need) {
+      if (p && need <= have) return;
+      if (p) (void)hipFree(p);
+      p = nullptr;
+      dev_alloc(p, need);
+      have = need;
+    };
+    grow(d_op_rep_, op_rep_elems_, ns);
+    grow(d_op_ptrs_, op_ptrs_elems_, need_ptrs);
+    grow(d_op_shift_, op_shift_elems_, ns);
+    grow(d_op_buf_, op_buf_elems_, need_buf);
+    grow(d_op_shp_, op_shp_elems_, (size_t)L_);
+    grow(d_op_offs_, op_offs_elems_, need_offs);
+    grow(d_op_norms_, op_norms_elems_, ns);
+    grow(d_op_iters_, op_iters_elems_, ns);
+  }
+  std::vector<void*> h_ptrs(need_ptrs);
+  std::vector<zc> h_shift(ns);
+  std::vector<long long> h_offs(need_offs);
+  for (size_t k = 0; k < ns; ++k) {
+    const Operator& o = eng_[(size_t)sel[k]]->ops_.find(op_id)->second;
+    void** q = h_ptrs.data() + k * 3 * L_;
+    for (int p = 0; p < L_; ++p) {
+      q[p] = o.sites[p].w2l.p;
+      q[L_ + p] = o.sites[p].w2el.p;
+      q[2 * L_ + p] = o.sites[p].w2er.p;
+    }
+    h_shift[k] = make_double2(o.shift.real(), o.shift.imag());
+  }
+  for (int b = 0; b <= L_; ++b) {
+    h_offs[(size_t)b] = plan.site[(size_t)b];
+    h_offs[(size_t)(L_ + 1) + b] = plan.mix[(size_t)b];
+    h_offs[(size_t)2 * (L_ + 1) + b] = plan.ov[(size_t)b];
+  }
+  // the sources are locals: they live until the host wait below
+  HIP_CHECK(hipMemcpyAsync(d_op_rep_, sel.data(), ns * sizeof(int), hipMemcpyHostToDevice, st_));
+  HIP_CHECK(hipMemcpyAsync(d_op_ptrs_, h_ptrs.data(), need_ptrs * sizeof(void*), hipMemcpyHostToDevice, st_));
+  HIP_CHECK(hipMemcpyAsync(d_op_shift_, h_shift.data(), ns * sizeof(zc), hipMemcpyHostToDevice, st_));
+  HIP_CHECK(hipMemcpyAsync(d_op_shp_, shp.data(), (size_t)L_ * sizeof(BatchShape), hipMemcpyHostToDevice, st_));
+  HIP_CHECK(hipMemcpyAsync(d_op_offs_, h_offs.data(), need_offs * sizeof(long long), hipMemcpyHostToDevice, st_));
+
+  BatchOperateArgs a{};
+  a.L = L_;
+  a.maxstep = maxstep;
+  a.conv_tol = conv_tol;
+  a.shp = d_op_shp_;
+  a.ptrs = d_ptrs_;
+  a.ptr_stride = (int)ptrs_per_replica();
+  a.replicas = d_op_rep_;
+  a.ops = d_op_ptrs_;
+  a.shift = d_op_shift_;
+  a.offs = d_op_offs_;
+  a.buf = d_op_buf_;
+  a.carve = BatchOperateCarve{plan.o_ket, plan.o_prev, plan.o_mix, plan.o_ov, plan.o_x, plan.o_y, plan.o_work, plan.o_spare,
+                              plan.o_h, plan.o_sig, plan.o_t0, plan.o_t1, plan.o_id, plan.total};
+  a.status = d_status_;
+  a.norms = d_op_norms_;
+  a.iters = d_op_iters_;
+  batch_operate_launch(st_, a, (int)ns);
+  n_launch_ += 1;
+
+  std::vector<int> st((size_t)B), h_iters(ns);
+  std::vector<double> h_norms(ns);
+  HIP_CHECK(hipMemcpyAsync(st.data(), d_status_, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipMemcpyAsync(h_norms.data(), d_op_norms_, ns * sizeof(double), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipMemcpyAsync(h_iters.data(), d_op_iters_, ns * sizeof(int), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipStreamSynchronize(st_));  // the one host wait of the call
+  eng_[0]->cnt_.n_launch += 1;           // the batch's launches are counted once
+  for (size_t k = 0; k < ns; ++k) {
+    const int r = sel[k];
+    Engine& e = *eng_[(size_t)r];
+    const bool ok = st[(size_t)r] == SS_OK;
+    for (int p = 0; p < L_; ++p) e.gauge_[p] = !ok ? MITDVP_GAUGE_C : (p == 0 ? MITDVP_GAUGE_PSI : MITDVP_GAUGE_B);
+    e.center_ = ok ? 0 : -1;
+    for (int b = 1; b < L_; ++b) { e.envL_ok_[b] = 0; e.envR_ok_[b] = 0; }  // the blocks describe the state before the fit
+    (void)e.take_env_checked();
+    if (norms) norms[r] = h_norms[k];
+    if (iters) iters[r] = h_iters[k];
+    if (statuses) statuses[r] = st[(size_t)r];
+  }
 }
 
 std::string Batch::status_message(int code) const {

@@ -930,6 +930,55 @@ def sample_request(nshots, seed=0) -> tuple[int, int]:
     return int(nshots), int(seed)
 
 
+def operate_request(n_replicas, op_id=0, maxstep=10, conv_tol=1.0e-8, replicas=None):
+    """The arguments of ``TDVPBatch.operate`` as plain numbers: ``(op_id, maxstep, conv_tol, replicas)`` with ``replicas``
+    a list of distinct replica indices or ``None`` for all ``n_replicas``.  ``ValueError`` naming the argument and the
+    limit for an ``op_id`` or ``maxstep`` that is not a whole number or does not fit the library's ``int``, a negative
+    ``op_id``, ``maxstep < 1``, a ``conv_tol`` that is not a number, is negative or not finite, and a replica that is not
+    a whole number, is outside ``0 .. n_replicas - 1`` or is listed twice; an empty list selects nothing and is refused
+    too.  Whether the replicas carry the operator, and its shapes, are the library's to check
+    (``mitdvp_batch_operate``).  Pure Python."""
+    import math
+    import numbers
+
+    def whole(name, x):
+        if isinstance(x, bool) or not isinstance(x, (numbers.Integral, np.integer)):
+            raise ValueError(f"operate: {name} = {x!r} is not a whole number")
+        if not -2**31 <= int(x) < 2**31:
+            raise ValueError(f"operate: {name} = {x!r} does not fit an int")
+        return int(x)
+
+    op_id, maxstep = whole("op_id", op_id), whole("maxstep", maxstep)
+    if op_id < 0:
+        raise ValueError(f"operate: op_id = {op_id} is negative (operator ids are >= 0)")
+    if maxstep < 1:
+        raise ValueError(f"operate: maxstep = {maxstep}, it must be >= 1")
+    if isinstance(conv_tol, bool) or not isinstance(conv_tol, (numbers.Real, np.floating, np.integer)):
+        raise ValueError(f"operate: conv_tol = {conv_tol!r} is not a number")
+    conv_tol = float(conv_tol)
+    if not math.isfinite(conv_tol) or conv_tol < 0.0:
+        raise ValueError(f"operate: conv_tol = {conv_tol!r}, it must be finite and >= 0")
+    if replicas is None:
+        return op_id, maxstep, conv_tol, None
+    if isinstance(replicas, (numbers.Integral, np.integer)) and not isinstance(replicas, bool):
+        replicas = [replicas]
+    try:
+        items = list(replicas)
+    except TypeError:
+        raise ValueError(f"operate: replicas = {replicas!r}: a list of replica indices, or None for all") from None
+    if not items:
+        raise ValueError("operate: replicas is empty (None selects all)")
+    out = []
+    for r in items:
+        r = whole("replica", r)
+        if not 0 <= r < n_replicas:
+            raise ValueError(f"operate: replica {r} is outside 0 .. {n_replicas - 1}")
+        if r in out:
+            raise ValueError(f"operate: replica {r} is listed twice")
+        out.append(r)
+    return op_id, maxstep, conv_tol, out
+
+
 class TDVPBatch:
     """B independent trajectories (replicas) of one chain shape on ONE GPU, any B: one kernel launch per half-sweep for the
     whole batch (``mitdvp_batch_step`` / ``k_batch_sweep``: one workgroup owns one replica, the replica index is the
@@ -960,6 +1009,7 @@ class TDVPBatch:
         self._samples = None
         self._expect = None
         self._cross_mpo = None
+        self.operated = {}
         self._lib = _lib.load()
         try:
             for _ in range(n_replicas):
@@ -988,6 +1038,7 @@ class TDVPBatch:
         self._samples = None
         self._expect = None
         self._cross_mpo = None
+        self.operated = {}
         self._lib = _lib.load()
         return self
 
@@ -1507,6 +1558,30 @@ class TDVPBatch:
         mean = np.zeros(nrec, dtype=np.complex128)
         _lib.check(self._lib.mitdvp_batch_cross_mpo_records(self._b, None if w is None else _dp(w), _dp(vals), _dp(mean), cnt))
         return vals, mean
+
+    # ---- an MPO applied to the replicas (mitdvp_batch_operate) ----
+    def operate(self, op_id: int = 0, maxstep: int = 10, conv_tol: float = 1.0e-8, replicas=None):
+        """``TDVPEngine.operate`` for every selected replica in ONE launch and one host wait (``k_batch_operate``, one
+        workgroup per selected replica): each replica's state becomes ``phi ~ O|psi> / |O|psi>|``, fitted in the bond
+        dimensions of ``psi`` by up to ``maxstep`` double sweeps, ``O`` the MPO the replica carries under ``op_id``
+        (``set_mpo``, its ``shift`` included); a replica stops on its own when ``|1 - |<phi_i|phi_{i-1}>|| < conv_tol``.
+        The fit is exact only where ``O psi`` fits the bonds.  ``replicas``: a list of distinct replica indices, default
+        all.  The selected replicas must have their centre at site 0 and are left normalised, centre at site 0.
+
+        Returns ``{"norms": (B,), "iterations": (B,) int, "statuses": list}`` indexed by replica: the norm ``|O psi|``
+        of the last apply and the double sweeps run; entries of replicas that were not selected are 0.  A replica that
+        the operator annihilates stops with norm 0 while the others finish; the call then raises that replica's error
+        and leaves every status in ``statuses``, as ``propagate`` does, and the norms and counts in ``operated``."""
+        n = len(self.engines)
+        op_id, maxstep, conv_tol, sel = operate_request(n, op_id, maxstep, conv_tol, replicas)
+        norms = np.zeros(n, dtype=np.float64)
+        iters = np.zeros(n, dtype=np.int32)
+        rep = None if sel is None else (C.c_int * len(sel))(*sel)
+        nsel = 0 if sel is None else len(sel)
+        self.operated = {"norms": norms, "iterations": iters}  # what the call filled in is kept when it raises
+        self._run(lambda b, st: self._lib.mitdvp_batch_operate(b, op_id, maxstep, conv_tol, rep, nsel, _dp(norms),
+                                                                iters.ctypes.data_as(C.POINTER(C.c_int)), st))
+        return {"norms": norms, "iterations": iters, "statuses": list(self.statuses)}
 
     def launches(self) -> int:
         """kernel launches counted so far on replica 0, where the batch's launches are counted once"""

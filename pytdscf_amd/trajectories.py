@@ -18,7 +18,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import units
-from .engine import TDVPBatch, density_key_legs, pair_key, sample_request, spectra_bonds
+from .engine import TDVPBatch, density_key_legs, operate_request, pair_key, sample_request, spectra_bonds
 from .mps import bond_dims, product_state_cores
 
 
@@ -165,6 +165,51 @@ def mpo_on_product(cores, vectors):
     return out
 
 
+def core_starts(starts, dims, D):
+    """``None`` when every start is a Hartree product (one vector per site).  Otherwise every start must be an MPS, one
+    ``(dl, d, dr)`` array per site, and the result is the starts as complex cores zero-padded to the bond dimensions of
+    ``model.m_aux_max`` (``bond_dims(dims, D)``), the shapes every replica of a batch shares.  ``ValueError`` naming the
+    start, the site and the limit for a site that is not of rank 3 (vectors and cores may not be mixed), a physical
+    dimension that is not the model's, neighbouring bonds that do not fit, outer bonds that are not 1, and a bond above
+    what ``model.m_aux_max`` allows there.  Pure Python: raised before any engine exists."""
+    starts = [list(s) for s in starts]
+    if all(np.ndim(c) == 1 for s in starts for c in s):
+        return None
+    full = bond_dims(list(dims), D)
+    out = []
+    for k, s in enumerate(starts):
+        who = f"correlation_function: start {k}"
+        if len(s) != len(dims):
+            raise ValueError(f"{who} has {len(s)} cores, the chain has {len(dims)} sites")
+        left, cores = 1, []
+        for p, (c, d) in enumerate(zip(s, dims)):
+            c = np.asarray(c, dtype=np.complex128)
+            if c.ndim != 3:
+                raise ValueError(f"{who}, site {p}: an MPS core is (dl, d, dr), got an array of rank {c.ndim} (shape {c.shape}); "
+                                 "a start is cores at every site or vectors at every site, and so are all starts")
+            if c.shape[1] != d:
+                raise ValueError(f"{who}, site {p}: the core has physical dimension {c.shape[1]}, the model's is {d}")
+            if c.shape[0] != left:
+                raise ValueError(f"{who}, site {p}: the core has the left bond {c.shape[0]}, expected {left}")
+            if c.shape[2] > full[p][1]:
+                raise ValueError(f"{who}: bond {c.shape[2]} between sites {p} and {p + 1} is above {full[p][1]}, what "
+                                 f"model.m_aux_max = {D} allows there")
+            left = c.shape[2]
+            z = np.zeros((full[p][0], d, full[p][1]), dtype=np.complex128)
+            z[:c.shape[0], :, :c.shape[2]] = c
+            cores.append(z)
+        if left != 1:
+            raise ValueError(f"{who}: the last core ends in a bond of {left}, it must be 1")
+        out.append(cores)
+    return out
+
+
+def site_operator_mpo(site, mat, dims):
+    """the one-site operator ``mat`` on ``site`` as an MPO of bond 1: identity cores elsewhere"""
+    return [(np.asarray(mat, dtype=np.complex128) if p == site else np.eye(d, dtype=np.complex128))[None, :, :, None].copy()
+            for p, d in enumerate(dims)]
+
+
 def _mps_norm(cores):
     T = np.ones((1, 1), dtype=np.complex128)
     for c in cores:
@@ -173,7 +218,8 @@ def _mps_norm(cores):
 
 
 def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every=1, weights=None, integrator="arnoldi",
-                         conserve_norm=False, thresh_sil=1.0e-09, per_trajectory=False, device=0):
+                         conserve_norm=False, thresh_sil=1.0e-09, per_trajectory=False, device=0, operate_maxstep=10,
+                         operate_tol=1.0e-8):
     """Two-time correlation functions of an ensemble of Hartree products in ONE batch, contracted and averaged on the device
     (``k_batch_cross``, ``mitdvp_batch_run``): no t/2 trick, so complex starts and Hamiltonians that are not complex
     symmetric are fine.
@@ -195,6 +241,18 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
     ``<psi| A(t) B |psi>`` for a Hamiltonian that generates a unitary propagation.  With both ``None`` there is one
     replica per start and a snapshot at t = 0: ``C(t) = sum_s w_s <psi_s(0)|psi_s(t)>``, the autocorrelation function.
     ``weights``: one number per start, default equal weights.
+
+    A start may also be a correlated state: MPS cores, one ``(dl, d, dr)`` array per site, with bonds inside
+    ``model.m_aux_max`` (a relaxed ground state, a propagated state, any MPS; all starts are then given so).  It is
+    zero-padded to the model's bond dimensions, brought to canonical form and normalised, as a Hartree product is.  For
+    such starts ``B`` in any of its three forms is applied ON THE DEVICE: ``phi_s`` is set as a copy of ``psi_s``, ``B`` is
+    given to every replica as operator 2 (a one-site ``B`` as an MPO of bond 1), and one ``TDVPBatch.operate`` over the
+    ``phi`` replicas (``k_batch_operate``, one launch) replaces each by the normalised fit of ``B psi_s`` in the bond
+    dimensions of ``psi_s``, up to ``operate_maxstep`` double sweeps, stopped per start at ``operate_tol``.  The norms
+    ``|B psi_s|`` it returns multiply the weights of the cross entries, and the ``per_trajectory`` values on the host; the
+    tensors are not rescaled.  The fit is exact only where ``B psi`` fits the bonds -- there is no ``ValueError`` for an
+    MPO wider than the bond here, the state is the best one the bonds hold after those sweeps.  A start that ``B``
+    annihilates raises with the library's message, naming the replica.  Everything for Hartree products is as it was.
 
     ``model``, ``starts``, ``stepsize`` (fs) and the observation convention are those of ``propagate_trajectories``: the
     states are observed BEFORE steps 0, every, 2 every, ... < ``maxstep``; steps after the last observation are not run.
@@ -224,16 +282,19 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
     nsite = len(dims)
     D = model.m_aux_max if model.m_aux_max is not None else 10**9
     a_mpo = b_mpo = None
+    starts = [list(s) for s in starts]
+    mps_starts = core_starts(starts, dims, D)  # None: Hartree products, everything below as it was
+    if mps_starts is not None:
+        operate_request(2 * len(starts), 2, operate_maxstep, operate_tol)  # a bad maxstep or tolerance raises here
     if A is not None:
         fa, fb = _operator_form("A", A, model, dims), _operator_form("B", B, model, dims)
         A = fa[1:] if fa[0] == "site" else None
         B = fb[1:] if fb[0] == "site" else None
         a_mpo = fa[1] if fa[0] == "mpo" else None
         b_mpo = fb[1] if fb[0] == "mpo" else None
-        if b_mpo is not None:
+        if b_mpo is not None and mps_starts is None:
             check_mpo_fits_bonds("B", b_mpo, dims, D)
     two = A is not None or a_mpo is not None
-    starts = [list(s) for s in starts]
     if not starts:
         raise ValueError("no start states")
     ns = len(starts)
@@ -242,7 +303,12 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
         raise ValueError(f"weights must be {ns} numbers, one per start (got shape {w.shape})")
     # replica 2 s is psi_s, replica 2 s + 1 is phi_s = B psi_s with its norm
     states, scales = [], []
-    for k, s in enumerate(starts):
+    on_device = mps_starts is not None and two  # B is applied by TDVPBatch.operate
+    if on_device:
+        b_cores = b_mpo if b_mpo is not None else site_operator_mpo(B[0], B[1], dims)
+    for s in mps_starts or []:  # psi_s and, with A and B, the copy of it that becomes phi_s
+        states += [s, s] if two else [s]
+    for k, s in enumerate(starts if mps_starts is None else []):
         states.append(s)
         scales.append(1.0)
         if b_mpo is not None:
@@ -266,14 +332,27 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
     nsteps = (maxstep - 1) // every * every
     mpo = model.project_mpo(model.hamiltonian.as_mpo(model.dims))
     bt = TDVPBatch(len(states), nsite, device=device, integrator=integrator, conserve_norm=conserve_norm, thresh=thresh_sil)
+    norms = None
     try:
-        for e, s, scale in zip(bt.engines, states, scales):
+        for i, (e, s) in enumerate(zip(bt.engines, states)):
             e.set_mpo(mpo, 0, shift=model.hamiltonian.coupleJ[0][0])
             if a_mpo is not None:
                 e.set_mpo(a_mpo, 1)
-            e.set_mps(product_state_cores(s, D, space=model.space), canonicalize=True, scale=scale)
+            if mps_starts is None:
+                e.set_mps(product_state_cores(s, D, space=model.space), canonicalize=True, scale=scales[i])
+                continue
+            if on_device:
+                e.set_mpo(b_cores, 2)
+            if not two or i % 2 == 0:  # a start is brought to canonical form once; phi_s gets those very tensors
+                e.set_mps(s, canonicalize=True, scale=1.0)
+                canonical = e.get_mps()
+            else:
+                e.set_mps(canonical)
         if gates:
             bt.set_gates(gates)
+        if on_device:
+            norms = bt.operate(2, operate_maxstep, operate_tol, replicas=range(1, 2 * ns, 2))["norms"][1::2].copy()
+            w = w * norms
         key = "cross"
         if a_mpo is not None:
             key = "cross_mpo"
@@ -289,7 +368,7 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
     nrec = nsteps // every + 1
     out = {"time": np.arange(nrec) * every * dt_au * units.au_in_fs, "mean": rec["mean_" + key]}
     if per_trajectory:
-        out["trajectories"] = rec[key]
+        out["trajectories"] = rec[key] if norms is None else rec[key] * norms[None, :]
     return out
 
 
