@@ -120,6 +120,54 @@ __device__ __forceinline__ void wg_gemm(int M, int N, int K, zc* tiles, FA&& fa,
   __syncthreads();
 }
 
+// The two products of one site of an overlap walk, T (dl x dl) -> T' (dr x dr) between a ket tensor K and a bra tensor:
+//   U[m][(j,s)] = sum_n T[m][n] K[n][(j,s)]
+__device__ __forceinline__ void wg_walk_u(const zc* T, const zc* Kt, zc* U, int dl, int ddr, zc* tiles) {
+  wg_gemm<true, false>(dl, ddr, dl, tiles,
+      [&](int m, int kk) { return T[(long)m * dl + kk]; },
+      [&](int kk, int n) { return Kt[(long)kk * ddr + n]; },
+      [&](int m, int n, zc z) { U[(long)m * ddr + n] = z; });
+}
+//   T'[i][j] = sum_(m,s) conj(Bra[(m,s)][i]) U[(m,s)][j], K = dl d; CONJ = false: Bra as it stands (the autocorrelation)
+template <bool CONJ>
+__device__ __forceinline__ void wg_walk_t(const zc* Bt, const zc* U, zc* T2, int dr, int K, zc* tiles) {
+  wg_gemm<false, false>(dr, dr, K, tiles,
+      [&](int m, int kk) { const zc z = Bt[(long)kk * dr + m]; return CONJ ? make_double2(z.x, -z.y) : z; },
+      [&](int kk, int n) { return U[(long)kk * dr + n]; },
+      [&](int m, int n, zc z) { T2[(long)m * dr + n] = z; });
+}
+// The plain overlap <bra | ket> over all L sites: T starts as [1]; ket(p, soff) / bra(p, soff) give the tensors of site
+// p, soff being the sum of the sizes of the sites before it.  Returns the block that holds the 1 x 1 result.
+template <class FK, class FB>
+__device__ __forceinline__ const zc* wg_overlap(int L, const BatchShape* shp, FK&& ket, FB&& bra, zc* T, zc* T2, zc* U, zc* tiles) {
+  if (threadIdx.x == 0) T[0] = make_double2(1.0, 0.0);
+  __syncthreads();
+  size_t soff = 0;
+  for (int p = 0; p < L; ++p) {
+    const BatchShape s = shp[p];
+    const int dl = s.dl, d = s.d, dr = s.dr, ddr = d * dr;
+    wg_walk_u(T, ket(p, soff), U, dl, ddr, tiles);
+    wg_walk_t<true>(bra(p, soff), U, T2, dr, dl * d, tiles);
+    zc* t = T; T = T2; T2 = t;
+    soff += (size_t)dl * ddr;
+  }
+  return T;
+}
+
+// A state of a cross request: index i < B is replica i, whose tensors come through its row of the pointer table; index
+// i >= B is snapshot i - B, whose tensors lie site after site in the batch's buffer.
+struct BtState {
+  const zc* const* tab;  // the replica's row, nullptr for a snapshot
+  const zc* snap;        // the snapshot's base, nullptr for a replica
+  __device__ BtState(int i, int B, void* const* ptrs, int ptr_stride, const zc* snaps, size_t snap_len)
+      : tab(i < B ? reinterpret_cast<const zc* const*>(ptrs + (size_t)i * ptr_stride) : nullptr),
+        snap(i < B ? nullptr : snaps + (size_t)(i - B) * snap_len) {}
+  // the tensor of site p; soff: the sum of the sizes of the sites before p
+  __device__ const zc* at(int p, size_t soff) const { return tab ? tab[p] : snap + soff; }
+  // a replica that failed in an earlier launch; a snapshot is never dead
+  __device__ static bool dead(int i, int B, const int* status) { return i < B && status[i] != SS_OK; }
+};
+
 // out[a,i,r] = sum L[a,c,b] W[c,i,j,t] R[r,t,s] (scl * v)[b,j,s]   (small_site.h stages 1-3; Engine::chain_heff)
 __device__ __noinline__ void bt_heff(const BatchShape& s, const zc* Lb, const zc* W2, const zc* Rb, const zc* v, double scl, zc* X,
                         zc* Y, zc* out, zc* tiles) {
@@ -157,15 +205,27 @@ __device__ __noinline__ void bt_keff(int dim, int m, const zc* Lb, const zc* Rb,
       [&](int mm, int n, zc z) { out[(long)mm * dim + n] = z; });
 }
 
-// env'[a,q,r] = sum conj(T)(b,c,a) env[b,p,s] W2e[(q,t)][(c,p)] T(s,t,r)   (Engine::chain_env), T(in, phys, out) =
-// T[in * sTi + phys * sTd + out * sTo]: the site tensor itself (->) or its mirror image (<-) without a copy.
-// env (din, min, din) -> env' (dout, mout, dout).
-__device__ __noinline__ void bt_env(const zc* env, const zc* T, long sTi, long sTd, long sTo, const zc* W2e, int din, int min_, int d,
-                       int dout, int mout, zc* X, zc* Y, zc* out, zc* tiles) {
+// The tiles of a product function are LDS, whoever calls it.  The compiler works that out by itself only while EVERY
+// caller hands over a __shared__ array directly; k_batch_operate hands it over through BopCtx, and then the product loops
+// of bt_env and bt_matmul read the tiles through flat loads instead of LDS loads: 3-4 % of a whole batch step
+// (profiles/batch_shared_products.txt).  So those two say it.
+__device__ __forceinline__ void assume_lds(const zc* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __builtin_assume(__builtin_amdgcn_is_shared(p));
+#endif
+}
+
+// env'[a,q,r] = sum conj(Bra)(b,c,a) env[b,p,s] W2e[(q,t)][(c,p)] Ket(s,t,r)   (Engine::chain_env), T(in, phys, out) =
+// T[in * sTi + phys * sTd + out * sTo] for both tensors: the site tensor itself (->) or its mirror image (<-) without a
+// copy.  env (din, min, din) -> env' (dout, mout, dout).  The block update of a sweep passes the site tensor twice.
+// This is the one text of the three products; bt_env below is the function the kernels call.
+__device__ __forceinline__ void bt_env_body(const zc* env, const zc* Tb, const zc* Tk, long sTi, long sTd, long sTo, const zc* W2e,
+                                            int din, int min_, int d, int dout, int mout, zc* X, zc* Y, zc* out, zc* tiles) {
+  assume_lds(tiles);
   const int nx = min_ * din;
-  // X[(c,a)][(p,s)] = sum_b conj(T(b,c,a)) env[b][(p,s)]
+  // X[(c,a)][(p,s)] = sum_b conj(Bra(b,c,a)) env[b][(p,s)]
   wg_gemm<false, false>(d * dout, nx, din, tiles,
-      [&](int m, int k) { const int c = m / dout, a = m - c * dout; const zc z = T[k * sTi + c * sTd + a * sTo]; return make_double2(z.x, -z.y); },
+      [&](int m, int k) { const int c = m / dout, a = m - c * dout; const zc z = Tb[k * sTi + c * sTd + a * sTo]; return make_double2(z.x, -z.y); },
       [&](int k, int n) { return env[(long)k * nx + n]; },
       [&](int m, int n, zc z) { X[(long)m * nx + n] = z; });
   // Y[a][(q,t)][s] = sum_(c,p) W2e[(q,t)][(c,p)] X[c][a][p][s]
@@ -177,16 +237,27 @@ __device__ __noinline__ void bt_env(const zc* env, const zc* T, long sTi, long s
         return X[(((long)c * dout + a) * min_ + p) * din + ss];
       },
       [&](int m, int n, zc z) { const int a = n / din, ss = n - a * din; Y[((long)a * mw + m) * din + ss] = z; });
-  // out[(a,q)][r] = sum_(t,s) Y[(a,q)][(t,s)] T(s,t,r)
+  // out[(a,q)][r] = sum_(t,s) Y[(a,q)][(t,s)] Ket(s,t,r)
   const int kr = d * din;
   wg_gemm<true, false>(dout * mout, dout, kr, tiles,
       [&](int m, int k) { return Y[(long)m * kr + k]; },
-      [&](int k, int n) { const int t = k / din, ss = k - t * din; return T[ss * sTi + t * sTd + n * sTo]; },
+      [&](int k, int n) { const int t = k / din, ss = k - t * din; return Tk[ss * sTi + t * sTd + n * sTo]; },
       [&](int m, int n, zc z) { out[(long)m * dout + n] = z; });
+}
+__device__ __noinline__ void bt_env(const zc* env, const zc* Tb, const zc* Tk, long sTi, long sTd, long sTo, const zc* W2e, int din,
+                                    int min_, int d, int dout, int mout, zc* X, zc* Y, zc* out, zc* tiles) {
+  bt_env_body(env, Tb, Tk, sTi, sTd, sTo, W2e, din, min_, d, dout, mout, X, Y, out, tiles);
+}
+// k_batch_cross_mpo's own instance, the forward roles only: with the strides (d dout, dout, 1) known at compile time its
+// walk measured faster than through bt_env (profiles/batch_shared_products.txt)
+__device__ __noinline__ void bt_env_fwd(const zc* env, const zc* Tb, const zc* Tk, const zc* W2e, int din, int min_, int d, int dout,
+                                        int mout, zc* X, zc* Y, zc* out, zc* tiles) {
+  bt_env_body(env, Tb, Tk, (long)d * dout, dout, 1, W2e, din, min_, d, dout, mout, X, Y, out, tiles);
 }
 
 // dst = A (M x K) . B (K x N), all row-major, by way of tmp (dst may be A or B): the absorb of a sweep
 __device__ __noinline__ void bt_matmul(const zc* A, const zc* B, zc* tmp, zc* dst, int M, int N, int K, zc* tiles) {
+  assume_lds(tiles);
   wg_gemm<true, false>(M, N, K, tiles,
       [&](int m, int k) { return A[(long)m * K + k]; },
       [&](int k, int n) { return B[(long)k * N + n]; },
@@ -508,9 +579,14 @@ __device__ __noinline__ int bt_exp(const BtOp& op, zc* x, zc* U, long N, int* kp
 // body SPILLS 93 vector and 31 scalar registers around the calls of its stage functions (a few times per site of the
 // sweep), and the argument blocks those functions take by reference live there too.  The stages are separate
 // (non-inlined) device functions because inlined into one body the spills sat inside the product loops (119 VGPRs, 928
-// bytes); the product functions bt_heff / bt_keff / bt_env / bt_matmul themselves use 178-196 VGPRs and no private
+// bytes); the product functions bt_heff / bt_keff / bt_env / bt_matmul themselves use 194 / 178 / 196 / 136 VGPRs and no private
 // memory, bt_exp 254 VGPRs and 16 bytes.  This misses the "no spills" aim; what it costs is measured, not guessed:
 // profiles/batch_probe.txt and DESIGN.md section 7.3.
+// The batch kernels SHARE these product functions (and wg_walk_u / wg_walk_t / wg_overlap above): there is one text per
+// product, so a new caller may move the register figures of the kernels that already call it.  What a feature is held to
+// is: no new vector or scalar spills, no new private memory inside a product loop, unchanged occupancy, and measured time
+// (profiles/batch_shared_products.txt has the figures of every kernel and the old-against-new timings of the merge).  A
+// kernel that measures slower through a shared function gets a non-inlined instance of the same text, as bt_env_fwd.
 __global__ __launch_bounds__(SS_THREADS) void k_batch_sweep(BatchArgs g) {
   __shared__ __attribute__((aligned(16))) zc s_mats[6 * MAXK * MAXK];
   __shared__ zc s_z[3 * MAXK + (MAXK + 1) * MAXK + 2 * BATCH_MAX_BOND];
@@ -567,7 +643,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_sweep(BatchArgs g) {
       // 2. Psi2Asigma: A in place of Psi, sigma (dr x dr)
       bt_qr(site[p], site[p], dr, 1, sig, dr, 1, dl * d, dr, work, sh);
       // 3. L[p + 1]
-      bt_env(envL[p], site[p], (long)d * dr, dr, 1, w2el[p], dl, s.ml, d, dr, s.mr, X, Y, envL[p + 1], tiles);
+      bt_env(envL[p], site[p], site[p], (long)d * dr, dr, 1, w2el[p], dl, s.ml, d, dr, s.mr, X, Y, envL[p + 1], tiles);
       // 4. exp(scale * K_eff) on sigma
       const zc* Lb = envL[p + 1];
       const zc* Rb = envR[p + 1];
@@ -585,7 +661,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_sweep(BatchArgs g) {
       const int mq = d * dr;
       bt_qr(site[p], site[p], 1, mq, sig, 1, dl, mq, dl, work, sh);
       // 3. R[p] from the mirror image of B (dr, d, dl), read in place
-      bt_env(envR[p + 1], site[p], 1, dr, (long)d * dr, w2er[p], dr, s.mr, d, dl, s.ml, X, Y, envR[p], tiles);
+      bt_env(envR[p + 1], site[p], site[p], 1, dr, (long)d * dr, w2er[p], dr, s.mr, d, dl, s.ml, X, Y, envR[p], tiles);
       // 4. exp(scale * K_eff) on sigma
       const zc* Lb = envL[p];
       const zc* Rb = envR[p];
@@ -719,16 +795,9 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_observe(BatchObsArgs g) {
       const BatchShape s = g.shp[p];
       const int dl = s.dl, d = s.d, dr = s.dr, ddr = d * dr;
       const zc* C = site[p];
-      // U[m][(j,s)] = sum_n T[m][n] C[n][(j,s)]
-      wg_gemm<true, false>(dl, ddr, dl, tiles,
-          [&](int m, int kk) { return T[(long)m * dl + kk]; },
-          [&](int kk, int n) { return C[(long)kk * ddr + n]; },
-          [&](int m, int n, zc z) { U[(long)m * ddr + n] = z; });
-      // T'[i][j] = sum_(m,s) C[(m,s)][i] U[(m,s)][j]
-      wg_gemm<false, false>(dr, dr, dl * d, tiles,
-          [&](int m, int kk) { return C[(long)kk * dr + m]; },
-          [&](int kk, int n) { return U[(long)kk * dr + n]; },
-          [&](int m, int n, zc z) { T2[(long)m * dr + n] = z; });
+      // U = T C, T' = C^T U: the overlap walk with bra = conj(ket)
+      wg_walk_u(T, C, U, dl, ddr, tiles);
+      wg_walk_t<false>(C, U, T2, dr, dl * d, tiles);
       zc* t = T; T = T2; T2 = t;
     }
     if (tid == 0) { const zc z = T[0]; rec[2] = z.x; rec[3] = z.y; }
@@ -974,9 +1043,9 @@ __device__ __noinline__ void bc_weights(const zc* ops, int K, const zc* C, int d
   __syncthreads();
 }
 
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 200 VGPRs -- those of the
-// non-inlined bt_env / bt_matmul shared with k_batch_sweep -- so occupancy 2 waves per SIMD (one workgroup per compute
-// unit); no vector or scalar register spills; 160 bytes of private memory per lane (the argument blocks of the calls);
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 196 VGPRs -- those of the
+// non-inlined bt_env shared with k_batch_sweep -- so occupancy 2 waves per SIMD (one workgroup per compute unit); 98
+// SGPRs; no vector or scalar register spills; 160 bytes of private memory per lane (the argument blocks of the calls);
 // 20 168 bytes of LDS.
 __global__ __launch_bounds__(SS_THREADS) void k_batch_channel(BatchChanArgs g) {
   __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
@@ -1046,7 +1115,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_channel(BatchChanArgs g) {
       const int dl = s.dl, d = s.d, dr = s.dr;
       // Psi2Asigma, L[p + 1], Psi(p + 1) = sigma . B(p + 1), as the forward sweep
       bt_qr(site[p], site[p], dr, 1, sig, dr, 1, dl * d, dr, work, sh);
-      bt_env(envL[p], site[p], (long)d * dr, dr, 1, w2el[p], dl, s.ml, d, dr, s.mr, X, Y, envL[p + 1], tiles);
+      bt_env(envL[p], site[p], site[p], (long)d * dr, dr, 1, w2el[p], dl, s.ml, d, dr, s.mr, X, Y, envL[p + 1], tiles);
       const BatchShape q = g.shp[p + 1];
       zc* nxt = site[p + 1];
       bt_matmul(sig, nxt, spare, nxt, dr, q.d * q.dr, dr, tiles);
@@ -1380,11 +1449,11 @@ __device__ __noinline__ void bp_cprime(const zc* T, const zc* Bp, zc* Cp, int m,
       [&](int mm, int nn, zc z) { Cp[(long)mm * r + nn] = make_double2(z.x * scl, z.y * scl); });
 }
 
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 248 VGPRs, 106 SGPRs, no vector
-// register spills, 20 scalar registers spilled around the calls of the stage functions, 384 bytes of private memory per lane
-// (BopCtx, which the stage functions take by reference and read BEFORE their products, and the shape blocks bt_heff takes
-// by reference: none of it inside a product loop), 20 032 bytes of LDS; occupancy 2 waves per SIMD, i.e. one workgroup
-// (replica) per compute unit.  The other batch kernels compile to what they compiled to before.  DESIGN.md section 7.3.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 196 VGPRs -- those of the
+// non-inlined bt_env shared with k_batch_sweep -- 106 SGPRs, no vector register spills, 15 scalar registers spilled around
+// the calls of the stage functions, 224 bytes of private memory per lane (the argument blocks of those calls, none of it
+// inside a product, QR or Jacobi loop), 26 088 bytes of LDS; occupancy 2 waves per SIMD, i.e. one workgroup (replica) per
+// compute unit.  DESIGN.md section 7.3.
 __global__ __launch_bounds__(SS_THREADS) void k_batch_pair(BatchPairArgs gp) {
   __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
   __shared__ zc s_z[3 * BATCH_MAX_BOND];
@@ -1475,7 +1544,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_pair(BatchPairArgs gp) {
       const int dl = s.dl, d = s.d, dr = s.dr;
       // Psi2Asigma, L[p + 1], Psi(p + 1) = sigma . B(p + 1), as the forward sweep
       bt_qr(site[p], site[p], dr, 1, sig, dr, 1, dl * d, dr, work, sh);
-      bt_env(envL[p], site[p], (long)d * dr, dr, 1, w2el[p], dl, s.ml, d, dr, s.mr, X, Y, envL[p + 1], tiles);
+      bt_env(envL[p], site[p], site[p], (long)d * dr, dr, 1, w2el[p], dl, s.ml, d, dr, s.mr, X, Y, envL[p + 1], tiles);
       const BatchShape q = g.shp[p + 1];
       zc* nxt = site[p + 1];
       bt_matmul(sig, nxt, spare, nxt, dr, q.d * q.dr, dr, tiles);
@@ -1521,16 +1590,11 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_cross(BatchCrossArgs g) {
   const int q = blockIdx.x, tid = threadIdx.x, L = g.L, B = g.nrep;
   const BatchCrossPair pr = g.pairs[q];
   double* rec = g.rec + 2 * (size_t)q;
-  const bool dead = (pr.bra < B && g.status[pr.bra] != SS_OK) || (pr.ket < B && g.status[pr.ket] != SS_OK);
-  if (dead) {  // the same decision in every thread of the workgroup
+  if (BtState::dead(pr.bra, B, g.status) || BtState::dead(pr.ket, B, g.status)) {  // the same decision in every thread
     if (tid == 0) { rec[0] = 0.0; rec[1] = 0.0; }
     return;
   }
-  // a replica's tensors come through its row of the pointer table, a snapshot's lie site after site in the batch's buffer
-  const zc* const* braTab = pr.bra < B ? reinterpret_cast<const zc* const*>(g.ptrs + (size_t)pr.bra * g.ptr_stride) : nullptr;
-  const zc* const* ketTab = pr.ket < B ? reinterpret_cast<const zc* const*>(g.ptrs + (size_t)pr.ket * g.ptr_stride) : nullptr;
-  const zc* braSnap = pr.bra < B ? nullptr : g.snap + (size_t)(pr.bra - B) * g.snap_len;
-  const zc* ketSnap = pr.ket < B ? nullptr : g.snap + (size_t)(pr.ket - B) * g.snap_len;
+  const BtState bra(pr.bra, B, g.ptrs, g.ptr_stride, g.snap, g.snap_len), ket(pr.ket, B, g.ptrs, g.ptr_stride, g.snap, g.snap_len);
   const zc* O = g.ops + pr.off;
   zc* T = g.buf + (size_t)q * g.buf_len;
   zc* T2 = T + g.o_t2;
@@ -1542,13 +1606,9 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_cross(BatchCrossArgs g) {
   for (int p = 0; p < L; ++p) {
     const BatchShape s = g.shp[p];
     const int dl = s.dl, d = s.d, dr = s.dr, ddr = d * dr;
-    const zc* Kt = ketTab ? ketTab[p] : ketSnap + soff;
-    const zc* Bt = braTab ? braTab[p] : braSnap + soff;
-    // U[m][(j,s)] = sum_n T[m][n] K[n][(j,s)]
-    wg_gemm<true, false>(dl, ddr, dl, tiles,
-        [&](int m, int kk) { return T[(long)m * dl + kk]; },
-        [&](int kk, int n) { return Kt[(long)kk * ddr + n]; },
-        [&](int m, int n, zc z) { U[(long)m * ddr + n] = z; });
+    const zc* Kt = ket.at(p, soff);
+    const zc* Bt = bra.at(p, soff);
+    wg_walk_u(T, Kt, U, dl, ddr, tiles);
     // T'[i][j] = sum_(m,s) conj(Bra[(m,s)][i]) U[(m,s)][j], U with the operator on its physical index at the pair's site
     if (p == pr.site)
       wg_gemm<false, false>(dr, dr, dl * d, tiles,
@@ -1567,10 +1627,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_cross(BatchCrossArgs g) {
           },
           [&](int m, int n, zc z) { T2[(long)m * dr + n] = z; });
     else
-      wg_gemm<false, false>(dr, dr, dl * d, tiles,
-          [&](int m, int kk) { const zc z = Bt[(long)kk * dr + m]; return make_double2(z.x, -z.y); },
-          [&](int kk, int n) { return U[(long)kk * dr + n]; },
-          [&](int m, int n, zc z) { T2[(long)m * dr + n] = z; });
+      wg_walk_t<true>(Bt, U, T2, dr, dl * d, tiles);
     zc* t = T; T = T2; T2 = t;
     soff += (size_t)dl * ddr;
   }
@@ -1638,7 +1695,7 @@ __device__ __noinline__ void bs_record(int chi, const BpSh& ps, double* srt, dou
 // non-inlined stage functions it shares with k_batch_pair (bt_qr, bp_jacobi, bp_merge) -- 106 SGPRs, no vector or scalar
 // register spills, 224 bytes of private memory per lane (the argument blocks of the calls of the stage functions, none of
 // it inside a QR, Jacobi or product loop), 22 376 bytes of LDS; occupancy 3 waves per SIMD, i.e. one workgroup per
-// compute unit.  The other batch kernels compile to what they compiled to before.  DESIGN.md section 7.3.
+// compute unit.  DESIGN.md section 7.3.
 __global__ __launch_bounds__(SS_THREADS) void k_batch_spectra(BatchSpecArgs g) {
   __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
   __shared__ zc s_z[2 * BATCH_MAX_BOND];
@@ -1713,8 +1770,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_spectra(BatchSpecArgs g) {
 // workgroup, every loop is bounded by the shapes and nshots.
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 110 VGPRs, 82 SGPRs, no vector
 // or scalar register spills, no private memory (wg_gemm is inlined: there is no call and no argument block), 26 368 bytes
-// of LDS; occupancy 4 waves per SIMD, i.e. two workgroups per compute unit.  The other batch kernels compile to what they
-// compiled to before.  DESIGN.md section 7.3.
+// of LDS; occupancy 4 waves per SIMD, i.e. two workgroups per compute unit.  DESIGN.md section 7.3.
 __device__ __forceinline__ double bsm_uniform(unsigned long long base, unsigned long long site, unsigned long long shot) {
   // base = mix(mix(seed ^ trajectory) + step): key = mix(mix(base + site) + shot)
   const unsigned long long key = bc_mix(bc_mix(base + site) + shot);
@@ -1842,11 +1898,10 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_sample(BatchSampleArgs g) 
 // and status words are only read.  Every element has one owner thread and every sum one order: a value depends on its
 // replica and its operator only, not on B, nops, the operator's place in the list or the compute unit.  No atomics, nothing
 // waits for another workgroup, every loop is bounded by the shapes.
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 200 VGPRs -- those of the
-// non-inlined product functions bt_env / bt_heff it shares with k_batch_sweep and k_batch_observe -- 105 SGPRs, no vector or
-// scalar register spills, 32 bytes of private memory per lane (the shape block bt_heff takes by reference, none of it
-// inside a product loop), 17 472 bytes of LDS; occupancy 2 waves per SIMD, i.e. one workgroup per compute unit.  The other
-// batch kernels compile to what they compiled to before.  DESIGN.md section 7.3.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 196 VGPRs -- those of the
+// non-inlined product function bt_env it shares with k_batch_sweep -- 83 SGPRs, no vector or scalar register spills, 32
+// bytes of private memory per lane (the shape block bt_heff takes by reference, none of it inside a product loop), 17 472
+// bytes of LDS; occupancy 2 waves per SIMD, i.e. one workgroup per compute unit.  DESIGN.md section 7.3.
 __global__ __launch_bounds__(SS_THREADS) void k_batch_expect(BatchExpectArgs g) {
   __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
   __shared__ double s_d[SS_WAVES * 8 + 8];
@@ -1879,7 +1934,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_expect(BatchExpectArgs g) 
 
   for (int p = L - 1; p >= 1; --p) {
     const BatchShape s = shp[p];
-    bt_env(cur, site[p], 1, s.dr, (long)s.d * s.dr, w2er[p], s.dr, s.mr, s.d, s.dl, s.ml, X, Y, Ea, tiles);
+    bt_env(cur, site[p], site[p], 1, s.dr, (long)s.d * s.dr, w2er[p], s.dr, s.mr, s.d, s.dl, s.ml, X, Y, Ea, tiles);
     cur = Ea;
     zc* t = Ea; Ea = Eb; Eb = t;
   }
@@ -1909,14 +1964,12 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_expect(BatchExpectArgs g) 
 // operator); the states are named as in k_batch_cross, the operator's cores and scalar term are those of the ket's owner,
 // replica ket mod B.  Two different states share no canonical form, so the walk runs over all L sites, left to right:
 //   T (bra bond, MPO bond, ket bond) = the 1 x 1 x 1 block [1]
-//   p = 0 .. L-1:  T <- bt_env2(T, Bra_p, Ket_p, w2el of the operator at p): the three products of bt_env in the roles of
-//                  the forward sweep, strides (d dr, dr, 1); stage 1 reads conj of the BRA tensor, stage 3 the KET
+//   p = 0 .. L-1:  T <- bt_env_fwd(T, Bra_p, Ket_p, w2el of the operator at p): the three products of bt_env in the roles
+//                  of the forward sweep, strides (d dr, dr, 1); stage 1 reads conj of the BRA tensor, stage 3 the KET
 //                  tensor; written alternately into the entry's two blocks
 //   value = the 1 x 1 x 1 block after site L-1, <bra | O | ket>, not normalised
-// With a non-zero scalar term the same workgroup then runs k_batch_cross's plain-overlap walk (site = -1) with that
-// kernel's products and adds shift * <bra | ket>; the decision is the same in every thread.
-// bt_env2 is a product function of its own: bt_env, and with it k_batch_sweep / _channel / _pair / _expect, compile to
-// what they compiled to before.
+// With a non-zero scalar term the same workgroup then runs the plain-overlap walk (wg_overlap: the products of
+// k_batch_cross with site = -1) and adds shift * <bra | ket>; the decision is the same in every thread.
 // What is resident where: LDS holds the two operand tiles of wg_gemm (16 896 bytes); the two blocks, X and Y live in the
 // ENTRY's carve of the request's own buffer [P][carve] -- several entries may read one replica at the same time, so
 // nothing of a walk may sit in a replica's scratch area -- written and re-read by this workgroup only between workgroup
@@ -1924,51 +1977,21 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_expect(BatchExpectArgs g) 
 // status words are only read.  Every element has one owner thread and every sum one order: a value depends on its two
 // states and its operator only, not on the number of entries, its place in the list, B or the compute unit.  No atomics,
 // nothing waits for another workgroup, every loop is bounded by the shapes.
-__device__ __noinline__ void bt_env2(const zc* env, const zc* Tb, const zc* Tk, long sTi, long sTd, long sTo, const zc* W2e, int din,
-                                     int min_, int d, int dout, int mout, zc* X, zc* Y, zc* out, zc* tiles) {
-  const int nx = min_ * din;
-  // X[(c,a)][(p,s)] = sum_b conj(Bra(b,c,a)) env[b][(p,s)]
-  wg_gemm<false, false>(d * dout, nx, din, tiles,
-      [&](int m, int k) { const int c = m / dout, a = m - c * dout; const zc z = Tb[k * sTi + c * sTd + a * sTo]; return make_double2(z.x, -z.y); },
-      [&](int k, int n) { return env[(long)k * nx + n]; },
-      [&](int m, int n, zc z) { X[(long)m * nx + n] = z; });
-  // Y[a][(q,t)][s] = sum_(c,p) W2e[(q,t)][(c,p)] X[c][a][p][s]
-  const int kw = d * min_, mw = mout * d;
-  wg_gemm<true, false>(mw, dout * din, kw, tiles,
-      [&](int m, int k) { return W2e[(long)m * kw + k]; },
-      [&](int k, int n) {
-        const int c = k / min_, p = k - c * min_, a = n / din, ss = n - a * din;
-        return X[(((long)c * dout + a) * min_ + p) * din + ss];
-      },
-      [&](int m, int n, zc z) { const int a = n / din, ss = n - a * din; Y[((long)a * mw + m) * din + ss] = z; });
-  // out[(a,q)][r] = sum_(t,s) Y[(a,q)][(t,s)] Ket(s,t,r)
-  const int kr = d * din;
-  wg_gemm<true, false>(dout * mout, dout, kr, tiles,
-      [&](int m, int k) { return Y[(long)m * kr + k]; },
-      [&](int k, int n) { const int t = k / din, ss = k - t * din; return Tk[ss * sTi + t * sTd + n * sTo]; },
-      [&](int m, int n, zc z) { out[(long)m * dout + n] = z; });
-}
-
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 184 VGPRs -- those of bt_env2 --
-// 82 SGPRs, no vector or scalar register spills, NO private memory (0 bytes per lane: bt_env2 takes its arguments in
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 180 VGPRs -- those of bt_env_fwd
+// -- 82 SGPRs, no vector or scalar register spills, NO private memory (0 bytes per lane: bt_env_fwd takes its arguments in
 // registers, so no access to private memory can sit inside a product loop), 16 896 bytes of LDS; occupancy 2 waves per
-// SIMD, i.e. one workgroup (entry) per compute unit.  The other batch kernels compile to what they compiled to before.
+// SIMD, i.e. one workgroup (entry) per compute unit.
 __global__ __launch_bounds__(SS_THREADS) void k_batch_cross_mpo(BatchCrossMpoArgs g) {
   __shared__ __attribute__((aligned(16))) zc tiles[2 * BT_TK * BT_LD];
   const int q = blockIdx.x, tid = threadIdx.x, L = g.L, B = g.nrep;
   const BatchCrossMpoEntry en = g.entries[q];
   double* rec = g.rec + 2 * (size_t)q;
-  const bool dead = (en.bra < B && g.status[en.bra] != SS_OK) || (en.ket < B && g.status[en.ket] != SS_OK);
-  if (dead) {  // the same decision in every thread of the workgroup
+  if (BtState::dead(en.bra, B, g.status) || BtState::dead(en.ket, B, g.status)) {  // the same decision in every thread
     if (tid == 0) { rec[0] = 0.0; rec[1] = 0.0; }
     return;
   }
   const int owner = en.ket < B ? en.ket : en.ket - B;
-  // a replica's tensors come through its row of the pointer table, a snapshot's lie site after site in the batch's buffer
-  const zc* const* braTab = en.bra < B ? reinterpret_cast<const zc* const*>(g.ptrs + (size_t)en.bra * g.ptr_stride) : nullptr;
-  const zc* const* ketTab = en.ket < B ? reinterpret_cast<const zc* const*>(g.ptrs + (size_t)en.ket * g.ptr_stride) : nullptr;
-  const zc* braSnap = en.bra < B ? nullptr : g.snap + (size_t)(en.bra - B) * g.snap_len;
-  const zc* ketSnap = en.ket < B ? nullptr : g.snap + (size_t)(en.ket - B) * g.snap_len;
+  const BtState bra(en.bra, B, g.ptrs, g.ptr_stride, g.snap, g.snap_len), ket(en.ket, B, g.ptrs, g.ptr_stride, g.snap, g.snap_len);
   const zc* const* w2el = reinterpret_cast<const zc* const*>(g.ops + ((size_t)owner * g.nops + en.op) * L);
   const BatchShape* shp = g.shp + (size_t)en.op * L;
   const zc sft = g.shift[(size_t)owner * g.nops + en.op];
@@ -1983,9 +2006,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_cross_mpo(BatchCrossMpoArg
   size_t soff = 0;
   for (int p = 0; p < L; ++p) {
     const BatchShape s = shp[p];
-    const zc* Kt = ketTab ? ketTab[p] : ketSnap + soff;
-    const zc* Bt = braTab ? braTab[p] : braSnap + soff;
-    bt_env2(Ea, Bt, Kt, (long)s.d * s.dr, s.dr, 1, w2el[p], s.dl, s.ml, s.d, s.dr, s.mr, X, Y, Eb, tiles);
+    bt_env_fwd(Ea, bra.at(p, soff), ket.at(p, soff), w2el[p], s.dl, s.ml, s.d, s.dr, s.mr, X, Y, Eb, tiles);
     zc* t = Ea; Ea = Eb; Eb = t;
     soff += (size_t)s.dl * s.d * s.dr;
   }
@@ -1995,31 +2016,9 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_cross_mpo(BatchCrossMpoArg
     return;
   }
   __syncthreads();  // every thread has read the value before the blocks are used again
-  // the plain overlap <bra | ket>: the walk and the products of k_batch_cross with site = -1
-  zc* T = Ea;
-  zc* T2 = Eb;
-  zc* U = X;
-  if (tid == 0) T[0] = make_double2(1.0, 0.0);
-  __syncthreads();
-  soff = 0;
-  for (int p = 0; p < L; ++p) {
-    const BatchShape s = shp[p];
-    const int dl = s.dl, d = s.d, dr = s.dr, ddr = d * dr;
-    const zc* Kt = ketTab ? ketTab[p] : ketSnap + soff;
-    const zc* Bt = braTab ? braTab[p] : braSnap + soff;
-    // U[m][(j,s)] = sum_n T[m][n] K[n][(j,s)]
-    wg_gemm<true, false>(dl, ddr, dl, tiles,
-        [&](int m, int kk) { return T[(long)m * dl + kk]; },
-        [&](int kk, int n) { return Kt[(long)kk * ddr + n]; },
-        [&](int m, int n, zc z) { U[(long)m * ddr + n] = z; });
-    // T'[i][j] = sum_(m,s) conj(Bra[(m,s)][i]) U[(m,s)][j]
-    wg_gemm<false, false>(dr, dr, dl * d, tiles,
-        [&](int m, int kk) { const zc z = Bt[(long)kk * dr + m]; return make_double2(z.x, -z.y); },
-        [&](int kk, int n) { return U[(long)kk * dr + n]; },
-        [&](int m, int n, zc z) { T2[(long)m * dr + n] = z; });
-    zc* t = T; T = T2; T2 = t;
-    soff += (size_t)dl * ddr;
-  }
+  // the plain overlap <bra | ket>, T and its successor in the two blocks, U in X
+  const zc* T = wg_overlap(L, shp, [&](int p, size_t so) { return ket.at(p, so); }, [&](int p, size_t so) { return bra.at(p, so); },
+                           Ea, Eb, X, tiles);
   if (tid == 0) {
     const zc ov = T[0];
     rec[0] = val.x + (sft.x * ov.x - sft.y * ov.y);
@@ -2033,23 +2032,23 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_cross_mpo(BatchCrossMpoArg
 // batch_site.h): phi ~ O|psi> / |O|psi>| in the bond dimensions of psi.  The bra, phi, lives in the replica's own site
 // tensors, which the kernel WRITES; the ket is a copy of them in the replica's carve of the request's buffer.
 //   setup      ket <- the replica's tensors (centre at site 0); blocks 0 and L of the mixed and of the overlap chain <- [1];
-//              p = L-1 .. 1: block p <- bt_env2(block p+1, bra_p, ket_p, w2er at p) in the mirror-image strides of the
+//              p = L-1 .. 1: block p <- bt_env(block p+1, bra_p, ket_p, w2er at p) in the mirror-image strides of the
 //              backward sweep (bra = ket here)
 //   double sweep it = 1 .. maxstep:
 //     prev <- bra
 //     p = 0 .. L-1:   bra_p <- bt_heff(block p, w2l at p, block p+1, ket_p)  [+ shift * the same apply of the overlap
 //                     blocks with the identity core]; nrm = |bra_p|; bra_p /= nrm; unless p = L-1: thin QR of bra_p (R
 //                     dropped: the next site is replaced) and of ket_p (R absorbed into ket_{p+1}), block p+1 <-
-//                     bt_env2(block p, bra_p, ket_p, w2el at p)  [and the overlap block with the identity core]
-//     p = L-1 .. 0:   the mirror image: QR of the transposes, R^T absorbed into ket_{p-1}, block p <- bt_env2(block p+1, ..,
+//                     bt_env(block p, bra_p, ket_p, w2el at p)  [and the overlap block with the identity core]
+//     p = L-1 .. 0:   the mirror image: QR of the transposes, R^T absorbed into ket_{p-1}, block p <- bt_env(block p+1, ..,
 //                     w2er at p)
-//     ov = <bra | prev> by k_batch_cross's plain-overlap walk; stop when |1 - |ov|| < conv_tol
+//     ov = <bra | prev> by the plain-overlap walk (wg_overlap); stop when |1 - |ov|| < conv_tol
 //   norms[j] = nrm of the last apply at site 0, iters[j] = double sweeps run.  A norm that is not > 0 stops the replica:
 //   SS_EZERO in its status word, norms[j] = 0; the decision is formed from a workgroup reduction, the same in every thread.
 // One array of L + 1 blocks serves both directions: block b is the left block while the centre is at a site >= b and the
 // right block otherwise, and a half-sweep overwrites it exactly when its other role is spent.  The scalar term goes
 // through the overlap blocks as the engine does it: the identity core of MPO bond 1 (written into the carve for the
-// site's d before each use) through the same bt_heff / bt_env2.  L = 1: one apply per half-sweep, no QR.
+// site's d before each use) through the same bt_heff / bt_env.  L = 1: one apply per half-sweep, no QR.
 // What is resident where: LDS holds the two operand tiles of wg_gemm, the Householder scalars of a gauge move and the
 // reduction partials (20 032 bytes); everything of tensor size lives in the replica's carve of the REQUEST's own buffer
 // (BatchOperatePlan: ket, prev, the blocks, X, Y, the QR work matrix, ...), written and re-read by this workgroup only
@@ -2068,44 +2067,6 @@ struct BopCtx {
   const long long *soff, *moff, *voff;
   zc *ket, *mix, *ov, *X, *Y, *work, *spare, *H, *sig, *Id, *tiles;
 };
-
-// bt_env2's three products under a name of the fit's own: the fit calls them with both stride patterns, and a second
-// caller of bt_env2 itself would make k_batch_cross_mpo, whose strides are constants, compile to something else
-__device__ __noinline__ void bop_env(const zc* env, const zc* Tb, const zc* Tk, long sTi, long sTd, long sTo, const zc* W2e, int din,
-                                     int min_, int d, int dout, int mout, zc* X, zc* Y, zc* out, zc* tiles) {
-  const int nx = min_ * din;
-  // X[(c,a)][(p,s)] = sum_b conj(Bra(b,c,a)) env[b][(p,s)]
-  wg_gemm<false, false>(d * dout, nx, din, tiles,
-      [&](int m, int k) { const int c = m / dout, a = m - c * dout; const zc z = Tb[k * sTi + c * sTd + a * sTo]; return make_double2(z.x, -z.y); },
-      [&](int k, int n) { return env[(long)k * nx + n]; },
-      [&](int m, int n, zc z) { X[(long)m * nx + n] = z; });
-  // Y[a][(q,t)][s] = sum_(c,p) W2e[(q,t)][(c,p)] X[c][a][p][s]
-  const int kw = d * min_, mw = mout * d;
-  wg_gemm<true, false>(mw, dout * din, kw, tiles,
-      [&](int m, int k) { return W2e[(long)m * kw + k]; },
-      [&](int k, int n) {
-        const int c = k / min_, p = k - c * min_, a = n / din, ss = n - a * din;
-        return X[(((long)c * dout + a) * min_ + p) * din + ss];
-      },
-      [&](int m, int n, zc z) { const int a = n / din, ss = n - a * din; Y[((long)a * mw + m) * din + ss] = z; });
-  // out[(a,q)][r] = sum_(t,s) Y[(a,q)][(t,s)] Ket(s,t,r)
-  const int kr = d * din;
-  wg_gemm<true, false>(dout * mout, dout, kr, tiles,
-      [&](int m, int k) { return Y[(long)m * kr + k]; },
-      [&](int k, int n) { const int t = k / din, ss = k - t * din; return Tk[ss * sTi + t * sTd + n * sTo]; },
-      [&](int m, int n, zc z) { out[(long)m * dout + n] = z; });
-}
-
-// bt_matmul likewise: with a further caller of bt_matmul itself k_batch_channel compiles to something else (8 scalar
-// registers fewer, as it happens -- but "as before" is what the other kernels are held to)
-__device__ __noinline__ void bop_matmul(const zc* A, const zc* B, zc* tmp, zc* dst, int M, int N, int K, zc* tiles) {
-  wg_gemm<true, false>(M, N, K, tiles,
-      [&](int m, int k) { return A[(long)m * K + k]; },
-      [&](int k, int n) { return B[(long)k * N + n]; },
-      [&](int m, int n, zc z) { tmp[(long)m * N + n] = z; });
-  for (long e = threadIdx.x; e < (long)M * N; e += SS_THREADS) dst[e] = tmp[e];
-  __syncthreads();
-}
 
 // the d x d identity: the core (1, d, d, 1) of the scalar term's operator in all three of its forms
 __device__ __noinline__ void bop_ident(zc* Id, int d) {
@@ -2169,11 +2130,11 @@ __device__ __noinline__ void bop_move(const BopCtx& c, int p, bool fwd, const Bt
     bt_qr(kt, kt, dr, 1, sig, dr, 1, dl * d, dr, work, sh);    // psi: Psi -> A sigma
     const BatchShape q = c.shp[p + 1];
     zc* nxt = c.ket + c.soff[p + 1];
-    bop_matmul(sig, nxt, spare, nxt, dr, q.d * q.dr, dr, tiles);
-    bop_env(c.mix + c.moff[p], bra, kt, (long)d * dr, dr, 1, c.w2el[p], dl, s.ml, d, dr, s.mr, X, Y, c.mix + c.moff[p + 1], tiles);
+    bt_matmul(sig, nxt, spare, nxt, dr, q.d * q.dr, dr, tiles);
+    bt_env(c.mix + c.moff[p], bra, kt, (long)d * dr, dr, 1, c.w2el[p], dl, s.ml, d, dr, s.mr, X, Y, c.mix + c.moff[p + 1], tiles);
     if (hs) {
       bop_ident(Id, d);
-      bop_env(c.ov + c.voff[p], bra, kt, (long)d * dr, dr, 1, Id, dl, 1, d, dr, 1, X, Y, c.ov + c.voff[p + 1], tiles);
+      bt_env(c.ov + c.voff[p], bra, kt, (long)d * dr, dr, 1, Id, dl, 1, d, dr, 1, X, Y, c.ov + c.voff[p + 1], tiles);
     }
   } else {
     const int mq = d * dr;
@@ -2181,43 +2142,29 @@ __device__ __noinline__ void bop_move(const BopCtx& c, int p, bool fwd, const Bt
     bt_qr(kt, kt, 1, mq, sig, 1, dl, mq, dl, work, sh);    // sigma = R^T (dl x dl)
     const BatchShape q = c.shp[p - 1];
     zc* prv = c.ket + c.soff[p - 1];
-    bop_matmul(prv, sig, spare, prv, q.dl * q.d, dl, dl, tiles);
-    bop_env(c.mix + c.moff[p + 1], bra, kt, 1, dr, (long)d * dr, c.w2er[p], dr, s.mr, d, dl, s.ml, X, Y, c.mix + c.moff[p], tiles);
+    bt_matmul(prv, sig, spare, prv, q.dl * q.d, dl, dl, tiles);
+    bt_env(c.mix + c.moff[p + 1], bra, kt, 1, dr, (long)d * dr, c.w2er[p], dr, s.mr, d, dl, s.ml, X, Y, c.mix + c.moff[p], tiles);
     if (hs) {
       bop_ident(Id, d);
-      bop_env(c.ov + c.voff[p + 1], bra, kt, 1, dr, (long)d * dr, Id, dr, 1, d, dl, 1, X, Y, c.ov + c.voff[p], tiles);
+      bt_env(c.ov + c.voff[p + 1], bra, kt, 1, dr, (long)d * dr, Id, dr, 1, d, dl, 1, X, Y, c.ov + c.voff[p], tiles);
     }
   }
 }
 
-// <bra | prev> over all sites: the walk and the products of k_batch_cross with site = -1; the same bits in every thread
+// <bra | prev> over all sites (wg_overlap), T and its successor in the two transfer blocks; the same bits in every thread
 __device__ __noinline__ zc bop_overlap(int L, const BatchShape* shp, zc* const* site, const zc* prev, const long long* soff, zc* T,
                                        zc* T2, zc* U, zc* tiles) {
-  if (threadIdx.x == 0) T[0] = make_double2(1.0, 0.0);
-  __syncthreads();
-  for (int p = 0; p < L; ++p) {
-    const BatchShape s = shp[p];
-    const int dl = s.dl, d = s.d, dr = s.dr, ddr = d * dr;
-    const zc* Kt = prev + soff[p];
-    const zc* Bt = site[p];
-    // U[m][(j,s)] = sum_n T[m][n] K[n][(j,s)]
-    wg_gemm<true, false>(dl, ddr, dl, tiles,
-        [&](int m, int kk) { return T[(long)m * dl + kk]; },
-        [&](int kk, int n) { return Kt[(long)kk * ddr + n]; },
-        [&](int m, int n, zc z) { U[(long)m * ddr + n] = z; });
-    // T'[i][j] = sum_(m,s) conj(Bra[(m,s)][i]) U[(m,s)][j]
-    wg_gemm<false, false>(dr, dr, dl * d, tiles,
-        [&](int m, int kk) { const zc z = Bt[(long)kk * dr + m]; return make_double2(z.x, -z.y); },
-        [&](int kk, int n) { return U[(long)kk * dr + n]; },
-        [&](int m, int n, zc z) { T2[(long)m * dr + n] = z; });
-    zc* t = T; T = T2; T2 = t;
-  }
-  const zc ov = T[0];
+  const zc ov = wg_overlap(L, shp, [&](int p, size_t) { return prev + soff[p]; }, [&](int p, size_t) { return site[p]; },
+                           T, T2, U, tiles)[0];
   __syncthreads();  // every thread has read the value before the blocks are used again
   return ov;
 }
 
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): see DESIGN.md section 7.3.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 246 VGPRs, 106 SGPRs, no vector
+// register spills, 22 scalar registers spilled around the calls of the stage functions, 384 bytes of private memory per lane
+// (BopCtx, which the stage functions take by reference and read BEFORE their products, and the shape blocks bt_heff takes
+// by reference: none of it inside a product loop), 20 032 bytes of LDS; occupancy 2 waves per SIMD, i.e. one workgroup
+// (replica) per compute unit.  DESIGN.md section 7.3.
 __global__ __launch_bounds__(SS_THREADS) void k_batch_operate(BatchOperateArgs g) {
   __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
   __shared__ zc s_z[2 * BATCH_MAX_BOND];
@@ -2276,12 +2223,12 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_operate(BatchOperateArgs g
   for (int p = L - 1; p >= 1; --p) {
     const BatchShape s = c.shp[p];
     const zc* kt = c.ket + c.soff[p];
-    bop_env(c.mix + c.moff[p + 1], c.site[p], kt, 1, s.dr, (long)s.d * s.dr, c.w2er[p], s.dr, s.mr, s.d, s.dl, s.ml, c.X, c.Y,
-            c.mix + c.moff[p], c.tiles);
+    bt_env(c.mix + c.moff[p + 1], c.site[p], kt, 1, s.dr, (long)s.d * s.dr, c.w2er[p], s.dr, s.mr, s.d, s.dl, s.ml, c.X, c.Y,
+           c.mix + c.moff[p], c.tiles);
     if (hs) {
       bop_ident(c.Id, s.d);
-      bop_env(c.ov + c.voff[p + 1], c.site[p], kt, 1, s.dr, (long)s.d * s.dr, c.Id, s.dr, 1, s.d, s.dl, 1, c.X, c.Y, c.ov + c.voff[p],
-              c.tiles);
+      bt_env(c.ov + c.voff[p + 1], c.site[p], kt, 1, s.dr, (long)s.d * s.dr, c.Id, s.dr, 1, s.d, s.dl, 1, c.X, c.Y, c.ov + c.voff[p],
+             c.tiles);
     }
   }
 

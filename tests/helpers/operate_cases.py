@@ -115,7 +115,7 @@ def _heff(Lb, W, Rb, v):
 
 
 def _env_fwd(E, bra, ket, W):
-    """bt_env2 in the forward roles: env (bra, mpo, ket) -> the block right of the site"""
+    """bt_env in the forward roles: env (bra, mpo, ket) -> the block right of the site"""
     X = np.einsum("bca,bps->caps", bra.conj(), E)
     Y = np.einsum("pctq,caps->aqts", W, X)
     return np.einsum("aqts,str->aqr", Y, ket)
