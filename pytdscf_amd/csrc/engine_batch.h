@@ -2,13 +2,80 @@
 // One-site and nearest-neighbour gates and quantum-jump channels set on the batch act between the two half-sweeps of a
 // time step: one more launch.
 #pragma once
+#include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
+#include "batch_records.h"
 #include "batch_site.h"
 #include "engine.h"
 
 namespace mitdvp {
+
+// An owning device array of the batch: move-only, freed in the destructor.  reserve grows only, does not preserve the
+// contents and allocates at least one element, so an array that was reserved is never null; fits says whether reserve
+// would leave the array where it is.  Whoever lets one grow waits first for the work queued on it (Batch::reserve_synced).
+template <class T>
+struct DevArr {
+  T* p = nullptr;
+  size_t n = 0;  // elements asked for
+
+  DevArr() = default;
+  DevArr(DevArr&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DevArr& operator=(DevArr&& o) noexcept {
+    std::swap(p, o.p);
+    std::swap(n, o.n);
+    return *this;
+  }
+  ~DevArr() { if (p) (void)hipFree(p); }
+
+  bool fits(size_t need) const { return p && need <= n; }
+  void reserve(size_t need) {
+    if (fits(need)) return;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+    HIP_CHECK(hipMalloc((void**)&p, std::max<size_t>(need, 1) * sizeof(T)));
+    n = need;
+  }
+  operator T*() const { return p; }
+};
+
+// The records of ONE request of the batch (cross, spectra, samples, expect, cross_mpo) and their means, laid out by
+// BatchRecords (batch_records.h): rec holds the nrec records [rows][len] of the last run() and, behind them, the slot of
+// the call on the current state, which therefore overwrites none of them; mean holds the run's means, the slot's mean and
+// the records' means under weights given later.  h_rec / h_mean mirror what the last run() copied back, h_now the slot
+// and its mean.  The stream and the launch counter are the batch's, and so is every host wait.
+struct RecordStore {
+  DevArr<double> rec, mean, w;
+  std::vector<double> h_rec, h_mean, h_w, h_now;
+  size_t rows = 0, len = 0;  // as last reserved
+  long nrec = 0;             // the records of the last run() that rec and h_rec hold
+  BatchRecords lay() const { return BatchRecords{rows, len, (size_t)nrec}; }
+
+  void drop() { nrec = 0; }  // the records are another request's, or of other shapes
+  // Room for l.nrec records and the slot behind them.  While records are held they must stay where they are, since
+  // X_records still reads them on the device: X() reserves for the run's own count, which fits; run() drops them first.
+  // A reserve for another count, other rows or len, or one that would move them throws std::logic_error and changes
+  // nothing.  reserve also takes rows and len from l, so it is called whether or not everything fits.
+  bool fits(const BatchRecords& l) const { return rec.fits(l.rec_elems()) && mean.fits(l.mean_elems()) && w.fits(l.rows); }
+  void reserve(const BatchRecords& l);
+  double* slot(long q) const { return rec.p + lay().rec_slot((size_t)q); }  // where the request's kernel writes record q
+  void weights(hipStream_t st, const double* weights);                      // rows doubles, null: 1 / rows each
+  // the end of a run of nrec records: ONE k_batch_mean over all of them (the weights are set first), then the copies back
+  void mean_of_run(hipStream_t st, long nrec, long long& n_launch);
+  void fetch_run(hipStream_t st);
+  // the call on the current state, once the request's kernel wrote slot(nrec): ONE k_batch_mean over the slot, the
+  // copies back and, after the host wait, the hand-out (null: not wanted)
+  void mean_of_slot(hipStream_t st, long long& n_launch);
+  void fetch_slot(hipStream_t st, bool values = true, bool mean = true);
+  void slot_out(double* values, double* mean) const;
+  // X_records: values from the mirror; mean from the mirror (weights null; false: nothing was queued) or by ONE
+  // k_batch_mean under the given weights into the third region of the mean buffer, copied straight to mean (true: the
+  // caller waits once)
+  bool records(hipStream_t st, const double* weights, double* values, double* mean, long long& n_launch);
+};
 
 class Batch {
  public:
@@ -73,112 +140,88 @@ class Batch {
            int* statuses) {
     run(dt, nsteps, every, sites, nsites, what, weights, out, statuses, DensOut());
   }
+
+  // ---- the five requests: cross, spectra, samples, expect, cross_mpo ----
+  // What they share, X standing for the request and a row being what a weight multiplies (a pair or an entry for cross and
+  // cross_mpo, a replica for the others):
+  // set_X registers the request, an empty one removes it; either way the records of the request before are dropped.  No
+  // launch, no wait.
+  // X() is the request on the current state: the request's kernel and k_batch_mean, TWO launches, one host wait.  weights:
+  // one double per row or null (1 / rows each); every output may be null.
+  // While a request is set every record of run() records it too: ONE more launch per record (the request's kernel behind
+  // the record's other launches) and ONE more k_batch_mean launch per call (weights 1 / rows); values and means are copied
+  // with the rest, no further host wait.  X_records returns what the last run() recorded: the arrays of X() with a leading
+  // record axis, each may be null, and counts with the number of records in front.  weights null: the means of the run,
+  // no launch and no wait; weights given: ONE k_batch_mean launch over the records, which are still on the device, and
+  // one host wait.  X() after a run leaves the run's records and means as they are, and so does X_records.
+  // Every refusal is an ArgError that names the entry point and the limit and leaves the request, the records, the
+  // snapshot and every engine as they were.
+
   // ---- cross overlaps and one-site matrix elements between replicas (k_batch_cross, k_batch_snapshot) ----
-  // A state index 0 .. B-1 names replica i, B + r the snapshot of replica r.  Every refusal is an ArgError that names the
-  // entry point and the limit and leaves the request, the snapshot and every engine as they were.
+  // A state index 0 .. B-1 names replica i, B + r the snapshot of replica r.
   // snapshot: ONE launch copies every site tensor of every replica into the batch's snapshot buffer; one host wait.  The
   // centre may be at site 0 or at site L-1 (where a batch call leaves it).
   void snapshot();
   // set_cross: registers npairs entries (bra, ket, site, operator); site -1 is the plain overlap, otherwise the entry
   // takes the next matrix of ops_reim (row-major [out][in], interleaved re / im) whose order is the next of op_dims.
-  // npairs = 0 removes the request.  Refused: an index outside 0 .. 2B-1, a snapshot index before any snapshot, a site
-  // outside -1 .. L-1, an order that is not the site's d, more than BATCH_CROSS_MAX_PAIRS pairs.  No launch, no wait.
+  // Refused: an index outside 0 .. 2B-1, a snapshot index before any snapshot, a site outside -1 .. L-1, an order that is
+  // not the site's d, more than BATCH_CROSS_MAX_PAIRS pairs.
   void set_cross(int npairs, const int* bra, const int* ket, const int* site, const double* ops_reim, const int* op_dims);
   bool has_cross() const { return !cross_.empty(); }
-  // cross: the request on the current state: k_batch_cross and k_batch_mean, TWO launches, one host wait.  weights:
-  // npairs doubles or null (1 / npairs); values [npairs][2] and mean [2] may each be null.
+  // weights: npairs doubles; values [npairs][2], mean [2]; counts {records, npairs}
   void cross(const double* weights, double* values, double* mean);
-  // While a request is set every record of run() records it too: ONE more launch per record (k_batch_cross behind the
-  // record's other launches) and ONE more k_batch_mean launch per call (weights 1 / npairs); values and means are copied
-  // with the rest, no further host wait.  cross_records returns what the last run() recorded: values
-  // [records][npairs][2], mean [records][2], counts {records, npairs}; each may be null.  weights null: the means of the
-  // run, no launch and no wait; weights given (npairs doubles): ONE k_batch_mean launch over the records, which are still
-  // on the device, and one host wait.
   void cross_records(const double* weights, double* values, double* mean, size_t* counts);
 
   // ---- bond spectra and entanglement entropies (k_batch_spectra) ----
   // The request is a strictly ascending list of bonds q in 0 .. L-2 (bond q lies between sites q and q+1); a replica's
-  // record is, per listed bond, BSPEC_HEAD + chi_q doubles (batch_site.h).  Every refusal is an ArgError that names the
-  // entry point and the limit and leaves the request, the records and every engine as they were.
-  // set_spectra: nbonds = 0 removes the request.  Refused: a bond outside 0 .. L-2, a list that is not strictly ascending,
-  // a record of more than BATCH_OBS_MAX_RDM doubles.  No launch, no wait.
+  // record is, per listed bond, BSPEC_HEAD + chi_q doubles (batch_site.h).
+  // set_spectra refuses: a bond outside 0 .. L-2, a list that is not strictly ascending, a record of more than
+  // BATCH_OBS_MAX_RDM doubles.
   void set_spectra(const int* bonds, int nbonds);
   bool has_spectra() const { return !spec_bonds_.empty(); }
-  // spectra: the request on the current state (centre at site 0): k_batch_spectra and k_batch_mean, TWO launches, one host
-  // wait.  weights: B doubles or null (1 / B); values [B][rec_len] and mean [rec_len] may each be null; counts {B,
+  // centre at site 0.  weights: B doubles; values [B][rec_len], mean [rec_len]; counts {B, rec_len} and {records, B,
   // rec_len}; with all outputs null only the counts are returned.  NotConverged, naming the replica and the bond, when a
   // Jacobi sweep did not converge (that replica's record is zeros; its status word and its tensors stay as they are).
   void spectra(const double* weights, double* values, double* mean, size_t* counts);
-  // While a request is set every record of run() records it too: ONE more launch per record (k_batch_spectra behind the
-  // record's other launches) and ONE more k_batch_mean launch per call (weights 1 / B); values and means are copied with
-  // the rest, no further host wait.  spectra_records returns what the last run() recorded: values
-  // [records][B][rec_len], mean [records][rec_len], counts {records, B, rec_len}; each may be null.  weights null: the
-  // means of the run, no launch and no wait; weights given (B doubles): ONE k_batch_mean launch over the records, which
-  // are still on the device, and one host wait.
   void spectra_records(const double* weights, double* values, double* mean, size_t* counts);
 
   // ---- sampled configurations (k_batch_sample) ----
   // The request is a number of shots and a seed of its own; a replica's record is configs [nshots][L] (int32), prob
-  // [nshots] and freq [F], F = sum d_p (batch_site.h).  Every refusal is an ArgError that names the entry point and the
-  // limit and leaves the request, the records and every engine as they were.
-  // set_samples: nshots = 0 removes the request.  Refused: nshots outside 0 .. BATCH_SAMPLE_MAX_SHOTS, nshots * L above
-  // BATCH_SAMPLE_MAX_CONFIG.  No launch, no wait.
+  // [nshots] and freq [F], F = sum d_p (batch_site.h); freq is what is averaged.
+  // set_samples refuses: nshots outside 0 .. BATCH_SAMPLE_MAX_SHOTS, nshots * L above BATCH_SAMPLE_MAX_CONFIG.
   void set_samples(int nshots, unsigned long long seed);
   bool has_samples() const { return smp_nshots_ > 0; }
-  // samples: the request on the current state (centre at site 0): k_batch_sample and k_batch_mean, TWO launches, one host
-  // wait.  weights: B doubles or null (1 / B); configs [B][nshots][L], prob [B][nshots], freq [B][F] and mean_freq [F]
-  // may each be null; counts {B, nshots, L, F}; with all outputs null only the counts are returned.
+  // centre at site 0.  weights: B doubles; configs [B][nshots][L], prob [B][nshots], freq [B][F], mean_freq [F]; counts
+  // {B, nshots, L, F} and {records, B, nshots, L, F}; with all outputs null only the counts are returned.
   void samples(const double* weights, int* configs, double* prob, double* freq, double* mean_freq, size_t* counts);
-  // While a request is set every record of run() records it too: ONE more launch per record (k_batch_sample behind the
-  // record's other launches) and ONE more k_batch_mean launch per call (weights 1 / B); values and means are copied with
-  // the rest, no further host wait.  samples_records returns what the last run() recorded, the arrays of samples() with a
-  // leading record axis, counts {records, B, nshots, L, F}; each may be null.  weights null: the means of the run, no
-  // launch and no wait; weights given (B doubles): ONE k_batch_mean launch over the records, which are still on the
-  // device, and one host wait.
   void samples_records(const double* weights, int* configs, double* prob, double* freq, double* mean_freq, size_t* counts);
 
   // ---- expectation values of MPO observables (k_batch_expect) ----
   // The request is a list of operator ids that every replica carries at every site (Engine::set_mpo_core); a replica's
-  // record is 2 nops doubles, (re, im) of <psi | O_k | psi> + shift_k <psi | psi> in list order, not normalised.  Every
-  // refusal is an ArgError that names the entry point, the operator, the site and the limit and leaves the request, the
-  // records and every engine as they were.
-  // set_expect: nops = 0 removes the request.  Refused: nops outside 0 .. BATCH_EXPECT_MAX_OPS, a repeated or negative id,
-  // an operator that a replica does not carry at every site, core shapes that differ between replicas or whose physical
-  // dimension is not the site's, MPO bonds above BATCH_MAX_MPO, outer MPO bonds that are not 1.  No launch, no wait.
+  // record is 2 nops doubles, (re, im) of <psi | O_k | psi> + shift_k <psi | psi> in list order, not normalised.  A
+  // refusal names the operator and the site too.
+  // set_expect refuses: nops outside 0 .. BATCH_EXPECT_MAX_OPS, a repeated or negative id, an operator that a replica does
+  // not carry at every site, core shapes that differ between replicas or whose physical dimension is not the site's, MPO
+  // bonds above BATCH_MAX_MPO, outer MPO bonds that are not 1.
   void set_expect(const int* op_ids, int nops);
   bool has_expect() const { return !exp_ops_.empty(); }
-  // expect: the request on the current state (centre at site 0): k_batch_expect and k_batch_mean, TWO launches, one host
-  // wait.  weights: B doubles or null (1 / B); values [B][nops][2] and mean [nops][2] may each be null; counts {B, nops};
+  // centre at site 0.  weights: B doubles; values [B][nops][2], mean [nops][2]; counts {B, nops} and {records, B, nops};
   // with all outputs null only the counts are returned.
   void expect(const double* weights, double* values, double* mean, size_t* counts);
-  // While a request is set every record of run() records it too: ONE more launch per record (k_batch_expect behind the
-  // record's other launches) and ONE more k_batch_mean launch per call (weights 1 / B); values and means are copied with
-  // the rest, no further host wait.  expect_records returns what the last run() recorded: values [records][B][nops][2],
-  // mean [records][nops][2], counts {records, B, nops}; each may be null.  weights null: the means of the run, no launch
-  // and no wait; weights given (B doubles): ONE k_batch_mean launch over the records, which are still on the device, and
-  // one host wait.
   void expect_records(const double* weights, double* values, double* mean, size_t* counts);
 
   // ---- MPO matrix elements between replicas (k_batch_cross_mpo) ----
   // An entry is (bra, ket, op_id): state indices as for set_cross, op_id an operator every replica carries at every site
   // (Engine::set_mpo_core); its value is <psi_bra | O | psi_ket> + shift <psi_bra | psi_ket> with the cores and the scalar
-  // term of the ket's owner (replica ket mod B), not normalised.  Every refusal is an ArgError that names the entry point,
-  // the entry, the operator, the site and the limit and leaves the request, the records, the snapshot and every engine as
-  // they were.
-  // set_cross_mpo: nentries = 0 removes the request.  Refused: an index outside 0 .. 2B-1, a snapshot index before any
-  // snapshot, a negative op_id, an operator that a replica does not carry at every site, core shapes that differ between
-  // replicas, MPO bonds outside 1 .. BATCH_MAX_MPO, neighbouring cores that do not fit, outer MPO bonds that are not 1,
-  // more than BATCH_CROSS_MAX_PAIRS entries, a buffer above BATCH_CROSS_MPO_MAX_BYTES.  No launch, no wait.
+  // term of the ket's owner (replica ket mod B), not normalised.  A refusal names the entry, the operator and the site too.
+  // set_cross_mpo refuses: an index outside 0 .. 2B-1, a snapshot index before any snapshot, a negative op_id, an operator
+  // that a replica does not carry at every site, core shapes that differ between replicas, MPO bonds outside
+  // 1 .. BATCH_MAX_MPO, neighbouring cores that do not fit, outer MPO bonds that are not 1, more than
+  // BATCH_CROSS_MAX_PAIRS entries, a buffer above BATCH_CROSS_MPO_MAX_BYTES.
   void set_cross_mpo(int nentries, const int* bra, const int* ket, const int* op_id);
   bool has_cross_mpo() const { return !xm_.empty(); }
-  // cross_mpo: the request on the current state (centre at site 0 or L-1): k_batch_cross_mpo and k_batch_mean, TWO
-  // launches, one host wait.  weights: nentries doubles or null (1 / nentries); values [nentries][2] and mean [2] may each
-  // be null.
+  // centre at site 0 or L-1.  weights: nentries doubles; values [nentries][2], mean [2]; counts {records, nentries}
   void cross_mpo(const double* weights, double* values, double* mean);
-  // While a request is set every record of run() records it too: ONE more launch per record and ONE more k_batch_mean
-  // launch per call (weights 1 / nentries), no further host wait.  cross_mpo_records returns what the last run() recorded:
-  // values [records][nentries][2], mean [records][2], counts {records, nentries}; each may be null.  weights null: the
-  // means of the run, no launch and no wait; weights given: ONE k_batch_mean launch over the records and one host wait.
   void cross_mpo_records(const double* weights, double* values, double* mean, size_t* counts);
 
   // ---- an MPO applied to the replicas (k_batch_operate) ----
@@ -212,17 +255,28 @@ class Batch {
   std::vector<BatchShape> shp_;
   bool shapes_dirty_ = true;
   BatchPlan plan_;
+  // reserve(need) of every (array, need) pair given; when one of them has to grow, ONE wait for the stream comes first:
+  // work queued on st_ may still use the buffer that is freed.  An array is a DevArr or a RecordStore.
+  template <class... A>
+  void reserve_synced(A&&... a) {
+    if (!all_fit(a...)) HIP_CHECK(hipStreamSynchronize(st_));
+    reserve_all(a...);  // a no-op for a DevArr that fits; a RecordStore takes its rows and len from it either way
+  }
+  static bool all_fit() { return true; }
+  template <class A, class N, class... R>
+  static bool all_fit(const A& a, const N& need, const R&... r) { return a.fits(need) && all_fit(r...); }
+  static void reserve_all() {}
+  template <class A, class N, class... R>
+  static void reserve_all(A& a, const N& need, R&... r) { a.reserve(need); reserve_all(r...); }
   // device tables; per replica [site L][envL L+1][envR L+1][w2l L][w2el L][w2er L][scratch 1]
   size_t ptrs_per_replica() const { return (size_t)6 * L_ + 3; }
-  void** d_ptrs_ = nullptr;
+  DevArr<void*> d_ptrs_;
   std::vector<void*> h_ptrs_;
-  BatchShape* d_shp_ = nullptr;
-  zc* d_shift_ = nullptr;
-  int* d_kprev_ = nullptr;
-  int* d_status_ = nullptr;
-  long long* d_stats_ = nullptr;
-  zc* d_scratch_ = nullptr;
-  size_t scratch_elems_ = 0;
+  DevArr<BatchShape> d_shp_;
+  DevArr<zc> d_shift_;
+  DevArr<int> d_kprev_, d_status_;
+  DevArr<long long> d_stats_;
+  DevArr<zc> d_scratch_;
   std::vector<zc> h_shift_;
   std::vector<int> h_kprev_;
   long long n_launch_ = 0;
@@ -230,18 +284,16 @@ class Batch {
   // observables: the carve behind the sweep's in a replica's scratch area, and the device buffers of a recorded run
   BatchObsPlan obs_plan_;
   size_t carve_ = 0;            // offset of the observation's carve, complex elements
-  double* d_rec_ = nullptr;     // [nrec][B][rec_len]
-  double* d_mean_ = nullptr;    // [nrec][rec_len]
-  double* d_w_ = nullptr;       // [B]
-  int* d_sites_ = nullptr;      // [L]
-  size_t rec_elems_ = 0, mean_elems_ = 0;
+  DevArr<double> d_rec_;        // [nrec][B][rec_len]
+  DevArr<double> d_mean_;       // [nrec][rec_len]
+  DevArr<double> d_w_;          // [B]
+  DevArr<int> d_sites_;         // [L]
   std::vector<double> h_w_, h_rec_, h_mean_;
   std::vector<int> h_sites_;
   // density keys: the leg table and the transfer blocks [B][2][need] of k_batch_density (both grow only)
   BatchDensPlan dens_plan_;
-  int* d_legs_ = nullptr;
-  zc* d_tbuf_ = nullptr;
-  size_t legs_elems_ = 0, tbuf_elems_ = 0;
+  DevArr<int> d_legs_;
+  DevArr<zc> d_tbuf_;
   std::vector<int> h_legs_;
 
   // channels: the table and the operators (host copies and their device images), the generator's seed, ids and step
@@ -252,77 +304,70 @@ class Batch {
   bool chan_dirty_ = false;
   std::vector<BatchChanSite> h_chan_;
   std::vector<zc> h_ops_;
-  BatchChanSite* d_chan_ = nullptr;
-  zc* d_ops_ = nullptr;
-  size_t ops_elems_ = 0;
+  DevArr<BatchChanSite> d_chan_;
+  DevArr<zc> d_ops_;
   unsigned long long seed_ = 0;
   // The BATCH's count of time steps launched since the seed was set, the `step` of the generator: it advances by nsteps
   // in every step / run call, with or without channels and whatever the replicas' statuses are -- it says nothing about
   // how far a replica that failed got (its status word does, and it draws nothing more).
   long long steps_done_ = 0;
   std::vector<unsigned long long> h_ids_;
-  unsigned long long* d_ids_ = nullptr;
-  long long* d_counts_ = nullptr;
+  DevArr<unsigned long long> d_ids_;
+  DevArr<long long> d_counts_;
   // pair channels: entry q is bond (q, q + 1); their operators follow the one-site ones in h_ops_ / d_ops_
   std::vector<BatchChanSite> pair_, h_pair_;  // [L]
   std::vector<std::vector<zc>> pair_ops_;     // [L]
   int npair_ = 0;
-  BatchChanSite* d_pair_ = nullptr;
-  long long* d_pcounts_ = nullptr;
-  double* d_disc_ = nullptr;
+  DevArr<BatchChanSite> d_pair_;
+  DevArr<long long> d_pcounts_;
+  DevArr<double> d_disc_;
+
+  // What the five requests share lies in their RecordStore; the tail of X_records is one function for all of them.
+  void records_of(RecordStore& s, const double* weights, double* values, double* mean);
 
   // cross request: the pairs and their operators (host copies and device images), the transfer buffers [P][buf_len] of
-  // k_batch_cross, the records [nrec + 1][P][2] (the slot behind a run's records is cross()'s own) and their means, the
-  // snapshot [B][snap_len]
+  // k_batch_cross, the records (rows = P, len = 2), the snapshot [B][snap_len]
   std::vector<BatchCrossPair> cross_;
   std::vector<zc> cross_ops_;
   bool cross_dirty_ = false, has_snap_ = false;
-  BatchCrossPair* d_cross_pairs_ = nullptr;
-  zc *d_cross_ops_ = nullptr, *d_cross_buf_ = nullptr, *d_snap_ = nullptr;
-  double *d_cross_rec_ = nullptr, *d_cross_mean_ = nullptr, *d_cross_w_ = nullptr;
-  size_t cross_pairs_elems_ = 0, cross_ops_elems_ = 0, cross_buf_elems_ = 0, cross_rec_slots_ = 0,
-         cross_mean_slots_ = 0, snap_elems_ = 0;  // cross_rec_slots_ / cross_mean_slots_: doubles
-  long cross_nrec_ = 0;  // records of the last run() held in d_cross_rec_ / h_cross_rec_
-  std::vector<double> h_cross_rec_, h_cross_mean_, h_cross_w_, h_cross_now_;
+  DevArr<BatchCrossPair> d_cross_pairs_;
+  DevArr<zc> d_cross_ops_, d_cross_buf_, d_snap_;
+  RecordStore cross_rec_;
   size_t snap_len() const;
   size_t cross_buf_len() const { return 2 * (size_t)plan_.max_bond + (size_t)plan_.max_site; }
   void check_cross(const char* entry) const;  // the request against the shapes and the snapshot as they are now
   void prepare_observing();                   // prepare() for a call that only reads the state: centre at 0 or at L-1
   void upload_cross(long nrec);               // device images of the request, room for nrec records and cross()'s slot
   void launch_cross(long record);
-  void cross_weights(const double* weights);
 
   // spectra request: the bonds (host copy and device image), the walk's buffers [B][buf_len], the word per replica that a
-  // Jacobi sweep without convergence sets, the records [nrec + 1][B][rec_len] (the slot behind a run's records is
-  // spectra()'s own) and their means
+  // Jacobi sweep without convergence sets, the records (rows = B, len = spec_rec_len())
   std::vector<int> spec_bonds_;
   bool spec_dirty_ = false;
-  int *d_spec_bonds_ = nullptr, *d_spec_fail_ = nullptr;
-  zc* d_spec_buf_ = nullptr;
-  double *d_spec_rec_ = nullptr, *d_spec_mean_ = nullptr, *d_spec_w_ = nullptr;
-  size_t spec_buf_elems_ = 0, spec_rec_slots_ = 0, spec_mean_slots_ = 0;  // the last two: doubles
-  long spec_nrec_ = 0;  // records of the last run() held in d_spec_rec_ / h_spec_rec_
-  std::vector<double> h_spec_rec_, h_spec_mean_, h_spec_w_, h_spec_now_;
+  DevArr<int> d_spec_bonds_, d_spec_fail_;
+  DevArr<zc> d_spec_buf_;
+  RecordStore spec_rec_;
   std::vector<int> h_spec_fail_;
   long spec_rec_len() const;
   size_t spec_buf_len() const { return 2 * (size_t)plan_.max_site + (size_t)plan_.max_bond; }
   void check_spectra(const char* entry) const;  // the request against the shapes as they are now
   void upload_spectra(long nrec);               // device image of the request, room for nrec records and spectra()'s slot
   void launch_spectra(long record);
-  void spectra_weights(const double* weights);
   void spectra_failed(const char* entry) const;  // NotConverged when h_spec_fail_ names a replica
 
-  // samples request: shots and seed, the walk's buffers [B][buf_len], the records [nrec + 1] of configurations,
-  // probabilities and frequencies (the slot behind a run's records is samples()'s own) and the frequencies' means
+  // samples request: shots and seed, the walk's buffers [B][buf_len], the records: the frequencies, the one averaged
+  // array, in the store (rows = B, len = F); configurations and probabilities beside it, sliced by smp_cfg_lay() and
+  // smp_prob_lay() with the store's count of records
   int smp_nshots_ = 0;
   unsigned long long smp_seed_ = 0;
-  zc* d_smp_buf_ = nullptr;
-  int* d_smp_cfg_ = nullptr;
-  double *d_smp_prob_ = nullptr, *d_smp_freq_ = nullptr, *d_smp_mean_ = nullptr, *d_smp_w_ = nullptr;
-  size_t smp_buf_elems_ = 0, smp_cfg_slots_ = 0, smp_prob_slots_ = 0, smp_freq_slots_ = 0, smp_mean_slots_ = 0;
-  long smp_nrec_ = 0;  // records of the last run() held in d_smp_* / h_smp_*
+  DevArr<zc> d_smp_buf_;
+  DevArr<int> d_smp_cfg_;
+  DevArr<double> d_smp_prob_;
+  RecordStore smp_rec_;
   std::vector<int> h_smp_cfg_, h_smp_cfg_now_;
-  std::vector<double> h_smp_prob_, h_smp_freq_, h_smp_mean_, h_smp_w_, h_smp_now_;
+  std::vector<double> h_smp_prob_, h_smp_prob_now_;
+  BatchRecords smp_cfg_lay(long nrec) const { return BatchRecords{eng_.size(), (size_t)smp_nshots_ * L_, (size_t)nrec}; }
+  BatchRecords smp_prob_lay(long nrec) const { return BatchRecords{eng_.size(), (size_t)smp_nshots_, (size_t)nrec}; }
   long smp_F() const;           // sum of the physical dimensions
   size_t smp_o_w() const;       // offsets of W and of the weights in a replica's part of d_smp_buf_, and its length
   size_t smp_o_g() const;
@@ -330,32 +375,25 @@ class Batch {
   void check_samples(const char* entry) const;  // the request against the shapes as they are now
   void upload_samples(long nrec);               // room for nrec records and samples()'s slot
   void launch_samples(long record, long long step);
-  void samples_weights(const double* weights);
 
   // expect request: the operator ids, the shapes [nops][L] with each operator's MPO bonds and the carve they give, the
   // device tables (operator blocks [B][nops][3 L], shapes, shifts [B][nops]; refreshed with the batch's own tables, since
-  // engines may be given new cores between calls), the walk's buffer [B][nops][carve], the records [nrec + 1][B][2 nops]
-  // (the slot behind a run's records is expect()'s own) and their means
+  // engines may be given new cores between calls), the walk's buffer [B][nops][carve], the records (rows = B, len = 2 nops)
   std::vector<int> exp_ops_;
   std::vector<BatchShape> exp_shp_;
   BatchExpectPlan exp_plan_;
   bool exp_shp_dirty_ = false;
-  void** d_exp_ptrs_ = nullptr;
-  BatchShape* d_exp_shp_ = nullptr;
-  zc *d_exp_shift_ = nullptr, *d_exp_buf_ = nullptr;
-  double *d_exp_rec_ = nullptr, *d_exp_mean_ = nullptr, *d_exp_w_ = nullptr;
-  size_t exp_ptrs_elems_ = 0, exp_shp_elems_ = 0, exp_shift_elems_ = 0, exp_buf_elems_ = 0, exp_rec_slots_ = 0,
-         exp_mean_slots_ = 0;  // the last two: doubles
-  long exp_nrec_ = 0;  // records of the last run() held in d_exp_rec_ / h_exp_rec_
+  DevArr<void*> d_exp_ptrs_;
+  DevArr<BatchShape> d_exp_shp_;
+  DevArr<zc> d_exp_shift_, d_exp_buf_;
+  RecordStore exp_rec_;
   std::vector<void*> h_exp_ptrs_;
   std::vector<zc> h_exp_shift_;
-  std::vector<double> h_exp_rec_, h_exp_mean_, h_exp_w_, h_exp_now_;
   // the shapes of the listed operators on the engines as they are now; ArgError naming the entry point otherwise
   void expect_shapes(const char* entry, const int* op_ids, int nops, std::vector<BatchShape>& shp, BatchExpectPlan& plan) const;
   void check_expect(const char* entry);  // the request against the engines as they are now; new shapes drop the records
   void upload_expect(long nrec);         // the device tables, room for nrec records and expect()'s slot
   void launch_expect(long record);
-  void expect_weights(const double* weights);
   // the shapes [nops][L] of the listed operators on the engines as they are now (the gathering half of expect_shapes);
   // ArgError naming the entry point, the operator, the site and the replica otherwise
   // only: the replicas to look at (nonly of them), null: all
@@ -365,43 +403,35 @@ class Batch {
   // operate(): the tables of one call (grow only): the selected replicas [nsel], w2l / w2el / w2er of the operator
   // [nsel][3][L], its scalar terms [nsel], the shapes [L] with its MPO bonds, the carve's prefix sums [3][L + 1], the
   // carves [nsel][total], the norms and sweep counts [nsel]
-  int* d_op_rep_ = nullptr;
-  void** d_op_ptrs_ = nullptr;
-  zc *d_op_shift_ = nullptr, *d_op_buf_ = nullptr;
-  BatchShape* d_op_shp_ = nullptr;
-  long long* d_op_offs_ = nullptr;
-  double* d_op_norms_ = nullptr;
-  int* d_op_iters_ = nullptr;
-  size_t op_rep_elems_ = 0, op_ptrs_elems_ = 0, op_shift_elems_ = 0, op_buf_elems_ = 0, op_shp_elems_ = 0, op_offs_elems_ = 0,
-         op_norms_elems_ = 0, op_iters_elems_ = 0;
+  DevArr<int> d_op_rep_, d_op_iters_;
+  DevArr<void*> d_op_ptrs_;
+  DevArr<zc> d_op_shift_, d_op_buf_;
+  DevArr<BatchShape> d_op_shp_;
+  DevArr<long long> d_op_offs_;
+  DevArr<double> d_op_norms_;
 
   // cross request of MPOs: the entries (op = index into xm_ops_, the distinct operator ids in order of first use), the
   // shapes [nops][L] and the carve they give, the device tables (w2el [B][nops][L], shapes, shifts [B][nops]; refreshed
   // with the batch's own tables, since engines may be given new cores between calls), the walk's buffer [P][carve], the
-  // records [nrec + 1][P][2] (the slot behind a run's records is cross_mpo()'s own) and their means, the weights [P]
+  // records (rows = P, len = 2)
   std::vector<BatchCrossMpoEntry> xm_;
   std::vector<int> xm_ops_;
   std::vector<BatchShape> xm_shp_;
   BatchCrossMpoPlan xm_plan_;
   bool xm_dirty_ = false;
-  BatchCrossMpoEntry* d_xm_ent_ = nullptr;
-  void** d_xm_ptrs_ = nullptr;
-  BatchShape* d_xm_shp_ = nullptr;
-  zc *d_xm_shift_ = nullptr, *d_xm_buf_ = nullptr;
-  double *d_xm_rec_ = nullptr, *d_xm_mean_ = nullptr, *d_xm_w_ = nullptr;
-  size_t xm_ent_elems_ = 0, xm_ptrs_elems_ = 0, xm_shp_elems_ = 0, xm_shift_elems_ = 0, xm_buf_elems_ = 0, xm_rec_slots_ = 0,
-         xm_mean_slots_ = 0, xm_w_elems_ = 0;  // xm_rec_slots_ / xm_mean_slots_: doubles
-  long xm_nrec_ = 0;  // records of the last run() held in d_xm_rec_ / h_xm_rec_
+  DevArr<BatchCrossMpoEntry> d_xm_ent_;
+  DevArr<void*> d_xm_ptrs_;
+  DevArr<BatchShape> d_xm_shp_;
+  DevArr<zc> d_xm_shift_, d_xm_buf_;
+  RecordStore xm_rec_;
   std::vector<void*> h_xm_ptrs_;
   std::vector<zc> h_xm_shift_;
-  std::vector<double> h_xm_rec_, h_xm_mean_, h_xm_w_, h_xm_now_;
   // shapes and carve of the listed operators on the engines as they are now, and the buffer cap for nentries entries
   void cross_mpo_shapes(const char* entry, const int* op_ids, int nops, size_t nentries, std::vector<BatchShape>& shp,
                         BatchCrossMpoPlan& plan) const;
   void check_cross_mpo(const char* entry);  // the request against the engines and the snapshot as they are now
   void upload_cross_mpo(long nrec);         // the device tables, room for nrec records and cross_mpo()'s slot
   void launch_cross_mpo(long record);
-  void cross_mpo_weights(const double* weights);
 
   static std::vector<BatchShape> shapes_of(Engine& e);
   void check_channels() const;

@@ -21,12 +21,72 @@ mitdvp_batch::~mitdvp_batch() = default;
 
 namespace mitdvp {
 
-namespace {
-template <class T>
-void dev_alloc(T*& p, size_t n) {
-  HIP_CHECK(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)));
+// ---- the records of one request (RecordStore, engine_batch.h) ----
+void RecordStore::reserve(const BatchRecords& l) {
+  if (nrec > 0 && ((long)l.nrec != nrec || l.rows != rows || l.len != len || !rec.fits(l.rec_elems()) || !mean.fits(l.mean_elems())))
+    throw std::logic_error("batch: the records of the last run are still held, and room is asked for others");
+  rec.reserve(l.rec_elems());
+  mean.reserve(l.mean_elems());
+  w.reserve(l.rows);
+  rows = l.rows;
+  len = l.len;
 }
-}  // namespace
+
+void RecordStore::weights(hipStream_t st, const double* weights) {
+  h_w.assign(rows, 1.0 / (double)rows);
+  if (weights) h_w.assign(weights, weights + rows);
+  HIP_CHECK(hipMemcpyAsync(w, h_w.data(), rows * sizeof(double), hipMemcpyHostToDevice, st));
+}
+
+void RecordStore::mean_of_run(hipStream_t st, long nrec_run, long long& n_launch) {
+  weights(st, nullptr);
+  nrec = nrec_run;
+  batch_mean_launch(st, rec, w, mean + lay().mean_run(), (int)rows, (long)len, nrec);
+  n_launch += 1;
+}
+
+void RecordStore::fetch_run(hipStream_t st) {
+  const BatchRecords l = lay();
+  h_rec.resize(l.rec_now());                  // the slots in front of the call's own
+  h_mean.resize(l.mean_now() - l.mean_run());  // the first region
+  HIP_CHECK(hipMemcpyAsync(h_rec.data(), rec, h_rec.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(h_mean.data(), mean + l.mean_run(), h_mean.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+}
+
+void RecordStore::mean_of_slot(hipStream_t st, long long& n_launch) {
+  const BatchRecords l = lay();
+  batch_mean_launch(st, rec + l.rec_now(), w, mean + l.mean_now(), (int)rows, (long)len, 1);
+  n_launch += 1;
+}
+
+void RecordStore::fetch_slot(hipStream_t st, bool values, bool mean_too) {
+  const BatchRecords l = lay();
+  h_now.resize(l.slot_elems() + len);
+  if (values) HIP_CHECK(hipMemcpyAsync(h_now.data(), rec + l.rec_now(), l.slot_elems() * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (mean_too) HIP_CHECK(hipMemcpyAsync(h_now.data() + l.slot_elems(), mean + l.mean_now(), len * sizeof(double), hipMemcpyDeviceToHost, st));
+}
+
+void RecordStore::slot_out(double* values, double* mean_out) const {
+  const size_t ne = lay().slot_elems();
+  if (values) std::memcpy(values, h_now.data(), ne * sizeof(double));
+  if (mean_out) std::memcpy(mean_out, h_now.data() + ne, len * sizeof(double));
+}
+
+bool RecordStore::records(hipStream_t st, const double* weights_in, double* values, double* mean_out, long long& n_launch) {
+  const BatchRecords l = lay();
+  if (values) std::memcpy(values, h_rec.data(), l.rec_now() * sizeof(double));
+  if (!mean_out) return false;
+  if (!weights_in) {
+    std::memcpy(mean_out, h_mean.data(), (l.mean_now() - l.mean_run()) * sizeof(double));
+    return false;
+  }
+  weights(st, weights_in);
+  double* dst = mean + l.mean_reweighted();  // behind the run's own means and the slot's: both stay as they are
+  batch_mean_launch(st, rec, w, dst, (int)rows, (long)len, nrec);
+  n_launch += 1;
+  HIP_CHECK(hipMemcpyAsync(mean_out, dst, (l.mean_now() - l.mean_run()) * sizeof(double), hipMemcpyDeviceToHost, st));
+  return true;
+}
 
 std::vector<BatchShape> Batch::shapes_of(Engine& e) {
   std::vector<BatchShape> s((size_t)e.L_);
@@ -90,10 +150,10 @@ void Batch::validate() {
     shp_ = s0;
     shapes_dirty_ = true;
     has_snap_ = false;  // a snapshot of other shapes names nothing any more
-    spec_nrec_ = 0;     // nor do spectra records of other bond dimensions
-    smp_nrec_ = 0;      // nor sampled configurations of other shapes
-    exp_nrec_ = 0;      // nor expectation values walked over other bonds
-    xm_nrec_ = 0;       // nor MPO matrix elements between states of other bonds
+    spec_rec_.drop();   // nor do spectra records of other bond dimensions
+    smp_rec_.drop();    // nor sampled configurations of other shapes
+    exp_rec_.drop();    // nor expectation values walked over other bonds
+    xm_rec_.drop();     // nor MPO matrix elements between states of other bonds
   }
   plan_ = pl;
   batch_observe_plan(plan_, obs_plan_);
@@ -112,25 +172,22 @@ Batch::Batch(const std::vector<Engine*>& engines) : eng_(engines) {
   const size_t n = eng_.size();
   ev_.assign(n, nullptr);
   for (size_t i = 0; i < n; ++i) HIP_CHECK(hipEventCreateWithFlags(&ev_[i], hipEventDisableTiming));
-  dev_alloc(d_ptrs_, n * ptrs_per_replica());
-  dev_alloc(d_shp_, (size_t)L_);
-  dev_alloc(d_shift_, n);
-  dev_alloc(d_kprev_, n * L_);
-  dev_alloc(d_status_, n);
-  dev_alloc(d_stats_, n * 4);
-  dev_alloc(d_w_, n);
-  dev_alloc(d_sites_, (size_t)L_);
-  dev_alloc(d_chan_, (size_t)L_);
-  dev_alloc(d_ids_, n);
-  dev_alloc(d_counts_, n * L_ * BATCH_MAX_JUMP);
-  dev_alloc(d_pair_, (size_t)L_);
-  dev_alloc(d_pcounts_, n * L_ * BATCH_MAX_JUMP);
-  dev_alloc(d_disc_, n);
-  dev_alloc(d_spec_bonds_, (size_t)L_);
-  dev_alloc(d_spec_fail_, n);
-  dev_alloc(d_spec_w_, n);
-  dev_alloc(d_smp_w_, n);
-  dev_alloc(d_exp_w_, n);
+  d_ptrs_.reserve(n * ptrs_per_replica());
+  d_shp_.reserve((size_t)L_);
+  d_shift_.reserve(n);
+  d_kprev_.reserve(n * L_);
+  d_status_.reserve(n);
+  d_stats_.reserve(n * 4);
+  d_w_.reserve(n);
+  d_sites_.reserve((size_t)L_);
+  d_chan_.reserve((size_t)L_);
+  d_ids_.reserve(n);
+  d_counts_.reserve(n * L_ * BATCH_MAX_JUMP);
+  d_pair_.reserve((size_t)L_);
+  d_pcounts_.reserve(n * L_ * BATCH_MAX_JUMP);
+  d_disc_.reserve(n);
+  d_spec_bonds_.reserve((size_t)L_);
+  d_spec_fail_.reserve(n);
   chan_.assign((size_t)L_, BatchChanSite{BCH_NONE, 0, 0});
   chan_ops_.assign((size_t)L_, {});
   pair_.assign((size_t)L_, BatchChanSite{BCH_NONE, 0, 0});
@@ -143,70 +200,8 @@ Batch::~Batch() {
   if (st_) (void)hipStreamSynchronize(st_);
   for (hipEvent_t e : ev_)
     if (e) (void)hipEventDestroy(e);
-  if (d_ptrs_) (void)hipFree(d_ptrs_);
-  if (d_shp_) (void)hipFree(d_shp_);
-  if (d_shift_) (void)hipFree(d_shift_);
-  if (d_kprev_) (void)hipFree(d_kprev_);
-  if (d_status_) (void)hipFree(d_status_);
-  if (d_stats_) (void)hipFree(d_stats_);
-  if (d_scratch_) (void)hipFree(d_scratch_);
-  if (d_rec_) (void)hipFree(d_rec_);
-  if (d_mean_) (void)hipFree(d_mean_);
-  if (d_w_) (void)hipFree(d_w_);
-  if (d_sites_) (void)hipFree(d_sites_);
-  if (d_chan_) (void)hipFree(d_chan_);
-  if (d_ops_) (void)hipFree(d_ops_);
-  if (d_ids_) (void)hipFree(d_ids_);
-  if (d_counts_) (void)hipFree(d_counts_);
-  if (d_pair_) (void)hipFree(d_pair_);
-  if (d_pcounts_) (void)hipFree(d_pcounts_);
-  if (d_disc_) (void)hipFree(d_disc_);
-  if (d_legs_) (void)hipFree(d_legs_);
-  if (d_tbuf_) (void)hipFree(d_tbuf_);
-  if (d_cross_pairs_) (void)hipFree(d_cross_pairs_);
-  if (d_cross_ops_) (void)hipFree(d_cross_ops_);
-  if (d_cross_buf_) (void)hipFree(d_cross_buf_);
-  if (d_cross_rec_) (void)hipFree(d_cross_rec_);
-  if (d_cross_mean_) (void)hipFree(d_cross_mean_);
-  if (d_cross_w_) (void)hipFree(d_cross_w_);
-  if (d_snap_) (void)hipFree(d_snap_);
-  if (d_spec_bonds_) (void)hipFree(d_spec_bonds_);
-  if (d_spec_fail_) (void)hipFree(d_spec_fail_);
-  if (d_spec_w_) (void)hipFree(d_spec_w_);
-  if (d_spec_buf_) (void)hipFree(d_spec_buf_);
-  if (d_spec_rec_) (void)hipFree(d_spec_rec_);
-  if (d_spec_mean_) (void)hipFree(d_spec_mean_);
-  if (d_smp_w_) (void)hipFree(d_smp_w_);
-  if (d_smp_buf_) (void)hipFree(d_smp_buf_);
-  if (d_smp_cfg_) (void)hipFree(d_smp_cfg_);
-  if (d_smp_prob_) (void)hipFree(d_smp_prob_);
-  if (d_smp_freq_) (void)hipFree(d_smp_freq_);
-  if (d_smp_mean_) (void)hipFree(d_smp_mean_);
-  if (d_exp_w_) (void)hipFree(d_exp_w_);
-  if (d_exp_ptrs_) (void)hipFree(d_exp_ptrs_);
-  if (d_exp_shp_) (void)hipFree(d_exp_shp_);
-  if (d_exp_shift_) (void)hipFree(d_exp_shift_);
-  if (d_exp_buf_) (void)hipFree(d_exp_buf_);
-  if (d_exp_rec_) (void)hipFree(d_exp_rec_);
-  if (d_exp_mean_) (void)hipFree(d_exp_mean_);
-  if (d_xm_ent_) (void)hipFree(d_xm_ent_);
-  if (d_xm_ptrs_) (void)hipFree(d_xm_ptrs_);
-  if (d_xm_shp_) (void)hipFree(d_xm_shp_);
-  if (d_xm_shift_) (void)hipFree(d_xm_shift_);
-  if (d_xm_buf_) (void)hipFree(d_xm_buf_);
-  if (d_xm_rec_) (void)hipFree(d_xm_rec_);
-  if (d_xm_mean_) (void)hipFree(d_xm_mean_);
-  if (d_xm_w_) (void)hipFree(d_xm_w_);
-  if (d_op_rep_) (void)hipFree(d_op_rep_);
-  if (d_op_ptrs_) (void)hipFree(d_op_ptrs_);
-  if (d_op_shift_) (void)hipFree(d_op_shift_);
-  if (d_op_buf_) (void)hipFree(d_op_buf_);
-  if (d_op_shp_) (void)hipFree(d_op_shp_);
-  if (d_op_offs_) (void)hipFree(d_op_offs_);
-  if (d_op_norms_) (void)hipFree(d_op_norms_);
-  if (d_op_iters_) (void)hipFree(d_op_iters_);
   if (st_) (void)hipStreamDestroy(st_);
-}
+}  // the device arrays free themselves behind this, with nothing queued on them any more
 
 // Brings every engine to the state a half-sweep in direction `forward` starts from, makes the block buffers of every
 // bond exist, and rebuilds the device tables when a shape or a buffer moved since the last call.
@@ -240,13 +235,7 @@ void Batch::prepare(bool forward, bool build_envs) {
   }
   // scratch (grows only when the shapes or the number of replicas grew: the one other synchronisation)
   const size_t per = carve_ + (obs_plan_.total + 15) / 16 * 16;  // the sweep's carve, then the observation's
-  if (per * n > scratch_elems_) {
-    HIP_CHECK(hipStreamSynchronize(st_));
-    if (d_scratch_) (void)hipFree(d_scratch_);
-    d_scratch_ = nullptr;
-    dev_alloc(d_scratch_, per * n);
-    scratch_elems_ = per * n;
-  }
+  reserve_synced(d_scratch_, per * n);
   // tables: [site L][envL L+1][envR L+1][w2l L][w2el L][w2er L][scratch 1] per replica
   const size_t ppr = ptrs_per_replica();
   std::vector<void*> h(n * ppr);
@@ -494,13 +483,7 @@ void Batch::upload_channels() {
     h_pair_[q].off = (long long)h_ops_.size();
     h_ops_.insert(h_ops_.end(), pair_ops_[q].begin(), pair_ops_[q].end());
   }
-  if (h_ops_.size() > ops_elems_) {
-    HIP_CHECK(hipStreamSynchronize(st_));
-    if (d_ops_) (void)hipFree(d_ops_);
-    d_ops_ = nullptr;
-    dev_alloc(d_ops_, h_ops_.size());
-    ops_elems_ = h_ops_.size();
-  }
+  reserve_synced(d_ops_, h_ops_.size());
   HIP_CHECK(hipMemcpyAsync(d_chan_, h_chan_.data(), h_chan_.size() * sizeof(BatchChanSite), hipMemcpyHostToDevice, st_));
   if (npair_) HIP_CHECK(hipMemcpyAsync(d_pair_, h_pair_.data(), h_pair_.size() * sizeof(BatchChanSite), hipMemcpyHostToDevice, st_));
   if (!h_ops_.empty()) HIP_CHECK(hipMemcpyAsync(d_ops_, h_ops_.data(), h_ops_.size() * sizeof(zc), hipMemcpyHostToDevice, st_));
@@ -671,41 +654,16 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   if (chan) check_channels();
   prepare(true, nsteps > 0 || (what & BOBS_ENERGY));
   if (chan) upload_channels();
-  if (cx) upload_cross(nrec);
-  if (sp) upload_spectra(nrec);
-  if (sm) upload_samples(nrec);
-  if (ex) upload_expect(nrec);
-  if (xm) upload_cross_mpo(nrec);
+  // nothing refuses from here on: the run replaces the records of the last one, so their buffers may now grow
+  if (cx) { cross_rec_.drop(); upload_cross(nrec); }
+  if (sp) { spec_rec_.drop(); upload_spectra(nrec); }
+  if (sm) { smp_rec_.drop(); upload_samples(nrec); }
+  if (ex) { exp_rec_.drop(); upload_expect(nrec); }
+  if (xm) { xm_rec_.drop(); upload_cross_mpo(nrec); }
   // buffers of the records and their means (grow only), the site list and the weights
   const size_t need_rec = (size_t)nrec * n * rec_len, need_mean = (size_t)nrec * rec_len;
   const size_t need_legs = (size_t)nkeys * L_, need_tbuf = nkeys ? n * 2 * dens_plan_.need : 0;
-  if (need_rec > rec_elems_ || need_mean > mean_elems_ || need_legs > legs_elems_ || need_tbuf > tbuf_elems_) {
-    HIP_CHECK(hipStreamSynchronize(st_));
-    if (need_legs > legs_elems_) {
-      if (d_legs_) (void)hipFree(d_legs_);
-      d_legs_ = nullptr;
-      dev_alloc(d_legs_, need_legs);
-      legs_elems_ = need_legs;
-    }
-    if (need_tbuf > tbuf_elems_) {
-      if (d_tbuf_) (void)hipFree(d_tbuf_);
-      d_tbuf_ = nullptr;
-      dev_alloc(d_tbuf_, need_tbuf);
-      tbuf_elems_ = need_tbuf;
-    }
-    if (need_rec > rec_elems_) {
-      if (d_rec_) (void)hipFree(d_rec_);
-      d_rec_ = nullptr;
-      dev_alloc(d_rec_, need_rec);
-      rec_elems_ = need_rec;
-    }
-    if (need_mean > mean_elems_) {
-      if (d_mean_) (void)hipFree(d_mean_);
-      d_mean_ = nullptr;
-      dev_alloc(d_mean_, need_mean);
-      mean_elems_ = need_mean;
-    }
-  }
+  reserve_synced(d_legs_, need_legs, d_tbuf_, need_tbuf, d_rec_, need_rec, d_mean_, need_mean);
   h_sites_.assign(sites, sites + nsites);
   h_w_.assign(n, 1.0 / (double)n);
   if (weights) h_w_.assign(weights, weights + n);
@@ -739,82 +697,34 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   const bool per_replica = own && (out.norm || out.autocorr || out.energy || out.rdm || dens.density);
   h_mean_.assign(need_mean, 0.0);
   if (own) HIP_CHECK(hipMemcpyAsync(h_mean_.data(), d_mean_, need_mean * sizeof(double), hipMemcpyDeviceToHost, st_));
-  int cross_launches = 0;
-  if (cx) {  // the request's values and their means (weights 1 / npairs) come back with the rest
-    const size_t np = cross_.size();
-    cross_weights(nullptr);
-    batch_mean_launch(st_, d_cross_rec_, d_cross_w_, d_cross_mean_, (int)np, 2, nrec);
-    n_launch_ += 1;
-    cross_launches = (int)nrec + 1;
-    h_cross_rec_.resize((size_t)nrec * np * 2);
-    h_cross_mean_.resize((size_t)nrec * 2);
-    HIP_CHECK(hipMemcpyAsync(h_cross_rec_.data(), d_cross_rec_, h_cross_rec_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
-    HIP_CHECK(hipMemcpyAsync(h_cross_mean_.data(), d_cross_mean_, h_cross_mean_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
-    cross_nrec_ = nrec;
-  }
-  int spec_launches = 0;
-  if (sp) {  // the same for the spectra request (weights 1 / B)
-    const size_t len = (size_t)spec_rec_len();
-    spectra_weights(nullptr);
-    batch_mean_launch(st_, d_spec_rec_, d_spec_w_, d_spec_mean_, (int)n, (long)len, nrec);
-    n_launch_ += 1;
-    spec_launches = (int)nrec + 1;
-    h_spec_rec_.resize((size_t)nrec * n * len);
-    h_spec_mean_.resize((size_t)nrec * len);
-    HIP_CHECK(hipMemcpyAsync(h_spec_rec_.data(), d_spec_rec_, h_spec_rec_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
-    HIP_CHECK(hipMemcpyAsync(h_spec_mean_.data(), d_spec_mean_, h_spec_mean_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
+  // every request that is set: ONE k_batch_mean over its records (weights 1 / rows); they and their means come back with
+  // the rest and are the request's records from here on
+  auto end_run = [&](RecordStore& s) {
+    s.mean_of_run(st_, nrec, n_launch_);
+    s.fetch_run(st_);
+  };
+  if (cx) end_run(cross_rec_);
+  if (sp) {
+    end_run(spec_rec_);
     HIP_CHECK(hipMemcpyAsync(h_spec_fail_.data(), d_spec_fail_, n * sizeof(int), hipMemcpyDeviceToHost, st_));
-    spec_nrec_ = nrec;
   }
-  int smp_launches = 0;
-  if (sm) {  // and for the samples request: the frequencies' means under 1 / B
-    const size_t ns = (size_t)smp_nshots_, F = (size_t)smp_F();
-    samples_weights(nullptr);
-    batch_mean_launch(st_, d_smp_freq_, d_smp_w_, d_smp_mean_, (int)n, (long)F, nrec);
-    n_launch_ += 1;
-    smp_launches = (int)nrec + 1;
-    h_smp_cfg_.resize((size_t)nrec * n * ns * L_);
-    h_smp_prob_.resize((size_t)nrec * n * ns);
-    h_smp_freq_.resize((size_t)nrec * n * F);
-    h_smp_mean_.resize((size_t)nrec * F);
+  if (sm) {  // the frequencies are what is averaged; configurations and probabilities are copied beside them
+    smp_rec_.mean_of_run(st_, nrec, n_launch_);
+    h_smp_cfg_.resize(smp_cfg_lay(nrec).rec_now());
+    h_smp_prob_.resize(smp_prob_lay(nrec).rec_now());
     HIP_CHECK(hipMemcpyAsync(h_smp_cfg_.data(), d_smp_cfg_, h_smp_cfg_.size() * sizeof(int), hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipMemcpyAsync(h_smp_prob_.data(), d_smp_prob_, h_smp_prob_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
-    HIP_CHECK(hipMemcpyAsync(h_smp_freq_.data(), d_smp_freq_, h_smp_freq_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
-    HIP_CHECK(hipMemcpyAsync(h_smp_mean_.data(), d_smp_mean_, h_smp_mean_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
-    smp_nrec_ = nrec;
+    smp_rec_.fetch_run(st_);
   }
-  int exp_launches = 0;
-  if (ex) {  // and for the expect request (weights 1 / B)
-    const size_t len = 2 * exp_ops_.size();
-    expect_weights(nullptr);
-    batch_mean_launch(st_, d_exp_rec_, d_exp_w_, d_exp_mean_, (int)n, (long)len, nrec);
-    n_launch_ += 1;
-    exp_launches = (int)nrec + 1;
-    h_exp_rec_.resize((size_t)nrec * n * len);
-    h_exp_mean_.resize((size_t)nrec * len);
-    HIP_CHECK(hipMemcpyAsync(h_exp_rec_.data(), d_exp_rec_, h_exp_rec_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
-    HIP_CHECK(hipMemcpyAsync(h_exp_mean_.data(), d_exp_mean_, h_exp_mean_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
-    exp_nrec_ = nrec;
-  }
-  int xm_launches = 0;
-  if (xm) {  // and for the cross request of MPOs (weights 1 / nentries)
-    const size_t np = xm_.size();
-    cross_mpo_weights(nullptr);
-    batch_mean_launch(st_, d_xm_rec_, d_xm_w_, d_xm_mean_, (int)np, 2, nrec);
-    n_launch_ += 1;
-    xm_launches = (int)nrec + 1;
-    h_xm_rec_.resize((size_t)nrec * np * 2);
-    h_xm_mean_.resize((size_t)nrec * 2);
-    HIP_CHECK(hipMemcpyAsync(h_xm_rec_.data(), d_xm_rec_, h_xm_rec_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
-    HIP_CHECK(hipMemcpyAsync(h_xm_mean_.data(), d_xm_mean_, h_xm_mean_.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
-    xm_nrec_ = nrec;
-  }
+  if (ex) end_run(exp_rec_);
+  if (xm) end_run(xm_rec_);
   if (per_replica) {
     h_rec_.resize(need_rec);
     HIP_CHECK(hipMemcpyAsync(h_rec_.data(), d_rec_, need_rec * sizeof(double), hipMemcpyDeviceToHost, st_));
   }
   steps_done_ += nsteps;
-  const int other = (int)nrec * per_rec + (own ? 1 : 0) + cross_launches + spec_launches + smp_launches + exp_launches + xm_launches;
+  const int nreq = (int)cx + (int)sp + (int)sm + (int)ex + (int)xm;  // each: its kernel per record and ONE k_batch_mean
+  const int other = (int)nrec * per_rec + (own ? 1 : 0) + nreq * ((int)nrec + 1);
   if (nsteps > 0) finish(false, nsteps * 2, statuses, other, chan ? nsteps : 0);
   else finish_observe(other, statuses);
 
@@ -855,13 +765,7 @@ void Batch::snapshot() {
   validate();
   prepare_observing();
   const size_t need = eng_.size() * snap_len();
-  if (need > snap_elems_) {
-    HIP_CHECK(hipStreamSynchronize(st_));
-    if (d_snap_) (void)hipFree(d_snap_);
-    d_snap_ = nullptr;
-    dev_alloc(d_snap_, need);
-    snap_elems_ = need;
-  }
+  reserve_synced(d_snap_, need);
   batch_snapshot_launch(st_, d_shp_, d_ptrs_, (int)ptrs_per_replica(), d_snap_, snap_len(), L_, (int)eng_.size());
   n_launch_ += 1;
   finish_observe(1, nullptr);
@@ -909,7 +813,7 @@ void Batch::set_cross(int npairs, const int* bra, const int* ket, const int* sit
   cross_ = std::move(pairs);
   cross_ops_ = std::move(ops);
   cross_dirty_ = true;
-  cross_nrec_ = 0;  // records of another request are not this one's
+  cross_rec_.drop();  // records of another request are not this one's
 }
 
 void Batch::check_cross(const char* entry) const {
@@ -932,31 +836,9 @@ void Batch::check_cross(const char* entry) const {
 }
 
 void Batch::upload_cross(long nrec) {
-  const size_t np = cross_.size(), need_buf = np * cross_buf_len(), slots = (size_t)nrec + 1;
-  if (np > cross_pairs_elems_ || cross_ops_.size() > cross_ops_elems_ || need_buf > cross_buf_elems_ || slots * np * 2 > cross_rec_slots_ ||
-      4 * slots > cross_mean_slots_ || !d_cross_ops_) {
-    HIP_CHECK(hipStreamSynchronize(st_));
-    auto grow = [&](auto*& p, size_t& have, size_t need) {
-      if (p && need <= have) return;
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      dev_alloc(p, need);
-      have = need;
-    };
-    const bool more_pairs = np > cross_pairs_elems_;
-    grow(d_cross_pairs_, cross_pairs_elems_, np);
-    grow(d_cross_ops_, cross_ops_elems_, cross_ops_.size());
-    grow(d_cross_buf_, cross_buf_elems_, need_buf);
-    if (more_pairs) {
-      if (d_cross_w_) (void)hipFree(d_cross_w_);
-      d_cross_w_ = nullptr;
-      dev_alloc(d_cross_w_, np);
-    }
-    // these two grow only with a new request or in run(): no record of the last run is lost
-    grow(d_cross_rec_, cross_rec_slots_, slots * np * 2);
-    // the means of the records, the one of cross(), and the records' means under the weights of cross_records
-    grow(d_cross_mean_, cross_mean_slots_, 2 * slots * 2);
-  }
+  const size_t np = cross_.size();
+  reserve_synced(cross_rec_, BatchRecords{np, 2, (size_t)nrec}, d_cross_pairs_, np, d_cross_ops_, cross_ops_.size(), d_cross_buf_,
+                 np * cross_buf_len());
   if (cross_dirty_) {
     HIP_CHECK(hipMemcpyAsync(d_cross_pairs_, cross_.data(), np * sizeof(BatchCrossPair), hipMemcpyHostToDevice, st_));
     if (!cross_ops_.empty())
@@ -981,16 +863,9 @@ void Batch::launch_cross(long record) {
   a.o_t2 = (size_t)plan_.max_bond;
   a.o_u = 2 * (size_t)plan_.max_bond;
   a.buf_len = cross_buf_len();
-  a.rec = d_cross_rec_ + (size_t)record * cross_.size() * 2;
+  a.rec = cross_rec_.slot(record);
   batch_cross_launch(st_, a, (int)cross_.size());
   n_launch_ += 1;
-}
-
-void Batch::cross_weights(const double* weights) {
-  const size_t np = cross_.size();
-  h_cross_w_.assign(np, 1.0 / (double)np);
-  if (weights) h_cross_w_.assign(weights, weights + np);
-  HIP_CHECK(hipMemcpyAsync(d_cross_w_, h_cross_w_.data(), np * sizeof(double), hipMemcpyHostToDevice, st_));
 }
 
 void Batch::cross(const double* weights, double* values, double* mean) {
@@ -998,39 +873,25 @@ void Batch::cross(const double* weights, double* values, double* mean) {
   validate();
   check_cross("mitdvp_batch_cross");
   prepare_observing();
-  upload_cross(cross_nrec_);
-  const size_t np = cross_.size();
-  const long slot = cross_nrec_;  // behind the records of the last run, which stay
-  cross_weights(weights);
-  launch_cross(slot);
-  batch_mean_launch(st_, d_cross_rec_ + (size_t)slot * np * 2, d_cross_w_, d_cross_mean_ + (size_t)slot * 2, (int)np, 2, 1);
-  n_launch_ += 1;
-  h_cross_now_.resize(np * 2 + 2);
-  HIP_CHECK(hipMemcpyAsync(h_cross_now_.data(), d_cross_rec_ + (size_t)slot * np * 2, np * 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
-  HIP_CHECK(hipMemcpyAsync(h_cross_now_.data() + np * 2, d_cross_mean_ + (size_t)slot * 2, 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
+  upload_cross(cross_rec_.nrec);  // the slot behind the records of the last run, which stay
+  cross_rec_.weights(st_, weights);
+  launch_cross(cross_rec_.nrec);
+  cross_rec_.mean_of_slot(st_, n_launch_);
+  cross_rec_.fetch_slot(st_);
   finish_observe(2, nullptr);
-  if (values) std::memcpy(values, h_cross_now_.data(), np * 2 * sizeof(double));
-  if (mean) std::memcpy(mean, h_cross_now_.data() + np * 2, 2 * sizeof(double));
+  cross_rec_.slot_out(values, mean);
+}
+
+// the tail of every X_records: nothing without records or without a destination; one host wait when a mean was launched
+void Batch::records_of(RecordStore& s, const double* weights, double* values, double* mean) {
+  if (s.nrec == 0 || (!values && !mean)) return;
+  if (mean && weights) HIP_CHECK(hipSetDevice(device_));
+  if (s.records(st_, weights, values, mean, n_launch_)) finish_observe(1, nullptr);
 }
 
 void Batch::cross_records(const double* weights, double* values, double* mean, size_t* counts) {
-  const size_t np = cross_.size(), nrec = (size_t)cross_nrec_;
-  if (counts) { counts[0] = nrec; counts[1] = np; }
-  if (nrec == 0 || (!values && !mean)) return;
-  if (values) std::memcpy(values, h_cross_rec_.data(), nrec * np * 2 * sizeof(double));
-  if (!mean) return;
-  if (!weights) {
-    std::memcpy(mean, h_cross_mean_.data(), nrec * 2 * sizeof(double));
-    return;
-  }
-  HIP_CHECK(hipSetDevice(device_));
-  cross_weights(weights);
-  // behind the slots of the records' own means and of cross(): the means of the run stay as they are
-  double* dst = d_cross_mean_ + (nrec + 1) * 2;
-  batch_mean_launch(st_, d_cross_rec_, d_cross_w_, dst, (int)np, 2, (long)nrec);
-  n_launch_ += 1;
-  HIP_CHECK(hipMemcpyAsync(mean, dst, nrec * 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
-  finish_observe(1, nullptr);
+  if (counts) { counts[0] = (size_t)cross_rec_.nrec; counts[1] = cross_.size(); }
+  records_of(cross_rec_, weights, values, mean);
 }
 
 // ---- bond spectra and entanglement entropies (k_batch_spectra) ----
@@ -1059,7 +920,7 @@ void Batch::set_spectra(const int* bonds, int nbonds) {
                    std::to_string(BATCH_OBS_MAX_RDM));
   spec_bonds_.assign(bonds, bonds + nbonds);
   spec_dirty_ = true;
-  spec_nrec_ = 0;  // records of another request are not this one's
+  spec_rec_.drop();  // records of another request are not this one's
 }
 
 void Batch::check_spectra(const char* entry) const {
@@ -1072,23 +933,8 @@ void Batch::check_spectra(const char* entry) const {
 }
 
 void Batch::upload_spectra(long nrec) {
-  const size_t n = eng_.size(), len = (size_t)spec_rec_len(), slots = (size_t)nrec + 1;
-  const size_t need_buf = n * spec_buf_len(), need_rec = slots * n * len, need_mean = 2 * slots * len;
-  if (need_buf > spec_buf_elems_ || need_rec > spec_rec_slots_ || need_mean > spec_mean_slots_) {
-    HIP_CHECK(hipStreamSynchronize(st_));
-    auto grow = [&](auto*& p, size_t& have, size_t need) {
-      if (p && need <= have) return;
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      dev_alloc(p, need);
-      have = need;
-    };
-    grow(d_spec_buf_, spec_buf_elems_, need_buf);
-    // these two grow only with a new request or in run(): no record of the last run is lost
-    grow(d_spec_rec_, spec_rec_slots_, need_rec);
-    // the means of the records, the one of spectra(), and the records' means under the weights of spectra_records
-    grow(d_spec_mean_, spec_mean_slots_, need_mean);
-  }
+  const size_t n = eng_.size();
+  reserve_synced(spec_rec_, BatchRecords{n, (size_t)spec_rec_len(), (size_t)nrec}, d_spec_buf_, n * spec_buf_len());
   if (spec_dirty_) {
     HIP_CHECK(hipMemcpyAsync(d_spec_bonds_, spec_bonds_.data(), spec_bonds_.size() * sizeof(int), hipMemcpyHostToDevice, st_));
     spec_dirty_ = false;
@@ -1112,16 +958,9 @@ void Batch::launch_spectra(long record) {
   a.buf_len = spec_buf_len();
   a.fail = d_spec_fail_;
   a.rec_len = spec_rec_len();
-  a.rec = d_spec_rec_ + (size_t)record * eng_.size() * (size_t)a.rec_len;
+  a.rec = spec_rec_.slot(record);
   batch_spectra_launch(st_, a, (int)eng_.size());
   n_launch_ += 1;
-}
-
-void Batch::spectra_weights(const double* weights) {
-  const size_t n = eng_.size();
-  h_spec_w_.assign(n, 1.0 / (double)n);
-  if (weights) h_spec_w_.assign(weights, weights + n);
-  HIP_CHECK(hipMemcpyAsync(d_spec_w_, h_spec_w_.data(), n * sizeof(double), hipMemcpyHostToDevice, st_));
 }
 
 void Batch::spectra_failed(const char* entry) const {
@@ -1147,40 +986,20 @@ void Batch::spectra(const double* weights, double* values, double* mean, size_t*
       throw ArgError(at + "replica " + std::to_string(i) + " has its centre at site " + std::to_string(eng_[i]->center_) +
                      "; the walk starts from the centre at site 0 (the state a batch step leaves)");
   prepare(true, false);
-  upload_spectra(spec_nrec_);
-  const size_t slot = (size_t)spec_nrec_;  // behind the records of the last run, which stay
-  spectra_weights(weights);
-  launch_spectra((long)slot);
-  batch_mean_launch(st_, d_spec_rec_ + slot * n * len, d_spec_w_, d_spec_mean_ + slot * len, (int)n, (long)len, 1);
-  n_launch_ += 1;
-  h_spec_now_.resize(n * len + len);
-  HIP_CHECK(hipMemcpyAsync(h_spec_now_.data(), d_spec_rec_ + slot * n * len, n * len * sizeof(double), hipMemcpyDeviceToHost, st_));
-  HIP_CHECK(hipMemcpyAsync(h_spec_now_.data() + n * len, d_spec_mean_ + slot * len, len * sizeof(double), hipMemcpyDeviceToHost, st_));
+  upload_spectra(spec_rec_.nrec);  // the slot behind the records of the last run, which stay
+  spec_rec_.weights(st_, weights);
+  launch_spectra(spec_rec_.nrec);
+  spec_rec_.mean_of_slot(st_, n_launch_);
+  spec_rec_.fetch_slot(st_);
   HIP_CHECK(hipMemcpyAsync(h_spec_fail_.data(), d_spec_fail_, n * sizeof(int), hipMemcpyDeviceToHost, st_));
   finish_observe(2, nullptr);
-  if (values) std::memcpy(values, h_spec_now_.data(), n * len * sizeof(double));
-  if (mean) std::memcpy(mean, h_spec_now_.data() + n * len, len * sizeof(double));
+  spec_rec_.slot_out(values, mean);
   spectra_failed("mitdvp_batch_spectra");
 }
 
 void Batch::spectra_records(const double* weights, double* values, double* mean, size_t* counts) {
-  const size_t n = eng_.size(), nrec = (size_t)spec_nrec_, len = spec_bonds_.empty() ? 0 : (size_t)spec_rec_len();
-  if (counts) { counts[0] = nrec; counts[1] = n; counts[2] = len; }
-  if (nrec == 0 || (!values && !mean)) return;
-  if (values) std::memcpy(values, h_spec_rec_.data(), nrec * n * len * sizeof(double));
-  if (!mean) return;
-  if (!weights) {
-    std::memcpy(mean, h_spec_mean_.data(), nrec * len * sizeof(double));
-    return;
-  }
-  HIP_CHECK(hipSetDevice(device_));
-  spectra_weights(weights);
-  // behind the slots of the records' own means and of spectra(): the means of the run stay as they are
-  double* dst = d_spec_mean_ + (nrec + 1) * len;
-  batch_mean_launch(st_, d_spec_rec_, d_spec_w_, dst, (int)n, (long)len, (long)nrec);
-  n_launch_ += 1;
-  HIP_CHECK(hipMemcpyAsync(mean, dst, nrec * len * sizeof(double), hipMemcpyDeviceToHost, st_));
-  finish_observe(1, nullptr);
+  if (counts) { counts[0] = (size_t)spec_rec_.nrec; counts[1] = eng_.size(); counts[2] = spec_bonds_.empty() ? 0 : (size_t)spec_rec_len(); }
+  records_of(spec_rec_, weights, values, mean);
 }
 
 // ---- sampled configurations (k_batch_sample) ----
@@ -1219,7 +1038,7 @@ void Batch::set_samples(int nshots, unsigned long long seed) {
                    " outcomes per replica, a request takes at most " + std::to_string(BATCH_SAMPLE_MAX_CONFIG));
   smp_nshots_ = nshots;
   smp_seed_ = seed;
-  smp_nrec_ = 0;  // records of another request are not this one's
+  smp_rec_.drop();  // records of another request are not this one's
 }
 
 void Batch::check_samples(const char* entry) const {
@@ -1231,31 +1050,13 @@ void Batch::check_samples(const char* entry) const {
 }
 
 void Batch::upload_samples(long nrec) {
-  const size_t n = eng_.size(), ns = (size_t)smp_nshots_, F = (size_t)smp_F(), slots = (size_t)nrec + 1;
-  const size_t need_buf = n * smp_buf_len(), need_cfg = slots * n * ns * L_, need_prob = slots * n * ns, need_freq = slots * n * F,
-               need_mean = 2 * slots * F;
-  if (need_buf > smp_buf_elems_ || need_cfg > smp_cfg_slots_ || need_prob > smp_prob_slots_ || need_freq > smp_freq_slots_ ||
-      need_mean > smp_mean_slots_) {
-    HIP_CHECK(hipStreamSynchronize(st_));
-    auto grow = [&](auto*& p, size_t& have, size_t need) {
-      if (p && need <= have) return;
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      dev_alloc(p, need);
-      have = need;
-    };
-    grow(d_smp_buf_, smp_buf_elems_, need_buf);
-    // these grow only with a new request, other shapes or in run(): no record of the last run is lost
-    grow(d_smp_cfg_, smp_cfg_slots_, need_cfg);
-    grow(d_smp_prob_, smp_prob_slots_, need_prob);
-    grow(d_smp_freq_, smp_freq_slots_, need_freq);
-    // the means of the records, the one of samples(), and the records' means under the weights of samples_records
-    grow(d_smp_mean_, smp_mean_slots_, need_mean);
-  }
+  // configurations and probabilities grow with the frequencies: only with a new request, other shapes or in run()
+  const size_t n = eng_.size();
+  reserve_synced(smp_rec_, BatchRecords{n, (size_t)smp_F(), (size_t)nrec}, d_smp_cfg_, smp_cfg_lay(nrec).rec_elems(), d_smp_prob_,
+                 smp_prob_lay(nrec).rec_elems(), d_smp_buf_, n * smp_buf_len());
 }
 
 void Batch::launch_samples(long record, long long step) {
-  const size_t n = eng_.size(), ns = (size_t)smp_nshots_;
   BatchSampleArgs a{};
   a.L = L_;
   a.nshots = smp_nshots_;
@@ -1271,18 +1072,11 @@ void Batch::launch_samples(long record, long long step) {
   a.o_g = smp_o_g();
   a.buf_len = smp_buf_len();
   a.F = smp_F();
-  a.configs = d_smp_cfg_ + (size_t)record * n * ns * L_;
-  a.prob = d_smp_prob_ + (size_t)record * n * ns;
-  a.freq = d_smp_freq_ + (size_t)record * n * (size_t)a.F;
-  batch_sample_launch(st_, a, (int)n);
+  a.configs = d_smp_cfg_ + smp_cfg_lay(smp_rec_.nrec).rec_slot((size_t)record);
+  a.prob = d_smp_prob_ + smp_prob_lay(smp_rec_.nrec).rec_slot((size_t)record);
+  a.freq = smp_rec_.slot(record);
+  batch_sample_launch(st_, a, (int)eng_.size());
   n_launch_ += 1;
-}
-
-void Batch::samples_weights(const double* weights) {
-  const size_t n = eng_.size();
-  h_smp_w_.assign(n, 1.0 / (double)n);
-  if (weights) h_smp_w_.assign(weights, weights + n);
-  HIP_CHECK(hipMemcpyAsync(d_smp_w_, h_smp_w_.data(), n * sizeof(double), hipMemcpyHostToDevice, st_));
 }
 
 void Batch::samples(const double* weights, int* configs, double* prob, double* freq, double* mean_freq, size_t* counts) {
@@ -1298,46 +1092,33 @@ void Batch::samples(const double* weights, int* configs, double* prob, double* f
       throw ArgError(at + "replica " + std::to_string(i) + " has its centre at site " + std::to_string(eng_[i]->center_) +
                      "; the walk starts from the centre at site 0 (the state a batch step leaves)");
   prepare(true, false);
-  upload_samples(smp_nrec_);
-  const size_t slot = (size_t)smp_nrec_;  // behind the records of the last run, which stay
-  samples_weights(weights);
-  launch_samples((long)slot, steps_done_);
-  batch_mean_launch(st_, d_smp_freq_ + slot * n * F, d_smp_w_, d_smp_mean_ + slot * F, (int)n, (long)F, 1);
-  n_launch_ += 1;
-  h_smp_cfg_now_.resize(n * ns * L_);
-  h_smp_now_.resize(n * ns + n * F + F);
-  double* hp = h_smp_now_.data();
-  if (configs) HIP_CHECK(hipMemcpyAsync(h_smp_cfg_now_.data(), d_smp_cfg_ + slot * n * ns * L_, n * ns * L_ * sizeof(int), hipMemcpyDeviceToHost, st_));
-  if (prob) HIP_CHECK(hipMemcpyAsync(hp, d_smp_prob_ + slot * n * ns, n * ns * sizeof(double), hipMemcpyDeviceToHost, st_));
-  if (freq) HIP_CHECK(hipMemcpyAsync(hp + n * ns, d_smp_freq_ + slot * n * F, n * F * sizeof(double), hipMemcpyDeviceToHost, st_));
-  if (mean_freq) HIP_CHECK(hipMemcpyAsync(hp + n * ns + n * F, d_smp_mean_ + slot * F, F * sizeof(double), hipMemcpyDeviceToHost, st_));
+  const long slot = smp_rec_.nrec;  // behind the records of the last run, which stay
+  const BatchRecords cl = smp_cfg_lay(slot), pl = smp_prob_lay(slot);
+  upload_samples(slot);
+  smp_rec_.weights(st_, weights);
+  launch_samples(slot, steps_done_);
+  smp_rec_.mean_of_slot(st_, n_launch_);
+  h_smp_cfg_now_.resize(cl.slot_elems());
+  h_smp_prob_now_.resize(pl.slot_elems());
+  if (configs) HIP_CHECK(hipMemcpyAsync(h_smp_cfg_now_.data(), d_smp_cfg_ + cl.rec_now(), cl.slot_elems() * sizeof(int), hipMemcpyDeviceToHost, st_));
+  if (prob) HIP_CHECK(hipMemcpyAsync(h_smp_prob_now_.data(), d_smp_prob_ + pl.rec_now(), pl.slot_elems() * sizeof(double), hipMemcpyDeviceToHost, st_));
+  smp_rec_.fetch_slot(st_, freq != nullptr, mean_freq != nullptr);
   finish_observe(2, nullptr);
-  if (configs) std::memcpy(configs, h_smp_cfg_now_.data(), n * ns * L_ * sizeof(int));
-  if (prob) std::memcpy(prob, hp, n * ns * sizeof(double));
-  if (freq) std::memcpy(freq, hp + n * ns, n * F * sizeof(double));
-  if (mean_freq) std::memcpy(mean_freq, hp + n * ns + n * F, F * sizeof(double));
+  if (configs) std::memcpy(configs, h_smp_cfg_now_.data(), cl.slot_elems() * sizeof(int));
+  if (prob) std::memcpy(prob, h_smp_prob_now_.data(), pl.slot_elems() * sizeof(double));
+  smp_rec_.slot_out(freq, mean_freq);
 }
 
 void Batch::samples_records(const double* weights, int* configs, double* prob, double* freq, double* mean_freq, size_t* counts) {
-  const size_t n = eng_.size(), nrec = (size_t)smp_nrec_, ns = (size_t)smp_nshots_, F = smp_nshots_ > 0 ? (size_t)smp_F() : 0;
-  if (counts) { counts[0] = nrec; counts[1] = n; counts[2] = ns; counts[3] = (size_t)L_; counts[4] = F; }
-  if (nrec == 0 || (!configs && !prob && !freq && !mean_freq)) return;
-  if (configs) std::memcpy(configs, h_smp_cfg_.data(), nrec * n * ns * L_ * sizeof(int));
-  if (prob) std::memcpy(prob, h_smp_prob_.data(), nrec * n * ns * sizeof(double));
-  if (freq) std::memcpy(freq, h_smp_freq_.data(), nrec * n * F * sizeof(double));
-  if (!mean_freq) return;
-  if (!weights) {
-    std::memcpy(mean_freq, h_smp_mean_.data(), nrec * F * sizeof(double));
-    return;
+  const long nrec = smp_rec_.nrec;
+  if (counts) {
+    counts[0] = (size_t)nrec; counts[1] = eng_.size(); counts[2] = (size_t)smp_nshots_; counts[3] = (size_t)L_;
+    counts[4] = smp_nshots_ > 0 ? (size_t)smp_F() : 0;
   }
-  HIP_CHECK(hipSetDevice(device_));
-  samples_weights(weights);
-  // behind the slots of the records' own means and of samples(): the means of the run stay as they are
-  double* dst = d_smp_mean_ + (nrec + 1) * F;
-  batch_mean_launch(st_, d_smp_freq_, d_smp_w_, dst, (int)n, (long)F, (long)nrec);
-  n_launch_ += 1;
-  HIP_CHECK(hipMemcpyAsync(mean_freq, dst, nrec * F * sizeof(double), hipMemcpyDeviceToHost, st_));
-  finish_observe(1, nullptr);
+  if (nrec == 0) return;
+  if (configs) std::memcpy(configs, h_smp_cfg_.data(), smp_cfg_lay(nrec).rec_now() * sizeof(int));
+  if (prob) std::memcpy(prob, h_smp_prob_.data(), smp_prob_lay(nrec).rec_now() * sizeof(double));
+  records_of(smp_rec_, weights, freq, mean_freq);
 }
 
 // ---- expectation values of MPO observables (k_batch_expect) ----
@@ -1398,7 +1179,7 @@ void Batch::set_expect(const int* op_ids, int nops) {
   exp_plan_ = plan;
   exp_shp_dirty_ = true;
   h_exp_ptrs_.clear();
-  exp_nrec_ = 0;  // records of another request are not this one's
+  exp_rec_.drop();  // records of another request are not this one's
 }
 
 void Batch::check_expect(const char* entry) {
@@ -1409,36 +1190,18 @@ void Batch::check_expect(const char* entry) {
   if (shp.size() != exp_shp_.size() || std::memcmp(shp.data(), exp_shp_.data(), shp.size() * sizeof(BatchShape)) != 0) {
     exp_shp_ = std::move(shp);
     exp_shp_dirty_ = true;
-    exp_nrec_ = 0;  // the engines were given cores of other shapes: records walked over the old ones are dropped
+    exp_rec_.drop();  // the engines were given cores of other shapes: records walked over the old ones are dropped
   }
   exp_plan_ = plan;
 }
 
 void Batch::upload_expect(long nrec) {
-  const size_t n = eng_.size(), nops = exp_ops_.size(), len = 2 * nops, slots = (size_t)nrec + 1;
+  const size_t n = eng_.size(), nops = exp_ops_.size();
   const size_t need_ptrs = n * nops * 3 * L_, need_shp = nops * L_, need_shift = n * nops;
-  const size_t need_buf = n * nops * exp_plan_.total, need_rec = slots * n * len, need_mean = 2 * slots * len;
-  if (need_ptrs > exp_ptrs_elems_ || need_shp > exp_shp_elems_ || need_shift > exp_shift_elems_ || need_buf > exp_buf_elems_ ||
-      need_rec > exp_rec_slots_ || need_mean > exp_mean_slots_) {
-    HIP_CHECK(hipStreamSynchronize(st_));
-    auto grow = [&](auto*& p, size_t& have, size_t need) {
-      if (p && need <= have) return;
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      dev_alloc(p, need);
-      have = need;
-    };
-    if (need_ptrs > exp_ptrs_elems_) h_exp_ptrs_.clear();
-    if (need_shp > exp_shp_elems_) exp_shp_dirty_ = true;
-    grow(d_exp_ptrs_, exp_ptrs_elems_, need_ptrs);
-    grow(d_exp_shp_, exp_shp_elems_, need_shp);
-    grow(d_exp_shift_, exp_shift_elems_, need_shift);
-    grow(d_exp_buf_, exp_buf_elems_, need_buf);
-    // these two grow only with a new request or in run(): no record of the last run is lost
-    grow(d_exp_rec_, exp_rec_slots_, need_rec);
-    // the means of the records, the one of expect(), and the records' means under the weights of expect_records
-    grow(d_exp_mean_, exp_mean_slots_, need_mean);
-  }
+  if (!d_exp_ptrs_.fits(need_ptrs)) h_exp_ptrs_.clear();  // a table that moves is uploaded again
+  if (!d_exp_shp_.fits(need_shp)) exp_shp_dirty_ = true;
+  reserve_synced(exp_rec_, BatchRecords{n, 2 * nops, (size_t)nrec}, d_exp_ptrs_, need_ptrs, d_exp_shp_, need_shp, d_exp_shift_, need_shift,
+                 d_exp_buf_, n * nops * exp_plan_.total);
   // tables: [w2l L][w2el L][w2er L] per (replica, operator); the engines may have been given new cores since the last call
   std::vector<void*> h(need_ptrs);
   h_exp_shift_.resize(need_shift);
@@ -1476,16 +1239,9 @@ void Batch::launch_expect(long record) {
   a.status = d_status_;
   a.buf = d_exp_buf_;
   a.plan = exp_plan_;
-  a.rec = d_exp_rec_ + (size_t)record * eng_.size() * 2 * exp_ops_.size();
+  a.rec = exp_rec_.slot(record);
   batch_expect_launch(st_, a, (int)eng_.size());
   n_launch_ += 1;
-}
-
-void Batch::expect_weights(const double* weights) {
-  const size_t n = eng_.size();
-  h_exp_w_.assign(n, 1.0 / (double)n);
-  if (weights) h_exp_w_.assign(weights, weights + n);
-  HIP_CHECK(hipMemcpyAsync(d_exp_w_, h_exp_w_.data(), n * sizeof(double), hipMemcpyHostToDevice, st_));
 }
 
 void Batch::expect(const double* weights, double* values, double* mean, size_t* counts) {
@@ -1493,7 +1249,7 @@ void Batch::expect(const double* weights, double* values, double* mean, size_t* 
   HIP_CHECK(hipSetDevice(device_));
   validate();
   check_expect("mitdvp_batch_expect");
-  const size_t n = eng_.size(), len = 2 * exp_ops_.size();
+  const size_t n = eng_.size();
   if (counts) { counts[0] = n; counts[1] = exp_ops_.size(); }
   if (!values && !mean) return;
   for (size_t i = 0; i < n; ++i)
@@ -1501,38 +1257,18 @@ void Batch::expect(const double* weights, double* values, double* mean, size_t* 
       throw ArgError(at + "replica " + std::to_string(i) + " has its centre at site " + std::to_string(eng_[i]->center_) +
                      "; the walk ends at the centre at site 0 (the state a batch step leaves)");
   prepare(true, false);
-  upload_expect(exp_nrec_);
-  const size_t slot = (size_t)exp_nrec_;  // behind the records of the last run, which stay
-  expect_weights(weights);
-  launch_expect((long)slot);
-  batch_mean_launch(st_, d_exp_rec_ + slot * n * len, d_exp_w_, d_exp_mean_ + slot * len, (int)n, (long)len, 1);
-  n_launch_ += 1;
-  h_exp_now_.resize(n * len + len);
-  HIP_CHECK(hipMemcpyAsync(h_exp_now_.data(), d_exp_rec_ + slot * n * len, n * len * sizeof(double), hipMemcpyDeviceToHost, st_));
-  HIP_CHECK(hipMemcpyAsync(h_exp_now_.data() + n * len, d_exp_mean_ + slot * len, len * sizeof(double), hipMemcpyDeviceToHost, st_));
+  upload_expect(exp_rec_.nrec);  // the slot behind the records of the last run, which stay
+  exp_rec_.weights(st_, weights);
+  launch_expect(exp_rec_.nrec);
+  exp_rec_.mean_of_slot(st_, n_launch_);
+  exp_rec_.fetch_slot(st_);
   finish_observe(2, nullptr);
-  if (values) std::memcpy(values, h_exp_now_.data(), n * len * sizeof(double));
-  if (mean) std::memcpy(mean, h_exp_now_.data() + n * len, len * sizeof(double));
+  exp_rec_.slot_out(values, mean);
 }
 
 void Batch::expect_records(const double* weights, double* values, double* mean, size_t* counts) {
-  const size_t n = eng_.size(), nrec = (size_t)exp_nrec_, len = 2 * exp_ops_.size();
-  if (counts) { counts[0] = nrec; counts[1] = n; counts[2] = exp_ops_.size(); }
-  if (nrec == 0 || (!values && !mean)) return;
-  if (values) std::memcpy(values, h_exp_rec_.data(), nrec * n * len * sizeof(double));
-  if (!mean) return;
-  if (!weights) {
-    std::memcpy(mean, h_exp_mean_.data(), nrec * len * sizeof(double));
-    return;
-  }
-  HIP_CHECK(hipSetDevice(device_));
-  expect_weights(weights);
-  // behind the slots of the records' own means and of expect(): the means of the run stay as they are
-  double* dst = d_exp_mean_ + (nrec + 1) * len;
-  batch_mean_launch(st_, d_exp_rec_, d_exp_w_, dst, (int)n, (long)len, (long)nrec);
-  n_launch_ += 1;
-  HIP_CHECK(hipMemcpyAsync(mean, dst, nrec * len * sizeof(double), hipMemcpyDeviceToHost, st_));
-  finish_observe(1, nullptr);
+  if (counts) { counts[0] = (size_t)exp_rec_.nrec; counts[1] = eng_.size(); counts[2] = exp_ops_.size(); }
+  records_of(exp_rec_, weights, values, mean);
 }
 
 // ---- MPO matrix elements between replicas (k_batch_cross_mpo) ----
@@ -1572,7 +1308,7 @@ void Batch::set_cross_mpo(int nentries, const int* bra, const int* ket, const in
   xm_plan_ = plan;
   xm_dirty_ = true;
   h_xm_ptrs_.clear();
-  xm_nrec_ = 0;  // records of another request are not this one's
+  xm_rec_.drop();  // records of another request are not this one's
 }
 
 void Batch::check_cross_mpo(const char* entry) {
@@ -1588,37 +1324,18 @@ void Batch::check_cross_mpo(const char* entry) {
   if (shp.size() != xm_shp_.size() || std::memcmp(shp.data(), xm_shp_.data(), shp.size() * sizeof(BatchShape)) != 0) {
     xm_shp_ = std::move(shp);
     xm_dirty_ = true;
-    xm_nrec_ = 0;  // the engines were given cores of other shapes: records walked over the old ones are dropped
+    xm_rec_.drop();  // the engines were given cores of other shapes: records walked over the old ones are dropped
   }
   xm_plan_ = plan;
 }
 
 void Batch::upload_cross_mpo(long nrec) {
-  const size_t n = eng_.size(), np = xm_.size(), nops = xm_ops_.size(), slots = (size_t)nrec + 1;
-  const size_t need_ptrs = n * nops * L_, need_shp = nops * L_, need_shift = n * nops, need_buf = np * xm_plan_.total;
-  if (np > xm_ent_elems_ || need_ptrs > xm_ptrs_elems_ || need_shp > xm_shp_elems_ || need_shift > xm_shift_elems_ ||
-      need_buf > xm_buf_elems_ || slots * np * 2 > xm_rec_slots_ || 4 * slots > xm_mean_slots_ || np > xm_w_elems_) {
-    HIP_CHECK(hipStreamSynchronize(st_));
-    auto grow = [&](auto*& p, size_t& have, size_t need) {
-      if (p && need <= have) return;
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      dev_alloc(p, need);
-      have = need;
-    };
-    if (np > xm_ent_elems_ || need_shp > xm_shp_elems_) xm_dirty_ = true;
-    if (need_ptrs > xm_ptrs_elems_) h_xm_ptrs_.clear();
-    grow(d_xm_ent_, xm_ent_elems_, np);
-    grow(d_xm_ptrs_, xm_ptrs_elems_, need_ptrs);
-    grow(d_xm_shp_, xm_shp_elems_, need_shp);
-    grow(d_xm_shift_, xm_shift_elems_, need_shift);
-    grow(d_xm_buf_, xm_buf_elems_, need_buf);
-    grow(d_xm_w_, xm_w_elems_, np);
-    // these two grow only with a new request or in run(): no record of the last run is lost
-    grow(d_xm_rec_, xm_rec_slots_, slots * np * 2);
-    // the means of the records, the one of cross_mpo(), and the records' means under the weights of cross_mpo_records
-    grow(d_xm_mean_, xm_mean_slots_, 2 * slots * 2);
-  }
+  const size_t n = eng_.size(), np = xm_.size(), nops = xm_ops_.size();
+  const size_t need_ptrs = n * nops * L_, need_shp = nops * L_, need_shift = n * nops;
+  if (!d_xm_ent_.fits(np) || !d_xm_shp_.fits(need_shp)) xm_dirty_ = true;  // a table that moves is uploaded again
+  if (!d_xm_ptrs_.fits(need_ptrs)) h_xm_ptrs_.clear();
+  reserve_synced(xm_rec_, BatchRecords{np, 2, (size_t)nrec}, d_xm_ent_, np, d_xm_ptrs_, need_ptrs, d_xm_shp_, need_shp, d_xm_shift_, need_shift,
+                 d_xm_buf_, np * xm_plan_.total);
   // tables: w2el of every site per (replica, operator); the engines may have been given new cores since the last call
   std::vector<void*> h(need_ptrs);
   h_xm_shift_.resize(need_shift);
@@ -1657,16 +1374,9 @@ void Batch::launch_cross_mpo(long record) {
   a.shift = d_xm_shift_;
   a.buf = d_xm_buf_;
   a.plan = xm_plan_;
-  a.rec = d_xm_rec_ + (size_t)record * xm_.size() * 2;
+  a.rec = xm_rec_.slot(record);
   batch_cross_mpo_launch(st_, a, (int)xm_.size());
   n_launch_ += 1;
-}
-
-void Batch::cross_mpo_weights(const double* weights) {
-  const size_t np = xm_.size();
-  h_xm_w_.assign(np, 1.0 / (double)np);
-  if (weights) h_xm_w_.assign(weights, weights + np);
-  HIP_CHECK(hipMemcpyAsync(d_xm_w_, h_xm_w_.data(), np * sizeof(double), hipMemcpyHostToDevice, st_));
 }
 
 void Batch::cross_mpo(const double* weights, double* values, double* mean) {
@@ -1674,39 +1384,18 @@ void Batch::cross_mpo(const double* weights, double* values, double* mean) {
   validate();
   check_cross_mpo("mitdvp_batch_cross_mpo");
   prepare_observing();
-  upload_cross_mpo(xm_nrec_);
-  const size_t np = xm_.size();
-  const long slot = xm_nrec_;  // behind the records of the last run, which stay
-  cross_mpo_weights(weights);
-  launch_cross_mpo(slot);
-  batch_mean_launch(st_, d_xm_rec_ + (size_t)slot * np * 2, d_xm_w_, d_xm_mean_ + (size_t)slot * 2, (int)np, 2, 1);
-  n_launch_ += 1;
-  h_xm_now_.resize(np * 2 + 2);
-  HIP_CHECK(hipMemcpyAsync(h_xm_now_.data(), d_xm_rec_ + (size_t)slot * np * 2, np * 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
-  HIP_CHECK(hipMemcpyAsync(h_xm_now_.data() + np * 2, d_xm_mean_ + (size_t)slot * 2, 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
+  upload_cross_mpo(xm_rec_.nrec);  // the slot behind the records of the last run, which stay
+  xm_rec_.weights(st_, weights);
+  launch_cross_mpo(xm_rec_.nrec);
+  xm_rec_.mean_of_slot(st_, n_launch_);
+  xm_rec_.fetch_slot(st_);
   finish_observe(2, nullptr);
-  if (values) std::memcpy(values, h_xm_now_.data(), np * 2 * sizeof(double));
-  if (mean) std::memcpy(mean, h_xm_now_.data() + np * 2, 2 * sizeof(double));
+  xm_rec_.slot_out(values, mean);
 }
 
 void Batch::cross_mpo_records(const double* weights, double* values, double* mean, size_t* counts) {
-  const size_t np = xm_.size(), nrec = (size_t)xm_nrec_;
-  if (counts) { counts[0] = nrec; counts[1] = np; }
-  if (nrec == 0 || (!values && !mean)) return;
-  if (values) std::memcpy(values, h_xm_rec_.data(), nrec * np * 2 * sizeof(double));
-  if (!mean) return;
-  if (!weights) {
-    std::memcpy(mean, h_xm_mean_.data(), nrec * 2 * sizeof(double));
-    return;
-  }
-  HIP_CHECK(hipSetDevice(device_));
-  cross_mpo_weights(weights);
-  // behind the slots of the records' own means and of cross_mpo(): the means of the run stay as they are
-  double* dst = d_xm_mean_ + (nrec + 1) * 2;
-  batch_mean_launch(st_, d_xm_rec_, d_xm_w_, dst, (int)np, 2, (long)nrec);
-  n_launch_ += 1;
-  HIP_CHECK(hipMemcpyAsync(mean, dst, nrec * 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
-  finish_observe(1, nullptr);
+  if (counts) { counts[0] = (size_t)xm_rec_.nrec; counts[1] = xm_.size(); }
+  records_of(xm_rec_, weights, values, mean);
 }
 
 // ---- an MPO applied to the replicas (k_batch_operate) ----
@@ -1750,25 +1439,8 @@ void Batch::operate(int op_id, int maxstep, double conv_tol, const int* replicas
 
   prepare(true, false);  // canonical chains around site 0; the pointer table, zeroed status words, the engines' streams
   const size_t need_ptrs = ns * 3 * L_, need_offs = (size_t)3 * (L_ + 1), need_buf = ns * plan.total;
-  if (ns > op_rep_elems_ || need_ptrs > op_ptrs_elems_ || ns > op_shift_elems_ || need_buf > op_buf_elems_ ||
-      (size_t)L_ > op_shp_elems_ || need_offs > op_offs_elems_ || ns > op_norms_elems_ || ns > op_iters_elems_) {
-    HIP_CHECK(hipStreamSynchronize(st_));
-    auto grow = [&](auto*& p, size_t& have, size_t need) {
-      if (p && need <= have) return;
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      dev_alloc(p, need);
-      have = need;
-    };
-    grow(d_op_rep_, op_rep_elems_, ns);
-    grow(d_op_ptrs_, op_ptrs_elems_, need_ptrs);
-    grow(d_op_shift_, op_shift_elems_, ns);
-    grow(d_op_buf_, op_buf_elems_, need_buf);
-    grow(d_op_shp_, op_shp_elems_, (size_t)L_);
-    grow(d_op_offs_, op_offs_elems_, need_offs);
-    grow(d_op_norms_, op_norms_elems_, ns);
-    grow(d_op_iters_, op_iters_elems_, ns);
-  }
+  reserve_synced(d_op_rep_, ns, d_op_ptrs_, need_ptrs, d_op_shift_, ns, d_op_buf_, need_buf, d_op_shp_, (size_t)L_, d_op_offs_, need_offs,
+                 d_op_norms_, ns, d_op_iters_, ns);
   std::vector<void*> h_ptrs(need_ptrs);
   std::vector<zc> h_shift(ns);
   std::vector<long long> h_offs(need_offs);

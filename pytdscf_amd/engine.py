@@ -1274,28 +1274,35 @@ class TDVPBatch:
         self._push_cross(packed)
         self._cross = packed if bra else None
 
-    def _cross_weights(self, weights):
-        if self._cross is None:
-            raise ValueError("no cross request is set (set_cross)")
+    def _request_weights(self, name, unit, weights):
+        """The weights of request ``name`` ("cross", "spectra", "samples", "expect", "cross_mpo") as a float64 array, or
+        None for the default.  ``unit`` says what one weight multiplies, and with it how many are expected: "replica", one
+        per replica, or an item of the request's first list ("pair", "entry").  ValueError when the request is not set or
+        the count is wrong."""
+        req = getattr(self, "_" + name)
+        if req is None:
+            title = "cross request of MPOs" if name == "cross_mpo" else f"{name} request"
+            raise ValueError(f"no {title} is set (set_{name})")
         if weights is None:
             return None
+        count = len(self.engines) if unit == "replica" else len(req[0])
         w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
-        if w.shape != (len(self._cross[0]),):
-            raise ValueError(f"cross weights must be {len(self._cross[0])} numbers, one per pair (got shape {w.shape})")
+        if w.shape != (count,):
+            raise ValueError(f"{name} weights must be {count} numbers, one per {unit} (got shape {w.shape})")
         return w
 
     def cross(self, weights=None):
         """The request of ``set_cross`` on the current state of the replicas: one launch for all pairs, a second one for
         their weighted sum (``mitdvp_batch_cross``).  Returns ``{"values": (P,) complex, "mean": complex}``; ``weights``:
         P numbers, default 1 / P each."""
-        w = self._cross_weights(weights)
+        w = self._request_weights("cross", "pair", weights)
         vals = np.zeros(len(self._cross[0]), dtype=np.complex128)
         mean = np.zeros(1, dtype=np.complex128)
         _lib.check(self._lib.mitdvp_batch_cross(self._handle(), None if w is None else _dp(w), _dp(vals), _dp(mean)))
         return {"values": vals, "mean": complex(mean[0])}
 
     def _cross_records(self, weights):
-        w = self._cross_weights(weights)
+        w = self._request_weights("cross", "pair", weights)
         cnt = (C.c_size_t * 2)()
         _lib.check(self._lib.mitdvp_batch_cross_records(self._b, None, None, None, cnt))
         nrec, npairs = int(cnt[0]), int(cnt[1])
@@ -1318,17 +1325,6 @@ class TDVPBatch:
         self._handle()
         self._push_spectra(bonds)
         self._spectra = bonds if bonds else None
-
-    def _spectra_weights(self, weights):
-        if self._spectra is None:
-            raise ValueError("no spectra request is set (set_spectra)")
-        if weights is None:
-            return None
-        n = len(self.engines)
-        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
-        if w.shape != (n,):
-            raise ValueError(f"spectra weights must be {n} numbers, one per replica (got shape {w.shape})")
-        return w
 
     def _split_spectra(self, values, mean, per_replica=True):
         """the flat records cut by bond: W, S1, S2, pmin and the chi weights of every requested bond"""
@@ -1357,7 +1353,7 @@ class TDVPBatch:
         Schmidt values, descending, not normalised; and, with ``per_replica``, the same names without ``mean_`` and with
         a leading B axis.  The entropies are those of each trajectory, THEN averaged: they are not functions of the
         averaged densities.  ``weights``: B numbers, default 1 / B each."""
-        w = self._spectra_weights(weights)
+        w = self._request_weights("spectra", "replica", weights)
         b = self._handle()
         cnt = (C.c_size_t * 2)()
         _lib.check(self._lib.mitdvp_batch_spectra(b, None, None, None, cnt))
@@ -1368,7 +1364,7 @@ class TDVPBatch:
         return self._split_spectra(vals, mean, per_replica)
 
     def _spectra_records(self, weights, per_replica=True):
-        w = self._spectra_weights(weights)
+        w = self._request_weights("spectra", "replica", weights)
         cnt = (C.c_size_t * 3)()
         _lib.check(self._lib.mitdvp_batch_spectra_records(self._b, None, None, None, cnt))
         nrec, n, rec_len = (int(c) for c in cnt)
@@ -1390,17 +1386,6 @@ class TDVPBatch:
         self._handle()
         self._push_samples(nshots, seed)
         self._samples = (nshots, seed) if nshots else None
-
-    def _samples_weights(self, weights):
-        if self._samples is None:
-            raise ValueError("no samples request is set (set_samples)")
-        if weights is None:
-            return None
-        n = len(self.engines)
-        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
-        if w.shape != (n,):
-            raise ValueError(f"samples weights must be {n} numbers, one per replica (got shape {w.shape})")
-        return w
 
     def _split_samples(self, configs, prob, freq, mean, per_replica=True):
         """the flat frequency axis cut by site: one (.., d_p) array per site"""
@@ -1437,12 +1422,12 @@ class TDVPBatch:
         ``configs`` ``(B, nshots, L)`` int32 (one basis index per site; -1 from the site on at which a zero state left no
         weight), ``prob`` ``(B, nshots)`` (``|<config|psi>|^2 / <psi|psi>``) and ``freq``, a list of ``(B, d_p)`` arrays.
         ``weights``: B numbers, default 1 / B each."""
-        w = self._samples_weights(weights)
+        w = self._request_weights("samples", "replica", weights)
         self._handle()
         return self._samples_call(self._lib.mitdvp_batch_samples, w, 0, per_replica)
 
     def _samples_records(self, weights, per_replica=True):
-        w = self._samples_weights(weights)
+        w = self._request_weights("samples", "replica", weights)
         return self._samples_call(self._lib.mitdvp_batch_samples_records, w, 1, per_replica)
 
     # ---- expectation values of MPO observables (mitdvp_batch_set_expect / _expect) ----
@@ -1462,24 +1447,13 @@ class TDVPBatch:
         self._push_expect(ops)
         self._expect = ops if ops else None
 
-    def _expect_weights(self, weights):
-        if self._expect is None:
-            raise ValueError("no expect request is set (set_expect)")
-        if weights is None:
-            return None
-        n = len(self.engines)
-        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
-        if w.shape != (n,):
-            raise ValueError(f"expect weights must be {n} numbers, one per replica (got shape {w.shape})")
-        return w
-
     def expect(self, weights=None, per_replica: bool = True):
         """``<psi | O_k | psi> + shift_k <psi | psi>`` (not normalised, as ``TDVPEngine.expectation``) of every operator of
         ``set_expect`` for every replica by ONE launch (``k_batch_expect``, one workgroup per replica and operator), the
         ensemble means by a second one (``mitdvp_batch_expect``); all replicas must have their centre at site 0 and are
         only read.  Returns ``mean`` of shape ``(nops,)`` and, with ``per_replica``, ``values`` ``(B, nops)``, complex, in
         the order of the request.  ``weights``: B numbers, default 1 / B each."""
-        w = self._expect_weights(weights)
+        w = self._request_weights("expect", "replica", weights)
         b = self._handle()
         cnt = (C.c_size_t * 2)()
         _lib.check(self._lib.mitdvp_batch_expect(b, None, None, None, cnt))
@@ -1490,7 +1464,7 @@ class TDVPBatch:
         return {"values": vals, "mean": mean} if per_replica else {"mean": mean}
 
     def _expect_records(self, weights, per_replica=True):
-        w = self._expect_weights(weights)
+        w = self._request_weights("expect", "replica", weights)
         cnt = (C.c_size_t * 3)()
         _lib.check(self._lib.mitdvp_batch_expect_records(self._b, None, None, None, cnt))
         nrec, n, nops = (int(c) for c in cnt)
@@ -1529,28 +1503,18 @@ class TDVPBatch:
         self._push_cross_mpo(packed)
         self._cross_mpo = packed if bra else None
 
-    def _cross_mpo_weights(self, weights):
-        if self._cross_mpo is None:
-            raise ValueError("no cross request of MPOs is set (set_cross_mpo)")
-        if weights is None:
-            return None
-        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
-        if w.shape != (len(self._cross_mpo[0]),):
-            raise ValueError(f"cross_mpo weights must be {len(self._cross_mpo[0])} numbers, one per entry (got shape {w.shape})")
-        return w
-
     def cross_mpo(self, weights=None):
         """The request of ``set_cross_mpo`` on the current state of the replicas: one launch for all entries
         (``k_batch_cross_mpo``, one workgroup per entry), a second one for their weighted sum (``mitdvp_batch_cross_mpo``).
         Returns ``{"values": (P,) complex, "mean": complex}``; ``weights``: P numbers, default 1 / P each."""
-        w = self._cross_mpo_weights(weights)
+        w = self._request_weights("cross_mpo", "entry", weights)
         vals = np.zeros(len(self._cross_mpo[0]), dtype=np.complex128)
         mean = np.zeros(1, dtype=np.complex128)
         _lib.check(self._lib.mitdvp_batch_cross_mpo(self._handle(), None if w is None else _dp(w), _dp(vals), _dp(mean)))
         return {"values": vals, "mean": complex(mean[0])}
 
     def _cross_mpo_records(self, weights):
-        w = self._cross_mpo_weights(weights)
+        w = self._request_weights("cross_mpo", "entry", weights)
         cnt = (C.c_size_t * 2)()
         _lib.check(self._lib.mitdvp_batch_cross_mpo_records(self._b, None, None, None, cnt))
         nrec, np_ = int(cnt[0]), int(cnt[1])
@@ -1657,15 +1621,16 @@ class TDVPBatch:
                   samples_weights=None, expect=False, expect_weights=None, cross_mpo=False, cross_mpo_weights=None):
         n = len(self.engines)
         if cross:
-            self._cross_weights(cross_weights)  # no request, or weights of the wrong length: raised before any library call
+            # no request, or weights of the wrong length: raised before any library call
+            self._request_weights("cross", "pair", cross_weights)
         if spectra:
-            self._spectra_weights(spectra_weights)
+            self._request_weights("spectra", "replica", spectra_weights)
         if samples:
-            self._samples_weights(samples_weights)
+            self._request_weights("samples", "replica", samples_weights)
         if expect:
-            self._expect_weights(expect_weights)
+            self._request_weights("expect", "replica", expect_weights)
         if cross_mpo:
-            self._cross_mpo_weights(cross_mpo_weights)
+            self._request_weights("cross_mpo", "entry", cross_mpo_weights)
         nsite = self.engines[0].nsite
         legs = [density_key_legs(k, nsite) for k in keys]  # a malformed key raises here, before any library call
         sites = [int(p) for p in sites]

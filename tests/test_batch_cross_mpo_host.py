@@ -176,10 +176,10 @@ def test_set_cross_mpo_entries_on_the_python_side():
         with pytest.raises(ValueError, match="set_cross_mpo: entry 0"):
             bt.set_cross_mpo(bad)
     with pytest.raises(ValueError, match="no cross request of MPOs is set"):
-        bt._cross_mpo_weights(None)
+        bt._request_weights("cross_mpo", "entry", None)
     bt._cross_mpo = ([0, 1], [1, 0], [1, 1])
     with pytest.raises(ValueError, match="cross_mpo weights must be 2 numbers, one per entry"):
-        bt._cross_mpo_weights([1.0])
+        bt._request_weights("cross_mpo", "entry", [1.0])
     bt._b = None  # what __del__ looks at
     bt.engines, bt._own = [], False
 
