@@ -248,7 +248,7 @@ int mitdvp_batch_jump_counts(mitdvp_batch* b, long long* counts);
  *       by mitdvp_batch_discarded_weight.  MITDVP_CHANNEL_JUMP (2 <= nops <= 16): the selection rule of the one-site
  *       jump channel bit for bit, on w_k = |B_k theta|^2, with the uniform of "site" nsite + site (distinct from every
  *       one-site draw); afterwards C' is rescaled so that the norm after the split equals the norm before the jump.
- *       W == 0 stops that replica only, as for a one-site channel; so does a split that does not converge in 30 sweeps
+ *       W == 0 stops that replica only, as for a one-site channel; so does a split that does not converge in 64 sweeps
  *       (MITDVP_ENOTCONV in its status).  MITDVP_EINVAL (message: mitdvp_last_error(NULL), naming the bond and the limit;
  *       nothing changed, every engine untouched) when the bond is out of range, d0 / d1 are not the two sites' physical
  *       dimensions, nops is out of range for the kind, dl d0 or d1 dr exceeds 128, theta and its copy do not fit the
@@ -326,7 +326,7 @@ int mitdvp_batch_cross_records(mitdvp_batch* b, const double* weights, double* v
  *       counts = {records, n, rec_len}; each may be NULL.  weights NULL: the means under 1 / n, formed by that call, no
  *       launch and no wait here; weights given (n doubles): ONE k_batch_mean launch over the records, which are still on
  *       the device, and one host wait.  A new request or no recording call yet: records = 0.
- * Jacobi sweeps that do not converge within 30 sweeps zero that replica's record; its status and its tensors stay as
+ * Jacobi sweeps that do not converge within 64 sweeps zero that replica's record; its status and its tensors stay as
  * they are (an observation never changes a replica), and the call returns MITDVP_ENOTCONV with a message in
  * mitdvp_last_error(NULL) naming the replica and the bond.  Every refusal is MITDVP_EINVAL with a message in
  * mitdvp_last_error(NULL) that names the entry point and the limit, and leaves the request, the records and every engine
@@ -880,6 +880,51 @@ typedef struct mitdvp_zgemm_reduce_args {
 } mitdvp_zgemm_reduce_args;
 int mitdvp_zgemm_reduce(int device, const mitdvp_zgemm_reduce_args* a, const double* A, size_t nA, const double* B, size_t nB,
                         const double* W, size_t nW, double* C, size_t nC, int* variant_out);
+/* One building block of the batched-trajectory kernels (csrc/batch_site.hip) in ONE workgroup, as those kernels call it:
+ * the workgroup product behind the absorb, the H_eff / K_eff applies, the environment update and the overlap walk, the
+ * in-workgroup Householder thin QR, and the Jacobi split of a two-site tensor.  Workgroup b of a grid of ncopies takes its
+ * own copy of the operands and writes its own copy of the results (a result may not depend on the grid).
+ *   op / variant / dims (all tensors row-major, complex128 as (re, im)):
+ *   MATMUL   (M, N, K)                 out0 = in0 (M x K) in1 (K x N); variant 0: into a buffer of its own, 1: in place of
+ *                                      in0 (N = K), 2: in place of in1 (M = K)
+ *   HEFF     (dl, d, dr, ml, mr)       out0[a,i,r] = sum in0[a,c,b] W[c,i,j,t] in2[r,t,s] scl in3[b,j,s]; in1 = W as
+ *                                      [(i,t)][(c,j)]
+ *   KEFF     (dim, m)                  out0[a,r] = sum in0[a,c,b] scl in3[b,s] in2[r,c,s]
+ *   ENV      (din, min, d, dout, mout) out0[a,q,r] = sum conj(bra)(b,i,a) in0[b,p,s] W[p,i,j,q] ket(s,j,r), in2 = bra,
+ *                                      in3 = ket; variant 0: tensors stored (in, phys, out), in1 = W as [(q,j)][(i,p)];
+ *                                      variant 1: tensors stored (out, phys, in), the mirror image a backward sweep reads
+ *                                      (W[p,i,j,q] is then core[q,i,j,p] of the MPO core); variant 2: as 0 through the
+ *                                      forward-only instance.  (in1 of HEFF / ENV 0, 2 / ENV 1 is the packing w2l / w2el /
+ *                                      w2er of a core (ml, d, d, mr): csrc/engine.h)
+ *   OVERLAP  (L, d, b_1 .. b_(L-1))    out0[0] = <bra | ket>, in0 / in1 = the L <= 6 site tensors of ket / bra one after
+ *                                      the other, site p of shape (b_p, d, b_(p+1)), b_0 = b_L = 1
+ *   QR       (m, n), m >= n            variant 0: in0 = A (m x n), out0 = Q (m x n), out1 = R (n x n); variant 1: in0 =
+ *                                      A^T (n x m), out0 = Q^T, out1 = R^T; no sign convention on diag(R)
+ *   SPLIT    (m, n, r)                 in0 = theta (m x n); out0 = B (r x n, orthonormal rows), out1 = C' = theta B^H
+ *                                      (m x r)
+ *   info, doubles, per copy: [0] the block's return code (0 = ok, 1 = not converged within the 64 Jacobi sweeps); SPLIT also [1] the kept
+ *   weight, [2] the discarded fraction, [3 .. 3 + m) the squared row norms (sigma^2) in descending order.
+ * n0 .. n3, nout0, nout1 count complex elements, ninfo doubles; the results hold ncopies copies one after the other.
+ * Before any HIP call MITDVP_EINVAL is returned for an unknown op or variant, a dimension below 1, a shape outside the
+ * kernels' own envelope (more than 8192 elements in a tensor, a bond above 64, an MPO bond above 16, QR with m < n, SPLIT
+ * with m or n above 128 or r above min(m, n, 64)), a buffer shorter than the operation's footprint
+ * (csrc/batch_block_check.h) or ncopies outside 1 .. 16. */
+#define MITDVP_BLOCK_MATMUL 0
+#define MITDVP_BLOCK_HEFF 1
+#define MITDVP_BLOCK_KEFF 2
+#define MITDVP_BLOCK_ENV 3
+#define MITDVP_BLOCK_OVERLAP 4
+#define MITDVP_BLOCK_QR 5
+#define MITDVP_BLOCK_SPLIT 6
+typedef struct mitdvp_batch_block_args {
+  int op, variant;
+  int dims[8];
+  int ncopies;
+  double scl; /* HEFF, KEFF: the factor on the vector */
+} mitdvp_batch_block_args;
+int mitdvp_batch_block(int device, const mitdvp_batch_block_args* a, const double* in0, size_t n0, const double* in1, size_t n1,
+                       const double* in2, size_t n2, const double* in3, size_t n3, double* out0, size_t nout0, double* out1,
+                       size_t nout1, double* info, size_t ninfo);
 /* Complex-product form of the MFMA zgemm kernel for everything that follows:
  * 0 = "4M" (textbook, 4 real MFMA products), 1 = "3M" (Karatsuba, 3 products,
  * normwise stable); the library default is 1 unless MITDVP_ZGEMM=4m is set. */

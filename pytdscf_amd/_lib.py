@@ -118,6 +118,14 @@ class ZgemmReduceArgs(C.Structure):
     ]
 
 
+class BatchBlockArgs(C.Structure):
+    """mitdvp_batch_block_args: one building block of the batch kernels, run by mitdvp_batch_block"""
+
+    _fields_ = [("op", C.c_int), ("variant", C.c_int), ("dims", C.c_int * 8), ("ncopies", C.c_int), ("scl", C.c_double)]
+
+
+BLOCK_MATMUL, BLOCK_HEFF, BLOCK_KEFF, BLOCK_ENV, BLOCK_OVERLAP, BLOCK_QR, BLOCK_SPLIT = range(7)
+
 OBS_NORM, OBS_AUTOCORR, OBS_ENERGY, OBS_RDM = 1, 2, 4, 8
 CHANNEL_GATE, CHANNEL_JUMP = 1, 2
 MAX_JUMP = 16  # operators of one jump channel (BATCH_MAX_JUMP)
@@ -233,6 +241,8 @@ def load() -> C.CDLL:
         "mitdvp_zgemm": (i, [i, i, i, i, i, i, i, i, dp, dp, dp, dp, dp, i, i, dp]),
         "mitdvp_zgemm_desc": (i, [i, C.POINTER(ZgemmArgs), dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, ip, C.c_size_t]),
         "mitdvp_zgemm_reduce": (i, [i, C.POINTER(ZgemmReduceArgs), dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, ip]),
+        "mitdvp_batch_block": (i, [i, C.POINTER(BatchBlockArgs), dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t,
+                                   dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t]),
         "mitdvp_bench_heff": (i, [i, i, i, i, i, i, i, i, dp]),
         "mitdvp_heff_selfcheck": (i, [i, i, i, i, i, i, dp]),
         "mitdvp_set_gemm_mode": (i, [i]),

@@ -16,5 +16,7 @@ constexpr int BATCH_MAX_MPO = 16;
 constexpr int BATCH_MAX_BOND = 64;
 // pairs of one cross request (k_batch_cross), entries of one cross request of MPOs (k_batch_cross_mpo)
 constexpr int BATCH_CROSS_MAX_PAIRS = 65536;
+// rows and columns of the two-site tensor of a pair channel (k_batch_pair; batch_site.h has the reasons)
+constexpr int BATCH_PAIR_MAX_DIM = 128;
 
 }  // namespace mitdvp

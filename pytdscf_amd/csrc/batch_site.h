@@ -3,6 +3,7 @@
 #pragma once
 #include <string>
 
+#include "batch_block_check.h"
 #include "batch_cross_mpo_plan.h"
 #include "batch_operate_plan.h"
 #include "batch_shape.h"
@@ -81,8 +82,13 @@ void batch_channel_launch(hipStream_t st, const BatchChanArgs& a, int nrep);
 // two-site tensor theta, seen as (dl d_q) x (d_{q+1} dr), has at most BATCH_PAIR_MAX_DIM rows and columns (row norms,
 // ranks and rotation scalars of the split live in LDS), and theta and its copy fit the Krylov-basis carve of the
 // replica's scratch area (BatchPlan::o_u), which is idle during the walk.
-constexpr int BATCH_PAIR_MAX_DIM = 128;
-constexpr int BATCH_PAIR_MAX_SWEEPS = 30;  // Jacobi sweeps of one split; a replica that reaches it gets SS_ENOTCONV
+// (BATCH_PAIR_MAX_DIM = 128: batch_shape.h, which needs no HIP)
+// Jacobi sweeps of one split; a replica that reaches it gets SS_ENOTCONV.  The cyclic sweeps run on the rows of theta as
+// they are (no preconditioning), so the count grows with the rows and with the spread of the spectrum: up to 60 rows 12
+// sweeps were the most seen, but 128 x 128 with singular values graded over 12 decades, or 128 of them 0.8 apart, takes 32
+// (tests/test_gpu_batch_blocks.py; the limit was 30 and such a split was SS_ENOTCONV).  A sweep that rotates nothing ends
+// the loop, so the limit costs nothing where fewer are needed.
+constexpr int BATCH_PAIR_MAX_SWEEPS = 64;
 // false + a message naming the bond and the limit
 bool batch_pair_fits(const BatchShape* shp, int L, const BatchPlan& plan, int q, std::string& why);
 struct BatchPairArgs {
@@ -338,5 +344,22 @@ struct BatchOperateArgs {
 };
 // one launch: grid = nsel workgroups
 void batch_operate_launch(hipStream_t st, const BatchOperateArgs& a, int nsel);
+
+// ---- test hook: one building block of the kernels above in one workgroup (k_batch_block) ----
+// Workgroup b copies the operands into its own part of work, runs the block on that copy with the LDS carve of
+// k_batch_pair, and writes its own copy of the results.  The shapes and footprints are batch_block_check.h's; the caller
+// has checked them (batch_block_check) -- the kernel itself checks nothing.
+struct BatchBlockArgs {
+  int op, variant;          // MITDVP_BLOCK_*
+  int dims[8];
+  double scl;
+  const zc* in[4];          // one copy of each operand, foot.in[k] elements
+  zc *out0, *out1;          // [ncopies][foot.out0], [ncopies][foot.out1]
+  double* info;             // [ncopies][foot.info]
+  zc* work;                 // [ncopies][foot.work_total()]: the operands' copies, then the three work areas
+  BatchBlockFoot foot;
+};
+// one launch: grid = ncopies workgroups
+void batch_block_launch(hipStream_t st, const BatchBlockArgs& a, int ncopies);
 
 }  // namespace mitdvp

@@ -254,6 +254,12 @@ __device__ __noinline__ void bt_env_fwd(const zc* env, const zc* Tb, const zc* T
                                         int mout, zc* X, zc* Y, zc* out, zc* tiles) {
   bt_env_body(env, Tb, Tk, (long)d * dout, dout, 1, W2e, din, min_, d, dout, mout, X, Y, out, tiles);
 }
+// k_batch_block's instance of the same: a second caller of bt_env_fwd moved the registers of k_batch_cross_mpo (180 -> 184
+// VGPRs: the tile address stops being a constant of the one caller)
+__device__ __noinline__ void bt_env_fwd_blk(const zc* env, const zc* Tb, const zc* Tk, const zc* W2e, int din, int min_, int d, int dout,
+                                            int mout, zc* X, zc* Y, zc* out, zc* tiles) {
+  bt_env_body(env, Tb, Tk, (long)d * dout, dout, 1, W2e, din, min_, d, dout, mout, X, Y, out, tiles);
+}
 
 // dst = A (M x K) . B (K x N), all row-major, by way of tmp (dst may be A or B): the absorb of a sweep
 __device__ __noinline__ void bt_matmul(const zc* A, const zc* B, zc* tmp, zc* dst, int M, int N, int K, zc* tiles) {
@@ -1137,9 +1143,13 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_channel(BatchChanArgs g) {
 //           rotated until all are mutually orthogonal (|<x, y>|^2 <= BP_TOL2 |x|^2 |y|^2); the rows are then sigma_j v_j^+,
 //           the r of largest norm, normalised, are B(p), and C'(p-1) = theta B(p)^+ from the kept copy: no U, no V.
 //           Rows whose norm^2 is <= BP_TINY |theta|^2 (|theta|^2 lies between the largest sigma^2 and m times it; a
-//           rank-deficient theta: a product start padded to D) are rounding noise: they are left out of the rotations,
-//           and those among the selected r are replaced by an orthonormal completion (bp_select), so B(p) B(p)^+ = 1
-//           whatever the rank.
+//           rank-deficient theta: a product start padded to D) are rounding noise: those among the selected r are
+//           replaced by an orthonormal completion (bp_select), so B(p) B(p)^+ = 1 whatever the rank.  A row is left out
+//           of the ROTATIONS only at or below BP_FREEZE |theta|^2, the unit roundoff of |theta| itself (with more rows
+//           than columns the surplus rows shrink towards 0 and would rotate for ever).  The two floors are apart on
+//           purpose: a row frozen at 1e-14 |theta| may still carry a part of a direction whose sigma lies just above,
+//           and some eighty such rows hid 3e-14 |theta| of a singular value at 127 x 65 and 128 x 128
+//           (tests/test_gpu_batch_blocks.py); at the roundoff floor all of them together hold 1e-15 |theta| at most.
 // After a jump C' is rescaled so that the norm after the split is the norm before the jump (operator and truncation
 // together); after a gate nothing is rescaled and the discarded weight sum_{j>r} sigma_j^2 / sum_j sigma_j^2 of every
 // split is added to disc[replica] by thread 0.  A split that does not converge in BATCH_PAIR_MAX_SWEEPS sweeps is
@@ -1154,6 +1164,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_channel(BatchChanArgs g) {
 // every sum one order; no atomics; the loops are bounded by the shapes and BATCH_PAIR_MAX_SWEEPS.
 constexpr double BP_TOL2 = 1.6e-29;  // (4e-15)^2: sqrt(128) eps = 2.5e-15 is what a 128-term inner product carries
 constexpr double BP_TINY = 1e-28;    // (1e-14)^2: a row this small against |theta| is rounding noise, not a direction
+constexpr double BP_FREEZE = 1e-32;  // (1e-16)^2: a row this small against |theta| takes no part in the rotations
 
 struct BpSh {
   double* rot;   // [4 * BATCH_PAIR_MAX_DIM / 2]  c, s, phase (re, im) of the round's pairs; s == 0: no rotation
@@ -1267,8 +1278,8 @@ __device__ __noinline__ int bp_jacobi(zc* T, int m, int n, const BpSh& ps, const
     double s1[1] = {0.0};
     for (long e = tid; e < (long)m * n; e += SS_THREADS) { const zc z = T[e]; s1[0] += z.x * z.x + z.y * z.y; }
     wg_reduce(s1, sh);
-    tiny = BP_TINY * sh.red[0];
-    if (tid == 0) ps.scal[2] = tiny;
+    tiny = BP_FREEZE * sh.red[0];
+    if (tid == 0) ps.scal[2] = BP_TINY * sh.red[0];  // bp_select's floor
   }
   int rc = SS_ENOTCONV;
   for (int sweep = 0; sweep < BATCH_PAIR_MAX_SWEEPS; ++sweep) {
@@ -1295,7 +1306,7 @@ __device__ __noinline__ int bp_jacobi(zc* T, int m, int n, const BpSh& ps, const
           gr = __shfl(wave_sum64(gr), 0, 64);
           gi = __shfl(wave_sum64(gi), 0, 64);
           const double g2 = gr * gr + gi * gi;
-          if (g2 > BP_TOL2 * a * b && a > tiny && b > tiny) {  // a row at rounding level takes no part: it is never kept
+          if (g2 > BP_TOL2 * a * b && a > tiny && b > tiny) {  // a row at the roundoff of |theta| takes no part
             const double ag = sqrt(g2), zeta = (a - b) / (2.0 * ag);
             const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
             c = 1.0 / sqrt(1.0 + tt * tt);
@@ -1342,7 +1353,8 @@ __device__ __noinline__ int bp_jacobi(zc* T, int m, int n, const BpSh& ps, const
 // index first), normalised; those of them at or below BP_TINY |theta|^2 (ps.scal[2]) are replaced one after the other by
 // the unit vector e_c furthest from the span so far (largest 1 - sum_k |B_k[c]|^2 >= 1 / n, the lowest c on a tie),
 // orthogonalised against it twice (classical Gram-Schmidt) and normalised.  ps.scal: kept weight, discarded fraction.
-__device__ __noinline__ void bp_select(const zc* T, zc* Bp, int m, int n, int r, const BpSh& ps, const BtSh& sh) {
+// This is the one text of the selection; bp_select below is the function k_batch_pair calls.
+__device__ __forceinline__ void bp_select_body(const zc* T, zc* Bp, int m, int n, int r, const BpSh& ps, const BtSh& sh) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   if (tid < r) ps.sel[tid] = tid;  // in range whatever the norms are (NaN compares false everywhere)
   __syncthreads();
@@ -1440,13 +1452,28 @@ __device__ __noinline__ void bp_select(const zc* T, zc* Bp, int m, int n, int r,
     __syncthreads();
   }
 }
+__device__ __noinline__ void bp_select(const zc* T, zc* Bp, int m, int n, int r, const BpSh& ps, const BtSh& sh) {
+  bp_select_body(T, Bp, m, n, r, ps, sh);
+}
+// k_batch_block's instance of the same text, as bt_env_fwd_blk: with a second caller the LDS addresses in ps and sh stop being
+// constants of bp_select, and k_batch_pair spilled 25 scalar registers around its calls instead of 15
+__device__ __noinline__ void bp_select_blk(const zc* T, zc* Bp, int m, int n, int r, const BpSh& ps, const BtSh& sh) {
+  bp_select_body(T, Bp, m, n, r, ps, sh);
+}
 
 // Cp[(a,i)][b] = scl * sum_c T[(a,i)][c] conj(Bp[b][c])
-__device__ __noinline__ void bp_cprime(const zc* T, const zc* Bp, zc* Cp, int m, int n, int r, double scl, zc* tiles) {
+// (one text; bp_cprime is the function k_batch_pair calls, bp_cprime_blk k_batch_block's instance, as bp_select_blk)
+__device__ __forceinline__ void bp_cprime_body(const zc* T, const zc* Bp, zc* Cp, int m, int n, int r, double scl, zc* tiles) {
   wg_gemm<true, true>(m, r, n, tiles,
       [&](int mm, int k) { return T[(long)mm * n + k]; },
       [&](int k, int nn) { const zc z = Bp[(long)nn * n + k]; return make_double2(z.x, -z.y); },
       [&](int mm, int nn, zc z) { Cp[(long)mm * r + nn] = make_double2(z.x * scl, z.y * scl); });
+}
+__device__ __noinline__ void bp_cprime(const zc* T, const zc* Bp, zc* Cp, int m, int n, int r, double scl, zc* tiles) {
+  bp_cprime_body(T, Bp, Cp, m, n, r, scl, tiles);
+}
+__device__ __noinline__ void bp_cprime_blk(const zc* T, const zc* Bp, zc* Cp, int m, int n, int r, double scl, zc* tiles) {
+  bp_cprime_body(T, Bp, Cp, m, n, r, scl, tiles);
 }
 
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 196 VGPRs -- those of the
@@ -2265,7 +2292,115 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_operate(BatchOperateArgs g
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Test hook: k_batch_block, ONE building block of the kernels above in one workgroup (mitdvp_batch_block; the shapes,
+// operands and footprints are batch_block_check.h's, and the host has checked them).  Workgroup b copies the operands to
+// its own part of g.work and runs the block there -- the function the kernels call, not a restatement of it -- with the
+// LDS of k_batch_pair: the tile array handed over directly (assume_lds above says why), BtSh and BpSh carved the same
+// way.  Everything a workgroup reads after the copy it wrote itself; nothing is shared between workgroups.
+__global__ __launch_bounds__(SS_THREADS) void k_batch_block(BatchBlockArgs g) {
+  __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
+  __shared__ zc s_z[3 * BATCH_MAX_BOND];
+  __shared__ double s_d[SS_WAVES * 8 + 8 + BATCH_MAX_BOND + 2 * BATCH_PAIR_MAX_DIM + 2 * BATCH_PAIR_MAX_DIM + 3];
+  __shared__ int s_i[BATCH_PAIR_MAX_DIM + BATCH_MAX_BOND + 2];
+  __shared__ BatchShape s_shp[BATCH_BLOCK_MAX_CHAIN];
+  BtSh sh{};
+  sh.mats = s_tiles;
+  sh.udiag = s_z; sh.rdiag = s_z + BATCH_MAX_BOND;
+  sh.wsh = s_d; sh.red = sh.wsh + SS_WAVES * 8; sh.gam = sh.red + 8;
+  BpSh ps;
+  ps.rot = sh.gam + BATCH_MAX_BOND; ps.nrm = ps.rot + 2 * BATCH_PAIR_MAX_DIM; ps.res = ps.nrm + BATCH_PAIR_MAX_DIM;
+  ps.scal = ps.res + BATCH_PAIR_MAX_DIM;  // [3]
+  ps.h = s_z + 2 * BATCH_MAX_BOND;
+  ps.rank = s_i; ps.sel = s_i + BATCH_PAIR_MAX_DIM; ps.flag = ps.sel + BATCH_MAX_BOND;
+
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const BatchBlockFoot& f = g.foot;
+  zc* c[4];  // this workgroup's copies of the operands
+  zc* w[3];  // and its work areas
+  {
+    zc* p = g.work + (size_t)b * (f.in[0] + f.in[1] + f.in[2] + f.in[3] + f.work[0] + f.work[1] + f.work[2]);  // work_total()
+    for (int k = 0; k < 4; ++k) {
+      c[k] = p;
+      for (size_t e = tid; e < f.in[k]; e += SS_THREADS) p[e] = g.in[k][e];
+      p += f.in[k];
+    }
+    for (int k = 0; k < 3; ++k) { w[k] = p; p += f.work[k]; }
+  }
+  zc* out0 = g.out0 + (size_t)b * f.out0;
+  zc* out1 = g.out1 + (size_t)b * f.out1;
+  double* info = g.info + (size_t)b * f.info;
+  __syncthreads();
+
+  const int* q = g.dims;
+  int rc = SS_OK;
+  switch (g.op) {
+    case MITDVP_BLOCK_MATMUL: {
+      const int M = q[0], N = q[1], K = q[2];
+      zc* dst = g.variant == 1 ? c[0] : g.variant == 2 ? c[1] : out0;
+      bt_matmul(c[0], c[1], w[0], dst, M, N, K, s_tiles);
+      if (dst != out0)
+        for (long e = tid; e < (long)M * N; e += SS_THREADS) out0[e] = dst[e];
+      break;
+    }
+    case MITDVP_BLOCK_HEFF: {
+      const BatchShape s{q[0], q[1], q[2], q[3], q[4]};
+      bt_heff(s, c[0], c[1], c[2], c[3], g.scl, w[0], w[1], out0, s_tiles);
+      break;
+    }
+    case MITDVP_BLOCK_KEFF:
+      bt_keff(q[0], q[1], c[0], c[2], c[3], g.scl, w[0], out0, s_tiles);
+      break;
+    case MITDVP_BLOCK_ENV: {
+      const int din = q[0], mi = q[1], d = q[2], dout = q[3], mo = q[4];
+      if (g.variant == 0) bt_env(c[0], c[2], c[3], (long)d * dout, dout, 1, c[1], din, mi, d, dout, mo, w[0], w[1], out0, s_tiles);
+      else if (g.variant == 1) bt_env(c[0], c[2], c[3], 1, din, (long)d * din, c[1], din, mi, d, dout, mo, w[0], w[1], out0, s_tiles);
+      else bt_env_fwd_blk(c[0], c[2], c[3], c[1], din, mi, d, dout, mo, w[0], w[1], out0, s_tiles);
+      break;
+    }
+    case MITDVP_BLOCK_OVERLAP: {
+      const int L = q[0];
+      if (tid < L) s_shp[tid] = BatchShape{tid == 0 ? 1 : q[1 + tid], q[1], tid == L - 1 ? 1 : q[2 + tid], 1, 1};
+      __syncthreads();
+      const zc* res = wg_overlap(L, s_shp, [&](int, size_t soff) { return c[0] + soff; }, [&](int, size_t soff) { return c[1] + soff; },
+                                 w[0], w[1], w[2], s_tiles);
+      if (tid == 0) out0[0] = res[0];
+      break;
+    }
+    case MITDVP_BLOCK_QR: {
+      const int m = q[0], n = q[1];
+      if (g.variant == 0) bt_qr(c[0], c[0], n, 1, out1, n, 1, m, n, w[0], sh);  // Psi2Asigma
+      else bt_qr(c[0], c[0], 1, m, out1, 1, n, m, n, w[0], sh);                 // Psi2sigmaB, on the transpose
+      for (long e = tid; e < (long)m * n; e += SS_THREADS) out0[e] = c[0][e];
+      break;
+    }
+    case MITDVP_BLOCK_SPLIT: {
+      const int m = q[0], n = q[1], r = q[2];
+      for (long e = tid; e < (long)m * n; e += SS_THREADS) w[0][e] = c[0][e];  // the work copy, as bp_apply leaves it
+      __syncthreads();
+      rc = bp_jacobi(w[0], m, n, ps, sh);
+      if (rc != SS_OK) break;
+      bp_select_blk(w[0], out0, m, n, r, ps, sh);
+      bp_cprime_blk(c[0], out0, out1, m, n, r, 1.0, s_tiles);  // its barriers order the reads of ps below
+      if (tid < m) info[3 + ps.rank[tid]] = ps.nrm[tid];
+      if (tid == 0) { info[1] = ps.scal[0]; info[2] = ps.scal[1]; }
+      break;
+    }
+    default: break;
+  }
+  if (tid == 0) info[0] = (double)rc;
+}
+
 }  // namespace
+
+void batch_block_launch(hipStream_t st, const BatchBlockArgs& a, int ncopies) {
+  if (ncopies < 1 || ncopies > BATCH_BLOCK_MAX_COPIES) throw ArgError("batch_block: ncopies outside 1 .. 16");
+  if (!a.out0 || !a.info || !a.work || (a.foot.out1 && !a.out1)) throw ArgError("batch_block: the hook has no buffers");
+  for (int k = 0; k < 4; ++k)
+    if (a.foot.in[k] && !a.in[k]) throw ArgError("batch_block: an operand is missing");
+  hipLaunchKernelGGL(k_batch_block, dim3(ncopies), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
 
 void batch_operate_launch(hipStream_t st, const BatchOperateArgs& a, int nsel) {
   if (nsel < 1 || a.L < 1 || a.maxstep < 1) throw ArgError("batch: no replica to apply the operator to");

@@ -880,6 +880,43 @@ int mitdvp_zgemm_reduce(int device, const mitdvp_zgemm_reduce_args* a, const dou
   });
 }
 
+// one building block of the batch kernels in one workgroup per copy (k_batch_block): batch_block_check.h refuses, before
+// any HIP call, what lies outside the kernels' envelope or the caller's buffers
+int mitdvp_batch_block(int device, const mitdvp_batch_block_args* a, const double* in0, size_t n0, const double* in1, size_t n1,
+                       const double* in2, size_t n2, const double* in3, size_t n3, double* out0, size_t nout0, double* out1,
+                       size_t nout1, double* info, size_t ninfo) {
+  return guard(nullptr, [&] {
+    using namespace mitdvp;
+    const void* const in[4] = {in0, in1, in2, in3};
+    const size_t nin[4] = {n0, n1, n2, n3};
+    BatchBlockFoot f;
+    if (const char* bad = batch_block_check(a, in, nin, out0, nout0, out1, nout1, info, ninfo, &f)) throw ArgError(bad);
+    HIP_CHECK(hipSetDevice(device));
+    hipStream_t st;
+    HIP_CHECK(hipStreamCreate(&st));
+    {
+      const size_t nc = (size_t)a->ncopies;
+      Dev d0(st, in0, f.in[0]), d1(st, in1, f.in[1]), d2(st, in2, f.in[2]), d3(st, in3, f.in[3]);
+      Dev dout0(nc * f.out0), dout1(nc * f.out1), dwork(nc * f.work_total()), dinfo((nc * f.info + 1) / 2);
+      HIP_CHECK(hipMemsetAsync(dout0.p(), 0, nc * f.out0 * sizeof(zc), st));
+      if (f.out1) HIP_CHECK(hipMemsetAsync(dout1.p(), 0, nc * f.out1 * sizeof(zc), st));
+      HIP_CHECK(hipMemsetAsync(dinfo.p(), 0, (nc * f.info + 1) / 2 * sizeof(zc), st));
+      BatchBlockArgs g{};
+      g.op = a->op; g.variant = a->variant; g.scl = a->scl;
+      for (int k = 0; k < 8; ++k) g.dims[k] = a->dims[k];
+      g.in[0] = f.in[0] ? d0.p() : nullptr; g.in[1] = f.in[1] ? d1.p() : nullptr;
+      g.in[2] = f.in[2] ? d2.p() : nullptr; g.in[3] = f.in[3] ? d3.p() : nullptr;
+      g.out0 = dout0.p(); g.out1 = dout1.p(); g.info = reinterpret_cast<double*>(dinfo.p()); g.work = dwork.p();
+      g.foot = f;
+      batch_block_launch(st, g, a->ncopies);
+      HIP_CHECK(hipMemcpyAsync(info, dinfo.p(), nc * f.info * sizeof(double), hipMemcpyDeviceToHost, st));
+      if (f.out1) HIP_CHECK(hipMemcpyAsync(out1, dout1.p(), nc * f.out1 * sizeof(zc), hipMemcpyDeviceToHost, st));
+      to_host(st, out0, dout0.p(), nc * f.out0);
+    }
+    HIP_CHECK(hipStreamDestroy(st));
+  });
+}
+
 int mitdvp_bench_heff(int device, int dl, int d, int dr, int ml, int mr, int reps, int warmup, double* ms_out) {
   return guard(nullptr, [&] {
     using namespace mitdvp;

@@ -732,6 +732,79 @@ def zgemm_reduce(args: dict, A, B, W, Cbuf, device=0):
     return out, variant.value
 
 
+BATCH_BLOCK_OPS = {"matmul": _lib.BLOCK_MATMUL, "heff": _lib.BLOCK_HEFF, "keff": _lib.BLOCK_KEFF, "env": _lib.BLOCK_ENV,
+                   "overlap": _lib.BLOCK_OVERLAP, "qr": _lib.BLOCK_QR, "split": _lib.BLOCK_SPLIT}
+
+
+def pack_w2(core, order: str) -> np.ndarray:
+    """The matrix a batch kernel reads an MPO core ``W[c, i, j, t]`` of shape (ml, d, d, mr) as (``MpoSite`` in
+    csrc/engine.h): ``w2l[(i,t)][(c,j)]`` (the W stage of H_eff), ``w2el[(t,j)][(i,c)]`` (environment update ->),
+    ``w2er[(c,j)][(i,t)]`` (environment update <-)."""
+    W = _c128(core)
+    ml, d, d2, mr = W.shape
+    if d != d2:
+        raise ValueError("pack_w2: need a square 4-leg core")
+    if order == "w2l":
+        return np.ascontiguousarray(W.transpose(1, 3, 0, 2)).reshape(d * mr, ml * d)
+    if order == "w2el":
+        return np.ascontiguousarray(W.transpose(3, 2, 1, 0)).reshape(mr * d, d * ml)
+    if order == "w2er":
+        return np.ascontiguousarray(W.transpose(0, 2, 1, 3)).reshape(ml * d, d * mr)
+    raise ValueError(f"pack_w2: unknown order {order!r}")
+
+
+def batch_block_footprint(op: str, dims) -> dict:
+    """Elements per copy of the results of ``batch_block``: ``out0`` and ``out1`` complex, ``info`` doubles (the table in
+    csrc/batch_block_check.h, which is what decides)."""
+    q = [int(v) for v in dims]
+    if op == "matmul":
+        return dict(out0=q[0] * q[1], out1=0, info=1)
+    if op == "heff":
+        return dict(out0=q[0] * q[1] * q[2], out1=0, info=1)
+    if op == "keff":
+        return dict(out0=q[0] * q[0], out1=0, info=1)
+    if op == "env":
+        return dict(out0=q[3] * q[4] * q[3], out1=0, info=1)
+    if op == "overlap":
+        return dict(out0=1, out1=0, info=1)
+    if op == "qr":
+        return dict(out0=q[0] * q[1], out1=q[1] * q[1], info=1)
+    if op == "split":
+        return dict(out0=q[2] * q[1], out1=q[0] * q[2], info=3 + q[0])
+    raise ValueError(f"batch_block: unknown op {op!r}")
+
+
+def batch_block(op: str, dims, *operands, ncopies=1, variant=0, scl=1.0, device=0):
+    """One building block of the batched-trajectory kernels in one workgroup per copy (``mitdvp_batch_block``; include/mitdvp.h
+    has the operations, their dims, variants and operand order).  ``operands``: up to four arrays in the layouts the kernels
+    see (``pack_w2`` for an MPO core), ``None`` for one the operation does not take.  Returns ``(out0, out1, info)`` with a
+    leading axis of ``ncopies``.  What lies outside the kernels' envelope raises ValueError before the GPU is touched."""
+    if op not in BATCH_BLOCK_OPS:
+        raise ValueError(f"batch_block: unknown op {op!r}")
+    if len(operands) > 4 or len(dims) > 8:
+        raise TypeError("batch_block: at most four operands and eight dims")
+    a = _lib.BatchBlockArgs()
+    a.op, a.variant, a.ncopies, a.scl = BATCH_BLOCK_OPS[op], int(variant), int(ncopies), float(scl)
+    for k, v in enumerate(dims):
+        a.dims[k] = int(v)
+    ins = [None if x is None else _c128(x).reshape(-1) for x in operands] + [None] * (4 - len(operands))
+    nc = max(int(ncopies), 0)
+    try:
+        foot = batch_block_footprint(op, list(dims) + [0] * 8)
+    except (OverflowError, MemoryError):
+        foot = dict(out0=0, out1=0, info=1)
+    if nc > 16 or min([int(v) for v in dims] or [0]) < 1 or max(foot.values()) > 1 << 24:
+        foot = dict(out0=0, out1=0, info=1)  # refused below by the library, which is what decides: nothing to allocate
+    out0 = np.zeros((nc, foot["out0"]), np.complex128)
+    out1 = np.zeros((nc, foot["out1"]), np.complex128)
+    info = np.zeros((nc, foot["info"]))
+    args = []
+    for x in ins:
+        args += [None, 0] if x is None else [_dp(x), x.size]
+    _lib.check(_lib.load().mitdvp_batch_block(device, C.byref(a), *args, _dp(out0), out0.size, _dp(out1), out1.size, _dp(info), info.size))
+    return out0, out1, info
+
+
 def thin_to_full(site, gauge: str, delta_rank: int, device=0) -> np.ndarray:
     """``SiteCoef.thin_to_full``: widen an "A" (or "B") isometry by ``delta_rank``
     orthonormal columns (rows) of its orthogonal complement (capped at its dimension)."""

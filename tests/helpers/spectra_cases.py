@@ -13,7 +13,7 @@ from . import jump_oracle as jo
 from . import pair_cases as pc
 
 HEAD = 4  # W, S1, S2, pmin in front of a bond's weights
-TOL2, TINY, MAX_SWEEPS = 1.6e-29, 1e-28, 30  # BP_TOL2, BP_TINY, BATCH_PAIR_MAX_SWEEPS of batch_site
+TOL2, FREEZE, MAX_SWEEPS = 1.6e-29, 1e-32, 64  # BP_TOL2, BP_FREEZE, BATCH_PAIR_MAX_SWEEPS of batch_site
 
 # the smallest shapes at which each part of the kernel can go wrong (tests/test_gpu_batch_spectra.py names why)
 SHAPES = {"mixed": ((2, 3, 2, 4, 2), 6), "odd": ((3,) * 5, 7), "wide": ((2,) * 12, 40)}
@@ -24,7 +24,7 @@ def jacobi_rows(R):
     of the pairs changes the unitary that is left on R, not the row norms).  Returns (rotated R, converged)."""
     R = np.array(R, dtype=np.complex128)
     m = R.shape[0]
-    tiny = TINY * np.sum(np.abs(R) ** 2)
+    tiny = FREEZE * np.sum(np.abs(R) ** 2)
     for _ in range(MAX_SWEEPS):
         any_rot = False
         for i in range(m - 1):
