@@ -925,6 +925,95 @@ typedef struct mitdvp_batch_block_args {
 int mitdvp_batch_block(int device, const mitdvp_batch_block_args* a, const double* in0, size_t n0, const double* in1, size_t n1,
                        const double* in2, size_t n2, const double* in3, size_t n3, double* out0, size_t nout0, double* out1,
                        size_t nout1, double* info, size_t ninfo);
+/* One call of ONE host wrapper of csrc/vecops.h -- the Krylov vector algebra, the leg shuffles, the block lists of the
+ * K_eff apply, the norm profiles and the identity tests -- on a stream of its own, exactly as the engine calls it (the
+ * wrapper's grid choice included).  All tensors row-major, complex128 as (re, im).  Buffers: z0 z1 z2 complex inputs, r0 a
+ * real input, idx an int array, mask 64 bits; zo0 zo1 complex and ro real RESULTS, which are in-out: the caller's contents
+ * go to the device first and the whole buffer comes back, so what lies between the written elements must be as it was.
+ * P = 256 partial sums (NPART); "v & 1": bit 0 of variant.
+ *   op                   dims; strides          buffers and what is computed
+ *   DOT                  n                      zo0[P] = partials of sum conj(z0) z1 (variant 1) or sum z0 z1 (variant 0)
+ *   SUMSQ                n                      ro[P] = partials of sum |z0|^2
+ *   LANCZOS_UPDATE       n                      zo0 = v -= alpha z0 (+ beta z1 if v & 1); alpha = sum z2[P], beta =
+ *                                               sqrt(sum r0[P]); ro[P] = partials of |v|^2
+ *   LANCZOS_UPDATE_DEF   n, l                   zo0 = H u_l -> u_(l+1), z0 = u_l, z1 = u_(l-1) (if v & 1), z2[P] = partials
+ *                                               of the raw dot, r0[l][P] = nrm_all, orthodox = v & 2, eps; ro[P]
+ *   LANCZOS_STEP_SMALL   n <= 16384             zo0 = w, z0 = vl, z1 = x (if v & 2; else x is vl itself), z2 = vm2 and r0[P]
+ *                                               = betaprev (if v & 1), eps; zo1[P] = alpha, ro[P] = |w|^2, each [0] = value
+ *   SCALE_INV_NORM       n                      zo0 /= sqrt(sum r0[P]) unless that is below eps
+ *   MULTI_DOT            n, k; ldv              zo0[k][P] = partials of <z0_j | z1>, z0 = V (k rows, ldv apart)
+ *   ARNOLDI_UPDATE       n, k; ldv              zo0 = v -= sum_j h_j V_j, z0 = V, z1[k][P] = partials of h; ro[P]
+ *   LINCOMB              n, k; ldv              zo0 = sum_j coef_j V_j (if v & 1), ro[P] = partials of its norm (if v & 2)
+ *   AXPBY                n                      zo0 = a z0 + b zo0
+ *   SCALE                n                      zo0 *= a
+ *   TRANSPOSE            rows, cols, batch;     zo0_b[c][r] = z0_b[r][c]; batches in_bs / out_bs apart, apart or interleaved
+ *                        ldi, ldo, in_bs, out_bs
+ *   TRANSPOSE_REV3       na, nj, ns             zo0[s][j][a] = z0[a][j][s]
+ *   PERMUTE_0213         n0, n1, n2, n3         zo0[i0][i2][i1][i3] = z0[i0][i1][i2][i3]
+ *   PERMUTE5             d0 .. d4; s0 .. s4     zo0 (C order) = z0 gathered with the strides; v & 1: idx = map2 replaces i2
+ *   PHYS_DIAG            dl, n, dr              zo0[b][c][e] = z0[b][c n + c][e]; variant 1: the trace over c
+ *   COPY2D               rows, cols, zero_to;   zo0[r][c] = a z0[r][c] (+ zo0[r][c] if v & 1), columns cols .. zero_to - 1
+ *                        ldd, lds               zeroed
+ *   COPY_RAW             n                      zo0 = z0
+ *   IDENTITY             rows, cols; ld         zo0 = the rows x cols identity
+ *   SCALE_COLS           rows, cols; ld         zo0[r][c] *= r0[c]
+ *   GATHER_BLOCKS        rows, cols, nbl,       zo0[a][k][:] = z0[a][idx[k]][:], k < nbl <= 64
+ *                        n_dst, m_src
+ *   FILL_SCALED_BLOCKS   rows, cols, nbl, pos0; zo0[a][pos0 + k][:] = f[k] z0[a][:]
+ *                        ldx
+ *   ACCUM_SCALED_BLOCKS  rows, cols, nbl; ldx   zo0[a][:] += sum_k f[k] z0[a][idx[k]][:] + both z1[a][:]
+ *   COL_SUMSQ            rows, cols             ro[c] = sum_r |z0[r][c]|^2
+ *   ROW_SUMSQ            rows, cols             ro[r] = sum_c |z0[r][c]|^2
+ *   SHELL_SUMSQ          n                      ro[t] = sum over max(i, j) = t of |z0[i][j]|^2
+ *   IDENT_DEV            n; ld                  ro[0] = max |z0 - 1|, 1e308 if an element is not finite
+ *   IDENT_DEV_MULTI      n, nblk; ld, blk_stride  ro[c] = max |block c - lam 1|, zo1[c] = lam, blocks of mask only;
+ *                                               variant 1 = clear, variant 0 = the maximum with what ro held
+ * Left out: fold_env_core, gram_env_core, gram_mirror_lower and strassen_* (tested with their own files), kry_diff (needs
+ * the device Krylov state), vec_randn, the clock and CU probes.
+ * Before any HIP call MITDVP_EINVAL is returned for an unknown op or variant, a negative dimension or stride, a buffer
+ * shorter than the footprint (csrc/vecop_check.h), a source that overlaps a result, k > 21, n > 16384 for the one-workgroup
+ * step, batch > 65535 for the transposes, more than 64 blocks, or more than 128 MB in all.  A zero-size call returns
+ * MITDVP_OK with the results untouched (k = 0 is zero-size for MULTI_DOT only: ARNOLDI_UPDATE still writes v and its norm,
+ * LINCOMB zeros).  After any other error code the contents of the results are undefined. */
+#define MITDVP_VECOP_DOT 0
+#define MITDVP_VECOP_SUMSQ 1
+#define MITDVP_VECOP_LANCZOS_UPDATE 2
+#define MITDVP_VECOP_LANCZOS_UPDATE_DEF 3
+#define MITDVP_VECOP_LANCZOS_STEP_SMALL 4
+#define MITDVP_VECOP_SCALE_INV_NORM 5
+#define MITDVP_VECOP_MULTI_DOT 6
+#define MITDVP_VECOP_ARNOLDI_UPDATE 7
+#define MITDVP_VECOP_LINCOMB 8
+#define MITDVP_VECOP_AXPBY 9
+#define MITDVP_VECOP_SCALE 10
+#define MITDVP_VECOP_TRANSPOSE 11
+#define MITDVP_VECOP_TRANSPOSE_REV3 12
+#define MITDVP_VECOP_PERMUTE_0213 13
+#define MITDVP_VECOP_PERMUTE5 14
+#define MITDVP_VECOP_PHYS_DIAG 15
+#define MITDVP_VECOP_COPY2D 16
+#define MITDVP_VECOP_COPY_RAW 17
+#define MITDVP_VECOP_IDENTITY 18
+#define MITDVP_VECOP_SCALE_COLS 19
+#define MITDVP_VECOP_GATHER_BLOCKS 20
+#define MITDVP_VECOP_FILL_SCALED_BLOCKS 21
+#define MITDVP_VECOP_ACCUM_SCALED_BLOCKS 22
+#define MITDVP_VECOP_COL_SUMSQ 23
+#define MITDVP_VECOP_ROW_SUMSQ 24
+#define MITDVP_VECOP_SHELL_SUMSQ 25
+#define MITDVP_VECOP_IDENT_DEV 26
+#define MITDVP_VECOP_IDENT_DEV_MULTI 27
+typedef struct mitdvp_vecop_args {
+  int op, variant;
+  long dims[5];
+  long strides[5];
+  double a[2], b[2], both[2], eps; /* complex scalars as (re, im) */
+  double coef[42];                 /* LINCOMB: 21 complex coefficients */
+  double f[128];                   /* block lists: 64 complex factors */
+} mitdvp_vecop_args;
+int mitdvp_vecop(int device, const mitdvp_vecop_args* a, const double* z0, size_t nz0, const double* z1, size_t nz1,
+                 const double* z2, size_t nz2, const double* r0, size_t nr0, const int* idx, size_t nidx,
+                 unsigned long long mask, double* zo0, size_t nzo0, double* zo1, size_t nzo1, double* ro, size_t nro);
 /* Complex-product form of the MFMA zgemm kernel for everything that follows:
  * 0 = "4M" (textbook, 4 real MFMA products), 1 = "3M" (Karatsuba, 3 products,
  * normwise stable); the library default is 1 unless MITDVP_ZGEMM=4m is set. */

@@ -126,6 +126,20 @@ class BatchBlockArgs(C.Structure):
 
 BLOCK_MATMUL, BLOCK_HEFF, BLOCK_KEFF, BLOCK_ENV, BLOCK_OVERLAP, BLOCK_QR, BLOCK_SPLIT = range(7)
 
+class VecopArgs(C.Structure):
+    """mitdvp_vecop_args: one call of one host wrapper of csrc/vecops.h, run by mitdvp_vecop"""
+
+    _fields_ = [("op", C.c_int), ("variant", C.c_int), ("dims", C.c_long * 5), ("strides", C.c_long * 5),
+                ("a", C.c_double * 2), ("b", C.c_double * 2), ("both", C.c_double * 2), ("eps", C.c_double),
+                ("coef", C.c_double * 42), ("f", C.c_double * 128)]
+
+
+# MITDVP_VECOP_*: the op table is the comment in include/mitdvp.h
+VECOP_NAMES = ("dot", "sumsq", "lanczos_update", "lanczos_update_def", "lanczos_step_small", "scale_inv_norm", "multi_dot",
+               "arnoldi_update", "lincomb", "axpby", "scale", "transpose", "transpose_rev3", "permute_0213", "permute5",
+               "phys_diag", "copy2d", "copy_raw", "identity", "scale_cols", "gather_blocks", "fill_scaled_blocks",
+               "accum_scaled_blocks", "col_sumsq", "row_sumsq", "shell_sumsq", "ident_dev", "ident_dev_multi")
+
 OBS_NORM, OBS_AUTOCORR, OBS_ENERGY, OBS_RDM = 1, 2, 4, 8
 CHANNEL_GATE, CHANNEL_JUMP = 1, 2
 MAX_JUMP = 16  # operators of one jump channel (BATCH_MAX_JUMP)
@@ -243,6 +257,8 @@ def load() -> C.CDLL:
         "mitdvp_zgemm_reduce": (i, [i, C.POINTER(ZgemmReduceArgs), dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, ip]),
         "mitdvp_batch_block": (i, [i, C.POINTER(BatchBlockArgs), dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t,
                                    dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t]),
+        "mitdvp_vecop": (i, [i, C.POINTER(VecopArgs), dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, ip, C.c_size_t,
+                             C.c_ulonglong, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t]),
         "mitdvp_bench_heff": (i, [i, i, i, i, i, i, i, i, dp]),
         "mitdvp_heff_selfcheck": (i, [i, i, i, i, i, i, dp]),
         "mitdvp_set_gemm_mode": (i, [i]),

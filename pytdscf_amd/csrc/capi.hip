@@ -7,6 +7,7 @@
 #include "engine_batch.h"
 #include "engine_internal.h"
 #include "engine_krylov.inc"
+#include "vecop_check.h"
 #include "zgemm_args_check.h"
 #include "zgemm_reduce_args_check.h"
 
@@ -914,6 +915,109 @@ int mitdvp_batch_block(int device, const mitdvp_batch_block_args* a, const doubl
       to_host(st, out0, dout0.p(), nc * f.out0);
     }
     HIP_CHECK(hipStreamDestroy(st));
+  });
+}
+
+// one call of one host wrapper of vecops.h on a stream of its own, on the caller's whole buffers (the results are in-out:
+// up first, the whole buffer back); vecop_check.h refuses, before any HIP call, whatever would leave a buffer
+int mitdvp_vecop(int device, const mitdvp_vecop_args* a, const double* z0, size_t nz0, const double* z1, size_t nz1,
+                 const double* z2, size_t nz2, const double* r0, size_t nr0, const int* idx, size_t nidx,
+                 unsigned long long mask, double* zo0, size_t nzo0, double* zo1, size_t nzo1, double* ro, size_t nro) {
+  return guard(nullptr, [&] {
+    using namespace mitdvp;
+    static_assert(VECOP_NPART == NPART && VECOP_MAXK == MAXK && VECOP_SMALL_VEC_N == SMALL_VEC_N, "vecop_check.h repeats vecops.h");
+    static_assert(VECOP_MAX_BLOCKS == sizeof(BlockList::idx) / sizeof(int), "vecop_check.h repeats BlockList");
+    const void* const zin[3] = {z0, z1, z2};
+    const size_t nzin[3] = {nz0, nz1, nz2};
+    const void* const zio[2] = {zo0, zo1};
+    const size_t nzio[2] = {nzo0, nzo1};
+    VecopFoot f;
+    if (const char* bad = vecop_check(a, zin, nzin, r0, nr0, idx, nidx, zio, nzio, ro, nro, &f)) throw ArgError(bad);
+    if (f.empty && !f.own_return) return;  // nothing to do: the results stay as they are, no device is touched
+    HIP_CHECK(hipSetDevice(device));
+    struct Stream {  // destroyed also when a wrapper or a HIP call throws
+      hipStream_t s = nullptr;
+      Stream() { HIP_CHECK(hipStreamCreate(&s)); }
+      ~Stream() { (void)hipStreamDestroy(s); }
+    } stream;
+    hipStream_t st = stream.s;
+    {
+      // a buffer the op does not take is not passed on: the wrapper gets a null pointer, as from the engine
+      Dev d0(st, z0, f.zin[0] ? nz0 : 0), d1(st, z1, f.zin[1] ? nz1 : 0), d2(st, z2, f.zin[2] ? nz2 : 0);
+      Dev dr(f.rin ? (nr0 + 1) / 2 : 0), di(f.idx ? (nidx + 3) / 4 : 0);
+      Dev o0(st, zo0, f.zio[0] ? nzo0 : 0), o1(st, zo1, f.zio[1] ? nzo1 : 0), dro(f.rio ? (nro + 1) / 2 : 0);
+      if (f.rin) HIP_CHECK(hipMemcpyAsync(dr.p(), r0, nr0 * sizeof(double), hipMemcpyHostToDevice, st));
+      if (f.idx) HIP_CHECK(hipMemcpyAsync(di.p(), idx, nidx * sizeof(int), hipMemcpyHostToDevice, st));
+      if (f.rio) HIP_CHECK(hipMemcpyAsync(dro.p(), ro, nro * sizeof(double), hipMemcpyHostToDevice, st));
+      const zc* x0 = f.zin[0] ? d0.p() : nullptr;
+      const zc* x1 = f.zin[1] ? d1.p() : nullptr;
+      const zc* x2 = f.zin[2] ? d2.p() : nullptr;
+      const double* xr = f.rin ? reinterpret_cast<const double*>(dr.p()) : nullptr;
+      const int* xi = f.idx ? reinterpret_cast<const int*>(di.p()) : nullptr;
+      zc* y0 = f.zio[0] ? o0.p() : nullptr;
+      zc* y1 = f.zio[1] ? o1.p() : nullptr;
+      double* yr = f.rio ? reinterpret_cast<double*>(dro.p()) : nullptr;
+      const long* d = a->dims;
+      const long* s = a->strides;
+      const int v = a->variant;
+      BlockList bl{};
+      switch (a->op) {
+        case MITDVP_VECOP_DOT: vec_dot(st, x0, x1, d[0], v != 0, y0); break;
+        case MITDVP_VECOP_SUMSQ: vec_sumsq(st, x0, d[0], yr); break;
+        case MITDVP_VECOP_LANCZOS_UPDATE: vec_lanczos_update(st, y0, x0, x1, d[0], x2, xr, yr); break;
+        case MITDVP_VECOP_LANCZOS_UPDATE_DEF:
+          vec_lanczos_update_deferred(st, y0, x0, x1, d[0], x2, xr, (int)d[1], (v & 2) != 0, a->eps, yr);
+          break;
+        case MITDVP_VECOP_LANCZOS_STEP_SMALL: vec_lanczos_step_small(st, y0, (v & 2) ? x1 : x0, x0, x2, d[0], y1, xr, yr, a->eps); break;
+        case MITDVP_VECOP_SCALE_INV_NORM: vec_scale_inv_norm(st, y0, d[0], xr, a->eps); break;
+        case MITDVP_VECOP_MULTI_DOT: vec_multi_dot(st, x0, s[0], (int)d[1], x1, d[0], y0); break;
+        case MITDVP_VECOP_ARNOLDI_UPDATE: vec_arnoldi_update(st, y0, x0, s[0], (int)d[1], d[0], x1, yr); break;
+        case MITDVP_VECOP_LINCOMB: {
+          Coefs c{};
+          for (int j = 0; j < MAXK; ++j) c.c[j] = make_double2(a->coef[2 * j], a->coef[2 * j + 1]);
+          vec_lincomb(st, y0, x0, s[0], (int)d[1], c, d[0], yr);
+          break;
+        }
+        case MITDVP_VECOP_AXPBY: vec_axpby(st, y0, x0, d[0], make_double2(a->a[0], a->a[1]), make_double2(a->b[0], a->b[1])); break;
+        case MITDVP_VECOP_SCALE: vec_scale(st, y0, d[0], make_double2(a->a[0], a->a[1])); break;
+        case MITDVP_VECOP_TRANSPOSE: transpose_batched(st, x0, y0, (int)d[0], (int)d[1], s[0], s[1], (int)d[2], s[2], s[3]); break;
+        case MITDVP_VECOP_TRANSPOSE_REV3: transpose_rev3(st, x0, y0, (int)d[0], (int)d[1], (int)d[2]); break;
+        case MITDVP_VECOP_PERMUTE_0213: permute_0213(st, x0, y0, d[0], (int)d[1], (int)d[2], (int)d[3]); break;
+        case MITDVP_VECOP_PERMUTE5: {
+          const int dims[5] = {(int)d[0], (int)d[1], (int)d[2], (int)d[3], (int)d[4]};
+          permute5(st, x0, y0, dims, s, (v & 1) ? xi : nullptr);
+          break;
+        }
+        case MITDVP_VECOP_PHYS_DIAG: phys_diag(st, x0, y0, (int)d[0], (int)d[1], (int)d[2], (v & 1) != 0); break;
+        case MITDVP_VECOP_COPY2D:
+          copy2d(st, y0, s[0], x0, s[1], d[0], (int)d[1], (int)d[2], make_double2(a->a[0], a->a[1]), (v & 1) != 0);
+          break;
+        case MITDVP_VECOP_COPY_RAW: vec_copy_raw(st, y0, x0, (size_t)d[0]); break;
+        case MITDVP_VECOP_IDENTITY: set_identity(st, y0, (int)d[0], (int)d[1], s[0]); break;
+        case MITDVP_VECOP_SCALE_COLS: scale_cols(st, y0, d[0], (int)d[1], s[0], xr); break;
+        case MITDVP_VECOP_GATHER_BLOCKS:
+        case MITDVP_VECOP_FILL_SCALED_BLOCKS:
+        case MITDVP_VECOP_ACCUM_SCALED_BLOCKS:
+          bl.n = (int)d[2];
+          for (int k = 0; k < bl.n; ++k) {
+            bl.idx[k] = f.idx ? idx[k] : 0;
+            bl.f[k] = make_double2(a->f[2 * k], a->f[2 * k + 1]);
+          }
+          if (a->op == MITDVP_VECOP_GATHER_BLOCKS) gather_blocks(st, y0, (int)d[3], x0, (int)d[4], d[0], (int)d[1], bl);
+          else if (a->op == MITDVP_VECOP_FILL_SCALED_BLOCKS) fill_scaled_blocks(st, y0, s[0], (int)d[3], x0, d[0], (int)d[1], bl);
+          else accum_scaled_blocks(st, y0, x0, s[0], x1, d[0], (int)d[1], bl, make_double2(a->both[0], a->both[1]));
+          break;
+        case MITDVP_VECOP_COL_SUMSQ: col_sumsq(st, x0, d[0], (int)d[1], yr); break;
+        case MITDVP_VECOP_ROW_SUMSQ: row_sumsq(st, x0, (int)d[0], d[1], yr); break;
+        case MITDVP_VECOP_SHELL_SUMSQ: shell_sumsq(st, x0, (int)d[0], yr); break;
+        case MITDVP_VECOP_IDENT_DEV: ident_deviation(st, x0, s[0], (int)d[0], yr); break;
+        default: ident_deviation_multi(st, x0, (int)d[1], s[1], s[0], (int)d[0], yr, y1, mask, (v & 1) != 0); break;
+      }
+      if (f.rio) HIP_CHECK(hipMemcpyAsync(ro, dro.p(), nro * sizeof(double), hipMemcpyDeviceToHost, st));
+      if (f.zio[1]) HIP_CHECK(hipMemcpyAsync(zo1, o1.p(), nzo1 * sizeof(zc), hipMemcpyDeviceToHost, st));
+      if (f.zio[0]) HIP_CHECK(hipMemcpyAsync(zo0, o0.p(), nzo0 * sizeof(zc), hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+    }
   });
 }
 

@@ -791,6 +791,7 @@ void transpose_batched(hipStream_t st, const zc* in, zc* out, int rows, int cols
 
 void phys_diag(hipStream_t st, const zc* C, zc* out, int dl, int n, int dr, bool trace) {
   const long tot = trace ? (long)dl * dr : (long)dl * n * dr;
+  if (tot <= 0) return;
   LAUNCH(k_phys_diag, (int)std::min<long>(4096, (tot + 255) / 256), st, C, out, dl, n, dr, trace ? 1 : 0);
 }
 

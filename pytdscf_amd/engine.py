@@ -805,6 +805,50 @@ def batch_block(op: str, dims, *operands, ncopies=1, variant=0, scl=1.0, device=
     return out0, out1, info
 
 
+VECOP_OPS = {name: k for k, name in enumerate(_lib.VECOP_NAMES)}
+
+
+def vecop(op: str, dims, strides=(), *, variant=0, z=(), r=None, idx=None, mask=(1 << 64) - 1, zo=(), ro=None, a=1.0, b=0.0,
+          both=0.0, eps=0.0, coef=(), f=(), device=0):
+    """One call of one host wrapper of csrc/vecops.h on a stream of its own (``mitdvp_vecop``; include/mitdvp.h has the ops,
+    their dims, strides, variants and buffers).  ``z``: up to three complex inputs, ``r`` a real input, ``idx`` an int array,
+    ``zo``: up to two complex results and ``ro`` a real result, all flat and whole; ``None`` for a buffer the op does not
+    take.  The results are in-out: returns ``(zo0, zo1, ro)``, copies of the caller's buffers as the device left them
+    (``None`` where none was given).  A descriptor that leaves a buffer raises ValueError before the GPU is touched."""
+    if op not in VECOP_OPS:
+        raise ValueError(f"vecop: unknown op {op!r}")
+    if len(dims) > 5 or len(strides) > 5 or len(z) > 3 or len(zo) > 2 or len(coef) > 21 or len(f) > 64:
+        raise TypeError("vecop: at most five dims and strides, three inputs, two results, 21 coefficients and 64 factors")
+    g = _lib.VecopArgs()
+    g.op, g.variant, g.eps = VECOP_OPS[op], int(variant), float(eps)
+    for k, v in enumerate(dims):
+        g.dims[k] = int(v)
+    for k, v in enumerate(strides):
+        g.strides[k] = int(v)
+    for name, val in (("a", a), ("b", b), ("both", both)):
+        getattr(g, name)[0], getattr(g, name)[1] = complex(val).real, complex(val).imag
+    for k, v in enumerate(coef):
+        g.coef[2 * k], g.coef[2 * k + 1] = complex(v).real, complex(v).imag
+    for k, v in enumerate(f):
+        g.f[2 * k], g.f[2 * k + 1] = complex(v).real, complex(v).imag
+    zin = [None if x is None else _c128(x).reshape(-1) for x in z] + [None] * (3 - len(z))
+    zout = [None if x is None else _c128(x).reshape(-1).copy() for x in zo] + [None] * (2 - len(zo))
+    rin = None if r is None else np.ascontiguousarray(r, dtype=np.float64).reshape(-1)
+    rout = None if ro is None else np.array(ro, dtype=np.float64).reshape(-1)
+    ind = None if idx is None else np.ascontiguousarray(idx, dtype=np.intc).reshape(-1)
+    args = []
+    for x in zin:
+        args += [None, 0] if x is None else [_dp(x), x.size]
+    args += [None, 0] if rin is None else [_dp(rin), rin.size]
+    args += [None, 0] if ind is None else [ind.ctypes.data_as(C.POINTER(C.c_int)), ind.size]
+    args.append(int(mask) & ((1 << 64) - 1))
+    for x in zout:
+        args += [None, 0] if x is None else [_dp(x), x.size]
+    args += [None, 0] if rout is None else [_dp(rout), rout.size]
+    _lib.check(_lib.load().mitdvp_vecop(device, C.byref(g), *args))
+    return zout[0], zout[1], rout
+
+
 def thin_to_full(site, gauge: str, delta_rank: int, device=0) -> np.ndarray:
     """``SiteCoef.thin_to_full``: widen an "A" (or "B") isometry by ``delta_rank``
     orthonormal columns (rows) of its orthogonal complement (capped at its dimension)."""
