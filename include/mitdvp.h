@@ -129,7 +129,8 @@ int mitdvp_ensemble_step(mitdvp_engine** hs, int n, double dt_au, int nsteps, in
  * per-replica Hamiltonians work -- which the batch borrows; it owns the pointer tables, status words and scratch only, and
  * must be destroyed before the engines.  mitdvp_batch_create returns MITDVP_EINVAL (message: mitdvp_last_error(NULL)) and
  * leaves every engine untouched unless: all handles are distinct and on one device, none is confined to a compute-unit
- * range (cu_count == 0), each is a single electronic state, none is adaptive, a segment or bond-sharded, relax is 0 or 1,
+ * range (cu_count == 0), each is a single electronic state, none is adaptive, a segment or bond-sharded, relax is 0, 1
+ * or 2 (with 2, improved relaxation, max_diag_krylov -- 0 means 64 -- is in 2 .. 64 and identical across the replicas),
  * no gates or Kraus maps are set, site and MPO shapes are identical across the replicas at every site, integrator,
  * lanczos_variant, conserve_norm, thresh, max_krylov and relax are identical, and the shapes are inside the kernel's
  * envelope: dl*d*dr <= 8192 per site (d = 4, D = 32 is 4096), MPO bonds <= 16, bonds <= 64, dl*d >= dr and d*dr >= dl; the
@@ -464,6 +465,22 @@ int mitdvp_batch_cross_mpo_records(mitdvp_batch* b, const double* weights, doubl
  * names both figures and the largest number of replicas that fits. */
 int mitdvp_batch_operate(mitdvp_batch* b, int op_id, int maxstep, double conv_tol, const int* replicas, int nsel, double* norms,
                          int* iters, int* statuses);
+/* Ground states of a batch by improved relaxation (k_batch_relax: one workgroup per replica; at every site the lowest
+ * eigenvector of H_eff + shift by Lanczos with the projected tridiagonal problem solved on the device, then the gauge move,
+ * the block update and the absorb; no bond step).  Replicas created with relax = 2 take mitdvp_batch_step / _sweep / _run /
+ * _run_keys like any others: a half-sweep is one launch, dt_au is ignored, a replica whose local solve does not converge in
+ * max_diag_krylov vectors gets MITDVP_ENOTCONV ("Lanczos Diagonalization is not converged in N basis") and stops, the others
+ * finish.  mitdvp_batch_relax runs up to maxstep steps (forward + backward half-sweep) of every replica in ONE launch and one
+ * host wait; the right blocks are built first where no step has built them.  E_n, a replica's energy after step n, is the
+ * lowest Ritz value of its last local solve (site 0; the scalar term included).  With conv_tol > 0 a replica stops on its
+ * own once |E_n - E_{n-1}| <= conv_tol, the others go on; conv_tol = 0 runs maxstep steps.  energies [n]: the last E_n;
+ * steps [n]: the steps run; history [n][maxstep]: E_1 .. E_n of each replica, NaN behind its stop; statuses [n]; each of
+ * the four may be NULL.  Afterwards every engine is an ordinary consistent engine, centre at site 0.  The jump generator's
+ * step counter, channels, the snapshot, every request and the records of the last run are untouched.
+ * Refused with MITDVP_EINVAL before the GPU is touched, everything left as it was, the message naming the entry point and
+ * the limit: maxstep outside 1 .. 2^20; conv_tol negative or not finite; replicas whose relax is not 2; a replica whose
+ * centre is not at site 0. */
+int mitdvp_batch_relax(mitdvp_batch* b, int maxstep, double conv_tol, double* energies, int* steps, double* history, int* statuses);
 /* propagate_along_sweep (_mps_cls.py:798-1014), one direction only. */
 int mitdvp_sweep(mitdvp_engine* h, double dt_au, int forward);
 /* The same half-sweep in parts: the next `nsites` local updates of the half-sweep in progress (one is started when none
@@ -922,6 +939,12 @@ typedef struct mitdvp_batch_block_args {
   int ncopies;
   double scl; /* HEFF, KEFF: the factor on the vector */
 } mitdvp_batch_block_args;
+/* Test hook: the projected eigen-solve of k_batch_relax alone (the same device function, one workgroup of one wave per
+ * case): the lowest eigenpair of ncases real symmetric tridiagonal matrices.  Case q has order k[q] in 1 .. 64, diagonal
+ * alpha[64 q .. 64 q + k) and off-diagonal beta[64 q .. 64 q + k - 1); the rest of a row is not read.  theta[q]: the lowest
+ * eigenvalue; vec[64 q ..): its unit eigenvector, first component non-negative, zeros behind k.  MITDVP_EINVAL before the
+ * GPU is touched for ncases outside 1 .. 65536, a NULL pointer, or a k outside 1 .. 64 (the message names the case). */
+int mitdvp_batch_trilow(int device, const double* alpha, const double* beta, const int* k, int ncases, double* theta, double* vec);
 int mitdvp_batch_block(int device, const mitdvp_batch_block_args* a, const double* in0, size_t n0, const double* in1, size_t n1,
                        const double* in2, size_t n2, const double* in3, size_t n3, double* out0, size_t nout0, double* out1,
                        size_t nout1, double* info, size_t ninfo);

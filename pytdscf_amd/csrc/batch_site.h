@@ -6,6 +6,7 @@
 #include "batch_block_check.h"
 #include "batch_cross_mpo_plan.h"
 #include "batch_operate_plan.h"
+#include "batch_relax_plan.h"
 #include "batch_shape.h"
 #include "common.h"
 #include "small_site.h"
@@ -28,8 +29,10 @@ struct BatchPlan {
   // per-replica scratch carve, offsets in complex elements
   size_t o_sig = 0, o_spare = 0, o_work = 0, o_x = 0, o_y = 0, o_u = 0, total = 0;
 };
-// false + a message naming the offending site and the limit when the chain is outside the envelope
-bool batch_plan(const BatchShape* shp, int L, BatchPlan& plan, std::string& why);
+// false + a message naming the offending site and the limit when the chain is outside the envelope.  relax /
+// max_diag_krylov size the Krylov-basis carve (batch_krylov_carve, batch_relax_plan.h): for relax 0 or 1 the plan does not
+// depend on them.
+bool batch_plan(const BatchShape* shp, int L, BatchPlan& plan, std::string& why, int relax = 0, int max_diag_krylov = 0);
 
 struct BatchArgs {
   int L, forward;
@@ -50,6 +53,35 @@ struct BatchArgs {
 
 // one launch: grid = nrep workgroups, a half-sweep of every replica
 void batch_sweep_launch(hipStream_t st, const BatchArgs& a, int nrep);
+
+// ---- improved relaxation (k_batch_relax) ----
+// nhalf half-sweeps of every replica in one launch, the first in direction `forward`, the directions alternating: at every
+// site the lowest eigenvector of H_eff + shift by Lanczos (bt_diag; Engine::krylov_diag), then the gauge move, the block
+// update and the absorb of k_batch_sweep -- the bond matrix is left alone.  After every backward half-sweep that follows a
+// forward one (a full step) the Ritz value of the solve at site 0 is the replica's energy E_n; with conv_tol > 0 a replica
+// stops once |E_n - E_{n-1}| <= conv_tol, the others go on.
+struct BatchRelaxArgs {
+  int L, forward, nhalf;
+  int kcap;                 // max_diag_krylov, 2 .. BATCH_RELAX_MAX_KRYLOV; a solve at a site of N elements takes min(N, kcap)
+  double thresh, conv_tol;  // of the local solve (coefficient space); of the energy, 0: never stop early
+  const BatchShape* shp;    // [L], device
+  void* const* ptrs;        // the pointer table of BatchArgs
+  int ptr_stride;
+  const zc* shift;          // [B]
+  int* kprev;               // [B * L]: the Krylov dimension of the last solve at every site
+  int* status;              // [B]: SS_ENOTCONV when a solve did not converge in min(N, kcap) vectors
+  long long* stats;         // [B * 4] as BatchArgs: [0] applies, [2] their flops
+  BatchPlan plan;           // sized with relax = 2
+  double* energy;           // [B]: the last E_n; null (with steps and history): not recorded
+  int* steps;               // [B]: full steps run
+  double* history;          // [B][hist_len]: E_1 .. E_n, the rest is left as the host set it (NaN)
+  int hist_len;
+};
+void batch_relax_launch(hipStream_t st, const BatchRelaxArgs& a, int nrep);
+// test hook (k_batch_trilow): the eigen-solve of bt_diag alone, one workgroup of one wave per case.  alpha / beta:
+// [ncases][64] diagonal and off-diagonal, k: [ncases] in 1 .. 64; theta: [ncases] the lowest eigenvalue, vec: [ncases][64]
+// its unit eigenvector with a non-negative first component, zeros behind k.  All device pointers.
+void batch_trilow_launch(hipStream_t st, const double* alpha, const double* beta, const int* k, int ncases, double* theta, double* vec);
 
 // ---- one-site channels between the half-sweeps (k_batch_channel) ----
 constexpr int BATCH_MAX_JUMP = 16;  // operators of one jump channel

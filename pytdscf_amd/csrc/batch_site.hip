@@ -6,7 +6,8 @@
 // workgroup per pair; k_batch_spectra, the Schmidt spectra of the requested bonds; k_batch_sample, configurations drawn
 // from every replica's state, one workgroup per replica; k_batch_expect, expectation values of MPO observables, one
 // workgroup per replica and operator; k_batch_cross_mpo, matrix elements of MPOs between two replicas or snapshots, one
-// workgroup per entry.)
+// workgroup per entry; k_batch_operate, an MPO applied to the replicas; k_batch_relax, right behind k_batch_sweep, the same
+// sweep with the lowest eigenvector of H_eff in place of the exponential: improved relaxation.)
 //
 // At trajectory shapes (d = 2..4, D <= 32, M <= 16) a local problem is a few tens of kilobytes, so one workgroup can own
 // one replica completely: the replica index is blockIdx.x, nothing is exchanged between workgroups, and therefore there is
@@ -683,6 +684,391 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_sweep(BatchArgs g) {
     }
   }
   if (rc != SS_OK && tid == 0) g.status[r] = rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Improved relaxation: k_batch_relax, ONE workgroup per replica as above, any number of half-sweeps per launch.  At every
+// site the centre tensor is replaced by the lowest eigenvector of H_eff + shift (bt_diag: matrix_diagonalize_lanczos,
+// _integrator.py:74-138, as Engine::krylov_diag restates it); the gauge move, the block update and the absorb are those of
+// k_batch_sweep, and the bond matrix is left alone (_mps_cls.py:1159-1160).
+// What is resident where: LDS holds the two operand tiles of wg_gemm, the reduction partials, the Householder scalars of
+// a gauge move and the scalars of the eigen-solve -- alpha, beta, the Ritz coefficients c and c_prev and the two pivot
+// sequences of the twisted factorisation, 64 doubles each (23 120 bytes in all).  The Lanczos basis, up to
+// min(N, kcap) + 1 NORMALISED vectors, lives in the replica's Krylov carve (BatchPlan::o_u, sized by batch_krylov_carve),
+// written and re-read by this workgroup only.
+// The projected problem: after every new vector wave 0 finds the lowest eigenpair of T_k (bt_trilow), the other seven
+// waves wait at the barrier that publishes the result.  Every loop is bounded: the Lanczos loop by kcap <= 64, the
+// multisection by BT_TRI_ROUNDS, the rest by k.
+
+struct BrSh {  // the eigen-solve's own LDS, 64 doubles each
+  double *alpha, *beta, *c, *cprev, *dp, *dm;
+  double* out;  // [2]: the lowest Ritz value, |c_k - pad(c_{k-1})|
+};
+
+__device__ __forceinline__ double wave_min64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// (wave_max64: small_exp_dev.h)
+
+constexpr int BT_TRI_ROUNDS = 24;  // multisection rounds: 9 shrink the Gershgorin interval by 63^9 > 2^53, a refused hint costs one
+
+// Lowest eigenpair of the real symmetric tridiagonal T_k (diagonal alpha[0 .. k), off-diagonal beta[0 .. k-1), both in
+// LDS), 1 <= k <= 64, by ONE WAVE, all 64 lanes of it: returns the eigenvalue (the same bits in every lane) and leaves the
+// unit eigenvector, first component non-negative, in c[0 .. k) and zeros in c[k .. 64).  dp, dm: 64 doubles of LDS each.
+//   eigenvalue   multisection on Sturm counts (the pivots q_i = (alpha_i - x) - beta_{i-1}^2 / q_{i-1} of T - x, negative
+//                ones counted, tiny ones replaced by -pivmin as LAPACK's dstebz does): every round the lanes count at 64
+//                points that span the interval, both ends included, and the interval becomes the one gap in which the
+//                count goes from 0 to >= 1.  Since the ends are counted too, a bracket is VERIFIED each round: the first one
+//                is the caller's hint [hint - slack, hint + tiny] when it gives one (interlacing: the lowest eigenvalue
+//                of T_k is not above that of T_{k-1}; the slack is a residual bound that usually, not always, holds), and
+//                a hint that does not bracket falls back to the Gershgorin interval.  Ends at a width of eps |T|.
+//   eigenvector  twisted factorisation (Fernando; Parlett & Dhillon): the pivots of T - theta from the top (lane 0) and
+//                from the bottom (lane 1), the twist at the smallest |gamma_r|, gamma_r = d+_r + d-_r - (alpha_r - theta),
+//                z_r = 1 and the two recurrences away from r.  The residual is |gamma_r| / |z|, small whatever the gap.
+__device__ __noinline__ double bt_trilow(const double* alpha, const double* beta, int k, double* c, double* dp, double* dm, bool has_hint,
+                                         double hint, double slack) {
+  const int lane = threadIdx.x & 63;
+  if (k <= 1) {
+    c[lane] = lane == 0 ? 1.0 : 0.0;
+    return alpha[0];
+  }
+  const double eps = 2.220446049250313e-16;
+  const double a = lane < k ? alpha[lane] : 0.0;
+  const double bl = lane > 0 && lane < k ? fabs(beta[lane - 1]) : 0.0;
+  const double br = lane + 1 < k ? fabs(beta[lane]) : 0.0;
+  double glo = wave_min64(lane < k ? a - bl - br : 1.0e300);
+  double ghi = wave_max64(lane < k ? a + bl + br : -1.0e300);
+  const double tnorm = fmax(fabs(glo), fabs(ghi));
+  const double bmax = wave_max64(fmax(bl, br));
+  const double pivmin = 2.2250738585072014e-308 * fmax(1.0, bmax * bmax);
+  const double wide = 2.0 * tnorm * eps * k + 2.0 * pivmin;
+  glo -= wide;
+  ghi += wide;
+  const double tol = eps * tnorm;
+
+  double lo = glo, hi = ghi;
+  bool on_hint = false;
+  if (has_hint && hint == hint && slack == slack) {  // NaN: no hint
+    const double l2 = hint - slack - 16.0 * tol, h2 = hint + 16.0 * tol;
+    if (l2 > glo && h2 < ghi) { lo = l2; hi = h2; on_hint = true; }
+  }
+  for (int round = 0; round < BT_TRI_ROUNDS; ++round) {
+    const double w = hi - lo;
+    double x = lo + w * ((double)lane * (1.0 / 63.0));
+    if (lane == 63) x = hi;
+    double q = alpha[0] - x;
+    if (fabs(q) < pivmin) q = -pivmin;
+    int cnt = q < 0.0 ? 1 : 0;
+    for (int i = 1; i < k; ++i) {
+      const double b = beta[i - 1];
+      q = (alpha[i] - x) - b * b / q;
+      if (fabs(q) < pivmin) q = -pivmin;
+      cnt += q < 0.0 ? 1 : 0;
+    }
+    const unsigned long long m = __ballot(cnt >= 1);
+    if (m == 0ull || (m & 1ull)) {  // no eigenvalue below hi, or one below lo: not a bracket
+      if (!on_hint) break;          // the widened Gershgorin interval always is one; keep what there is
+      on_hint = false;
+      lo = glo;
+      hi = ghi;
+      continue;
+    }
+    on_hint = false;  // verified
+    const int j = __ffsll((long long)m) - 1;  // 1 .. 63: the first point with an eigenvalue below it
+    const double nlo = __shfl(x, j - 1, 64), nhi = __shfl(x, j, 64);
+    const bool stall = !(nlo > lo || nhi < hi);
+    lo = nlo;
+    hi = nhi;
+    if (stall || hi - lo <= tol) break;
+  }
+  const double theta = 0.5 * (lo + hi);
+
+  // ---- the eigenvector ----
+  const double pivv = fmax(eps * tnorm, pivmin);
+  if (lane < 2) {  // the same text for both directions: lane 0 runs rows 0 .. k-1, lane 1 rows k-1 .. 0
+    const bool up = lane == 0;
+    double* d = up ? dp : dm;
+    int row = up ? 0 : k - 1;
+    double q = alpha[row] - theta;
+    if (fabs(q) < pivv) q = -pivv;
+    d[row] = q;
+    for (int i = 1; i < k; ++i) {
+      const double b = up ? beta[i - 1] : beta[k - 1 - i];
+      row = up ? i : k - 1 - i;
+      q = (alpha[row] - theta) - b * b / q;
+      if (fabs(q) < pivv) q = -pivv;
+      d[row] = q;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  const double gam = lane < k ? fabs(dp[lane] + dm[lane] - (a - theta)) : 1.0e300;
+  const double gmin = wave_min64(gam);
+  const int r = __ffsll((long long)__ballot(gam == gmin)) - 1;
+  if (lane == 0) c[r] = 1.0;
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  if (lane < 2) {  // lane 0 walks from the twist up to row 0, lane 1 down to row k-1
+    const bool up = lane == 0;
+    const int n = up ? r : k - 1 - r;
+    double z = 1.0;
+    for (int i = 1; i <= n; ++i) {
+      const int row = up ? r - i : r + i;
+      const double b = up ? beta[row] : beta[row - 1];
+      const double piv = up ? dp[row] : dm[row];
+      z = -(b / piv) * z;
+      c[row] = z;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  const double z = lane < k ? c[lane] : 0.0;
+  const double n2 = __shfl(wave_sum64(z * z), 0, 64);
+  const double z0 = __shfl(z, 0, 64);
+  const double inv = (z0 < 0.0 ? -1.0 : 1.0) / sqrt(n2);
+  c[lane] = z * inv;
+  return theta;
+}
+
+// x <- the lowest eigenvector of Op + shift, Op the H_eff of BtOp (bt_apply ends with a barrier): orthodox Lanczos,
+// alpha_l = Re <v_l | (Op + shift) v_l>, with one workgroup owning the whole vector; the basis is kept NORMALISED in
+// U[j * N ...), j = 0 .. kcap, slot 0 a copy of x as it came (the reference does not normalise its start either).
+// Element e belongs to thread e % 512 throughout.  After every new vector the lowest eigenpair of T_k; converged when
+// |c_k - pad(c_{k-1})| < thresh in coefficient space, or beta_k < SS_EPS, or k == N; then x = sum_j c_j v_j, renormalised.
+// SS_ENOTCONV after kcap vectors.  *kprev_p <- k; the lowest Ritz value is left in rs.out[0] (behind a barrier).
+__device__ __noinline__ int bt_diag(const BtOp& op, zc* x, zc* U, long N, int kcap_in, double thresh, zc shift, const BtSh& sh,
+                                    const BrSh& rs, int* kprev_p, long long* stats, long long flops_per_apply) {
+  const int tid = threadIdx.x;
+  const bool add_shift = shift.x != 0.0 || shift.y != 0.0;
+  const int kcap = (int)min((long)kcap_in, N);
+  for (long e = tid; e < N; e += SS_THREADS) U[e] = x[e];
+  __syncthreads();
+  int napply = 0;
+  int rc = SS_ENOTCONV, kdone = kcap;
+  for (int i = 0; i < kcap; ++i) {
+    const zc* vi = U + (size_t)i * N;
+    const zc* vm = U + (size_t)(i > 0 ? i - 1 : 0) * N;
+    zc* un = U + (size_t)(i + 1) * N;
+    bt_apply(op, vi, 1.0, un);
+    napply += 1;
+    {  // (Op + shift) v_i, and alpha_i
+      double s[1] = {0.0};
+      for (long e = tid; e < N; e += SS_THREADS) {
+        zc v = un[e];
+        const zc b = vi[e];
+        if (add_shift) {
+          v.x += shift.x * b.x - shift.y * b.y;
+          v.y += shift.x * b.y + shift.y * b.x;
+          un[e] = v;
+        }
+        s[0] += b.x * v.x + b.y * v.y;
+      }
+      wg_reduce(s, sh);
+    }
+    const double al = sh.red[0];
+    const double bprev = i > 0 ? rs.beta[i - 1] : 0.0;
+    {
+      double s[1] = {0.0};
+      for (long e = tid; e < N; e += SS_THREADS) {
+        zc u = un[e];
+        const zc b = vi[e];
+        u.x -= al * b.x;
+        u.y -= al * b.y;
+        if (i > 0) {
+          const zc m = vm[e];
+          u.x -= bprev * m.x;
+          u.y -= bprev * m.y;
+        }
+        un[e] = u;
+        s[0] += u.x * u.x + u.y * u.y;
+      }
+      wg_reduce(s, sh);
+    }
+    const double be = sqrt(sh.red[0]);
+    if (be >= SS_EPS) {
+      const double inv = 1.0 / be;
+      for (long e = tid; e < N; e += SS_THREADS) {  // the same thread wrote un[e] above
+        zc u = un[e];
+        u.x *= inv; u.y *= inv;
+        un[e] = u;
+      }
+    }
+    if (tid == 0) {
+      rs.alpha[i] = al;
+      rs.beta[i] = be;
+    }
+    __syncthreads();
+    const int k = i + 1;
+    if (tid < 64) {  // wave 0: the lowest eigenpair of T_k and the change of the Ritz coefficients
+      const bool hint = i > 0;
+      const double slack = hint ? fabs(rs.beta[i - 1] * rs.cprev[i - 1]) * 1.0625 : 0.0;
+      const double th = bt_trilow(rs.alpha, rs.beta, k, rs.c, rs.dp, rs.dm, hint, hint ? rs.out[0] : 0.0, slack);
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      const double dlt = tid < k ? rs.c[tid] - (tid < i ? rs.cprev[tid] : 0.0) : 0.0;
+      const double err = wave_sum64(dlt * dlt);
+      if (tid == 0) {
+        rs.out[0] = th;
+        rs.out[1] = sqrt(err);
+      }
+    }
+    __syncthreads();
+    bool done = be < SS_EPS || (long)k == N;
+    if (!done && i > 0) done = rs.out[1] < thresh;
+    if (done) {
+      rc = SS_OK;
+      kdone = k;
+      break;
+    }
+    if (tid < 64) rs.cprev[tid] = rs.c[tid];
+    __syncthreads();
+  }
+  if (rc == SS_OK) {  // x = sum_j c_j v_j, renormalised (get_C_sval_states_norm, _mps_cls.py:1083-1084)
+    double s[1] = {0.0};
+    for (long e = tid; e < N; e += SS_THREADS) {
+      double re = 0.0, im = 0.0;
+      for (int j = 0; j < kdone; ++j) {
+        const double cj = rs.c[j];
+        const zc v = U[(size_t)j * N + e];
+        re += cj * v.x;
+        im += cj * v.y;
+      }
+      x[e] = make_double2(re, im);
+      s[0] += re * re + im * im;
+    }
+    wg_reduce(s, sh);
+    const double inv = 1.0 / sqrt(sh.red[0]);
+    for (long e = tid; e < N; e += SS_THREADS) {  // the same thread wrote x[e] above
+      zc z = x[e];
+      z.x *= inv; z.y *= inv;
+      x[e] = z;
+    }
+  }
+  if (tid == 0) {
+    __hip_atomic_store(kprev_p, kdone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    stats[0] += napply;
+    stats[2] += (long long)napply * flops_per_apply;
+  }
+  __syncthreads();
+  return rc;
+}
+
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 248 VGPRs, 106 SGPRs, no vector
+// register spills, 52 scalar registers spilled around the calls of the stage functions, 304 bytes of private memory per
+// lane (the argument blocks the stage functions take by reference: none of it inside a product loop), 23 120 bytes of
+// LDS; occupancy 2 waves per SIMD, i.e. one workgroup (replica) per compute unit.  The kernels that were there before compile to the figures they had
+// (profiles/batch_relax_resources.txt has both listings).
+__global__ __launch_bounds__(SS_THREADS) void k_batch_relax(BatchRelaxArgs g) {
+  __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
+  __shared__ zc s_z[2 * BATCH_MAX_BOND];
+  __shared__ double s_d[SS_WAVES * 8 + 8 + BATCH_MAX_BOND + 6 * BATCH_RELAX_MAX_KRYLOV + 2];
+  BtSh sh{};
+  sh.mats = s_tiles;
+  sh.wsh = s_d;
+  sh.red = s_d + SS_WAVES * 8;
+  sh.gam = sh.red + 8;
+  sh.udiag = s_z;
+  sh.rdiag = s_z + BATCH_MAX_BOND;
+  BrSh rs;
+  rs.alpha = sh.gam + BATCH_MAX_BOND;
+  rs.beta = rs.alpha + BATCH_RELAX_MAX_KRYLOV;
+  rs.c = rs.beta + BATCH_RELAX_MAX_KRYLOV;
+  rs.cprev = rs.c + BATCH_RELAX_MAX_KRYLOV;
+  rs.dp = rs.cprev + BATCH_RELAX_MAX_KRYLOV;
+  rs.dm = rs.dp + BATCH_RELAX_MAX_KRYLOV;
+  rs.out = rs.dm + BATCH_RELAX_MAX_KRYLOV;
+
+  const int r = blockIdx.x, tid = threadIdx.x, L = g.L;
+  if (g.status[r] != SS_OK) return;  // a replica that failed in an earlier launch of the call does no more work
+  void* const* tab = g.ptrs + (size_t)r * g.ptr_stride;
+  zc* const* site = reinterpret_cast<zc* const*>(tab);
+  zc* const* envL = reinterpret_cast<zc* const*>(tab + L);
+  zc* const* envR = reinterpret_cast<zc* const*>(tab + 2 * L + 1);
+  const zc* const* w2l = reinterpret_cast<const zc* const*>(tab + 3 * L + 2);
+  const zc* const* w2el = reinterpret_cast<const zc* const*>(tab + 4 * L + 2);
+  const zc* const* w2er = reinterpret_cast<const zc* const*>(tab + 5 * L + 2);
+  zc* scr = reinterpret_cast<zc*>(tab[6 * L + 2]);
+  zc* sig = scr + g.plan.o_sig;
+  zc* spare = scr + g.plan.o_spare;
+  zc* work = scr + g.plan.o_work;
+  zc* X = scr + g.plan.o_x;
+  zc* Y = scr + g.plan.o_y;
+  zc* U = scr + g.plan.o_u;
+  int* kprev = g.kprev + (size_t)r * L;
+  long long* stats = g.stats + (size_t)r * 4;
+  const zc shift = g.shift[r];
+  zc* tiles = s_tiles;
+
+  int rc = SS_OK;
+  int nstep = 0;
+  double e_prev = 0.0;
+  bool fwd = g.forward != 0;
+  for (int h = 0; h < g.nhalf && rc == SS_OK; ++h, fwd = !fwd) {
+    double theta = 0.0;
+    for (int step = 0; step < L; ++step) {
+      const int p = fwd ? step : L - 1 - step;
+      const BatchShape s = g.shp[p];
+      const int dl = s.dl, d = s.d, dr = s.dr;
+      const long N = (long)dl * d * dr;
+      {  // 1. the lowest eigenvector of H_eff + shift in place of the centre tensor
+        const long long fl = (long long)(8.0 * ((double)dl * dl * s.ml * d * dr + (double)dl * dr * s.ml * s.mr * d * d +
+                                                (double)dl * dr * dr * s.mr * d));
+        const BtOp op{s, envL[p], w2l[p], envR[p + 1], 0, 0, X, Y, tiles};
+        rc = bt_diag(op, site[p], U, N, g.kcap, g.thresh, shift, sh, rs, kprev + p, stats, fl);
+        theta = rs.out[0];
+      }
+      if (rc != SS_OK || step == L - 1) break;
+      if (fwd) {
+        // 2. Psi2Asigma, 3. L[p + 1], 5. Psi(p + 1) = sigma . B(p + 1)
+        bt_qr(site[p], site[p], dr, 1, sig, dr, 1, dl * d, dr, work, sh);
+        bt_env(envL[p], site[p], site[p], (long)d * dr, dr, 1, w2el[p], dl, s.ml, d, dr, s.mr, X, Y, envL[p + 1], tiles);
+        const BatchShape q = g.shp[p + 1];
+        zc* nxt = site[p + 1];
+        bt_matmul(sig, nxt, spare, nxt, dr, q.d * q.dr, dr, tiles);
+      } else {
+        // 2. Psi2sigmaB, 3. R[p] from the mirror image of B, 5. Psi(p - 1) = A(p - 1) . sigma
+        const int mq = d * dr;
+        bt_qr(site[p], site[p], 1, mq, sig, 1, dl, mq, dl, work, sh);
+        bt_env(envR[p + 1], site[p], site[p], 1, dr, (long)d * dr, w2er[p], dr, s.mr, d, dl, s.ml, X, Y, envR[p], tiles);
+        const BatchShape q = g.shp[p - 1];
+        zc* prv = site[p - 1];
+        bt_matmul(prv, sig, spare, prv, q.dl * q.d, dl, dl, tiles);
+      }
+    }
+    if (rc != SS_OK) break;
+    if (!fwd && h > 0) {  // a full step ends here; theta is the Ritz value of the solve at site 0, workgroup-uniform
+      nstep += 1;
+      if (g.energy && tid == 0) {
+        g.energy[r] = theta;
+        g.steps[r] = nstep;
+        if (nstep <= g.hist_len) g.history[(size_t)r * g.hist_len + nstep - 1] = theta;
+      }
+      const bool stop = g.conv_tol > 0.0 && nstep > 1 && fabs(theta - e_prev) <= g.conv_tol;
+      e_prev = theta;
+      if (stop) break;
+    }
+  }
+  if (rc != SS_OK && tid == 0) g.status[r] = rc;
+}
+
+// test hook: bt_trilow alone, one workgroup of one wave per case
+__global__ __launch_bounds__(64) void k_batch_trilow(const double* __restrict__ alpha, const double* __restrict__ beta,
+                                                     const int* __restrict__ kk, double* __restrict__ theta, double* __restrict__ vec) {
+  __shared__ double s_d[5 * BATCH_RELAX_MAX_KRYLOV];
+  const int q = blockIdx.x, lane = threadIdx.x;
+  double* a = s_d;
+  double* b = a + BATCH_RELAX_MAX_KRYLOV;
+  double* c = b + BATCH_RELAX_MAX_KRYLOV;
+  a[lane] = alpha[(size_t)q * BATCH_RELAX_MAX_KRYLOV + lane];
+  b[lane] = beta[(size_t)q * BATCH_RELAX_MAX_KRYLOV + lane];
+  c[lane] = 0.0;
+  __syncthreads();
+  const double th = bt_trilow(a, b, kk[q], c, c + BATCH_RELAX_MAX_KRYLOV, c + 2 * BATCH_RELAX_MAX_KRYLOV, false, 0.0, 0.0);
+  __syncthreads();
+  if (lane == 0) theta[q] = th;
+  vec[(size_t)q * BATCH_RELAX_MAX_KRYLOV + lane] = c[lane];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2531,7 +2917,7 @@ void batch_pair_launch(hipStream_t st, const BatchPairArgs& a, int nrep) {
   HIP_CHECK(hipGetLastError());
 }
 
-bool batch_plan(const BatchShape* shp, int L, BatchPlan& plan, std::string& why) {
+bool batch_plan(const BatchShape* shp, int L, BatchPlan& plan, std::string& why, int relax, int max_diag_krylov) {
   plan = BatchPlan{};
   for (int p = 0; p < L; ++p) {
     const BatchShape& s = shp[p];
@@ -2568,7 +2954,8 @@ bool batch_plan(const BatchShape* shp, int L, BatchPlan& plan, std::string& why)
   plan.o_work = o; o += (size_t)plan.max_site;
   plan.o_x = o; o += (size_t)plan.nx;
   plan.o_y = o; o += (size_t)plan.ny;
-  plan.o_u = o; o += (size_t)MAXK * (size_t)std::max(plan.max_site, plan.max_bond);
+  static_assert(BATCH_EXP_KRYLOV_SLOTS == MAXK, "batch_relax_plan.h repeats vecops.h");
+  plan.o_u = o; o += batch_krylov_carve(plan.max_site, plan.max_bond, relax, max_diag_krylov);
   plan.total = o;
   return true;
 }
@@ -2577,6 +2964,23 @@ void batch_sweep_launch(hipStream_t st, const BatchArgs& a, int nrep) {
   if (nrep < 1 || a.L < 1) throw ArgError("batch: nothing to launch");
   if (a.e.max_krylov < 1 || a.e.max_krylov > MAXK - 1) throw ArgError("batch: max_krylov must be in [1, 20]");
   hipLaunchKernelGGL(k_batch_sweep, dim3(nrep), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
+
+void batch_relax_launch(hipStream_t st, const BatchRelaxArgs& a, int nrep) {
+  if (nrep < 1 || a.L < 1 || a.nhalf < 1) throw ArgError("batch: nothing to launch");
+  if (a.kcap < 2 || a.kcap > BATCH_RELAX_MAX_KRYLOV) throw ArgError("batch: max_diag_krylov must be in [2, 64]");
+  if (a.plan.total - a.plan.o_u < batch_krylov_carve(a.plan.max_site, a.plan.max_bond, 2, a.kcap))
+    throw ArgError("batch: the Krylov carve is too small for the improved relaxation");
+  if ((a.energy != nullptr) != (a.steps != nullptr) || (a.energy != nullptr) != (a.history != nullptr) || (a.energy && a.hist_len < 1))
+    throw ArgError("batch: the relaxation's outputs go together");
+  hipLaunchKernelGGL(k_batch_relax, dim3(nrep), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
+
+void batch_trilow_launch(hipStream_t st, const double* alpha, const double* beta, const int* k, int ncases, double* theta, double* vec) {
+  if (ncases < 1 || !alpha || !beta || !k || !theta || !vec) throw ArgError("batch_trilow: nothing to launch");
+  hipLaunchKernelGGL(k_batch_trilow, dim3(ncases), dim3(64), 0, st, alpha, beta, k, theta, vec);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -393,6 +393,16 @@ int mitdvp_batch_operate(mitdvp_batch* b, int op_id, int maxstep, double conv_to
   }
   return first;
 }
+int mitdvp_batch_relax(mitdvp_batch* b, int maxstep, double conv_tol, double* energies, int* steps, double* history, int* statuses) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_relax: null handle"; return MITDVP_EINVAL; }
+  std::vector<int> st((size_t)b->b->size(), 0);
+  const int rc = guard(nullptr, [&] { b->b->relax(maxstep, conv_tol, energies, steps, history, st.data()); });
+  if (rc != MITDVP_OK) return rc;
+  return batch_finish(b, st, statuses);
+}
+int mitdvp_batch_trilow(int device, const double* alpha, const double* beta, const int* k, int ncases, double* theta, double* vec) {
+  return guard(nullptr, [&] { mitdvp::batch_trilow(device, alpha, beta, k, ncases, theta, vec); });
+}
 void mitdvp_batch_destroy(mitdvp_batch* b) { delete b; }
 int mitdvp_invalidate_env(mitdvp_engine* h) { ENG_CALL(h, h->e->invalidate_env()); }
 int mitdvp_replace_site(mitdvp_engine* h, int isite, const double* reim, int gauge) {

@@ -77,11 +77,19 @@ struct RecordStore {
   bool records(hipStream_t st, const double* weights, double* values, double* mean, long long& n_launch);
 };
 
+constexpr int BATCH_RELAX_MAX_STEPS = 1 << 20;   // full steps of one relax() call
+constexpr int BATCH_TRILOW_MAX_CASES = 65536;    // cases of one batch_trilow call
+// test hook: the lowest eigenpair of ncases tridiagonal matrices by the eigen-solve of k_batch_relax (bt_trilow), one
+// workgroup per case.  Host pointers; alpha / beta / vec [ncases][64], k / theta [ncases].  ArgError before the GPU is
+// touched for ncases outside 1 .. BATCH_TRILOW_MAX_CASES, a null argument, or a k outside 1 .. 64.
+void batch_trilow(int device, const double* alpha, const double* beta, const int* k, int ncases, double* theta, double* vec);
+
 class Batch {
  public:
   // validates (ArgError otherwise, every engine untouched): one device, distinct engines, no CU mask, single electronic
-  // state, not adaptive, not a segment, not bond-sharded, relax 0 or 1, no gates / Kraus maps, identical site and MPO shapes
-  // and identical integrator settings across the replicas, shapes inside the envelope of batch_plan
+  // state, not adaptive, not a segment, not bond-sharded, no gates / Kraus maps, identical site and MPO shapes
+  // and identical integrator settings across the replicas, shapes inside the envelope of batch_plan; with relax == 2
+  // (improved relaxation) also max_diag_krylov in 2 .. 64 and equal across the replicas
   explicit Batch(const std::vector<Engine*>& engines);
   ~Batch();
   Batch(const Batch&) = delete;
@@ -241,6 +249,19 @@ class Batch {
   // 1 .. BATCH_MAX_MPO, outer MPO bonds that are not 1, neighbouring cores that do not fit, a buffer (selected replicas x
   // carve x 16 bytes, batch_operate_plan.h) above BATCH_OPERATE_MAX_BYTES.
   void operate(int op_id, int maxstep, double conv_tol, const int* replicas, int nsel, double* norms, int* iters, int* statuses);
+
+  // ---- ground states by improved relaxation (k_batch_relax) ----
+  // Replicas with relax == 2 take step / sweep / run like the others: a half-sweep is one launch of k_batch_relax, dt is
+  // ignored, there is no bond step.  relax() runs up to maxstep full steps (forward + backward half-sweep) of every replica
+  // in ONE launch and one host wait.  E_n, the energy of a replica after step n, is the Ritz value of its last local solve
+  // (site 0); with conv_tol > 0 a replica stops once |E_n - E_{n-1}| <= conv_tol, the others go on.  energies [B]: the last
+  // E_n; steps [B]: steps run; history [B][maxstep]: E_1 .. E_n, NaN behind the stop; statuses [B]: SS_OK, or SS_ENOTCONV
+  // when a local solve did not converge in max_diag_krylov vectors (that replica stops as in a step, the others finish).
+  // Every output may be null.  The jump generator's step counter, channels, the snapshot, every request and the records of
+  // the last run() are untouched.  Refused before the GPU is touched, with an ArgError that names the entry point and the
+  // limit and leaves everything as it was: maxstep outside 1 .. BATCH_RELAX_MAX_STEPS, conv_tol negative or not finite,
+  // replicas whose relax != 2, a replica whose centre is not at site 0.
+  void relax(int maxstep, double conv_tol, double* energies, int* steps, double* history, int* statuses);
 
   std::string status_message(int code) const;
   int size() const { return (int)eng_.size(); }
@@ -442,6 +463,9 @@ class Batch {
   void validate();
   void prepare(bool forward, bool build_envs = true);
   void launch(double dt, bool forward);
+  void launch_relax(bool forward, int nhalf, double conv_tol, double* energies, int* steps, double* history, int hist_len);
+  DevArr<double> d_rx_energy_, d_rx_hist_;  // relax(): [B], [B][maxstep]
+  DevArr<int> d_rx_steps_;                  // [B]
   void launch_observe(int what, int nsites, long record, long rec_len);
   void launch_density(int nkeys, bool zero_head, long record, long rec_len, long dens_off);
   void finish(bool ends_forward, int half_sweeps, int* statuses, int other_launches = 0, int channel_passes = 0);

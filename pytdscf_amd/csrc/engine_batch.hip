@@ -116,7 +116,7 @@ void Batch::validate() {
     if (e.adaptive_) throw ArgError(who + "has an adaptive bond dimension");
     if (e.segment_) throw ArgError(who + "is a segment of a site-sharded chain");
     if (e.nranks_ != 1) throw ArgError(who + "is bond-sharded over several GPUs");
-    if (e.cfg.relax != 0 && e.cfg.relax != 1) throw ArgError(who + "uses improved relaxation (relax must be 0 or 1)");
+    if (e.cfg.relax < 0 || e.cfg.relax > 2) throw ArgError(who + "has relax = " + std::to_string(e.cfg.relax) + " (relax must be 0, 1 or 2)");
     if (!e.gates_.empty() || !e.kraus_.empty()) throw ArgError(who + "has gates or Kraus maps set");
     if (e.sw_next_ >= 0) throw ArgError(who + "has a half-sweep in parts in progress");
     if (e.L_ != e0.L_) throw ArgError(who + "has another number of sites");
@@ -126,6 +126,14 @@ void Batch::validate() {
       throw ArgError(who + "differs from replica 0 in integrator, lanczos_variant, conserve_norm, thresh, max_krylov or relax");
   }
   if (e0.cfg.max_krylov < 1 || e0.cfg.max_krylov > MAXK - 1) throw ArgError("batch: max_krylov must be in [1, 20]");
+  if (e0.cfg.relax == 2) {  // improved relaxation: one cap of the eigen-solver's Krylov space for all replicas, 2 .. 64
+    for (int i = 1; i < n; ++i)
+      if (eng_[i]->max_diag_krylov_ != e0.max_diag_krylov_)
+        throw ArgError("batch: replica " + std::to_string(i) + " differs from replica 0 in max_diag_krylov (" +
+                       std::to_string(eng_[i]->max_diag_krylov_) + " against " + std::to_string(e0.max_diag_krylov_) + ")");
+    std::string bad;
+    if (!batch_relax_kcap_ok(e0.max_diag_krylov_, bad)) throw ArgError("batch: " + bad);
+  }
   std::vector<BatchShape> s0 = shapes_of(e0);
   for (int i = 1; i < n; ++i) {
     std::vector<BatchShape> s = shapes_of(*eng_[i]);
@@ -145,7 +153,7 @@ void Batch::validate() {
   if (s0[0].dl != 1 || s0[e0.L_ - 1].dr != 1) throw ArgError("open boundary bonds must be 1");
   BatchPlan pl;
   std::string why;
-  if (!batch_plan(s0.data(), e0.L_, pl, why)) throw ArgError(why);
+  if (!batch_plan(s0.data(), e0.L_, pl, why, e0.cfg.relax, e0.max_diag_krylov_)) throw ArgError(why);
   if (s0.size() != shp_.size() || std::memcmp(s0.data(), shp_.data(), s0.size() * sizeof(BatchShape)) != 0) {
     shp_ = s0;
     shapes_dirty_ = true;
@@ -277,9 +285,39 @@ void Batch::prepare(bool forward, bool build_envs) {
   }
 }
 
+// improved relaxation: nhalf half-sweeps of k_batch_relax in one launch; energies / steps / history null: not recorded
+void Batch::launch_relax(bool forward, int nhalf, double conv_tol, double* energies, int* steps, double* history, int hist_len) {
+  Engine& e0 = *eng_[0];
+  BatchRelaxArgs a{};
+  a.L = L_;
+  a.forward = forward ? 1 : 0;
+  a.nhalf = nhalf;
+  a.kcap = e0.max_diag_krylov_;
+  a.thresh = e0.cfg.thresh;
+  a.conv_tol = conv_tol;
+  a.shp = d_shp_;
+  a.ptrs = d_ptrs_;
+  a.ptr_stride = (int)ptrs_per_replica();
+  a.shift = d_shift_;
+  a.kprev = d_kprev_;
+  a.status = d_status_;
+  a.stats = d_stats_;
+  a.plan = plan_;
+  a.energy = energies;
+  a.steps = steps;
+  a.history = history;
+  a.hist_len = hist_len;
+  batch_relax_launch(st_, a, (int)eng_.size());
+  n_launch_ += 1;
+}
+
 void Batch::launch(double dt, bool forward) {
   const size_t n = eng_.size();
   Engine& e0 = *eng_[0];
+  if (e0.cfg.relax == 2) {  // dt means nothing to the eigen-solver, as in Engine::local_site_exp
+    launch_relax(forward, 1, 0.0, nullptr, nullptr, nullptr, 0);
+    return;
+  }
   BatchArgs a{};
   a.L = L_;
   a.forward = forward ? 1 : 0;
@@ -323,7 +361,7 @@ void Batch::finish(bool ends_forward, int half_sweeps, int* statuses, int other_
     e.cnt_.keff_flops += (double)stats[i * 4 + 3];
     if (st[i] == SS_OK) {  // a replica that stopped part-way did less: only what the device counted is added for it
       e.cnt_.n_exp_site += (long long)half_sweeps * L_;
-      e.cnt_.n_exp_bond += (long long)half_sweeps * (L_ - 1);
+      if (e.cfg.relax != 2) e.cnt_.n_exp_bond += (long long)half_sweeps * (L_ - 1);  // improved relaxation has no bond step
       e.cnt_.n_qr += (long long)half_sweeps * (L_ - 1);
       e.cnt_.n_env += (long long)half_sweeps * (L_ - 1);
       if (channel_passes) {  // a channel pass: two gauge moves and one left block per site above the lowest channel
@@ -1507,8 +1545,92 @@ void Batch::operate(int op_id, int maxstep, double conv_tol, const int* replicas
   }
 }
 
+// ---- ground states by improved relaxation (k_batch_relax) ----
+void Batch::relax(int maxstep, double conv_tol, double* energies, int* steps, double* history, int* statuses) {
+  const std::string at = "mitdvp_batch_relax: ";
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  const size_t n = eng_.size();
+  if (maxstep < 1) throw ArgError(at + "maxstep = " + std::to_string(maxstep) + ", it must be >= 1");
+  if (maxstep > BATCH_RELAX_MAX_STEPS)
+    throw ArgError(at + "maxstep = " + std::to_string(maxstep) + ", one call takes at most " + std::to_string(BATCH_RELAX_MAX_STEPS));
+  if (!(conv_tol >= 0.0) || !std::isfinite(conv_tol))
+    throw ArgError(at + "conv_tol = " + std::to_string(conv_tol) + ", it must be finite and >= 0");
+  if (eng_[0]->cfg.relax != 2)
+    throw ArgError(at + "the replicas have relax = " + std::to_string(eng_[0]->cfg.relax) + ", the call needs improved relaxation (relax must be 2)");
+  for (size_t i = 0; i < n; ++i)
+    if (eng_[i]->center_ != 0)
+      throw ArgError(at + "replica " + std::to_string(i) + " has its centre at site " + std::to_string(eng_[i]->center_) +
+                     "; a relaxation step starts from the centre at site 0 (the state a batch step leaves)");
+  prepare(true);  // the right blocks, where no step has built them
+  const size_t nh = n * (size_t)maxstep;
+  reserve_synced(d_rx_energy_, n, d_rx_steps_, n, d_rx_hist_, nh);
+  std::vector<double> h_e(n, std::nan("")), h_hist(nh, std::nan(""));
+  std::vector<int> h_steps(n, 0);
+  // the sources are locals: they live until the host wait in finish()
+  HIP_CHECK(hipMemcpyAsync(d_rx_energy_, h_e.data(), n * sizeof(double), hipMemcpyHostToDevice, st_));
+  HIP_CHECK(hipMemcpyAsync(d_rx_hist_, h_hist.data(), nh * sizeof(double), hipMemcpyHostToDevice, st_));
+  HIP_CHECK(hipMemsetAsync(d_rx_steps_, 0, n * sizeof(int), st_));
+  launch_relax(true, 2 * maxstep, conv_tol, d_rx_energy_, d_rx_steps_, d_rx_hist_, maxstep);
+  std::vector<double> o_e(n), o_hist(nh);
+  HIP_CHECK(hipMemcpyAsync(o_e.data(), d_rx_energy_, n * sizeof(double), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipMemcpyAsync(o_hist.data(), d_rx_hist_, nh * sizeof(double), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipMemcpyAsync(h_steps.data(), d_rx_steps_, n * sizeof(int), hipMemcpyDeviceToHost, st_));
+  // the one host wait of the call; the counters take the half-sweeps of the replica that ran the most, then each
+  // replica's own count is put right below (a replica that stopped early ran fewer)
+  finish(false, 0, statuses, 1);
+  for (size_t i = 0; i < n; ++i) {
+    Engine& e = *eng_[i];
+    const long long hs = 2LL * h_steps[i];
+    e.cnt_.n_exp_site += hs * L_;
+    e.cnt_.n_qr += hs * (L_ - 1);
+    e.cnt_.n_env += hs * (L_ - 1);
+  }
+  if (energies) std::memcpy(energies, o_e.data(), n * sizeof(double));
+  if (steps) std::memcpy(steps, h_steps.data(), n * sizeof(int));
+  if (history) std::memcpy(history, o_hist.data(), nh * sizeof(double));
+}
+
+// the eigen-solve of the improved relaxation alone (k_batch_trilow), for tests
+void batch_trilow(int device, const double* alpha, const double* beta, const int* k, int ncases, double* theta, double* vec) {
+  const std::string at = "mitdvp_batch_trilow: ";
+  if (ncases < 1 || ncases > BATCH_TRILOW_MAX_CASES)
+    throw ArgError(at + "ncases = " + std::to_string(ncases) + ", it must be in 1 .. " + std::to_string(BATCH_TRILOW_MAX_CASES));
+  if (!alpha || !beta || !k || !theta || !vec) throw ArgError(at + "null argument");
+  for (int q = 0; q < ncases; ++q)
+    if (k[q] < 1 || k[q] > BATCH_RELAX_MAX_KRYLOV)
+      throw ArgError(at + "case " + std::to_string(q) + " has k = " + std::to_string(k[q]) + ", it must be in 1 .. " +
+                     std::to_string(BATCH_RELAX_MAX_KRYLOV));
+  HIP_CHECK(hipSetDevice(device));
+  hipStream_t st;
+  HIP_CHECK(hipStreamCreate(&st));
+  {
+    const size_t nv = (size_t)ncases * BATCH_RELAX_MAX_KRYLOV;
+    // T of case q: its k diagonal and k - 1 off-diagonal entries, the rest of the row zeros
+    std::vector<double> ha(nv, 0.0), hb(nv, 0.0);
+    for (int q = 0; q < ncases; ++q)
+      for (int i = 0; i < k[q]; ++i) {
+        ha[(size_t)q * BATCH_RELAX_MAX_KRYLOV + i] = alpha[(size_t)q * BATCH_RELAX_MAX_KRYLOV + i];
+        if (i + 1 < k[q]) hb[(size_t)q * BATCH_RELAX_MAX_KRYLOV + i] = beta[(size_t)q * BATCH_RELAX_MAX_KRYLOV + i];
+      }
+    DevArr<double> da, db, dth, dv;
+    DevArr<int> dk;
+    da.reserve(nv); db.reserve(nv); dv.reserve(nv); dth.reserve((size_t)ncases); dk.reserve((size_t)ncases);
+    HIP_CHECK(hipMemcpyAsync(da, ha.data(), nv * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(db, hb.data(), nv * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(dk, k, (size_t)ncases * sizeof(int), hipMemcpyHostToDevice, st));
+    batch_trilow_launch(st, da, db, dk, ncases, dth, dv);
+    HIP_CHECK(hipMemcpyAsync(theta, dth, (size_t)ncases * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(vec, dv, nv * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  }
+  HIP_CHECK(hipStreamDestroy(st));
+}
+
 std::string Batch::status_message(int code) const {
   const Engine& e0 = *eng_[0];
+  if (code == SS_ENOTCONV && e0.cfg.relax == 2)  // Engine::krylov_diag's words; a site of fewer elements than the cap stops at k = N
+    return "Lanczos Diagonalization is not converged in " + std::to_string(e0.max_diag_krylov_) + " basis";
   if (code == SS_ENOTCONV)
     return std::string(has_pairs() ? "The split of a pair channel is not converged in " + std::to_string(BATCH_PAIR_MAX_SWEEPS) + " Jacobi sweeps, or " : "") +
            std::string(e0.cfg.integrator == MITDVP_LANCZOS ? "Short Iterative Lanczos" : "Short Iterative Arnoldi") +

@@ -63,8 +63,11 @@ class TDVPEngine:
         max_krylov: int = 20,
         lanczos_variant: str = "reference",
         cu_range: tuple[int, int] | None = None,
+        max_diag_krylov: int = 0,
     ):
-        """``cu_range = (first, count)``: confine the engine to ``count`` compute units starting at ``first`` (multiples of 8:
+        """``max_diag_krylov``: the most Krylov vectors one local solve of ``relax="improved"`` may take (0: the library's
+        default, 64; a solve that needs more raises "Lanczos Diagonalization is not converged in N basis").
+        ``cu_range = (first, count)``: confine the engine to ``count`` compute units starting at ``first`` (multiples of 8:
         8 k units are k CUs on every XCD); engines with disjoint ranges never compete for a compute unit (TDVPEnsemble)."""
         lib = _lib.load()
         cfg = _lib.Config()
@@ -76,6 +79,7 @@ class TDVPEngine:
         cfg.thresh = thresh
         cfg.max_krylov = max_krylov
         cfg.lanczos_variant = {"reference": 0, "orthodox": 1}[lanczos_variant]
+        cfg.max_diag_krylov = int(max_diag_krylov)
         if cu_range is not None:
             cfg.cu_first, cfg.cu_count = int(cu_range[0]), int(cu_range[1])
         self._lib = lib
@@ -808,6 +812,36 @@ def batch_block(op: str, dims, *operands, ncopies=1, variant=0, scl=1.0, device=
 VECOP_OPS = {name: k for k, name in enumerate(_lib.VECOP_NAMES)}
 
 
+def tridiag_lowest(alpha, beta, device=0):
+    """The lowest eigenpair of real symmetric tridiagonal matrices of order 1 .. 64 by the device function that
+    ``k_batch_relax`` runs after every Lanczos vector (``mitdvp_batch_trilow``, one workgroup per matrix).  ``alpha`` /
+    ``beta``: the diagonal (k numbers) and the off-diagonal (k - 1) of one matrix, or lists of them.  Returns
+    ``(theta, vec)`` -- the eigenvalue and its unit eigenvector, first component non-negative -- or two lists."""
+    single = np.ndim(alpha[0]) == 0 if len(alpha) else True
+    al = [alpha] if single else list(alpha)
+    be = [beta] if single else list(beta)
+    if len(al) != len(be) or not al:
+        raise ValueError("tridiag_lowest: one off-diagonal per diagonal, at least one matrix")
+    n = len(al)
+    A = np.zeros((n, 64), dtype=np.float64)
+    Bm = np.zeros((n, 64), dtype=np.float64)
+    ks = np.zeros(n, dtype=np.int32)
+    for q, (a, b) in enumerate(zip(al, be)):
+        a = np.asarray(a, dtype=np.float64).reshape(-1)
+        b = np.asarray(b, dtype=np.float64).reshape(-1)
+        if b.size != max(a.size - 1, 0):
+            raise ValueError(f"tridiag_lowest: matrix {q} has {a.size} diagonal and {b.size} off-diagonal entries")
+        ks[q] = a.size  # an order outside 1 .. 64 is the library's to refuse
+        A[q, :min(a.size, 64)] = a[:64]
+        Bm[q, :min(b.size, 64)] = b[:64]
+    theta = np.zeros(n, dtype=np.float64)
+    vec = np.zeros((n, 64), dtype=np.float64)
+    lib = _lib.load()
+    _lib.check(lib.mitdvp_batch_trilow(int(device), _dp(A), _dp(Bm), ks.ctypes.data_as(C.POINTER(C.c_int)), n, _dp(theta), _dp(vec)))
+    vecs = [vec[q, :ks[q]].copy() for q in range(n)]
+    return (float(theta[0]), vecs[0]) if single else (list(theta), vecs)
+
+
 def vecop(op: str, dims, strides=(), *, variant=0, z=(), r=None, idx=None, mask=(1 << 64) - 1, zo=(), ro=None, a=1.0, b=0.0,
           both=0.0, eps=0.0, coef=(), f=(), device=0):
     """One call of one host wrapper of csrc/vecops.h on a stream of its own (``mitdvp_vecop``; include/mitdvp.h has the ops,
@@ -1106,6 +1140,12 @@ class TDVPBatch:
 
     ``propagate`` raises the first failing replica's error (a replica that does not converge stops, the others finish)
     and leaves every replica's status code in ``statuses``.
+
+    With ``relax="improved"`` (and ``from_engines`` of such engines) the batch finds ground states: every half-sweep
+    replaces each site tensor by the lowest eigenvector of its effective Hamiltonian (``k_batch_relax``; a Lanczos solver
+    that stays on the device) and skips the bond step.  ``propagate``, ``sweep`` and ``propagate(observe=...)`` work as
+    ever, two launches per step; their ``dt_au`` means nothing there, as for ``TDVPEngine(relax="improved")``.  ``relax``
+    runs many steps in one launch and stops each replica when its energy has converged.
     """
 
     def __init__(self, n_replicas: int, nsite: int, *, device: int = 0, **engine_kw):
@@ -1127,6 +1167,7 @@ class TDVPBatch:
         self._expect = None
         self._cross_mpo = None
         self.operated = {}
+        self.relaxed = {}
         self._lib = _lib.load()
         try:
             for _ in range(n_replicas):
@@ -1156,6 +1197,7 @@ class TDVPBatch:
         self._expect = None
         self._cross_mpo = None
         self.operated = {}
+        self.relaxed = {}
         self._lib = _lib.load()
         return self
 
@@ -1663,6 +1705,33 @@ class TDVPBatch:
         self._run(lambda b, st: self._lib.mitdvp_batch_operate(b, op_id, maxstep, conv_tol, rep, nsel, _dp(norms),
                                                                 iters.ctypes.data_as(C.POINTER(C.c_int)), st))
         return {"norms": norms, "iterations": iters, "statuses": list(self.statuses)}
+
+    # ---- ground states by improved relaxation (mitdvp_batch_relax) ----
+    def relax(self, maxstep: int = 20, conv_tol: float = 0.0):
+        """Up to ``maxstep`` improved-relaxation steps of every replica in ONE launch and one host wait
+        (``k_batch_relax``); the replicas must have been made with ``relax="improved"`` and have their centre at site 0.
+        ``E_n``, a replica's energy after step ``n``, is the lowest Ritz value of its last local solve.  With
+        ``conv_tol > 0`` a replica stops on its own once ``|E_n - E_{n-1}| <= conv_tol`` while the others go on;
+        ``conv_tol = 0`` runs ``maxstep`` steps.
+
+        Returns ``{"energy": (B,), "steps": (B,) int, "history": (B, maxstep)}``: the last ``E_n``, the steps run, and
+        ``E_1 .. E_n`` of each replica with NaN behind its stop.  A replica whose local solve does not converge in
+        ``max_diag_krylov`` vectors stops while the others finish; the call then raises that replica's error and leaves
+        every status in ``statuses`` and what was filled in in ``relaxed``, as ``propagate`` does."""
+        n = len(self.engines)
+        maxstep = int(maxstep)
+        conv_tol = float(conv_tol)
+        if maxstep < 1:
+            raise ValueError(f"relax: maxstep = {maxstep}, it must be >= 1")
+        if not (conv_tol >= 0.0) or not np.isfinite(conv_tol):
+            raise ValueError(f"relax: conv_tol = {conv_tol}, it must be finite and >= 0")
+        energy = np.full(n, np.nan, dtype=np.float64)
+        steps = np.zeros(n, dtype=np.int32)
+        history = np.full((n, maxstep), np.nan, dtype=np.float64)
+        self.relaxed = {"energy": energy, "steps": steps, "history": history}
+        self._run(lambda b, st: self._lib.mitdvp_batch_relax(b, maxstep, conv_tol, _dp(energy),
+                                                              steps.ctypes.data_as(C.POINTER(C.c_int)), _dp(history), st))
+        return dict(self.relaxed)
 
     def launches(self) -> int:
         """kernel launches counted so far on replica 0, where the batch's launches are counted once"""

@@ -11,6 +11,9 @@ applies to the merged two-site tensor and splits again at the bond's dimension (
 trick and ``<psi| A(t) B |psi>``, contracted for all trajectories by one launch per record (``k_batch_cross``; ``k_batch_cross_mpo``
 when ``A`` is a sum over the chain given as an MPO).
 
+``relax_trajectories`` is the first link of relax -> dipole -> propagate over an ensemble: the ground states of a list of
+models (static disorder) by improved relaxation, all in one launch (``k_batch_relax``).
+
 Nothing falls back: a model the batched kernels do not take raises with the library's message."""
 
 from __future__ import annotations
@@ -369,6 +372,58 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
     out = {"time": np.arange(nrec) * every * dt_au * units.au_in_fs, "mean": rec["mean_" + key]}
     if per_trajectory:
         out["trajectories"] = rec[key] if norms is None else rec[key] * norms[None, :]
+    return out
+
+
+def relax_trajectories(models, starts=None, maxstep=20, conv_tol=1.0e-10, thresh_sil=1.0e-09, device=0):
+    """Ground states of an ensemble by improved relaxation in ONE batch and one launch (``TDVPBatch.relax``,
+    ``k_batch_relax``): the reference's ``Simulator.relax(improved=True)`` for every realisation at once.
+
+    ``models``: one model, or a list of models of equal site dimensions, ``m_aux_max`` and MPO bonds -- one replica each
+    with its own Hamiltonian (static disorder).  ``starts``: one start per replica, Hartree products (one vector per site)
+    or MPS cores as ``core_starts`` takes them (``correlation_function`` explains both); default: each model's own initial
+    state, ``init_HartreeProduct`` padded to ``m_aux_max``.  A replica stops on its own once its energy changes by no
+    more than ``conv_tol`` from one step to the next, ``maxstep`` steps at the most; ``thresh_sil`` is the threshold of
+    the local Lanczos solver.
+
+    Returns ``{"energy": (B,), "steps": (B,) int, "history": (B, maxstep) with NaN behind a replica's stop, "states":
+    [cores of replica 0, ...]}``; the states are normalised MPS cores with the centre at site 0, in the form
+    ``correlation_function(starts=...)`` and ``propagate_trajectories`` accept.  The energies contain the Hamiltonian's
+    scalar term.  A model the batch does not take raises with the library's message; nothing falls back."""
+    models = list(models) if isinstance(models, (list, tuple)) else [models]
+    if not models:
+        raise ValueError("relax_trajectories: no model")
+    m0 = models[0]
+    dims = list(m0.dims)
+    nsite = len(dims)
+    D = m0.m_aux_max if m0.m_aux_max is not None else 10**9
+    for k, m in enumerate(models):
+        if m.nstate != 1 or m.space != "hilbert":
+            raise NotImplementedError(f"relax_trajectories: model {k}: one electronic state in Hilbert space")
+        if list(m.dims) != dims or m.m_aux_max != m0.m_aux_max:
+            raise ValueError(f"relax_trajectories: model {k} has dims {list(m.dims)} and m_aux_max {m.m_aux_max}, model 0 has "
+                             f"{dims} and {m0.m_aux_max}: the replicas of a batch share their shapes")
+    ns = len(models)
+    if starts is not None:
+        starts = [list(s) for s in starts]
+        if len(starts) != ns:
+            raise ValueError(f"relax_trajectories: {len(starts)} starts for {ns} models (one start per replica)")
+        mps_starts = core_starts(starts, dims, D)
+    bt = TDVPBatch(ns, nsite, device=device, relax="improved", thresh=thresh_sil)
+    try:
+        for k, (e, m) in enumerate(zip(bt.engines, models)):
+            e.set_mpo(m.project_mpo(m.hamiltonian.as_mpo(m.dims)), 0, shift=m.hamiltonian.coupleJ[0][0])
+            if starts is None:
+                cores = m.initial_cores(0)
+            elif mps_starts is None:
+                cores = product_state_cores(starts[k], D, space=m.space)
+            else:
+                cores = mps_starts[k]
+            e.set_mps(cores, canonicalize=True, scale=1.0)
+        out = bt.relax(maxstep, conv_tol)
+        out["states"] = [e.get_mps() for e in bt.engines]
+    finally:
+        bt.close()
     return out
 
 
