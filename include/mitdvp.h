@@ -824,6 +824,37 @@ int mitdvp_keff_apply(int device, const double* L, const double* R, const double
                       int dl, int dr, int m, double* out);
 int mitdvp_env_update(int device, int left, const double* env, const double* site, const double* W,
                       int dl, int d, int dr, int ml, int mr, double* out);
+/* -- the one-launch small-bond kernel (k_small_site) under a chosen launch plan.
+ *    kind and dims name one of its three contraction chains:
+ *      MITDVP_SMALL_HEFF  dims = (dl, d, dr, ml, mr)
+ *      MITDVP_SMALL_KEFF  dims = (d1, d2, m)
+ *      MITDVP_SMALL_ENV   dims = (din, min, d, dout, mout): block (din, min, din) -> (dout, mout, dout)
+ *    mitdvp_small_plan: the plan an engine with n_cu compute units gives that chain, APPLY (exp_mode 0) or EXP mode
+ *    (the engine plans environment updates in APPLY mode only).  Host arithmetic, no device call.  ok = 0: the chain does
+ *    not qualify for the family there (the other fields are then 0).  grid = ceil(slabs / spw) * nsc workgroups,
+ *    lds_bytes what the plan carves (the launch asks for at least 84 KiB), sg_aliases_x: the chunk partial reuses X's LDS. */
+enum { MITDVP_SMALL_HEFF = 0, MITDVP_SMALL_KEFF = 1, MITDVP_SMALL_ENV = 2 };
+typedef struct {
+  int ok, nsc, cs, spw, a_resident, grid, lds_bytes, sg_aliases_x;
+} mitdvp_small_plan_t;
+int mitdvp_small_plan(int kind, const int* dims, int exp_mode, int n_cu, mitdvp_small_plan_t* out);
+/*    mitdvp_small_apply: one H_eff / K_eff apply or environment update through Engine::heff_apply / keff_apply /
+ *    env_update (the production dispatch) on an engine confined to the compute units [0, cu_count) -- 0: the whole
+ *    device, else a multiple of 8 -- with a complex shift (out += shift * v; H_eff and K_eff only).
+ *      HEFF  a = L (dl, ml, dl), w = W (ml, d, d, mr), r = R (dr, mr, dr), v = psi (dl, d, dr), out (dl, d, dr)
+ *      KEFF  a = L (d1, m, d1), r = R (d2, m, d2), v = sigma (d1, d2), out (d1, d2); w unused
+ *      ENV   dims = (dl, d, dr, ml, mr) of the SITE and its core, as mitdvp_env_update: v = site (dl, d, dr), w = W;
+ *            left != 0: a = env (dl, ml, dl) -> out (dr, mr, dr); left == 0: a = env (dr, mr, dr) -> out (dl, ml, dl)
+ *            through the mirrored tensor; r unused.  The plan's dims are (dl, ml, d, dr, mr) / (dr, mr, d, dl, ml).
+ *    info: n_launch = launches the call issued (1: the one-launch family served it; plan is then the plan it ran,
+ *    as launched), plan.ok = 0 otherwise. */
+typedef struct {
+  int n_launch;
+  mitdvp_small_plan_t plan;
+} mitdvp_small_info;
+int mitdvp_small_apply(int device, int cu_count, int kind, int left, const int* dims, const double* a, const double* w,
+                       const double* r, const double* v, double shift_re, double shift_im, double* out,
+                       mitdvp_small_info* info);
 /* SiteCoef.gauge_trf (_site_cls.py:138-292): key 0 "Psi2Asigma", 1 "Psi2sigmaB". */
 int mitdvp_gauge_trf(int device, int key, const double* psi, int dl, int d, int dr,
                      double* site_out, double* sigma_out);

@@ -124,6 +124,23 @@ class BatchBlockArgs(C.Structure):
     _fields_ = [("op", C.c_int), ("variant", C.c_int), ("dims", C.c_int * 8), ("ncopies", C.c_int), ("scl", C.c_double)]
 
 
+class SmallPlan(C.Structure):
+    """mitdvp_small_plan_t: a launch plan of the one-launch small-bond kernel"""
+
+    _fields_ = [(k, C.c_int) for k in ("ok", "nsc", "cs", "spw", "a_resident", "grid", "lds_bytes", "sg_aliases_x")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SmallInfo(C.Structure):
+    """mitdvp_small_info: what mitdvp_small_apply ran"""
+
+    _fields_ = [("n_launch", C.c_int), ("plan", SmallPlan)]
+
+
+SMALL_HEFF, SMALL_KEFF, SMALL_ENV = range(3)
+
 BLOCK_MATMUL, BLOCK_HEFF, BLOCK_KEFF, BLOCK_ENV, BLOCK_OVERLAP, BLOCK_QR, BLOCK_SPLIT = range(7)
 
 class VecopArgs(C.Structure):
@@ -249,6 +266,8 @@ def load() -> C.CDLL:
         "mitdvp_heff_apply": (i, [i, dp, dp, dp, dp, i, i, i, i, i, dp, i, dp]),
         "mitdvp_keff_apply": (i, [i, dp, dp, dp, i, i, i, dp]),
         "mitdvp_env_update": (i, [i, i, dp, dp, dp, i, i, i, i, i, dp]),
+        "mitdvp_small_plan": (i, [i, ip, i, i, C.POINTER(SmallPlan)]),
+        "mitdvp_small_apply": (i, [i, i, i, i, ip, dp, dp, dp, dp, d, d, dp, C.POINTER(SmallInfo)]),
         "mitdvp_gauge_trf": (i, [i, i, dp, i, i, i, dp, dp]),
         "mitdvp_expm_dense": (i, [i, i, i, i, dp, i, dp, d, d, d, i, dp, ip]),
         "mitdvp_expm_dense_counted": (i, [i, i, i, i, dp, i, dp, d, d, d, i, dp, ip, C.POINTER(Counters)]),

@@ -720,6 +720,112 @@ int mitdvp_env_update(int device, int left, const double* env, const double* sit
   });
 }
 
+// ---- the one-launch small-bond kernel under a chosen launch plan ------------
+namespace {
+// the unplanned chain of a kind (operands null: only "is there a W stage" matters to the plan)
+void small_chain_of(mitdvp::SmallChain& c, int kind, const int* q) {
+  using namespace mitdvp;
+  static const zc w_stage{};  // any non-null address: the plan reads W2 as a flag
+  if (!q) throw ArgError("null argument");
+  const int n = kind == MITDVP_SMALL_KEFF ? 3 : 5;
+  for (int k = 0; k < n; ++k)
+    if (q[k] < 1) throw ArgError("small chain: every extent must be at least 1");
+  if (kind == MITDVP_SMALL_HEFF) small_chain_heff(c, nullptr, &w_stage, nullptr, q[0], q[1], q[2], q[3], q[4]);
+  else if (kind == MITDVP_SMALL_KEFF) small_chain_keff(c, nullptr, nullptr, q[0], q[1], q[2]);
+  else if (kind == MITDVP_SMALL_ENV) small_chain_env(c, nullptr, &w_stage, q[0], q[1], q[2], q[3], q[4]);
+  else throw ArgError("small chain: kind is MITDVP_SMALL_HEFF, _KEFF or _ENV");
+}
+}  // namespace
+
+int mitdvp_small_plan(int kind, const int* dims, int exp_mode, int n_cu, mitdvp_small_plan_t* out) {
+  return guard(nullptr, [&] {
+    using namespace mitdvp;
+    NEED(out);
+    if (n_cu < 1) throw ArgError("mitdvp_small_plan: n_cu must be at least 1");
+    *out = mitdvp_small_plan_t{};
+    SmallChain c;
+    small_chain_of(c, kind, dims);
+    if (!small_chain_plan(c, exp_mode != 0, n_cu)) return;
+    const Carve cv = ss_carve(c, exp_mode != 0);
+    out->ok = 1;
+    out->nsc = c.nsc; out->cs = c.cs; out->spw = c.spw; out->a_resident = c.a_resident;
+    out->grid = ((c.na + c.spw - 1) / c.spw) * c.nsc;
+    out->lds_bytes = (int)small_chain_lds(c, exp_mode != 0);
+    out->sg_aliases_x = cv.Sg == cv.Xs ? 1 : 0;
+  });
+}
+
+int mitdvp_small_apply(int device, int cu_count, int kind, int left, const int* dims, const double* a, const double* w,
+                       const double* r, const double* v, double shift_re, double shift_im, double* out,
+                       mitdvp_small_info* info) {
+  return guard(nullptr, [&] {
+    using namespace mitdvp;
+    NEED(dims); NEED(a); NEED(v); NEED(out); NEED(info);
+    *info = mitdvp_small_info{};
+    const hzc shift(shift_re, shift_im);
+    mitdvp_config cfg = unit_cfg(device);
+    cfg.cu_first = 0;
+    cfg.cu_count = cu_count;  // Engine: a multiple of 8 inside the device
+    Engine e(cfg);
+    hipStream_t st = e.stream();
+    mitdvp_counters c0{}, c1{};
+    if (kind == MITDVP_SMALL_KEFF) {
+      NEED(r);
+      const int d1 = dims[0], d2 = dims[1], m = dims[2];
+      if (d1 < 1 || d2 < 1 || m < 1) throw ArgError("mitdvp_small_apply: every extent must be at least 1");
+      e.ensure_work((long)d1 * d2, (long)d1 * m * d2, 1, 1, 1);
+      Dev dL(st, a, (size_t)d1 * m * d1), dR(st, r, (size_t)d2 * m * d2), ds(st, v, (size_t)d1 * d2), dout((size_t)d1 * d2);
+      e.counters_get(&c0);
+      e.keff_apply(dL.p(), dR.p(), ds.p(), dout.p(), d1, d2, m, shift);
+      e.counters_get(&c1);
+      to_host(st, out, dout.p(), (size_t)d1 * d2);
+    } else if (kind == MITDVP_SMALL_HEFF || kind == MITDVP_SMALL_ENV) {
+      NEED(w);
+      const int dl = dims[0], d = dims[1], dr = dims[2], ml = dims[3], mr = dims[4];
+      if (dl < 1 || d < 1 || dr < 1 || ml < 1 || mr < 1) throw ArgError("mitdvp_small_apply: every extent must be at least 1");
+      e.set_mpo_core(0, 0, w, ml, d, d, mr);
+      const long ns = (long)dl * d * dr, mm = std::max(ml, mr);
+      e.ensure_work(ns, (long)dl * dr * d * mm, (long)dl * dr * d * mm, 1, 1);
+      const MpoSite& ws = e.mpo(0, 0);
+      Dev dv(st, v, ns);
+      if (kind == MITDVP_SMALL_HEFF) {
+        NEED(r);
+        Dev dL(st, a, (size_t)dl * ml * dl), dR(st, r, (size_t)dr * mr * dr), dout(ns);
+        e.counters_get(&c0);
+        e.heff_apply(dL.p(), ws, dR.p(), dv.p(), dout.p(), dl, d, dr, shift);
+        e.counters_get(&c1);
+        to_host(st, out, dout.p(), ns);
+      } else {
+        if (shift != hzc(0.0, 0.0)) throw ArgError("mitdvp_small_apply: an environment update takes no shift");
+        if (left) {  // as Engine's -> sweep issues it: the small-site core w2el beside the general one
+          Dev denv(st, a, (size_t)dl * ml * dl), dout((size_t)dr * mr * dr);
+          e.counters_get(&c0);
+          e.env_update(denv.p(), dv.p(), ws.w2l.p, dout.p(), dl, ml, d, dr, mr, ws.w2el.p);
+          e.counters_get(&c1);
+          to_host(st, out, dout.p(), (size_t)dr * mr * dr);
+        } else {  // <- sweep: the mirrored tensor and w2r / w2er
+          Dev denv(st, a, (size_t)dr * mr * dr), dout((size_t)dl * ml * dl), dbt(ns);
+          transpose_rev3(st, dv.p(), dbt.p(), dl, d, dr);
+          e.counters_get(&c0);
+          e.env_update(denv.p(), dbt.p(), ws.w2r.p, dout.p(), dr, mr, d, dl, ml, ws.w2er.p);
+          e.counters_get(&c1);
+          to_host(st, out, dout.p(), (size_t)dl * ml * dl);
+        }
+      }
+    } else {
+      throw ArgError("mitdvp_small_apply: kind is MITDVP_SMALL_HEFF, _KEFF or _ENV");
+    }
+    e.check_device_errors();  // a launch that gave up (an exchange timed out) is an error of this call
+    info->n_launch = (int)(c1.n_launch - c0.n_launch);
+    const SmallSync::Last& p = e.small_last();
+    if (info->n_launch == 1 && p.mode == SS_MODE_APPLY) {
+      info->plan.ok = 1;
+      info->plan.nsc = p.nsc; info->plan.cs = p.cs; info->plan.spw = p.spw; info->plan.a_resident = p.a_resident;
+      info->plan.grid = p.grid; info->plan.lds_bytes = (int)p.lds; info->plan.sg_aliases_x = p.sg_aliases_x;
+    }
+  });
+}
+
 int mitdvp_gauge_trf(int device, int key, const double* psi, int dl, int d, int dr, double* site_out,
                      double* sigma_out) {
   return guard(nullptr, [&] {

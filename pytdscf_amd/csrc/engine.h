@@ -326,6 +326,7 @@ class Engine {
   // raised here.  The C surface calls it at the end of EVERY entry point, so no call returns tensors, blocks or
   // observables computed by a launch that gave up (fold_block, get_env, expect, ... launch them without a sweep).
   void check_device_errors() { ss_check(); }
+  const SmallSync::Last& small_last() const { return ss_.last; }  // the plan of the most recent one-launch kernel
   const MpoSite& mpo(int op_id, int isite);
   mitdvp_config cfg;
 

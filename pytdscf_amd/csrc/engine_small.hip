@@ -57,36 +57,45 @@ bool Engine::small_ok() const {
 }
 
 // sigma[a,i,r] = sum L[a,c,b] W[c,i,j,t] R[r,t,s] psi[b,j,s]   (_contraction.py:1182-1243)
-bool Engine::chain_heff(SmallChain& c, const zc* L, const MpoSite& w, const zc* R, int dl, int d, int dr, bool exp_mode) const {
+void small_chain_heff(SmallChain& c, const zc* L, const zc* w2l, const zc* R, int dl, int d, int dr, int ml, int mr) {
   c = SmallChain{};
-  c.A = L; c.sAa = (long)w.ml * dl; c.sAc = dl; c.sAb = 1; c.conjA = 0;
-  c.R = R; c.sRr = (long)w.mr * dr; c.sRt = dr; c.sRs = 1;
-  c.W2 = w.w2l.p;
+  c.A = L; c.sAa = (long)ml * dl; c.sAc = dl; c.sAb = 1; c.conjA = 0;
+  c.R = R; c.sRr = (long)mr * dr; c.sRt = dr; c.sRs = 1;
+  c.W2 = w2l;
   c.sBb = (long)d * dr; c.sBj = dr; c.sBs = 1;
-  c.na = dl; c.nb = dl; c.nc = w.ml; c.nj = d; c.ni = d; c.nt = w.mr; c.ns = dr; c.nr = dr;
+  small_extents_heff(c, dl, d, dr, ml, mr);
+}
+bool Engine::chain_heff(SmallChain& c, const zc* L, const MpoSite& w, const zc* R, int dl, int d, int dr, bool exp_mode) const {
+  small_chain_heff(c, L, w.w2l.p, R, dl, d, dr, w.ml, w.mr);
   return small_chain_plan(c, exp_mode, n_cu_);
 }
 
 // sigma'[a,r] = sum L[a,c,b] sigma[b,s] R[r,c,s]   (_contraction.py:1339-1352)
-bool Engine::chain_keff(SmallChain& c, const zc* L, const zc* R, int d1, int d2, int m, bool exp_mode) const {
+void small_chain_keff(SmallChain& c, const zc* L, const zc* R, int d1, int d2, int m) {
   c = SmallChain{};
   c.A = L; c.sAa = (long)m * d1; c.sAc = d1; c.sAb = 1; c.conjA = 0;
   c.R = R; c.sRr = (long)m * d2; c.sRt = d2; c.sRs = 1;
   c.W2 = nullptr;
   c.sBb = d2; c.sBj = 0; c.sBs = 1;
-  c.na = d1; c.nb = d1; c.nc = m; c.nj = 1; c.ni = 1; c.nt = m; c.ns = d2; c.nr = d2;
+  small_extents_keff(c, d1, d2, m);
+}
+bool Engine::chain_keff(SmallChain& c, const zc* L, const zc* R, int d1, int d2, int m, bool exp_mode) const {
+  small_chain_keff(c, L, R, d1, d2, m);
   return small_chain_plan(c, exp_mode, n_cu_);
 }
 
 // env'[i,q,j] = sum conj(T)[m,r,i] env[m,p,n] W2[(r,q),(p,s)] T[n,s,j]   (_contraction.py:148-397):
 // slab = new bra index i; stage 1 contracts the old bra index m, stage 3 the old ket index n.
-bool Engine::chain_env(SmallChain& c, const zc* T, const zc* w2e, int din, int min_, int d, int dout, int mout) const {
+void small_chain_env(SmallChain& c, const zc* T, const zc* w2e, int din, int min_, int d, int dout, int mout) {
   c = SmallChain{};
   c.A = T; c.sAa = 1; c.sAc = dout; c.sAb = (long)d * dout; c.conjA = 1;
   c.R = T; c.sRr = 1; c.sRt = dout; c.sRs = (long)d * dout;
   c.W2 = w2e;
   c.sBb = (long)min_ * din; c.sBj = din; c.sBs = 1;
-  c.na = dout; c.nb = din; c.nc = d; c.nj = min_; c.ni = mout; c.nt = d; c.ns = din; c.nr = dout;
+  small_extents_env(c, din, min_, d, dout, mout);
+}
+bool Engine::chain_env(SmallChain& c, const zc* T, const zc* w2e, int din, int min_, int d, int dout, int mout) const {
+  small_chain_env(c, T, w2e, din, min_, d, dout, mout);
   return small_chain_plan(c, false, n_cu_);
 }
 

@@ -3,6 +3,7 @@
 // k x k projected exponential and the convergence test on the device, no host round trip).
 #pragma once
 #include "common.h"
+#include "small_chain_plan.h"
 #include "vecops.h"
 
 namespace mitdvp {
@@ -40,6 +41,8 @@ struct SmallSync {
   unsigned launches = 0;      // launch sequence number (exchange tags are unique per launch)
   int max_grid = 0;           // compute units this engine may fill with one persistent launch (0: the device's)
   bool partitioned = false;   // the engine's stream owns its compute units (CU mask): no admission control needed
+  // the plan of the most recent launch, as launched (host side; what mitdvp_small_apply reports)
+  struct Last { int mode = -1, nsc = 0, cs = 0, spw = 0, a_resident = 0, grid = 0, sg_aliases_x = 0; size_t lds = 0; } last;
 };
 
 struct SmallExp {
@@ -54,10 +57,18 @@ struct SmallExp {
   long long flops_per_apply;  // algorithmic flops of one apply, summed on the device into stats[2 + stat_slot]
 };
 
-// LDS bytes the chain needs (0 when it does not fit the small family)
+// The carve and the planner are host arithmetic in small_chain_plan.h; these are their instances for SmallChain.
+// LDS bytes the chain needs under its plan
 size_t small_chain_lds(const SmallChain& c, bool exp_mode);
-// choose nsc / cs for a chain whose other fields are set; false when the chain does not qualify
+// choose nsc / cs / spw / a_resident for a chain whose other fields are set; false when the chain does not qualify
 bool small_chain_plan(SmallChain& c, bool exp_mode, int n_cu);
+
+// The three chains, unplanned: operand views and extents (engine_small.hip).  Engine::chain_heff / chain_keff / chain_env
+// plan them for the engine's compute units; mitdvp_small_plan plans them for a number of compute units it is given.
+// w2l: MpoSite::w2l, w2e: MpoSite::w2el / w2er (only "is there a W stage" matters to the plan).
+void small_chain_heff(SmallChain& c, const zc* L, const zc* w2l, const zc* R, int dl, int d, int dr, int ml, int mr);
+void small_chain_keff(SmallChain& c, const zc* L, const zc* R, int d1, int d2, int m);
+void small_chain_env(SmallChain& c, const zc* T, const zc* w2e, int din, int min_, int d, int dout, int mout);
 
 // Persistent launches (kernels whose workgroups exchange data inside the launch and must all be resident, one per
 // compute unit) of several engines on one GPU are admitted against a per-device budget of compute units while more

@@ -45,7 +45,6 @@
 namespace mitdvp {
 namespace {
 
-constexpr int SS_MAXG = 256;
 constexpr int SS_NGR = 2 * SS_PAYMAX;  // granules per workgroup and exchange
 
 #define SS_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
@@ -302,34 +301,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_kry_ritz(KryRitzArgs a) {
   }
 }
 
-// LDS carve (units: zc unless noted); the same arithmetic runs on the host in small_chain_lds
-struct Carve {
-  size_t As, Rs, Ws, Bs, Xs, Ys, Sg, misc, total;  // offsets in zc
-};
-__host__ __device__ inline Carve ss_carve(const SmallChain& c, bool exp_mode) {
-  Carve k{};
-  size_t o = 0;
-  // A_a of the workgroup's slabs: all of them when they fit (a_resident), else one slot re-staged per slab
-  k.As = o; o += (size_t)c.nc * c.nb * (c.a_resident && c.spw > 1 ? c.spw : 1);
-  k.Rs = o; o += (size_t)c.nt * c.cs * c.nr;
-  k.Ws = o; o += c.W2 ? (size_t)c.ni * c.nt * c.nc * c.nj : 0;
-  k.Bs = o;
-  size_t bs = (size_t)c.nb * c.nj * c.cs;
-  if (exp_mode) bs = bs > (size_t)6 * MAXK * MAXK ? bs : (size_t)6 * MAXK * MAXK;  // also the k x k exponential's scratch
-  o += bs;
-  k.Xs = o; o += (size_t)c.nc * c.nj * c.cs;
-  k.Ys = o; o += c.W2 ? (size_t)c.ni * c.nt * c.cs : 0;
-  // this chunk's partial of the output slab; with a W stage it may reuse X's space (stage 3 reads Y and R only)
-  if (c.W2 && (size_t)c.ni * c.nr <= (size_t)c.nc * c.nj * c.cs) k.Sg = k.Xs;
-  else { k.Sg = o; o += (size_t)c.ni * c.nr; }
-  k.misc = o;
-  // misc: pay[SS_PAYMAX] red[SS_PAYMAX] wsh[SS_WAVES*SS_PAYMAX] (doubles) + alpha[MAXK] coef[MAXK] cprev[MAXK] (zc)
-  //       + hess[(MAXK+1)*MAXK] (zc) + beta[MAXK] invb[MAXK+1] (doubles) + ints
-  o += (size_t)((2 + SS_WAVES) * SS_PAYMAX + 1) / 2 + 3 * MAXK + (size_t)(MAXK + 1) * MAXK + (2 * MAXK + 2) / 2 + 8;
-  k.total = o;
-  return k;
-}
-
+// (the LDS carve ss_carve: small_chain_plan.h -- the same arithmetic runs on the host in small_chain_lds)
 __global__ __launch_bounds__(SS_THREADS) void k_small_site(SsArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   zc* sm = reinterpret_cast<zc*>(smem);
@@ -805,67 +777,10 @@ void kry_ritz(hipStream_t st, const KryRitzArgs& a) {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-size_t small_chain_lds(const SmallChain& c, bool exp_mode) { return ss_carve(c, exp_mode).total * sizeof(zc); }
+// the carve and the planner themselves: small_chain_plan.h (host arithmetic, tested on the CPU)
+size_t small_chain_lds(const SmallChain& c, bool exp_mode) { return small_chain_lds_of(c, exp_mode); }
 
-bool small_chain_plan(SmallChain& c, bool exp_mode, int n_cu) {
-  if (c.na < 1 || c.ns < 1 || c.nr < 1 || c.nb < 1) return false;
-  const int gmax = std::min(n_cu, SS_MAXG);
-  c.spw = 1;
-  c.a_resident = 1;
-  // chunks over s: enough workgroups that one holds about 0.4 Mflop of the chain (beyond that the exchanges
-  // between workgroups, not the arithmetic, set the pace), at least 4 columns per chunk, LDS permitting
-  const double flops = 8.0 * c.na * ((double)c.nc * c.nb * c.nj * c.ns + (c.W2 ? (double)c.ni * c.nt * c.nc * c.nj * c.ns : 0.0) +
-                                     (double)c.ni * c.nt * c.ns * c.nr);
-  int want = 1;
-  while (want < 8 && flops / ((double)c.na * want) > 0.6e6) want *= 2;
-  if (c.na <= gmax) {
-    for (int nsc = want; nsc <= 8; nsc *= 2) {
-      if (c.na * nsc > gmax) break;
-      const int cs = (c.ns + nsc - 1) / nsc;
-      if (nsc > 1 && cs < 4) break;
-      if ((nsc - 1) * cs >= c.ns) continue;  // every chunk must be non-empty
-      c.nsc = nsc;
-      c.cs = cs;
-      if (small_chain_lds(c, exp_mode) <= 155 * 1024) return true;
-    }
-    // fewer chunks than wanted: an engine confined to part of the chip (ensemble mode) has fewer compute units than the
-    // chain would like workgroups
-    for (int nsc = want / 2; nsc >= 1; nsc /= 2) {
-      if (c.na * nsc > gmax) continue;
-      const int cs = (c.ns + nsc - 1) / nsc;
-      if ((nsc - 1) * cs >= c.ns) continue;
-      c.nsc = nsc;
-      c.cs = cs;
-      if (small_chain_lds(c, exp_mode) <= 155 * 1024) return true;
-    }
-  }
-  // Still not placed: one slab per workgroup wants more workgroups, or more LDS per workgroup (wide chunks), than the
-  // slice offers.  Several slabs per workgroup (round 5): narrow chunks keep B / R / X / Y small, the grid is
-  // ceil(na / spw) * nsc <= gmax.  Fewest slabs per workgroup first, then the most chunks that fit; A resident if it fits.
-  // (only for slices of at most 64 compute units -- four or more replicas: on larger grids a chain that does not fit with
-  // one slab per workgroup is better served by the general multi-launch kernels, which is what it got before)
-  if (n_cu > 64) return false;
-  for (int spw = 2; spw <= 64 && spw <= 2 * c.na; spw *= 2) {
-    const int ngrp = (c.na + spw - 1) / spw;
-    if (ngrp > gmax) continue;
-    for (int nsc = 8; nsc >= 1; nsc /= 2) {
-      if (ngrp * nsc > gmax) continue;
-      const int cs = (c.ns + nsc - 1) / nsc;
-      if (nsc > 1 && cs < 4) continue;
-      if ((nsc - 1) * cs >= c.ns) continue;
-      c.nsc = nsc;
-      c.cs = cs;
-      c.spw = spw;
-      for (int res = 1; res >= 0; --res) {
-        c.a_resident = res;
-        if (small_chain_lds(c, exp_mode) <= 155 * 1024) return true;
-      }
-    }
-  }
-  c.spw = 1;
-  c.a_resident = 1;
-  return false;
-}
+bool small_chain_plan(SmallChain& c, bool exp_mode, int n_cu) { return small_chain_plan_of(c, exp_mode, n_cu); }
 
 // ---- persistent launches of several engines on one GPU ---------------------------------------------------------
 // k_small_site exchanges data BETWEEN its workgroups inside one launch, so all workgroups of a launch
@@ -1026,6 +941,11 @@ static void ss_launch(hipStream_t st, SmallSync& sy, SsArgs& g, bool exp_mode) {
   }
   g.trace = tracing ? trace_buf : nullptr;
   if (tracing) HIP_CHECK(hipMemsetAsync(trace_buf, 0, 1024 * sizeof(long long), st));
+  {  // what is being launched, for the unit seam that reports it (mitdvp_small_apply)
+    const Carve cv = ss_carve(c, exp_mode);
+    sy.last.mode = g.mode; sy.last.nsc = c.nsc; sy.last.cs = c.cs; sy.last.spw = spw_; sy.last.a_resident = c.a_resident;
+    sy.last.grid = grid_; sy.last.lds = cv.total * sizeof(zc); sy.last.sg_aliases_x = cv.Sg == cv.Xs ? 1 : 0;
+  }
   {
     PersistentLaunch chain(st, grid_, sy.partitioned);  // admitted only when it fits beside the persistent launches in flight
     hipLaunchKernelGGL(k_small_site, dim3(grid_), dim3(SS_THREADS), lds, st, g);

@@ -1,11 +1,11 @@
 // vecops.h -- Krylov vector kernels, transposes, RNG (see vecops.hip)
 #pragma once
 #include "common.h"
+#include "small_chain_plan.h"  // MAXK
 
 namespace mitdvp {
 
 constexpr int NPART = 256;  // partial sums written by every reduction kernel
-constexpr int MAXK = 21;    // Krylov vectors kept: ndim (<= 20) + 1
 
 constexpr int SMALL_VEC_EPT = 16;                 // elements per thread of the single-workgroup kernels
 constexpr long SMALL_VEC_N = 1024L * SMALL_VEC_EPT;  // longest vector they take

@@ -617,6 +617,51 @@ def env_update(env, site, W, left: bool, device=0):
     return out
 
 
+_SMALL_KINDS = {"heff": _lib.SMALL_HEFF, "keff": _lib.SMALL_KEFF, "env": _lib.SMALL_ENV}
+
+
+def small_plan(kind: str, dims, exp_mode: bool = False, n_cu: int = 256):
+    """The launch plan of the one-launch small-bond kernel for a chain on ``n_cu`` compute units (host arithmetic, no GPU):
+    ``kind`` "heff" with dims (dl, d, dr, ml, mr), "keff" (d1, d2, m) or "env" (din, min, d, dout, mout).  A dict with
+    ok, nsc, cs, spw, a_resident, grid, lds_bytes, sg_aliases_x; ok = 0 where the chain does not qualify."""
+    q = (C.c_int * len(dims))(*[int(x) for x in dims])
+    if len(dims) != (3 if kind == "keff" else 5):
+        raise ValueError(f"{kind}: {len(dims)} dims")
+    out = _lib.SmallPlan()
+    _lib.check(_lib.load().mitdvp_small_plan(_SMALL_KINDS[kind], q, int(bool(exp_mode)), int(n_cu), C.byref(out)))
+    return out.as_dict()
+
+
+def small_apply(kind: str, operands, shift=0.0, cu_count: int = 0, left: bool = True, device=0):
+    """One H_eff / K_eff apply or environment update through the engine's production dispatch, on an engine confined to
+    the compute units [0, cu_count) (0: the whole device), with a complex ``shift`` (H_eff, K_eff).  ``operands``:
+    "heff" (L, W, R, psi), "keff" (L, R, sigma), "env" (env, site, W) with ``left``.  Returns (out, info): info["n_launch"]
+    is 1 when the one-launch kernel served the call, and info["plan"] is then the plan it ran."""
+    ops = [_c128(x) for x in operands]
+    null = C.POINTER(C.c_double)()
+    if kind == "heff":
+        L, W, R, v = ops
+        dims = (*v.shape, W.shape[0], W.shape[3])
+        a, w, r, out = L, W, R, np.empty_like(v)
+    elif kind == "keff":
+        L, R, v = ops
+        dims = (v.shape[0], v.shape[1], L.shape[1])
+        a, w, r, out = L, None, R, np.empty_like(v)
+    else:
+        a, v, w = ops
+        dl, d, dr = v.shape
+        ml, mr = w.shape[0], w.shape[3]
+        dims, r = (dl, d, dr, ml, mr), None
+        out = np.empty((dr, mr, dr) if left else (dl, ml, dl), dtype=np.complex128)
+    q = (C.c_int * len(dims))(*dims)
+    info = _lib.SmallInfo()
+    s = complex(shift)
+    _lib.check(_lib.load().mitdvp_small_apply(
+        device, int(cu_count), _SMALL_KINDS[kind], int(bool(left)), q, _dp(a), null if w is None else _dp(w),
+        null if r is None else _dp(r), _dp(v), s.real, s.imag, _dp(out), C.byref(info)))
+    return out, {"n_launch": info.n_launch, "plan": info.plan.as_dict()}
+
+
 def gauge_trf(psi, key: str, device=0):
     """key: "Psi2Asigma" -> (A, sigma);  "Psi2sigmaB" -> (B, sigma)."""
     psi = _c128(psi)
