@@ -261,6 +261,35 @@ int mitdvp_batch_jump_counts(mitdvp_batch* b, long long* counts);
 int mitdvp_batch_set_pair_channel(mitdvp_batch* b, int site, int kind, const double* ops_reim, int nops, int d0, int d1);
 int mitdvp_batch_pair_jump_counts(mitdvp_batch* b, long long* counts);
 int mitdvp_batch_discarded_weight(mitdvp_batch* b, double* weights);
+/* Time-dependent one-site fields of a batch: H(t) = H0 + sum_p a_p(t) G_p with G_p Hermitian on site p and a_p real -- a
+ * laser pulse E(t) on the dipoles, or dynamic disorder xi_p(t) per trajectory.  In the symmetric splitting of a time step
+ * (forward half-sweep dt/2, maps, backward half-sweep dt/2) the term is the one-site unitary exp(-i dt a_p G_p) with a_p at
+ * the step's midpoint: ONE more launch per step for the whole batch while at least one field is set (k_batch_field: one
+ * workgroup per replica), after the forward half-sweep and before the channels' launch; the step is accurate to O(dt^2).
+ * A unitary on the physical index keeps gauge A, so it is applied in place -- no gauge move -- and only the left blocks
+ * above the lowest field site are rebuilt.  With no field set nothing changes.
+ *   mitdvp_batch_set_field: G = V diag(g) V^+ arrives decomposed: `vecs_reim` is V, d x d, row-major [i][k] with column
+ *       k the k-th eigenvector, interleaved re / im; `evals` the d eigenvalues g.  NULL vecs_reim removes the site's
+ *       field.  MITDVP_FIELD_TABLE: the amplitude of the n-th time step of the FIELD CLOCK -- the time steps the batch
+ *       has completed since the last mitdvp_batch_set_field or mitdvp_batch_set_seed -- is table[n] (per_replica == 0:
+ *       ntab doubles shared by all replicas; otherwise [n replicas][ntab], one row each), and 0 from step ntab on; the
+ *       caller supplies midpoint values.  MITDVP_FIELD_OU: a stationary Ornstein-Uhlenbeck process per (trajectory, site),
+ *       constant over a step: xi_0 = sigma z_0, xi_n = a xi_{n-1} + sigma sqrt(1 - a^2) z_n with a = exp(-|dt| / tau)
+ *       (tau == 0: a = 0, white noise; tau in the unit of dt) and z = sqrt(-2 log1p(-u1)) cos(2 pi u2), u1 / u2 the
+ *       uniforms of mitdvp_batch_set_seed for "site" 2 nsite + 2 p and 2 nsite + 2 p + 1 (distinct from every jump draw)
+ *       at the batch's step counter: a trajectory's noise depends on seed, id, site and the sequence of dt only.  ANY
+ *       call resets the field clock and the noise of all sites.  MITDVP_EINVAL (message: mitdvp_last_error(NULL), naming
+ *       the site and the limit; nothing changed, every engine untouched) when the site is out of range, d is not the
+ *       site's physical dimension or above 64, the kind is unknown, ntab < 1 or table is NULL for a table field, sigma or
+ *       tau is negative or not finite, or the replicas run in imaginary time (relax != 0).  mitdvp_batch_sweep refuses
+ *       while a field is set.
+ *   mitdvp_batch_field_values: values[n][nsite], the amplitudes a_p applied in the last time step, 0 where none was.
+ *       One host wait. */
+#define MITDVP_FIELD_TABLE 1
+#define MITDVP_FIELD_OU 2
+int mitdvp_batch_set_field(mitdvp_batch* b, int site, int d, const double* vecs_reim, const double* evals, int kind,
+                           const double* table, int ntab, int per_replica, double sigma, double tau);
+int mitdvp_batch_field_values(mitdvp_batch* b, double* values);
 /* Cross overlaps and one-site matrix elements between two states of a batch (k_batch_cross: one workgroup per PAIR, the
  * pair index is the workgroup index, ONE launch forms every requested pair; k_batch_mean averages them on the device,
  * pair after pair in index order).  A state index 0 .. n-1 names replica i as it is now, n + r names the snapshot of

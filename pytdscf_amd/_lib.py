@@ -160,6 +160,8 @@ VECOP_NAMES = ("dot", "sumsq", "lanczos_update", "lanczos_update_def", "lanczos_
 OBS_NORM, OBS_AUTOCORR, OBS_ENERGY, OBS_RDM = 1, 2, 4, 8
 CHANNEL_GATE, CHANNEL_JUMP = 1, 2
 MAX_JUMP = 16  # operators of one jump channel (BATCH_MAX_JUMP)
+FIELD_TABLE, FIELD_OU = 1, 2
+MAX_FIELD_D = 64  # physical dimension of a site with a field (BATCH_FIELD_MAX_D)
 MAX_DENSITY_KEYS = 64  # keys of one density request (BATCH_DENS_MAX_KEYS)
 
 COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t)
@@ -325,6 +327,8 @@ def load() -> C.CDLL:
         "mitdvp_batch_set_pair_channel": (i, [vp, i, i, dp, i, i, i]),
         "mitdvp_batch_pair_jump_counts": (i, [vp, C.POINTER(C.c_longlong)]),
         "mitdvp_batch_discarded_weight": (i, [vp, dp]),
+        "mitdvp_batch_set_field": (i, [vp, i, i, dp, dp, i, dp, i, i, d, d]),
+        "mitdvp_batch_field_values": (i, [vp, dp]),
         "mitdvp_batch_snapshot": (i, [vp]),
         "mitdvp_batch_set_cross": (i, [vp, i, ip, ip, ip, dp, ip]),
         "mitdvp_batch_cross": (i, [vp, dp, dp, dp]),

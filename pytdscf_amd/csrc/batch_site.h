@@ -108,6 +108,42 @@ struct BatchChanArgs {
 // blocks (the state a forward half-sweep leaves); the same state is left, with the channels applied.
 void batch_channel_launch(hipStream_t st, const BatchChanArgs& a, int nrep);
 
+// ---- time-dependent one-site fields between the half-sweeps (k_batch_field) ----
+// H(t) = H0 + sum_p a_p(t) G_p, G_p = V diag(g) V^+ Hermitian and a_p real: the one-site unitary exp(-i dt a_p G_p) applied
+// IN PLACE to the site tensor (no gauge move), then the left blocks above the lowest field site rebuilt.
+constexpr int BATCH_FIELD_MAX_D = 64;  // physical dimension of a site with a field (its d phases live in LDS)
+enum { BFLD_NONE = 0, BFLD_TABLE = 1, BFLD_OU = 2 };  // the values of MITDVP_FIELD_* (include/mitdvp.h)
+struct BatchFieldSite {
+  int kind, d;            // BFLD_*; the order of G
+  int ntab, per_replica;  // BFLD_TABLE: entries of the table; 0: one row for all replicas, 1: [B][ntab]
+  long long off_v;        // V in BatchFieldArgs::vecs, complex elements: d x d, row-major V[i][k], column k the k-th eigenvector
+  long long off_g;        // g in BatchFieldArgs::evals, doubles: d eigenvalues
+  long long off_t;        // the table in BatchFieldArgs::tables, doubles
+  double sigma;           // BFLD_OU: stationary standard deviation
+};
+struct BatchFieldArgs {
+  int L, lo;                    // lo: the lowest site that carries a field
+  const BatchShape* shp;        // [L], device
+  void* const* ptrs;            // the pointer table of BatchArgs
+  int ptr_stride;
+  const int* status;            // [B]: a replica whose word is set does nothing
+  BatchPlan plan;
+  const BatchFieldSite* fld;    // [L], device
+  const zc* vecs;               // device, V of all fields
+  const double* evals;          // device, g of all fields
+  const double* tables;         // device, the tables of all table fields
+  const double* decay;          // [L][2], device: exp(-|dt| / tau) and sigma sqrt(1 - that^2) of the call's dt (BFLD_OU)
+  double dt;
+  unsigned long long seed;
+  long long step;               // completed time steps of the batch since the seed was set (the generator's counter)
+  long long clock;              // completed time steps since a field or the seed was last set: the table index; 0 draws xi afresh
+  const unsigned long long* ids;  // [B] trajectory ids
+  double* xi;                   // [B][L]: the Ornstein-Uhlenbeck values, the generator's only state
+  double* amp;                  // [B][L]: the amplitudes applied in this step, 0 where the site carries no field
+};
+// one launch: grid = nrep workgroups; precondition and result as batch_channel_launch
+void batch_field_launch(hipStream_t st, const BatchFieldArgs& a, int nrep);
+
 // ---- nearest-neighbour (pair) channels in the same walk (k_batch_pair) ----
 // A pair channel sits on a bond (q, q+1): a gate (one matrix) or a jump channel (2 .. BATCH_MAX_JUMP matrices), each
 // (d_q d_{q+1}) x (d_q d_{q+1}), row-major over (i_q, i_{q+1}).  Envelope, decided on the host (batch_pair_fits): the

@@ -1,6 +1,7 @@
 // batch_site.hip -- batched trajectories: k_batch_sweep, ONE workgroup per replica, a whole half-sweep per launch.
 // (Further down: k_batch_observe / k_batch_mean, the observables of every replica and their ensemble means, one launch each;
 // k_batch_channel, one-site gates and quantum-jump channels between the two half-sweeps of a time step, one launch;
+// k_batch_field, time-dependent one-site fields (pulses, noise) as unitaries applied in place in the same slot, one launch;
 // k_batch_pair, the same walk with nearest-neighbour gates and jump channels: merge, apply, truncated re-split;
 // k_batch_cross / k_batch_snapshot, overlaps and one-site matrix elements between two replicas or their snapshots, one
 // workgroup per pair; k_batch_spectra, the Schmidt spectra of the requested bonds; k_batch_sample, configurations drawn
@@ -1516,6 +1517,125 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_channel(BatchChanArgs g) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Time-dependent one-site fields: k_batch_field, ONE workgroup per replica, one launch per time step while at least one
+// field is set, between the forward half-sweep and the channel launch.  H(t) = H0 + sum_p a_p(t) G_p with G_p = V diag(g) V^+
+// Hermitian (decomposed on the host: the device holds V and g and nothing else) and a_p real: in the symmetric splitting
+// of a time step the term is the one-site unitary exp(-i dt a_p G_p) with a_p taken at the step's midpoint.
+// Precondition and result: the state a forward half-sweep leaves (centre at L-1, sites 0 .. L-2 in gauge A, left blocks
+// valid).  A unitary on the physical index of an isometry leaves it an isometry, so there is NO gauge move -- no QR, no
+// sigma, no absorb: for every site p with a field, ascending,
+//   amplitude  thread 0: a table entry (entry `clock` of the site's table, shared or the replica's own row; 0 past its end)
+//              or the site's Ornstein-Uhlenbeck value xi (xi = sigma z when clock == 0, else decay xi + innov z with
+//              z = sqrt(-2 log1p(-u1)) cos(2 pi u2), u1 / u2 = bc_uniform(seed, id, step, 2L + 2p / 2L + 2p + 1): the keys
+//              from 2L on meet neither the one-site jump keys 0 .. L-1 nor the pair keys L .. 2L-2); it stores xi and
+//              the applied amplitude -- both written by this workgroup only -- and publishes a through LDS
+//   phases     phi_k = exp(-i dt a g_k), thread k < d, in LDS
+//   unitary    T[a,k,s] = phi_k sum_j conj(V[j][k]) C[a,j,s] into the spare tensor, then C[a,i,s] = sum_k V[i][k] T[a,k,s]:
+//              j, then k, ascending, fused multiply-adds; element e belongs to thread e % 512 in both passes; no d x d
+//              matrix per replica is ever formed
+// and then L[p+1] for p = lo .. L-2 (lo: the lowest site with a field) by bt_env in the forward sweep's roles, as the
+// upward walk of k_batch_channel.  An amplitude that is exactly 0 (a table past its end, sigma = 0) skips its site: exp(0)
+// is the identity, the tensor keeps its bits, and lo is the lowest site whose amplitude was not 0 -- none: no block is
+// rebuilt.  The amplitude is the replica's own number, the same in every thread, so the branch is uniform.  No atomics, nothing waits on another workgroup, every loop is bounded by the shapes.
+__device__ __noinline__ void bf_rotate(const zc* V, const zc* phi, zc* C, zc* tmp, int dl, int d, int dr) {
+  const int ddr = d * dr;
+  const long N = (long)dl * ddr;
+  for (long e = threadIdx.x; e < N; e += SS_THREADS) {
+    const int a = (int)(e / ddr), rem = (int)(e - (long)a * ddr), k = rem / dr, s = rem - k * dr;
+    const zc* col = C + (long)a * ddr + s;
+    double re = 0.0, im = 0.0;
+    for (int j = 0; j < d; ++j) {  // conj(V[j][k]) C[a,j,s]
+      const zc v = V[(long)j * d + k], c = col[(long)j * dr];
+      re = fma(v.x, c.x, re); re = fma(v.y, c.y, re);
+      im = fma(v.x, c.y, im); im = fma(-v.y, c.x, im);
+    }
+    const zc f = phi[k];
+    tmp[e] = make_double2(fma(f.x, re, -f.y * im), fma(f.x, im, f.y * re));
+  }
+  __syncthreads();
+  for (long e = threadIdx.x; e < N; e += SS_THREADS) {
+    const int a = (int)(e / ddr), rem = (int)(e - (long)a * ddr), i = rem / dr, s = rem - i * dr;
+    const zc* col = tmp + (long)a * ddr + s;
+    const zc* row = V + (long)i * d;
+    double re = 0.0, im = 0.0;
+    for (int k = 0; k < d; ++k) {
+      const zc v = row[k], c = col[(long)k * dr];
+      re = fma(v.x, c.x, re); re = fma(-v.y, c.y, re);
+      im = fma(v.x, c.y, im); im = fma(v.y, c.x, im);
+    }
+    C[e] = make_double2(re, im);
+  }
+  __syncthreads();
+}
+
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 196 VGPRs -- those of the
+// non-inlined bt_env shared with k_batch_sweep -- so occupancy 2 waves per SIMD (one workgroup per compute unit); 106
+// SGPRs; no vector or scalar register spills; no private memory; 17 928 bytes of LDS (the tiles of bt_env, d phases, the
+// amplitude).  This caller of bt_env moved no figure of k_batch_sweep, k_batch_channel, k_batch_pair or any other kernel
+// of this file (profiles/batch_field_probe.txt), so it needs no instance of its own.
+__global__ __launch_bounds__(SS_THREADS) void k_batch_field(BatchFieldArgs g) {
+  __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
+  __shared__ zc s_phi[BATCH_FIELD_MAX_D];
+  __shared__ double s_amp;
+  zc* tiles = s_tiles;
+
+  const int r = blockIdx.x, tid = threadIdx.x, L = g.L;
+  if (g.status[r] != SS_OK) return;  // a replica that failed in an earlier launch of the call does no more work
+  void* const* tab = g.ptrs + (size_t)r * g.ptr_stride;
+  zc* const* site = reinterpret_cast<zc* const*>(tab);
+  zc* const* envL = reinterpret_cast<zc* const*>(tab + L);
+  const zc* const* w2el = reinterpret_cast<const zc* const*>(tab + 4 * L + 2);
+  zc* scr = reinterpret_cast<zc*>(tab[6 * L + 2]);
+  zc* spare = scr + g.plan.o_spare;
+  zc* X = scr + g.plan.o_x;
+  zc* Y = scr + g.plan.o_y;
+  int lo = -1;  // the lowest site this replica rotated in this step (>= g.lo)
+
+  for (int p = 0; p < L; ++p) {
+    const BatchFieldSite f = g.fld[p];
+    if (f.kind == BFLD_NONE) {
+      if (tid == 0) g.amp[(size_t)r * L + p] = 0.0;
+      continue;
+    }
+    const BatchShape s = g.shp[p];
+    if (tid == 0) {
+      double a = 0.0;
+      if (f.kind == BFLD_TABLE) {
+        if (g.clock < f.ntab) a = g.tables[f.off_t + (f.per_replica ? (long long)r * f.ntab : 0LL) + g.clock];
+      } else {
+        const unsigned long long key = 2ULL * (unsigned long long)L + 2ULL * (unsigned long long)p;
+        const double u1 = bc_uniform(g.seed, g.ids[r], (unsigned long long)g.step, key);
+        const double u2 = bc_uniform(g.seed, g.ids[r], (unsigned long long)g.step, key + 1);
+        const double z = sqrt(-2.0 * log1p(-u1)) * cos(6.283185307179586 * u2);
+        double* xi = g.xi + (size_t)r * L + p;
+        a = g.clock == 0 ? f.sigma * z : fma(g.decay[2 * p], *xi, g.decay[2 * p + 1] * z);
+        *xi = a;
+      }
+      g.amp[(size_t)r * L + p] = a;
+      s_amp = a;
+    }
+    __syncthreads();
+    const double a = s_amp;
+    __syncthreads();  // every thread has its copy: thread 0 may publish the next site's
+    if (a == 0.0) continue;  // exp(0) is the identity exactly: the tensor keeps its bits (a pulse that is over costs nothing)
+    if (lo < 0) lo = p;
+    if (tid < f.d) {
+      const double th = -g.dt * a * g.evals[f.off_g + tid];
+      double sn, cs;
+      sincos(th, &sn, &cs);
+      s_phi[tid] = make_double2(cs, sn);
+    }
+    __syncthreads();
+    bf_rotate(g.vecs + f.off_v, s_phi, site[p], spare, s.dl, s.d, s.dr);  // its closing barrier frees s_phi
+  }
+  if (lo < 0) return;  // nothing was rotated: every left block is still valid
+  for (int p = lo; p < L - 1; ++p) {
+    const BatchShape s = g.shp[p];
+    bt_env(envL[p], site[p], site[p], (long)s.d * s.dr, s.dr, 1, w2el[p], s.dl, s.ml, s.d, s.dr, s.mr, X, Y, envL[p + 1], tiles);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // The same walk with nearest-neighbour (pair) channels: k_batch_pair, ONE workgroup per replica, one launch per time step
 // in the place of k_batch_channel whenever a pair channel is set (k_batch_channel itself is untouched and stays in use
 // otherwise).  Walking down with the centre at p the one-site channel of p acts as above; then, if bond (p-1, p) carries
@@ -2988,6 +3108,14 @@ void batch_channel_launch(hipStream_t st, const BatchChanArgs& a, int nrep) {
   if (nrep < 1 || a.L < 1) throw ArgError("batch: nothing to launch");
   if (a.lo < 0 || a.lo >= a.L) throw ArgError("batch: no channel is set");
   hipLaunchKernelGGL(k_batch_channel, dim3(nrep), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
+
+void batch_field_launch(hipStream_t st, const BatchFieldArgs& a, int nrep) {
+  if (nrep < 1 || a.L < 1) throw ArgError("batch: nothing to launch");
+  if (a.lo < 0 || a.lo >= a.L || !a.fld || !a.vecs || !a.evals || !a.tables || !a.decay || !a.xi || !a.amp)
+    throw ArgError("batch: no field is set");
+  hipLaunchKernelGGL(k_batch_field, dim3(nrep), dim3(SS_THREADS), 0, st, a);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -305,6 +305,15 @@ int mitdvp_batch_discarded_weight(mitdvp_batch* b, double* weights) {
   if (!b || !b->b) { g_err = "null handle"; return MITDVP_EINVAL; }
   return guard(nullptr, [&] { b->b->discarded_weight(weights); });
 }
+int mitdvp_batch_set_field(mitdvp_batch* b, int site, int d, const double* vecs_reim, const double* evals, int kind,
+                           const double* table, int ntab, int per_replica, double sigma, double tau) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_set_field: null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->set_field(site, d, vecs_reim, evals, kind, table, ntab, per_replica, sigma, tau); });
+}
+int mitdvp_batch_field_values(mitdvp_batch* b, double* values) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_field_values: null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->field_values(values); });
+}
 int mitdvp_batch_snapshot(mitdvp_batch* b) {
   if (!b || !b->b) { g_err = "mitdvp_batch_snapshot: null handle"; return MITDVP_EINVAL; }
   return guard(nullptr, [&] { b->b->snapshot(); });

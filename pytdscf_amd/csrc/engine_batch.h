@@ -1,6 +1,7 @@
 // engine_batch.h -- batched trajectories (engine_batch.hip): B borrowed engines stepped by one launch per half-sweep.
 // One-site and nearest-neighbour gates and quantum-jump channels set on the batch act between the two half-sweeps of a
-// time step: one more launch.
+// time step: one more launch.  Time-dependent one-site fields (pulse tables, Ornstein-Uhlenbeck noise) act in the same
+// slot, before the channels: one more launch of their own (k_batch_field).
 #pragma once
 #include <algorithm>
 #include <string>
@@ -96,7 +97,7 @@ class Batch {
   Batch& operator=(const Batch&) = delete;
 
   void step(double dt, int nsteps, int* statuses);        // statuses[i]: SS_OK / SS_ENOTCONV / SS_EZERO of replica i
-  void sweep(double dt, bool forward, int* statuses);  // refused while a channel is set
+  void sweep(double dt, bool forward, int* statuses);  // refused while a channel or a field is set
 
   // One-site channels applied between the two half-sweeps of every time step (k_batch_channel, one more launch per step
   // while at least one is set).  kind: BCH_GATE (nops == 1) or BCH_JUMP (2 <= nops <= BATCH_MAX_JUMP); ops_reim: nops
@@ -117,6 +118,22 @@ class Batch {
   // [B]: sum over the splits since the seed or a channel was last set of the weight each split discarded
   void discarded_weight(double* out);
   bool has_pairs() const { return npair_ > 0; }
+
+  // Time-dependent one-site fields H(t) = H0 + sum_p a_p(t) G_p, applied between the forward half-sweep and the channels
+  // of every time step (k_batch_field, one more launch per step while at least one is set).  G = V diag(g) V^+ arrives
+  // decomposed: vecs_reim is V, d x d, row-major [i][k] with column k the k-th eigenvector, interleaved re / im; evals its
+  // d eigenvalues; null vecs_reim removes the site's field.  kind BFLD_TABLE: the amplitude of the n-th time step of the
+  // field clock is table[n] (per_replica 0: ntab doubles for all replicas; 1: [B][ntab]), 0 past the end; the caller
+  // supplies midpoint values.  kind BFLD_OU: a stationary Ornstein-Uhlenbeck process per (trajectory, site) of standard
+  // deviation sigma and correlation time tau (the unit of dt; 0: white noise), piecewise constant over a step.  The field
+  // clock counts the time steps completed since the last set_field or set_seed call; ANY call of set_field resets it and
+  // the noise state of all sites.  ArgError naming the site and the limit (nothing changed) when the site is out of
+  // range, d is not the site's physical dimension or above BATCH_FIELD_MAX_D, the kind is unknown, ntab < 1 or the table
+  // is null for a table field, sigma or tau is negative or not finite, or the replicas run in imaginary time.
+  void set_field(int site, int d, const double* vecs_reim, const double* evals, int kind, const double* table, int ntab,
+                 int per_replica, double sigma, double tau);
+  void field_values(double* out);  // [B][L]: the amplitudes applied in the last time step, 0 where none was applied
+  bool has_fields() const { return fld_lo_ >= 0; }
 
   // Host destinations of the observables, every one may be null; nrec records on the leading axis (mitdvp_batch_out).
   struct ObsOut {
@@ -343,6 +360,27 @@ class Batch {
   DevArr<long long> d_pcounts_;
   DevArr<double> d_disc_;
 
+  // fields: the table per site with V, g and the amplitude tables (host copies and their device images), the
+  // Ornstein-Uhlenbeck coefficients of the dt they were last computed for, the field clock, the noise state and the
+  // amplitudes of the last step
+  std::vector<BatchFieldSite> fld_, h_fld_;    // [L]
+  std::vector<std::vector<zc>> fld_vecs_;      // [L]
+  std::vector<std::vector<double>> fld_evals_, fld_tabs_;  // [L]
+  std::vector<double> fld_tau_;                // [L]
+  int fld_lo_ = -1;                            // lowest site with a field, -1: none
+  bool fld_dirty_ = false;
+  bool fld_decay_set_ = false;
+  double fld_decay_dt_ = 0.0;
+  long long field_clock_ = 0;
+  std::vector<zc> h_fvecs_;
+  std::vector<double> h_fevals_, h_ftabs_, h_fdecay_;
+  DevArr<BatchFieldSite> d_fld_;
+  DevArr<zc> d_fvecs_;
+  DevArr<double> d_fevals_, d_ftabs_, d_fdecay_, d_fxi_, d_famp_;
+  void check_fields() const;
+  void upload_fields(double dt);
+  void launch_field(double dt, long long step, long long clock);
+
   // What the five requests share lies in their RecordStore; the tail of X_records is one function for all of them.
   void records_of(RecordStore& s, const double* weights, double* values, double* mean);
 
@@ -468,7 +506,7 @@ class Batch {
   DevArr<int> d_rx_steps_;                  // [B]
   void launch_observe(int what, int nsites, long record, long rec_len);
   void launch_density(int nkeys, bool zero_head, long record, long rec_len, long dens_off);
-  void finish(bool ends_forward, int half_sweeps, int* statuses, int other_launches = 0, int channel_passes = 0);
+  void finish(bool ends_forward, int half_sweeps, int* statuses, int other_launches = 0, int channel_passes = 0, int field_passes = 0);
   void finish_observe(int launches, int* statuses);
 };
 

@@ -200,6 +200,16 @@ Batch::Batch(const std::vector<Engine*>& engines) : eng_(engines) {
   chan_ops_.assign((size_t)L_, {});
   pair_.assign((size_t)L_, BatchChanSite{BCH_NONE, 0, 0});
   pair_ops_.assign((size_t)L_, {});
+  d_fld_.reserve((size_t)L_);
+  d_fdecay_.reserve((size_t)2 * L_);
+  d_fxi_.reserve(n * L_);
+  d_famp_.reserve(n * L_);
+  fld_.assign((size_t)L_, BatchFieldSite{BFLD_NONE, 0, 0, 0, 0, 0, 0, 0.0});
+  fld_vecs_.assign((size_t)L_, {});
+  fld_evals_.assign((size_t)L_, {});
+  fld_tabs_.assign((size_t)L_, {});
+  fld_tau_.assign((size_t)L_, 0.0);
+  HIP_CHECK(hipMemsetAsync(d_famp_, 0, n * L_ * sizeof(double), st_));
   reset_generator(0, nullptr);  // nothing is queued on the new stream: no wait; a batch without channels pays two small async operations
 }
 
@@ -339,7 +349,7 @@ void Batch::launch(double dt, bool forward) {
 }
 
 // after the launches of a call: statuses, Krylov memories, counters, and the engines' own bookkeeping
-void Batch::finish(bool ends_forward, int half_sweeps, int* statuses, int other_launches, int channel_passes) {
+void Batch::finish(bool ends_forward, int half_sweeps, int* statuses, int other_launches, int channel_passes, int field_passes) {
   const size_t n = eng_.size();
   std::vector<int> st(n), kp(n * L_);
   std::vector<long long> stats(n * 4);
@@ -368,8 +378,9 @@ void Batch::finish(bool ends_forward, int half_sweeps, int* statuses, int other_
         e.cnt_.n_qr += (long long)channel_passes * 2 * (L_ - 1 - chan_lo_);
         e.cnt_.n_env += (long long)channel_passes * (L_ - 1 - chan_lo_);
       }
+      if (field_passes) e.cnt_.n_env += (long long)field_passes * (L_ - 1 - fld_lo_);  // a field pass: left blocks only
     }
-    if (i == 0) e.cnt_.n_launch += half_sweeps + other_launches + channel_passes;  // the batch's launches are counted once
+    if (i == 0) e.cnt_.n_launch += half_sweeps + other_launches + channel_passes + field_passes;  // the batch's launches are counted once
     const int centre = ends_forward ? L_ - 1 : 0;
     for (int p = 0; p < L_; ++p) e.gauge_[p] = p < centre ? MITDVP_GAUGE_A : (p == centre ? MITDVP_GAUGE_PSI : MITDVP_GAUGE_B);
     e.center_ = centre;
@@ -396,16 +407,21 @@ void Batch::step(double dt, int nsteps, int* statuses) {
     return;
   }
   check_channels();
+  check_fields();
   prepare(true);
   const bool chan = has_channels();  // without a channel: the two launches per step of before, nothing else
+  const bool fld = has_fields();     // nor without a field
   if (chan) upload_channels();
+  if (fld) upload_fields(dt);
   for (int s = 0; s < nsteps; ++s) {
     launch(dt, true);
+    if (fld) launch_field(dt, steps_done_ + s, field_clock_ + s);
     if (chan) launch_channel(steps_done_ + s);
     launch(dt, false);
   }
   steps_done_ += nsteps;
-  finish(false, nsteps * 2, statuses, 0, chan ? nsteps : 0);
+  field_clock_ += nsteps;
+  finish(false, nsteps * 2, statuses, 0, chan ? nsteps : 0, fld ? nsteps : 0);
 }
 
 void Batch::sweep(double dt, bool forward, int* statuses) {
@@ -415,6 +431,9 @@ void Batch::sweep(double dt, bool forward, int* statuses) {
     throw ArgError("batch: a single half-sweep is refused while channels are set (site " + std::to_string(chan_lo_) +
                    (chan_[chan_lo_].kind != BCH_NONE ? " carries one" : " is the lower end of a pair channel") +
                    "): they act between the two half-sweeps of a time step");
+  if (has_fields())
+    throw ArgError("batch: a single half-sweep is refused while fields are set (site " + std::to_string(fld_lo_) +
+                   " carries one): they act between the two half-sweeps of a time step");
   prepare(forward);
   launch(dt, forward);
   finish(L_ > 1 ? forward : false, 1, statuses);
@@ -556,6 +575,138 @@ void Batch::launch_channel(long long step) {
   n_launch_ += 1;
 }
 
+// ---- time-dependent one-site fields between the half-sweeps (k_batch_field) ----
+void Batch::set_field(int site, int d, const double* vecs_reim, const double* evals, int kind, const double* table, int ntab,
+                      int per_replica, double sigma, double tau) {
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  if (site < 0 || site >= L_) throw ArgError("batch: field site " + std::to_string(site) + " is out of range (the chain has " + std::to_string(L_) + " sites)");
+  const std::string at = "batch: field on site " + std::to_string(site) + ": ";
+  const size_t n = eng_.size();
+  if (vecs_reim) {
+    if (kind != BFLD_TABLE && kind != BFLD_OU) throw ArgError(at + "kind must be MITDVP_FIELD_TABLE or MITDVP_FIELD_OU");
+    if (d != shp_[site].d)
+      throw ArgError(at + "the generator is " + std::to_string(d) + " x " + std::to_string(d) + ", the site's physical dimension is " +
+                     std::to_string(shp_[site].d));
+    if (d > BATCH_FIELD_MAX_D)
+      throw ArgError(at + "the physical dimension is " + std::to_string(d) + ", a field takes at most " + std::to_string(BATCH_FIELD_MAX_D));
+    if (!evals) throw ArgError(at + "null eigenvalues");
+    if (kind == BFLD_TABLE && (ntab < 1 || !table))
+      throw ArgError(at + "a table field takes a table of at least 1 entry (got " + (table ? std::to_string(ntab) + " entries" : std::string("a null table")) + ")");
+    if (kind == BFLD_OU && (!std::isfinite(sigma) || sigma < 0.0 || !std::isfinite(tau) || tau < 0.0))
+      throw ArgError(at + "sigma and tau must be finite and >= 0 (got " + std::to_string(sigma) + ", " + std::to_string(tau) + ")");
+    if (eng_[0]->cfg.relax != 0) throw ArgError(at + "fields do not go with imaginary time (relax must be 0)");
+    std::vector<zc> v((size_t)d * d);
+    for (size_t e = 0; e < v.size(); ++e) v[e] = make_double2(vecs_reim[2 * e], vecs_reim[2 * e + 1]);
+    fld_vecs_[site] = std::move(v);
+    fld_evals_[site].assign(evals, evals + d);
+    BatchFieldSite f{kind, d, 0, 0, 0, 0, 0, 0.0};
+    if (kind == BFLD_TABLE) {
+      f.ntab = ntab;
+      f.per_replica = per_replica ? 1 : 0;
+      fld_tabs_[site].assign(table, table + (size_t)ntab * (per_replica ? n : 1));
+      fld_tau_[site] = 0.0;
+    } else {
+      f.sigma = sigma;
+      fld_tabs_[site].clear();
+      fld_tau_[site] = tau;
+    }
+    fld_[site] = f;
+  } else {
+    fld_vecs_[site].clear();
+    fld_evals_[site].clear();
+    fld_tabs_[site].clear();
+    fld_tau_[site] = 0.0;
+    fld_[site] = BatchFieldSite{BFLD_NONE, 0, 0, 0, 0, 0, 0, 0.0};
+  }
+  fld_lo_ = -1;
+  for (int p = L_ - 1; p >= 0; --p)
+    if (fld_[p].kind != BFLD_NONE) fld_lo_ = p;
+  fld_dirty_ = true;
+  fld_decay_set_ = false;
+  field_clock_ = 0;  // any call: the tables start again and the noise of all sites is drawn afresh
+  HIP_CHECK(hipMemsetAsync(d_fxi_, 0, n * L_ * sizeof(double), st_));
+  HIP_CHECK(hipMemsetAsync(d_famp_, 0, n * L_ * sizeof(double), st_));
+}
+
+void Batch::field_values(double* out) {
+  if (!out) throw ArgError("batch: null destination for the field amplitudes");
+  HIP_CHECK(hipSetDevice(device_));
+  HIP_CHECK(hipMemcpyAsync(out, d_famp_, eng_.size() * L_ * sizeof(double), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+// what may have changed on the engines since the fields were set (validate() has just refreshed shp_)
+void Batch::check_fields() const {
+  if (!has_fields()) return;
+  if (eng_[0]->cfg.relax != 0) throw ArgError("batch: fields do not go with imaginary time (relax must be 0)");
+  for (int p = 0; p < L_; ++p)
+    if (fld_[p].kind != BFLD_NONE && fld_[p].d != shp_[p].d)
+      throw ArgError("batch: field on site " + std::to_string(p) + ": the generator no longer matches the site's physical dimension " +
+                     std::to_string(shp_[p].d));
+}
+
+// the device images of the fields, and the Ornstein-Uhlenbeck coefficients of this call's dt
+void Batch::upload_fields(double dt) {
+  if (fld_dirty_) {
+    h_fld_ = fld_;
+    h_fvecs_.clear();
+    h_fevals_.clear();
+    h_ftabs_.clear();
+    for (int p = 0; p < L_; ++p) {
+      h_fld_[p].off_v = (long long)h_fvecs_.size();
+      h_fld_[p].off_g = (long long)h_fevals_.size();
+      h_fld_[p].off_t = (long long)h_ftabs_.size();
+      h_fvecs_.insert(h_fvecs_.end(), fld_vecs_[p].begin(), fld_vecs_[p].end());
+      h_fevals_.insert(h_fevals_.end(), fld_evals_[p].begin(), fld_evals_[p].end());
+      h_ftabs_.insert(h_ftabs_.end(), fld_tabs_[p].begin(), fld_tabs_[p].end());
+    }
+    reserve_synced(d_fvecs_, h_fvecs_.size(), d_fevals_, h_fevals_.size(), d_ftabs_, h_ftabs_.size());
+    HIP_CHECK(hipMemcpyAsync(d_fld_, h_fld_.data(), h_fld_.size() * sizeof(BatchFieldSite), hipMemcpyHostToDevice, st_));
+    if (!h_fvecs_.empty()) HIP_CHECK(hipMemcpyAsync(d_fvecs_, h_fvecs_.data(), h_fvecs_.size() * sizeof(zc), hipMemcpyHostToDevice, st_));
+    if (!h_fevals_.empty()) HIP_CHECK(hipMemcpyAsync(d_fevals_, h_fevals_.data(), h_fevals_.size() * sizeof(double), hipMemcpyHostToDevice, st_));
+    if (!h_ftabs_.empty()) HIP_CHECK(hipMemcpyAsync(d_ftabs_, h_ftabs_.data(), h_ftabs_.size() * sizeof(double), hipMemcpyHostToDevice, st_));
+    fld_dirty_ = false;
+  }
+  if (!fld_decay_set_ || dt != fld_decay_dt_) {  // a = exp(-|dt| / tau) (tau = 0: 0, white noise) and sigma sqrt(1 - a^2)
+    h_fdecay_.assign((size_t)2 * L_, 0.0);
+    for (int p = 0; p < L_; ++p) {
+      if (fld_[p].kind != BFLD_OU) continue;
+      const double a = fld_tau_[p] > 0.0 ? std::exp(-std::fabs(dt) / fld_tau_[p]) : 0.0;
+      h_fdecay_[2 * p] = a;
+      h_fdecay_[2 * p + 1] = fld_[p].sigma * std::sqrt(1.0 - a * a);
+    }
+    HIP_CHECK(hipMemcpyAsync(d_fdecay_, h_fdecay_.data(), h_fdecay_.size() * sizeof(double), hipMemcpyHostToDevice, st_));
+    fld_decay_set_ = true;
+    fld_decay_dt_ = dt;
+  }
+}
+
+void Batch::launch_field(double dt, long long step, long long clock) {
+  BatchFieldArgs a{};
+  a.L = L_;
+  a.lo = fld_lo_;
+  a.shp = d_shp_;
+  a.ptrs = d_ptrs_;
+  a.ptr_stride = (int)ptrs_per_replica();
+  a.status = d_status_;
+  a.plan = plan_;
+  a.fld = d_fld_;
+  a.vecs = d_fvecs_;
+  a.evals = d_fevals_;
+  a.tables = d_ftabs_;
+  a.decay = d_fdecay_;
+  a.dt = dt;
+  a.seed = seed_;
+  a.step = step;
+  a.clock = clock;
+  a.ids = d_ids_;
+  a.xi = d_fxi_;
+  a.amp = d_famp_;
+  batch_field_launch(st_, a, (int)eng_.size());
+  n_launch_ += 1;
+}
+
 void Batch::set_seed(unsigned long long seed, const unsigned long long* ids) {
   HIP_CHECK(hipSetDevice(device_));
   HIP_CHECK(hipStreamSynchronize(st_));  // h_ids_ may still be the source of an earlier copy
@@ -566,6 +717,7 @@ void Batch::reset_generator(unsigned long long seed, const unsigned long long* i
   const size_t n = eng_.size();
   seed_ = seed;
   steps_done_ = 0;
+  field_clock_ = 0;  // the noise of the fields is drawn afresh, their tables start again
   h_ids_.resize(n);
   for (size_t i = 0; i < n; ++i) h_ids_[i] = ids ? ids[i] : (unsigned long long)i;
   HIP_CHECK(hipMemcpyAsync(d_ids_, h_ids_.data(), n * sizeof(unsigned long long), hipMemcpyHostToDevice, st_));
@@ -690,8 +842,11 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   const int per_rec = (what ? 1 : 0) + (nkeys ? 1 : 0);  // launches per record
   const bool chan = has_channels() && nsteps > 0;
   if (chan) check_channels();
+  const bool fld = has_fields() && nsteps > 0;
+  if (fld) check_fields();
   prepare(true, nsteps > 0 || (what & BOBS_ENERGY));
   if (chan) upload_channels();
+  if (fld) upload_fields(dt);
   // nothing refuses from here on: the run replaces the records of the last one, so their buffers may now grow
   if (cx) { cross_rec_.drop(); upload_cross(nrec); }
   if (sp) { spec_rec_.drop(); upload_spectra(nrec); }
@@ -724,6 +879,7 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
   record(0, steps_done_);
   for (int s = 0; s < nsteps; ++s) {
     launch(dt, true);
+    if (fld) launch_field(dt, steps_done_ + s, field_clock_ + s);
     if (chan) launch_channel(steps_done_ + s);
     launch(dt, false);
     if ((s + 1) % every == 0) record((s + 1) / every, steps_done_ + s + 1);
@@ -761,9 +917,10 @@ void Batch::run(double dt, int nsteps, int every, const int* sites, int nsites, 
     HIP_CHECK(hipMemcpyAsync(h_rec_.data(), d_rec_, need_rec * sizeof(double), hipMemcpyDeviceToHost, st_));
   }
   steps_done_ += nsteps;
+  field_clock_ += nsteps;
   const int nreq = (int)cx + (int)sp + (int)sm + (int)ex + (int)xm;  // each: its kernel per record and ONE k_batch_mean
   const int other = (int)nrec * per_rec + (own ? 1 : 0) + nreq * ((int)nrec + 1);
-  if (nsteps > 0) finish(false, nsteps * 2, statuses, other, chan ? nsteps : 0);
+  if (nsteps > 0) finish(false, nsteps * 2, statuses, other, chan ? nsteps : 0, fld ? nsteps : 0);
   else finish_observe(other, statuses);
 
   for (long q = 0; q < nrec; ++q) {

@@ -1175,6 +1175,64 @@ def operate_request(n_replicas, op_id=0, maxstep=10, conv_tol=1.0e-8, replicas=N
     return op_id, maxstep, conv_tol, out
 
 
+def field_request(fields, dims, n_replicas):
+    """The table of ``TDVPBatch.set_fields`` as what the library takes: ``{site: (V, g, kind, table, sigma, tau)}`` with
+    ``G = V diag(g) V^+`` by ``numpy.linalg.eigh``, ``table`` a ``(n,)`` or ``(n_replicas, n)`` array of doubles for a
+    pulse and ``None`` for noise.  ``fields``: ``{site: dict(G=(d, d) Hermitian, pulse=array (n,) | (B, n))}`` or
+    ``dict(G=..., sigma=s, tau=t)``; ``None`` or ``{}`` is no field.  ``ValueError`` naming the site and what is wrong for
+    a site out of range, a ``G`` that is not square, not Hermitian (``|G - G^+|`` above ``1e-12 |G|``) or not of the
+    site's order ``dims[site]``, an unknown key, both ``pulse`` and ``sigma`` or neither, a pulse that is not ``(n,)`` or
+    ``(n_replicas, n)`` with ``n >= 1`` finite real numbers, and a ``sigma`` or ``tau`` that is negative or not finite.
+    Pure Python."""
+    out = {}
+    for site, spec in dict(fields or {}).items():
+        if isinstance(site, bool) or not isinstance(site, (int, np.integer)) or not 0 <= int(site) < len(dims):
+            raise ValueError(f"fields: site {site!r} is out of range (the chain has sites 0 .. {len(dims) - 1})")
+        site = int(site)
+        who = f"fields[{site}]"
+        if not isinstance(spec, dict) or "G" not in spec:
+            raise ValueError(f"{who} must be dict(G=..., pulse=...) or dict(G=..., sigma=..., tau=...)")
+        unknown = sorted(set(spec) - {"G", "pulse", "sigma", "tau"})
+        if unknown:
+            raise ValueError(f"{who}: unknown key {unknown[0]!r} (G, pulse, sigma, tau)")
+        G = np.asarray(spec["G"], dtype=np.complex128)
+        if G.ndim != 2 or G.shape[0] != G.shape[1]:
+            raise ValueError(f"{who}: G must be a square matrix, got shape {G.shape}")
+        if G.shape[0] != dims[site]:
+            raise ValueError(f"{who}: G is of order {G.shape[0]}, the site's physical dimension is {dims[site]}")
+        if not np.all(np.isfinite(G)) or np.linalg.norm(G - G.conj().T) > 1e-12 * np.linalg.norm(G):
+            raise ValueError(f"{who}: G is not Hermitian (|G - G^+| = {np.linalg.norm(G - G.conj().T):.3e}, |G| = "
+                             f"{np.linalg.norm(G):.3e})")
+        has_pulse, has_noise = spec.get("pulse") is not None, spec.get("sigma") is not None
+        if has_pulse == has_noise:
+            raise ValueError(f"{who}: give either pulse (a table of amplitudes) or sigma and tau (noise), "
+                             f"{'not both' if has_pulse else 'one of them'}")
+        g, V = np.linalg.eigh(0.5 * (G + G.conj().T))
+        V, g = np.ascontiguousarray(V, dtype=np.complex128), np.ascontiguousarray(g, dtype=np.float64)
+        if has_pulse:
+            if "tau" in spec and spec["tau"] is not None:
+                raise ValueError(f"{who}: tau goes with sigma (noise), not with pulse")
+            tab = np.asarray(spec["pulse"])
+            if np.iscomplexobj(tab) or tab.dtype == object:
+                raise ValueError(f"{who}: pulse must be real numbers")
+            tab = np.ascontiguousarray(tab, dtype=np.float64)
+            if tab.ndim not in (1, 2) or tab.shape[-1] < 1 or (tab.ndim == 2 and tab.shape[0] != n_replicas):
+                raise ValueError(f"{who}: pulse must have shape (n,) or ({n_replicas}, n) with n >= 1 -- one row per replica; "
+                                 f"got {tab.shape}")
+            if not np.all(np.isfinite(tab)):
+                raise ValueError(f"{who}: pulse must be finite numbers")
+            out[site] = (V, g, _lib.FIELD_TABLE, tab, 0.0, 0.0)
+        else:
+            try:
+                sigma, tau = float(spec["sigma"]), float(spec.get("tau") or 0.0)
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: sigma and tau must be numbers") from None
+            if not (np.isfinite(sigma) and sigma >= 0.0 and np.isfinite(tau) and tau >= 0.0):
+                raise ValueError(f"{who}: sigma = {sigma!r} and tau = {tau!r} must be finite and >= 0")
+            out[site] = (V, g, _lib.FIELD_OU, None, sigma, tau)
+    return out
+
+
 class TDVPBatch:
     """B independent trajectories (replicas) of one chain shape on ONE GPU, any B: one kernel launch per half-sweep for the
     whole batch (``mitdvp_batch_step`` / ``k_batch_sweep``: one workgroup owns one replica, the replica index is the
@@ -1205,6 +1263,7 @@ class TDVPBatch:
         self.statuses = []
         self.records = {}
         self._channels = {}
+        self._fields = {}
         self._seed = None
         self._cross = None
         self._spectra = None
@@ -1235,6 +1294,7 @@ class TDVPBatch:
         self.statuses = []
         self.records = {}
         self._channels = {}
+        self._fields = {}
         self._seed = None
         self._cross = None
         self._spectra = None
@@ -1276,6 +1336,11 @@ class TDVPBatch:
                         raise ValueError(f"the batch has {n} replicas now, trajectory_ids were given for {len(ids)}: "
                                          "call set_jumps again")
                     self._push_seed(seed, ids)
+                for site, spec in self._fields.items():
+                    if spec[3] is not None and spec[3].ndim == 2 and spec[3].shape[0] != n:  # the library reads one row per replica
+                        raise ValueError(f"the batch has {n} replicas now, the pulse of site {site} has {spec[3].shape[0]} rows: "
+                                         "call set_fields again")
+                    self._push_field(site, spec)
                 if self._cross is not None:  # the new handle has no snapshot: a request that names one is refused here
                     self._push_cross(self._cross)
                 if self._spectra is not None:
@@ -1430,6 +1495,55 @@ class TDVPBatch:
         ``sum_{j>r} sigma_j^2 / sum_j sigma_j^2`` (r: the bond's dimension), since the seed or a channel was last set."""
         out = np.zeros(len(self.engines), dtype=np.float64)
         _lib.check(self._lib.mitdvp_batch_discarded_weight(self._handle(), _dp(out)))
+        return out
+
+    # ---- time-dependent one-site fields between the half-sweeps (mitdvp_batch_set_field) ----
+    def _push_field(self, site, spec):
+        if spec is None:
+            _lib.check(self._lib.mitdvp_batch_set_field(self._b, int(site), 0, None, None, 0, None, 0, 0, 0.0, 0.0))
+            return
+        V, g, kind, tab, sigma, tau = spec
+        ntab, per = (0, 0) if tab is None else (tab.shape[-1], int(tab.ndim == 2))
+        _lib.check(self._lib.mitdvp_batch_set_field(self._b, int(site), V.shape[0], _dp(V), _dp(g), kind,
+                                                    None if tab is None else _dp(tab), ntab, per, sigma, tau))
+
+    def set_fields(self, fields):
+        """Time-dependent one-site terms ``H(t) = H0 + sum_p a_p(t) G_p`` for every replica: ``fields`` maps a site to
+        ``dict(G=(d, d) Hermitian, pulse=array (n,) | (B, n))`` -- ``a_p`` of the n-th time step since this call (or the
+        last ``set_jumps``, which sets the seed) is ``pulse[n]``, the same for all replicas or one row per replica, and 0
+        once the table is used up; give midpoint values (``trajectories.pulse_table``) -- or to
+        ``dict(G=..., sigma=s, tau=t)``: a stationary Ornstein-Uhlenbeck process per (trajectory, site) of standard
+        deviation ``s`` and correlation time ``t`` (the unit of ``dt_au``; 0: white noise), the numbers of
+        ``trajectories.field_noise_path`` under the seed and ids of ``set_jumps``.  The table REPLACES the fields set
+        before; ``{}`` or ``None`` removes them all.  Amplitude times ``G`` is in the Hamiltonian's unit.
+
+        Each term acts as the one-site unitary ``exp(-i dt a_p G_p)`` between the two half-sweeps of a time step
+        (``k_batch_field``, one more launch per step while a field is set), before the gates and jump channels; the step
+        is accurate to O(dt^2).  ``G`` is diagonalised here (``numpy.linalg.eigh``).  ``ValueError`` before the library
+        is touched for what ``field_request`` refuses; the library refuses a site of physical dimension above 64 and
+        replicas in imaginary time.  The fields are set again on a library object made anew (see ``set_jumps``)."""
+        n = len(self.engines)
+        dims = [self.engines[0].get_site_shape(p)[1] for p in range(self.engines[0].nsite)]
+        new = field_request(fields, dims, n)
+        self._handle()
+        old = self._fields
+        try:
+            for site in old:
+                if site not in new:
+                    self._push_field(site, None)
+            for site, spec in new.items():
+                self._push_field(site, spec)
+        except Exception:
+            for site in set(old) | set(new):  # back to what was set before
+                self._push_field(site, old.get(site))
+            raise
+        self._fields = new
+
+    def field_values(self):
+        """(B, L) numbers: the amplitude ``a_p`` every replica applied on every site in the last time step, 0 where no
+        field acted."""
+        out = np.zeros((len(self.engines), self.engines[0].nsite), dtype=np.float64)
+        _lib.check(self._lib.mitdvp_batch_field_values(self._handle(), _dp(out)))
         return out
 
     # ---- cross overlaps and one-site matrix elements between replicas (mitdvp_batch_set_cross / _cross) ----

@@ -5,7 +5,9 @@
 One-site gates (``Model(one_gate_to_apply=...)``) and sampled one-site Kraus channels (``jumps=``: quantum-jump
 trajectories at Hilbert-space cost) act between the two half-sweeps of every step, inside the batch (``k_batch_channel``);
 so do sampled nearest-neighbour channels (``jumps={(q, q + 1): B}``: incoherent hopping, correlated decay), which the batch
-applies to the merged two-site tensor and splits again at the bond's dimension (``k_batch_pair``).
+applies to the merged two-site tensor and splits again at the bond's dimension (``k_batch_pair``).  Time-dependent one-site
+terms (``fields=``: a laser pulse of finite length, Ornstein-Uhlenbeck noise per trajectory and site) act in the same slot
+as one-site unitaries applied in place (``k_batch_field``); ``field_normal`` / ``field_noise_path`` restate their generator.
 
 ``correlation_function`` relates two states of the batch to each other: the autocorrelation function without the t/2
 trick and ``<psi| A(t) B |psi>``, contracted for all trajectories by one launch per record (``k_batch_cross``; ``k_batch_cross_mpo``
@@ -54,6 +56,69 @@ def sample_uniform(seed: int, trajectory_id: int, step: int, site: int, shot: in
     seed, trajectory_id, step, site, shot = (int(x) & _M64 for x in (seed, trajectory_id, step, site, shot))
     key = _mix((_mix((_mix((_mix(seed ^ trajectory_id) + step) & _M64) + site) & _M64) + shot) & _M64)
     return (key >> 11) * 2.0 ** -53
+
+
+def field_normal(seed: int, trajectory_id: int, step: int, site: int, nsite: int) -> float:
+    """The standard normal that ``k_batch_field`` draws for the noise on ``site`` of trajectory ``trajectory_id`` in time
+    step ``step`` (completed steps since the seed was set): ``z = sqrt(-2 log1p(-u1)) cos(2 pi u2)`` with
+    ``u1 = jump_uniform(seed, id, step, 2 nsite + 2 site)`` and ``u2 = jump_uniform(seed, id, step, 2 nsite + 2 site + 1)``
+    -- keys that meet neither the one-site jump keys ``0 .. nsite-1`` nor the pair keys ``nsite .. 2 nsite - 2``."""
+    import math
+
+    key = 2 * int(nsite) + 2 * int(site)
+    u1, u2 = jump_uniform(seed, trajectory_id, step, key), jump_uniform(seed, trajectory_id, step, key + 1)
+    return math.sqrt(-2.0 * math.log1p(-u1)) * math.cos(6.283185307179586 * u2)
+
+
+def field_noise_path(seed: int, trajectory_id: int, site: int, nsite: int, sigma: float, tau: float, dts, first_step: int = 0):
+    """The Ornstein-Uhlenbeck amplitudes ``k_batch_field`` applies on ``site`` of trajectory ``trajectory_id`` in the time
+    steps of lengths ``dts`` that follow a reset of the field clock (``set_fields`` or ``set_jumps``) made when the
+    batch's step counter stood at ``first_step``: ``xi_0 = sigma z_0``, ``xi_n = a_n xi_{n-1} + sigma sqrt(1 - a_n^2) z_n``
+    with ``a_n = exp(-|dt_n| / tau)`` (``tau = 0``: 0, white noise) and ``z_n = field_normal(seed, id, first_step + n, site,
+    nsite)``.  ``tau`` in the unit of ``dts``.  Returns an array ``(len(dts),)``."""
+    import math
+
+    out, xi = [], 0.0
+    for n, dt in enumerate(dts):
+        z = field_normal(seed, trajectory_id, first_step + n, site, nsite)
+        if n == 0:
+            xi = sigma * z
+        else:
+            a = math.exp(-abs(dt) / tau) if tau > 0.0 else 0.0
+            xi = a * xi + (sigma * math.sqrt(1.0 - a * a)) * z
+        out.append(xi)
+    return np.array(out, dtype=np.float64)
+
+
+def pulse_table(f, stepsize: float, nsteps: int, t0: float = 0.0):
+    """Midpoint samples of a pulse shape for ``TDVPBatch.set_fields``: ``f(t0 + (n + 1/2) stepsize)`` for
+    ``n = 0 .. nsteps - 1``, the amplitude the symmetric splitting wants for the step from ``t0 + n stepsize`` on."""
+    nsteps = int(nsteps)
+    if nsteps < 1:
+        raise ValueError("pulse_table: nsteps must be >= 1")
+    return np.array([float(f(t0 + (n + 0.5) * stepsize)) for n in range(nsteps)], dtype=np.float64)
+
+
+def _field_table(fields, dims, nrep, stepsize, nsteps):
+    """``fields`` of ``propagate_trajectories`` / ``correlation_function`` as ``TDVPBatch.set_fields`` takes it, checked
+    before any engine exists (``engine.field_request``): a callable ``pulse`` becomes its midpoint table over the run
+    (time in the unit of ``stepsize``), ``tau`` goes from the unit of ``stepsize`` to atomic units."""
+    from .engine import field_request
+
+    table = {}
+    for site, spec in dict(fields or {}).items():
+        if isinstance(spec, dict):
+            spec = dict(spec)
+            if callable(spec.get("pulse")):
+                spec["pulse"] = pulse_table(spec["pulse"], stepsize, max(nsteps, 1))
+            if spec.get("tau") is not None and spec.get("sigma") is not None:
+                try:
+                    spec["tau"] = float(spec["tau"]) / units.au_in_fs
+                except (TypeError, ValueError):
+                    pass  # field_request names it
+        table[site] = spec
+    field_request(table, dims, nrep)
+    return table
 
 
 def _jump_table(jumps, dims):
@@ -222,7 +287,7 @@ def _mps_norm(cores):
 
 def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every=1, weights=None, integrator="arnoldi",
                          conserve_norm=False, thresh_sil=1.0e-09, per_trajectory=False, device=0, operate_maxstep=10,
-                         operate_tol=1.0e-8):
+                         operate_tol=1.0e-8, fields=None):
     """Two-time correlation functions of an ensemble of Hartree products in ONE batch, contracted and averaged on the device
     (``k_batch_cross``, ``mitdvp_batch_run``): no t/2 trick, so complex starts and Hamiltonians that are not complex
     symmetric are fine.
@@ -266,6 +331,11 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
 
     Returns ``{"time": (nrec,) in fs, "mean": (nrec,) complex}`` and, with ``per_trajectory``, ``"trajectories"``
     ``(nrec, len(starts))``.
+
+    ``fields``: time-dependent one-site terms ``H(t) = H0 + sum_p a_p(t) G_p`` as ``propagate_trajectories`` takes them; they
+    act on both replicas of a start.  A per-replica ``pulse`` has one row per REPLICA (two per start with ``A`` and ``B``),
+    and noise is drawn per replica: ``psi_s`` and ``phi_s`` see different paths, so only a shared ``pulse`` gives
+    ``<psi| A(t) B |psi>`` of one driven system.
 
     There is no ``jumps`` argument: under sampled jump channels ``psi`` and ``phi`` would have to jump together with
     probabilities of the pair, which is a different scheme from the independent sampling of ``propagate_trajectories``.
@@ -333,6 +403,7 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
     gates = model.one_gate_to_apply.one_site_gates(model.dims) if model.one_gate_to_apply is not None else {}
     dt_au = stepsize / units.au_in_fs
     nsteps = (maxstep - 1) // every * every
+    field_table = _field_table(fields, dims, len(states), stepsize, nsteps)
     mpo = model.project_mpo(model.hamiltonian.as_mpo(model.dims))
     bt = TDVPBatch(len(states), nsite, device=device, integrator=integrator, conserve_norm=conserve_norm, thresh=thresh_sil)
     norms = None
@@ -365,6 +436,8 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
         else:
             bt.snapshot()
             bt.set_cross([(bt.snap(k), k) for k in range(ns)])
+        if field_table:  # after operate and the snapshot: the field clock starts with the run
+            bt.set_fields(field_table)
         rec = bt.propagate(dt_au, nsteps, observe={"norm": False, "per_replica": False, key: True, key + "_weights": w}, every=every)
     finally:
         bt.close()
@@ -456,7 +529,7 @@ def observable_names(model, observables) -> list[str]:
 def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, weights=None, integrator="lanczos",
                            conserve_norm=True, per_trajectory=False, thresh_sil=1.0e-09, device=0, jumps=None, seed=0,
                            replicas_per_start=1, first_trajectory=0, densities=None, entanglement=None, shots=None,
-                           shot_seed=0, observables=None):
+                           shot_seed=0, observables=None, fields=None):
     """Propagate every Hartree product of ``starts`` under ``model`` and average their reduced densities.
 
     ``model``: a ``Model`` as the shell takes it (one electronic state, Hilbert space); its ``one_gate_to_apply``
@@ -511,7 +584,16 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
     ``"expectations"``, ``{name: (nrec,) complex}`` -- the weighted mean over the trajectories of ``<psi|O|psi>``, not
     normalised, what ``expectations.dat`` holds for one state -- and, with ``per_trajectory``,
     ``"expectation_trajectories"``, ``{name: (nrec, ntraj)}``.  A name the model does not have is a ``ValueError`` naming
-    it.  The default ``None`` leaves the result as it is without the keyword."""
+    it.  The default ``None`` leaves the result as it is without the keyword.
+
+    ``fields``: time-dependent one-site terms ``H(t) = H0 + sum_p a_p(t) G_p``, ``{site: dict(G=(d, d) Hermitian,
+    pulse=...)}`` or ``{site: dict(G=..., sigma=s, tau=t)}`` as ``TDVPBatch.set_fields`` takes them.  ``pulse`` is a table
+    of midpoint amplitudes, ``(n,)`` for all trajectories or ``(ntraj, n)`` (0 once it is used up), or a callable of time,
+    sampled at the midpoints of the run's steps (``pulse_table``); ``sigma`` / ``tau`` is Ornstein-Uhlenbeck noise per
+    (trajectory, site) -- dynamic disorder -- trajectory i of the expanded list drawing ``field_noise_path(seed,
+    first_trajectory + i, site, nsite, ...)``.  Times and ``tau`` are in the unit of ``stepsize`` (fs); amplitude times
+    ``G`` is in the Hamiltonian's unit.  Each term acts as ``exp(-i dt a_p G_p)`` between the half-sweeps, before gates and
+    jumps (``k_batch_field``, one more launch per step); the step is accurate to O(dt^2)."""
     if integrator not in ("lanczos", "arnoldi"):
         raise ValueError(f"Invalid integrator: {integrator}")
     obs_names = observable_names(model, observables)  # an unknown name raises here, before any engine exists
@@ -554,6 +636,7 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
     sites = sorted(set(key_sites))
     dt_au = stepsize / units.au_in_fs
     nsteps = (maxstep - 1) // every * every
+    field_table = _field_table(fields, list(model.dims), nrep, stepsize, nsteps)
     D = model.m_aux_max if model.m_aux_max is not None else 10**9
     mpo = model.project_mpo(model.hamiltonian.as_mpo(model.dims))
     obs_mpos = [model.observables[name].as_mpo(model.dims) for name in obs_names]
@@ -578,8 +661,12 @@ def propagate_trajectories(model, starts, maxstep, stepsize, reduced_density, we
         if bonds:
             bt.set_spectra(bonds)
             req.update(spectra=True, spectra_weights=weights)
+        if field_table:
+            if not jump_table:  # the ids of the noise; with jumps set_jumps has registered these very ids
+                bt.set_jumps({}, seed=seed, trajectory_ids=range(first_trajectory, first_trajectory + nrep))
+            bt.set_fields(field_table)
         if shots is not None:
-            if not jump_table:  # the ids of the draws; with jumps set_jumps has registered these very ids
+            if not jump_table and not field_table:  # the ids of the draws; with jumps set_jumps has registered these very ids
                 bt.set_jumps({}, seed=seed, trajectory_ids=range(first_trajectory, first_trajectory + nrep))
             bt.set_samples(shots, shot_seed)
             req.update(samples=True, samples_weights=weights)
