@@ -510,6 +510,23 @@ int mitdvp_batch_operate(mitdvp_batch* b, int op_id, int maxstep, double conv_to
  * the limit: maxstep outside 1 .. 2^20; conv_tol negative or not finite; replicas whose relax is not 2; a replica whose
  * centre is not at site 0. */
 int mitdvp_batch_relax(mitdvp_batch* b, int maxstep, double conv_tol, double* energies, int* steps, double* history, int* statuses);
+/* Thick restarts of the local Lanczos solve of a relax = 2 batch.  A local solve takes at most min(N, max_diag_krylov)
+ * <= 64 Krylov vectors at a site of N elements (one lane of a wave per row of the projected matrix).  With max_restarts > 0
+ * a solve that has not converged by then keeps its lowest Ritz vector u_0 = sum_j c_j v_j and the next Lanczos vector
+ * u_1 = v_m, on which the projected matrix is tridiagonal again (alpha_0 = theta, beta_0 = beta_{m-1} c_{m-1}), and goes on
+ * from there: no apply of H_eff and no memory beyond the max_diag_krylov + 1 slots the solve has anyway, so that a small
+ * max_diag_krylov (a small scratch area per replica) becomes usable.  The stop rule is unchanged and carries across a
+ * restart.  A solve that is not converged after max_restarts restarts gives its replica MITDVP_ENOTCONV ("Lanczos
+ * Diagonalization is not converged in N basis after R restarts"); the others finish.  max_restarts = 0, the default, is
+ * the solve without restarts: a batch that never calls this launches and computes what it always did, bit for bit.  The
+ * setting holds for mitdvp_batch_relax and for mitdvp_batch_step / _sweep / _run / _run_keys alike, until it is set again.
+ * The call clears the counters below.  MITDVP_EINVAL before the GPU is touched, the message naming the entry point and the
+ * limit: a NULL handle, replicas whose relax is not 2, max_restarts outside 0 .. 4096. */
+int mitdvp_batch_set_relax_restarts(mitdvp_batch* b, int max_restarts);
+/* The restart counters since the last mitdvp_batch_set_relax_restarts (or the creation of the batch).  total [n]: the
+ * restarts replica i has taken; most [n]: the most restarts of any one of its local solves.  Either may be NULL.  One host
+ * wait.  (The applies of H_eff of all cycles are counted in the engines' counters as ever.) */
+int mitdvp_batch_relax_restarts(mitdvp_batch* b, long long* total, int* most);
 /* propagate_along_sweep (_mps_cls.py:798-1014), one direction only. */
 int mitdvp_sweep(mitdvp_engine* h, double dt_au, int forward);
 /* The same half-sweep in parts: the next `nsites` local updates of the half-sweep in progress (one is started when none

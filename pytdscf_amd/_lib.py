@@ -347,6 +347,8 @@ def load() -> C.CDLL:
         "mitdvp_batch_cross_mpo_records": (i, [vp, dp, dp, dp, C.POINTER(C.c_size_t)]),
         "mitdvp_batch_operate": (i, [vp, i, i, d, ip, i, dp, ip, ip]),
         "mitdvp_batch_relax": (i, [vp, i, d, dp, ip, dp, ip]),
+        "mitdvp_batch_set_relax_restarts": (i, [vp, i]),
+        "mitdvp_batch_relax_restarts": (i, [vp, C.POINTER(C.c_longlong), ip]),
         "mitdvp_batch_trilow": (i, [i, dp, dp, ip, i, dp, dp]),
         "mitdvp_cu_mask_probe": (i, [i, C.POINTER(C.c_uint), i, i, C.c_size_t, i, ip]),
     }

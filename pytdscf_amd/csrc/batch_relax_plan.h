@@ -1,6 +1,7 @@
 // batch_relax_plan.h -- the host side of the batched improved relaxation (k_batch_relax, batch_site.hip) that needs no
-// HIP: the cap of the Lanczos eigen-solver's Krylov space and the size of a replica's Krylov-basis carve.  Nothing here
-// includes a HIP header, so that a test can compile it with a plain C++ compiler (tests/helpers/relax_plan_shim.cpp).
+// HIP: the cap of the Lanczos eigen-solver's Krylov space, the range of its restarts and the size of a replica's
+// Krylov-basis carve.  Nothing here includes a HIP header, so that a test can compile it with a plain C++ compiler
+// (tests/helpers/relax_plan_shim.cpp, relax_restart_shim.cpp).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -21,6 +22,18 @@ inline bool batch_relax_kcap_ok(int max_diag_krylov, std::string& why) {
   if (k >= 2 && k <= BATCH_RELAX_MAX_KRYLOV) return true;
   why = "max_diag_krylov = " + std::to_string(k) + ", the batched improved relaxation takes 2 to " +
         std::to_string(BATCH_RELAX_MAX_KRYLOV) + " (one lane of a wave per row of the projected matrix)";
+  return false;
+}
+
+// Thick restarts one local solve may take (BatchRelaxArgs::max_restarts): after min(N, max_diag_krylov) vectors without
+// convergence the basis is folded into its lowest Ritz vector and the next Lanczos vector, and the solve goes on.  0: none.
+constexpr int BATCH_RELAX_MAX_RESTARTS = 4096;
+
+// false + a message naming the value and the range when max_restarts is outside 0 .. BATCH_RELAX_MAX_RESTARTS
+inline bool batch_relax_restarts_ok(int max_restarts, std::string& why) {
+  if (max_restarts >= 0 && max_restarts <= BATCH_RELAX_MAX_RESTARTS) return true;
+  why = "max_restarts = " + std::to_string(max_restarts) + ", the batched improved relaxation takes 0 to " +
+        std::to_string(BATCH_RELAX_MAX_RESTARTS) + " restarts of a local solve";
   return false;
 }
 

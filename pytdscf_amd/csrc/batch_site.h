@@ -63,14 +63,17 @@ void batch_sweep_launch(hipStream_t st, const BatchArgs& a, int nrep);
 struct BatchRelaxArgs {
   int L, forward, nhalf;
   int kcap;                 // max_diag_krylov, 2 .. BATCH_RELAX_MAX_KRYLOV; a solve at a site of N elements takes min(N, kcap)
+  int max_restarts;         // 0 .. BATCH_RELAX_MAX_RESTARTS thick restarts of one local solve (bt_diag); 0: none, as ever
   double thresh, conv_tol;  // of the local solve (coefficient space); of the energy, 0: never stop early
   const BatchShape* shp;    // [L], device
   void* const* ptrs;        // the pointer table of BatchArgs
   int ptr_stride;
   const zc* shift;          // [B]
   int* kprev;               // [B * L]: the Krylov dimension of the last solve at every site
-  int* status;              // [B]: SS_ENOTCONV when a solve did not converge in min(N, kcap) vectors
-  long long* stats;         // [B * 4] as BatchArgs: [0] applies, [2] their flops
+  int* status;              // [B]: SS_ENOTCONV when a solve did not converge in min(N, kcap) vectors and max_restarts restarts
+  long long* stats;         // [B * 4] as BatchArgs: [0] applies (over all cycles of a restarted solve), [2] their flops
+  long long* total;         // [B]: restarts taken, added up over the launches
+  int* most;                // [B]: the most restarts of any one local solve
   BatchPlan plan;           // sized with relax = 2
   double* energy;           // [B]: the last E_n; null (with steps and history): not recorded
   int* steps;               // [B]: full steps run

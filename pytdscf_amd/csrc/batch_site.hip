@@ -698,12 +698,15 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_sweep(BatchArgs g) {
 // min(N, kcap) + 1 NORMALISED vectors, lives in the replica's Krylov carve (BatchPlan::o_u, sized by batch_krylov_carve),
 // written and re-read by this workgroup only.
 // The projected problem: after every new vector wave 0 finds the lowest eigenpair of T_k (bt_trilow), the other seven
-// waves wait at the barrier that publishes the result.  Every loop is bounded: the Lanczos loop by kcap <= 64, the
-// multisection by BT_TRI_ROUNDS, the rest by k.
+// waves wait at the barrier that publishes the result.  Every loop is bounded: the Lanczos loop by (max_restarts + 1) kcap,
+// kcap <= 64 and max_restarts <= BATCH_RELAX_MAX_RESTARTS, the multisection by BT_TRI_ROUNDS, the rest by k.
 
 struct BrSh {  // the eigen-solve's own LDS, 64 doubles each
   double *alpha, *beta, *c, *cprev, *dp, *dm;
   double* out;  // [2]: the lowest Ritz value, |c_k - pad(c_{k-1})|
+  int max_restarts;      // thick restarts one local solve may take (BatchRelaxArgs::max_restarts)
+  long long* rst_total;  // the replica's counters: restarts taken,
+  int* rst_most;         // the most of any one local solve
 };
 
 __device__ __forceinline__ double wave_min64(double v) {
@@ -838,7 +841,9 @@ __device__ __noinline__ double bt_trilow(const double* alpha, const double* beta
 // U[j * N ...), j = 0 .. kcap, slot 0 a copy of x as it came (the reference does not normalise its start either).
 // Element e belongs to thread e % 512 throughout.  After every new vector the lowest eigenpair of T_k; converged when
 // |c_k - pad(c_{k-1})| < thresh in coefficient space, or beta_k < SS_EPS, or k == N; then x = sum_j c_j v_j, renormalised.
-// SS_ENOTCONV after kcap vectors.  *kprev_p <- k; the lowest Ritz value is left in rs.out[0] (behind a barrier).
+// After kcap vectors without convergence: a thick restart (below) while rs.max_restarts allows one, else SS_ENOTCONV; with
+// rs.max_restarts == 0 the loop is the one it always was.  *kprev_p <- k of the last cycle; stats count the applies of all
+// cycles; the lowest Ritz value is left in rs.out[0] (behind a barrier).
 __device__ __noinline__ int bt_diag(const BtOp& op, zc* x, zc* U, long N, int kcap_in, double thresh, zc shift, const BtSh& sh,
                                     const BrSh& rs, int* kprev_p, long long* stats, long long flops_per_apply) {
   const int tid = threadIdx.x;
@@ -846,9 +851,9 @@ __device__ __noinline__ int bt_diag(const BtOp& op, zc* x, zc* U, long N, int kc
   const int kcap = (int)min((long)kcap_in, N);
   for (long e = tid; e < N; e += SS_THREADS) U[e] = x[e];
   __syncthreads();
-  int napply = 0;
+  int napply = 0, nrest = 0;
   int rc = SS_ENOTCONV, kdone = kcap;
-  for (int i = 0; i < kcap; ++i) {
+  for (int i = 0; i < kcap; ++i) {  // a restart at the end of the body sets i back: at most (max_restarts + 1) kcap passes
     const zc* vi = U + (size_t)i * N;
     const zc* vm = U + (size_t)(i > 0 ? i - 1 : 0) * N;
     zc* un = U + (size_t)(i + 1) * N;
@@ -923,8 +928,51 @@ __device__ __noinline__ int bt_diag(const BtOp& op, zc* x, zc* U, long N, int kc
       kdone = k;
       break;
     }
-    if (tid < 64) rs.cprev[tid] = rs.c[tid];
-    __syncthreads();
+    if (k < kcap || nrest >= rs.max_restarts) {
+      if (tid < 64) rs.cprev[tid] = rs.c[tid];
+      __syncthreads();
+      continue;
+    }
+    // Thick restart with the one retained Ritz vector: u_0 = sum_j c_j v_j renormalised, u_1 = v_kcap.  H u_0 = theta u_0 +
+    // s u_1 with s = beta_{kcap-1} c_{kcap-1}, so T stays tridiagonal with alpha_0 = theta and beta_0 = s (signed), and the
+    // recurrence goes on at i = 1.  c_prev = e_1 is the old c in the old basis: the stop rule carries across, and so does
+    // the hint of bt_trilow (out[0] = theta, slack |s|, the exact residual of u_0).  No apply, no new LDS: one pass over
+    // the basis.  Element e is read in every slot and then written in slots 0 and 1 by its owning thread, so there is no
+    // barrier between the combination (summed in the order of the final one below) and the copy.
+    {
+      const zc* vk = U + (size_t)kcap * N;
+      zc* u1 = U + (size_t)N;
+      double s[1] = {0.0};
+      for (long e = tid; e < N; e += SS_THREADS) {
+        double re = 0.0, im = 0.0;
+        for (int j = 0; j < kcap; ++j) {
+          const double cj = rs.c[j];
+          const zc v = U[(size_t)j * N + e];
+          re += cj * v.x;
+          im += cj * v.y;
+        }
+        const zc nx = vk[e];
+        U[e] = make_double2(re, im);
+        u1[e] = nx;
+        s[0] += re * re + im * im;
+      }
+      const double sb = rs.beta[kcap - 1] * rs.c[kcap - 1];
+      wg_reduce(s, sh);  // its first barrier stands behind every read of c and beta above
+      const double inv = 1.0 / sqrt(sh.red[0]);
+      for (long e = tid; e < N; e += SS_THREADS) {  // the same thread wrote U[e] above
+        zc z = U[e];
+        z.x *= inv; z.y *= inv;
+        U[e] = z;
+      }
+      if (tid < 64) rs.cprev[tid] = tid == 0 ? 1.0 : 0.0;
+      if (tid == 0) {
+        rs.alpha[0] = rs.out[0];
+        rs.beta[0] = sb;
+      }
+      __syncthreads();
+    }
+    nrest += 1;
+    i = 0;  // the loop's ++i makes it 1
   }
   if (rc == SS_OK) {  // x = sum_j c_j v_j, renormalised (get_C_sval_states_norm, _mps_cls.py:1083-1084)
     double s[1] = {0.0};
@@ -951,16 +999,20 @@ __device__ __noinline__ int bt_diag(const BtOp& op, zc* x, zc* U, long N, int kc
     __hip_atomic_store(kprev_p, kdone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     stats[0] += napply;
     stats[2] += (long long)napply * flops_per_apply;
+    if (nrest > 0) {
+      *rs.rst_total += nrest;
+      if (nrest > *rs.rst_most) *rs.rst_most = nrest;
+    }
   }
   __syncthreads();
   return rc;
 }
 
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 248 VGPRs, 106 SGPRs, no vector
-// register spills, 52 scalar registers spilled around the calls of the stage functions, 304 bytes of private memory per
+// register spills, 46 scalar registers spilled around the calls of the stage functions, 320 bytes of private memory per
 // lane (the argument blocks the stage functions take by reference: none of it inside a product loop), 23 120 bytes of
-// LDS; occupancy 2 waves per SIMD, i.e. one workgroup (replica) per compute unit.  The kernels that were there before compile to the figures they had
-// (profiles/batch_relax_resources.txt has both listings).
+// LDS; occupancy 2 waves per SIMD, i.e. one workgroup (replica) per compute unit.  The other kernels compile to the figures
+// they had (profiles/batch_relax_resources.txt, batch_relax_restart_resources.txt have the listings).
 __global__ __launch_bounds__(SS_THREADS) void k_batch_relax(BatchRelaxArgs g) {
   __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
   __shared__ zc s_z[2 * BATCH_MAX_BOND];
@@ -982,6 +1034,9 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_relax(BatchRelaxArgs g) {
   rs.out = rs.dm + BATCH_RELAX_MAX_KRYLOV;
 
   const int r = blockIdx.x, tid = threadIdx.x, L = g.L;
+  rs.max_restarts = g.max_restarts;
+  rs.rst_total = g.total + r;
+  rs.rst_most = g.most + r;
   if (g.status[r] != SS_OK) return;  // a replica that failed in an earlier launch of the call does no more work
   void* const* tab = g.ptrs + (size_t)r * g.ptr_stride;
   zc* const* site = reinterpret_cast<zc* const*>(tab);
@@ -3090,6 +3145,8 @@ void batch_sweep_launch(hipStream_t st, const BatchArgs& a, int nrep) {
 void batch_relax_launch(hipStream_t st, const BatchRelaxArgs& a, int nrep) {
   if (nrep < 1 || a.L < 1 || a.nhalf < 1) throw ArgError("batch: nothing to launch");
   if (a.kcap < 2 || a.kcap > BATCH_RELAX_MAX_KRYLOV) throw ArgError("batch: max_diag_krylov must be in [2, 64]");
+  if (a.max_restarts < 0 || a.max_restarts > BATCH_RELAX_MAX_RESTARTS) throw ArgError("batch: max_restarts must be in [0, 4096]");
+  if (!a.total || !a.most) throw ArgError("batch: the relaxation needs its restart counters");
   if (a.plan.total - a.plan.o_u < batch_krylov_carve(a.plan.max_site, a.plan.max_bond, 2, a.kcap))
     throw ArgError("batch: the Krylov carve is too small for the improved relaxation");
   if ((a.energy != nullptr) != (a.steps != nullptr) || (a.energy != nullptr) != (a.history != nullptr) || (a.energy && a.hist_len < 1))

@@ -409,6 +409,14 @@ int mitdvp_batch_relax(mitdvp_batch* b, int maxstep, double conv_tol, double* en
   if (rc != MITDVP_OK) return rc;
   return batch_finish(b, st, statuses);
 }
+int mitdvp_batch_set_relax_restarts(mitdvp_batch* b, int max_restarts) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_set_relax_restarts: null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->set_relax_restarts(max_restarts); });
+}
+int mitdvp_batch_relax_restarts(mitdvp_batch* b, long long* total, int* most) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_relax_restarts: null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->relax_restarts(total, most); });
+}
 int mitdvp_batch_trilow(int device, const double* alpha, const double* beta, const int* k, int ncases, double* theta, double* vec) {
   return guard(nullptr, [&] { mitdvp::batch_trilow(device, alpha, beta, k, ncases, theta, vec); });
 }

@@ -279,6 +279,15 @@ class Batch {
   // limit and leaves everything as it was: maxstep outside 1 .. BATCH_RELAX_MAX_STEPS, conv_tol negative or not finite,
   // replicas whose relax != 2, a replica whose centre is not at site 0.
   void relax(int maxstep, double conv_tol, double* energies, int* steps, double* history, int* statuses);
+  // Thick restarts of the local Lanczos solve (bt_diag): a solve that has not converged after min(N, max_diag_krylov)
+  // vectors folds its basis into the lowest Ritz vector and the next Lanczos vector and goes on, up to max_restarts times;
+  // only then the replica gets SS_ENOTCONV.  0, the default: no restart.  The setting holds for relax(), step, sweep and
+  // run alike.  The call clears the counters.  Refused before the GPU is touched, with an ArgError that names the entry
+  // point and the limit: replicas whose relax != 2, max_restarts outside 0 .. BATCH_RELAX_MAX_RESTARTS.
+  void set_relax_restarts(int max_restarts);
+  // total [B]: the restarts every replica has taken since the setting was made; most [B]: the most of any one of its local
+  // solves.  Either may be null.  One host wait.
+  void relax_restarts(long long* total, int* most);
 
   std::string status_message(int code) const;
   int size() const { return (int)eng_.size(); }
@@ -504,6 +513,9 @@ class Batch {
   void launch_relax(bool forward, int nhalf, double conv_tol, double* energies, int* steps, double* history, int hist_len);
   DevArr<double> d_rx_energy_, d_rx_hist_;  // relax(): [B], [B][maxstep]
   DevArr<int> d_rx_steps_;                  // [B]
+  int rx_restarts_ = 0;                     // set_relax_restarts()
+  DevArr<long long> d_rx_rst_total_;        // [B] restarts taken; made and zeroed by the first launch_relax
+  DevArr<int> d_rx_rst_most_;               // [B] the most of one local solve
   void launch_observe(int what, int nsites, long record, long rec_len);
   void launch_density(int nkeys, bool zero_head, long record, long rec_len, long dens_off);
   void finish(bool ends_forward, int half_sweeps, int* statuses, int other_launches = 0, int channel_passes = 0, int field_passes = 0);

@@ -298,11 +298,18 @@ void Batch::prepare(bool forward, bool build_envs) {
 // improved relaxation: nhalf half-sweeps of k_batch_relax in one launch; energies / steps / history null: not recorded
 void Batch::launch_relax(bool forward, int nhalf, double conv_tol, double* energies, int* steps, double* history, int hist_len) {
   Engine& e0 = *eng_[0];
+  const size_t n = eng_.size();
+  if (!d_rx_rst_total_.fits(n) || !d_rx_rst_most_.fits(n)) {  // once in the life of a batch
+    reserve_synced(d_rx_rst_total_, n, d_rx_rst_most_, n);
+    HIP_CHECK(hipMemsetAsync(d_rx_rst_total_, 0, n * sizeof(long long), st_));
+    HIP_CHECK(hipMemsetAsync(d_rx_rst_most_, 0, n * sizeof(int), st_));
+  }
   BatchRelaxArgs a{};
   a.L = L_;
   a.forward = forward ? 1 : 0;
   a.nhalf = nhalf;
   a.kcap = e0.max_diag_krylov_;
+  a.max_restarts = rx_restarts_;
   a.thresh = e0.cfg.thresh;
   a.conv_tol = conv_tol;
   a.shp = d_shp_;
@@ -312,12 +319,14 @@ void Batch::launch_relax(bool forward, int nhalf, double conv_tol, double* energ
   a.kprev = d_kprev_;
   a.status = d_status_;
   a.stats = d_stats_;
+  a.total = d_rx_rst_total_;
+  a.most = d_rx_rst_most_;
   a.plan = plan_;
   a.energy = energies;
   a.steps = steps;
   a.history = history;
   a.hist_len = hist_len;
-  batch_relax_launch(st_, a, (int)eng_.size());
+  batch_relax_launch(st_, a, (int)n);
   n_launch_ += 1;
 }
 
@@ -1748,6 +1757,35 @@ void Batch::relax(int maxstep, double conv_tol, double* energies, int* steps, do
   if (history) std::memcpy(history, o_hist.data(), nh * sizeof(double));
 }
 
+void Batch::set_relax_restarts(int max_restarts) {
+  const std::string at = "mitdvp_batch_set_relax_restarts: ";
+  if (eng_[0]->cfg.relax != 2)
+    throw ArgError(at + "the replicas have relax = " + std::to_string(eng_[0]->cfg.relax) + ", restarts belong to improved relaxation (relax must be 2)");
+  std::string bad;
+  if (!batch_relax_restarts_ok(max_restarts, bad)) throw ArgError(at + bad);
+  rx_restarts_ = max_restarts;
+  const size_t n = eng_.size();
+  if (d_rx_rst_total_.fits(n) && d_rx_rst_most_.fits(n)) {  // behind the launches queued so far; before the first launch there is nothing to clear
+    HIP_CHECK(hipSetDevice(device_));
+    HIP_CHECK(hipMemsetAsync(d_rx_rst_total_, 0, n * sizeof(long long), st_));
+    HIP_CHECK(hipMemsetAsync(d_rx_rst_most_, 0, n * sizeof(int), st_));
+  }
+}
+
+void Batch::relax_restarts(long long* total, int* most) {
+  const size_t n = eng_.size();
+  std::vector<long long> t(n, 0);
+  std::vector<int> m(n, 0);
+  if (d_rx_rst_total_.fits(n) && d_rx_rst_most_.fits(n)) {
+    HIP_CHECK(hipSetDevice(device_));
+    HIP_CHECK(hipMemcpyAsync(t.data(), d_rx_rst_total_, n * sizeof(long long), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipMemcpyAsync(m.data(), d_rx_rst_most_, n * sizeof(int), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+  }
+  if (total) std::memcpy(total, t.data(), n * sizeof(long long));
+  if (most) std::memcpy(most, m.data(), n * sizeof(int));
+}
+
 // the eigen-solve of the improved relaxation alone (k_batch_trilow), for tests
 void batch_trilow(int device, const double* alpha, const double* beta, const int* k, int ncases, double* theta, double* vec) {
   const std::string at = "mitdvp_batch_trilow: ";
@@ -1787,7 +1825,8 @@ void batch_trilow(int device, const double* alpha, const double* beta, const int
 std::string Batch::status_message(int code) const {
   const Engine& e0 = *eng_[0];
   if (code == SS_ENOTCONV && e0.cfg.relax == 2)  // Engine::krylov_diag's words; a site of fewer elements than the cap stops at k = N
-    return "Lanczos Diagonalization is not converged in " + std::to_string(e0.max_diag_krylov_) + " basis";
+    return "Lanczos Diagonalization is not converged in " + std::to_string(e0.max_diag_krylov_) + " basis" +
+           (rx_restarts_ > 0 ? " after " + std::to_string(rx_restarts_) + " restarts" : std::string());
   if (code == SS_ENOTCONV)
     return std::string(has_pairs() ? "The split of a pair channel is not converged in " + std::to_string(BATCH_PAIR_MAX_SWEEPS) + " Jacobi sweeps, or " : "") +
            std::string(e0.cfg.integrator == MITDVP_LANCZOS ? "Short Iterative Lanczos" : "Short Iterative Arnoldi") +

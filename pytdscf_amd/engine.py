@@ -1248,7 +1248,9 @@ class TDVPBatch:
     replaces each site tensor by the lowest eigenvector of its effective Hamiltonian (``k_batch_relax``; a Lanczos solver
     that stays on the device) and skips the bond step.  ``propagate``, ``sweep`` and ``propagate(observe=...)`` work as
     ever, two launches per step; their ``dt_au`` means nothing there, as for ``TDVPEngine(relax="improved")``.  ``relax``
-    runs many steps in one launch and stops each replica when its energy has converged.
+    runs many steps in one launch and stops each replica when its energy has converged.  A local solve takes at most
+    ``max_diag_krylov`` <= 64 vectors; ``set_relax_restarts`` lets it restart from its lowest Ritz vector instead of
+    giving up there.
     """
 
     def __init__(self, n_replicas: int, nsite: int, *, device: int = 0, **engine_kw):
@@ -1272,6 +1274,7 @@ class TDVPBatch:
         self._cross_mpo = None
         self.operated = {}
         self.relaxed = {}
+        self._restarts = None
         self._lib = _lib.load()
         try:
             for _ in range(n_replicas):
@@ -1303,6 +1306,7 @@ class TDVPBatch:
         self._cross_mpo = None
         self.operated = {}
         self.relaxed = {}
+        self._restarts = None
         self._lib = _lib.load()
         return self
 
@@ -1351,6 +1355,8 @@ class TDVPBatch:
                     self._push_expect(self._expect)
                 if self._cross_mpo is not None:
                     self._push_cross_mpo(self._cross_mpo)
+                if self._restarts is not None:
+                    _lib.check(self._lib.mitdvp_batch_set_relax_restarts(self._b, self._restarts))
             except Exception:
                 self._drop()
                 raise
@@ -1895,6 +1901,28 @@ class TDVPBatch:
     def launches(self) -> int:
         """kernel launches counted so far on replica 0, where the batch's launches are counted once"""
         return int(self.engines[0].counters()["n_launch"])
+
+    def set_relax_restarts(self, n: int):
+        """Lets a local Lanczos solve of ``relax="improved"`` replicas restart up to ``n`` times
+        (``mitdvp_batch_set_relax_restarts``): a solve that has not converged after ``max_diag_krylov`` (at most 64)
+        vectors keeps its lowest Ritz vector and the next Lanczos vector and goes on, at no further apply and no further
+        memory, so that hard realisations converge and a small ``max_diag_krylov`` becomes usable.  ``n = 0``, the default
+        of a batch, is the solve without restarts, bit for bit; ``n`` is at most 4096.  The setting holds for ``relax``,
+        ``propagate`` and ``sweep`` alike, and the call clears the counters of ``relax_restarts``.  The library validates
+        (the replicas' ``relax``, the range) and a refused call leaves the setting before in place."""
+        n = int(n)
+        _lib.check(self._lib.mitdvp_batch_set_relax_restarts(self._handle(), n))
+        self._restarts = n
+
+    def relax_restarts(self):
+        """``{"total": (B,) int64, "most": (B,) int32}``: the restarts every replica has taken since
+        ``set_relax_restarts`` (or since the batch was made), and the most restarts of any one of its local solves."""
+        n = len(self.engines)
+        total = np.zeros(n, dtype=np.int64)
+        most = np.zeros(n, dtype=np.int32)
+        _lib.check(self._lib.mitdvp_batch_relax_restarts(self._handle(), total.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                         most.ctypes.data_as(C.POINTER(C.c_int))))
+        return {"total": total, "most": most}
 
     def _run(self, call):
         n = len(self.engines)

@@ -448,7 +448,8 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
     return out
 
 
-def relax_trajectories(models, starts=None, maxstep=20, conv_tol=1.0e-10, thresh_sil=1.0e-09, device=0):
+def relax_trajectories(models, starts=None, maxstep=20, conv_tol=1.0e-10, thresh_sil=1.0e-09, device=0, max_diag_krylov=0,
+                       max_restarts=0):
     """Ground states of an ensemble by improved relaxation in ONE batch and one launch (``TDVPBatch.relax``,
     ``k_batch_relax``): the reference's ``Simulator.relax(improved=True)`` for every realisation at once.
 
@@ -457,12 +458,17 @@ def relax_trajectories(models, starts=None, maxstep=20, conv_tol=1.0e-10, thresh
     or MPS cores as ``core_starts`` takes them (``correlation_function`` explains both); default: each model's own initial
     state, ``init_HartreeProduct`` padded to ``m_aux_max``.  A replica stops on its own once its energy changes by no
     more than ``conv_tol`` from one step to the next, ``maxstep`` steps at the most; ``thresh_sil`` is the threshold of
-    the local Lanczos solver.
+    the local Lanczos solver.  ``max_diag_krylov``: the most Krylov vectors of one local solve, 2 .. 64 (0: 64);
+    ``max_restarts``: the restarts such a solve may take before its replica gives up (``TDVPBatch.set_relax_restarts``;
+    0: none).  From random or product starts some realisations need more than 64 vectors at a site: a few restarts let
+    them through, and with restarts a small ``max_diag_krylov`` (a scratch area per replica of ``max_diag_krylov + 1``
+    site tensors) converges too, at more applies.
 
     Returns ``{"energy": (B,), "steps": (B,) int, "history": (B, maxstep) with NaN behind a replica's stop, "states":
     [cores of replica 0, ...]}``; the states are normalised MPS cores with the centre at site 0, in the form
     ``correlation_function(starts=...)`` and ``propagate_trajectories`` accept.  The energies contain the Hamiltonian's
-    scalar term.  A model the batch does not take raises with the library's message; nothing falls back."""
+    scalar term.  With ``max_restarts > 0`` there is also ``"restarts"``: (B,) int64, the restarts every replica took.
+    A model the batch does not take raises with the library's message; nothing falls back."""
     models = list(models) if isinstance(models, (list, tuple)) else [models]
     if not models:
         raise ValueError("relax_trajectories: no model")
@@ -482,7 +488,8 @@ def relax_trajectories(models, starts=None, maxstep=20, conv_tol=1.0e-10, thresh
         if len(starts) != ns:
             raise ValueError(f"relax_trajectories: {len(starts)} starts for {ns} models (one start per replica)")
         mps_starts = core_starts(starts, dims, D)
-    bt = TDVPBatch(ns, nsite, device=device, relax="improved", thresh=thresh_sil)
+    kw = {"max_diag_krylov": max_diag_krylov} if max_diag_krylov else {}
+    bt = TDVPBatch(ns, nsite, device=device, relax="improved", thresh=thresh_sil, **kw)
     try:
         for k, (e, m) in enumerate(zip(bt.engines, models)):
             e.set_mpo(m.project_mpo(m.hamiltonian.as_mpo(m.dims)), 0, shift=m.hamiltonian.coupleJ[0][0])
@@ -493,7 +500,11 @@ def relax_trajectories(models, starts=None, maxstep=20, conv_tol=1.0e-10, thresh
             else:
                 cores = mps_starts[k]
             e.set_mps(cores, canonicalize=True, scale=1.0)
+        if max_restarts:
+            bt.set_relax_restarts(max_restarts)
         out = bt.relax(maxstep, conv_tol)
+        if max_restarts:
+            out["restarts"] = bt.relax_restarts()["total"]
         out["states"] = [e.get_mps() for e in bt.engines]
     finally:
         bt.close()
