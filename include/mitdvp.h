@@ -527,6 +527,37 @@ int mitdvp_batch_set_relax_restarts(mitdvp_batch* b, int max_restarts);
  * restarts replica i has taken; most [n]: the most restarts of any one of its local solves.  Either may be NULL.  One host
  * wait.  (The applies of H_eff of all cycles are counted in the engines' counters as ever.) */
 int mitdvp_batch_relax_restarts(mitdvp_batch* b, long long* total, int* most);
+/* Excited states of a relax = 2 batch by deflation against stored states (the penalty method).  A batch owns up to 8
+ * slots; each holds a copy of every replica's site tensors and one weight per replica.  While the set is not empty,
+ * mitdvp_batch_relax and the relax = 2 paths of mitdvp_batch_step / _sweep / _run / _run_keys solve every local problem on
+ *   H_eff + shift + sum_k w_k |q_k><q_k|,
+ * q_k being the stored state phi_k projected into the replica's current site basis: the same number of launches, one
+ * workgroup per replica (k_batch_relax_defl); the overlap blocks that give q_k are built at the start of every launch from
+ * the tensors as they stand and carried through the sweep, nothing of them persists between launches.  The stop rule, the
+ * restarts, the Krylov memories and the status words are those of mitdvp_batch_relax; E_n, the lowest Ritz value at site
+ * 0, is then the energy PLUS sum_k w_k |<phi_k|psi>|^2 (use the energy observable for <psi|H|psi>).  With an empty set
+ * the batch launches the kernel it always launched and computes the same bits.
+ * The method finds state k only if every w exceeds the gap to it from the stored states below: a weight that is too small
+ * lets the solve fall back onto a stored state.  A fresh start must not BE a stored state: that is an exact eigenvector of
+ * the penalised operator (eigenvalue E + w) and the Lanczos solve stops on it at once.
+ * mitdvp_batch_deflate_push copies the present state of every replica into the next free slot (ONE launch, one host wait).
+ * The centre must be at site 0 and the chain canonical around it, the state mitdvp_batch_relax leaves.  weights: n doubles,
+ * one per replica, each finite and > 0.  The states are stored as they are: the penalty is w |<phi|psi>|^2, so the caller
+ * pushes normalised states (mitdvp_batch_relax leaves them normalised).  Refused with MITDVP_EINVAL before the GPU is
+ * touched, everything left as it was, the message naming the entry point and the limit: a NULL handle; replicas whose
+ * relax is not 2; a replica whose centre is not at site 0; a ninth push; NULL weights; a weight that is not finite or not
+ * > 0 (the message names the replica); a work buffer (replicas x slots x (sum_p dl_p^2 + max_p N_p) x 16 bytes) above 2^32
+ * bytes: the message names both figures and the largest number of slots that fits.
+ * mitdvp_batch_deflate_clear empties the set; mitdvp_batch_deflate_count reports how many slots are filled.  The set is
+ * also dropped when the replicas' shapes change (where the snapshot is dropped); it is independent of the snapshot, of
+ * the cross / expect / spectra / samples requests, of channels and of fields.
+ * mitdvp_batch_deflate_overlaps: reim [count][n][2] receives <phi_k|psi_r> for every slot k and replica r (ONE launch,
+ * one workgroup per (slot, replica), one host wait; an empty set: no launch, nothing written).  The centre may be at site
+ * 0 or at site nsite-1.  Neither the replicas nor the slots are written. */
+int mitdvp_batch_deflate_push(mitdvp_batch* b, const double* weights);
+int mitdvp_batch_deflate_clear(mitdvp_batch* b);
+int mitdvp_batch_deflate_count(mitdvp_batch* b, int* count);
+int mitdvp_batch_deflate_overlaps(mitdvp_batch* b, double* reim);
 /* propagate_along_sweep (_mps_cls.py:798-1014), one direction only. */
 int mitdvp_sweep(mitdvp_engine* h, double dt_au, int forward);
 /* The same half-sweep in parts: the next `nsites` local updates of the half-sweep in progress (one is started when none

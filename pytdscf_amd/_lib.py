@@ -349,6 +349,10 @@ def load() -> C.CDLL:
         "mitdvp_batch_relax": (i, [vp, i, d, dp, ip, dp, ip]),
         "mitdvp_batch_set_relax_restarts": (i, [vp, i]),
         "mitdvp_batch_relax_restarts": (i, [vp, C.POINTER(C.c_longlong), ip]),
+        "mitdvp_batch_deflate_push": (i, [vp, dp]),
+        "mitdvp_batch_deflate_clear": (i, [vp]),
+        "mitdvp_batch_deflate_count": (i, [vp, ip]),
+        "mitdvp_batch_deflate_overlaps": (i, [vp, dp]),
         "mitdvp_batch_trilow": (i, [i, dp, dp, ip, i, dp, dp]),
         "mitdvp_cu_mask_probe": (i, [i, C.POINTER(C.c_uint), i, i, C.c_size_t, i, ip]),
     }

@@ -5,6 +5,7 @@
 
 #include "batch_block_check.h"
 #include "batch_cross_mpo_plan.h"
+#include "batch_deflate_plan.h"
 #include "batch_operate_plan.h"
 #include "batch_relax_plan.h"
 #include "batch_shape.h"
@@ -81,6 +82,40 @@ struct BatchRelaxArgs {
   int hist_len;
 };
 void batch_relax_launch(hipStream_t st, const BatchRelaxArgs& a, int nrep);
+
+// ---- excited states by deflation against stored states (k_batch_relax_defl, k_batch_defl_overlaps) ----
+// The same sweep with every local solve on H_eff + shift + sum_k w_k |q_k><q_k|, q_k the stored state phi_k projected
+// into the replica's basis at the site (the penalty method).  A stored state is a copy of all site tensors of every
+// replica in the snapshot's layout [B][snap_len]; the overlap blocks that give q_k are built at the start of the launch
+// and carried through the sweep in `work` (BatchDeflatePlan, batch_deflate_plan.h, which needs no HIP).  E_n is then the
+// energy plus sum_k w_k |<phi_k|psi>|^2.  BATCH_MAX_DEFLATE = 8 stored states.
+struct BatchDeflArgs {
+  int count;                            // stored states, 1 .. BATCH_MAX_DEFLATE
+  const zc* slot[BATCH_MAX_DEFLATE];    // [B][snap_len] each, device
+  size_t snap_len;                      // sum of the site sizes, complex elements
+  const double* w;                      // [count][B]: the weights
+  zc* work;                             // [B][plan.per]: blocks [count][blk_len], then q_k [count][max_site]
+  BatchDeflatePlan plan;                // for `count` slots
+};
+struct BatchRelaxDeflArgs {
+  BatchRelaxArgs r;
+  BatchDeflArgs d;
+};
+// one launch: grid = nrep workgroups, as batch_relax_launch; the stored states are only read
+void batch_relax_defl_launch(hipStream_t st, const BatchRelaxArgs& a, const BatchDeflArgs& d, int nrep);
+struct BatchDeflOvArgs {
+  int L, nrep, count;
+  const BatchShape* shp;                // [L], device
+  void* const* ptrs;                    // the pointer table of BatchArgs (only its site tensors are read)
+  int ptr_stride;
+  const zc* slot[BATCH_MAX_DEFLATE];
+  size_t snap_len;
+  zc* buf;                              // [count * B][buf_len]: T, its successor and U of each workgroup
+  size_t o_t2, o_u, buf_len;            // as BatchCrossArgs
+  double* rec;                          // [count][B][2]: (re, im) of <phi_k | psi_r>
+};
+// one launch: grid = count * nrep workgroups; replicas and stored states are only read
+void batch_defl_overlaps_launch(hipStream_t st, const BatchDeflOvArgs& a);
 // test hook (k_batch_trilow): the eigen-solve of bt_diag alone, one workgroup of one wave per case.  alpha / beta:
 // [ncases][64] diagonal and off-diagonal, k: [ncases] in 1 .. 64; theta: [ncases] the lowest eigenvalue, vec: [ncases][64]
 // its unit eigenvector with a non-negative first component, zeros behind k.  All device pointers.

@@ -8,7 +8,9 @@
 // from every replica's state, one workgroup per replica; k_batch_expect, expectation values of MPO observables, one
 // workgroup per replica and operator; k_batch_cross_mpo, matrix elements of MPOs between two replicas or snapshots, one
 // workgroup per entry; k_batch_operate, an MPO applied to the replicas; k_batch_relax, right behind k_batch_sweep, the same
-// sweep with the lowest eigenvector of H_eff in place of the exponential: improved relaxation.)
+// sweep with the lowest eigenvector of H_eff in place of the exponential: improved relaxation; k_batch_relax_defl, the same
+// text with rank-one penalties on stored states added to every local solve: excited states by deflation, and
+// k_batch_defl_overlaps, the overlaps with the stored states.)
 //
 // At trajectory shapes (d = 2..4, D <= 32, M <= 16) a local problem is a few tens of kilobytes, so one workgroup can own
 // one replica completely: the replica index is blockIdx.x, nothing is exchanged between workgroups, and therefore there is
@@ -844,8 +846,58 @@ __device__ __noinline__ double bt_trilow(const double* alpha, const double* beta
 // After kcap vectors without convergence: a thick restart (below) while rs.max_restarts allows one, else SS_ENOTCONV; with
 // rs.max_restarts == 0 the loop is the one it always was.  *kprev_p <- k of the last cycle; stats count the applies of all
 // cycles; the lowest Ritz value is left in rs.out[0] (behind a barrier).
-__device__ __noinline__ int bt_diag(const BtOp& op, zc* x, zc* U, long N, int kcap_in, double thresh, zc shift, const BtSh& sh,
-                                    const BrSh& rs, int* kprev_p, long long* stats, long long flops_per_apply) {
+// DEFL: the operator is Op + shift + sum_k w_k |q_k><q_k| with the df.K projected stored states of BtDefl (k_batch_relax_defl);
+// the rank-one terms are added to un right behind the apply, element e by its owning thread, so nothing else changes.
+// This is the one text of the solve; bt_diag and bt_diag_defl below are the functions the kernels call.
+struct BtDefl {
+  int K;            // stored states, 1 .. BATCH_MAX_DEFLATE
+  const zc* q;      // q_k at q + k * qs: phi_k in the replica's basis at this site, N elements each
+  size_t qs;
+  const double* w;  // w_k at w[k * ws]
+  size_t ws;
+};
+// un += sum_k w_k q_k <q_k | v>, four slots per round (red holds 8 doubles).  Element e of un is read and written by its
+// owning thread e % 512 only, which is also the one that reads it next in the solve; the apply before ended with a barrier.
+__device__ __noinline__ void bt_defl_add(const BtDefl& df, const zc* vi, zc* un, long N, const BtSh& sh) {
+  const int tid = threadIdx.x;
+  for (int k0 = 0; k0 < df.K; k0 += 4) {
+    const int nk = min(4, df.K - k0);
+    const zc* q0 = df.q + (size_t)k0 * df.qs;
+    double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (long e = tid; e < N; e += SS_THREADS) {
+      const zc v = vi[e];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < nk) {
+          const zc q = q0[(size_t)j * df.qs + e];
+          s[2 * j] += q.x * v.x + q.y * v.y;  // conj(q) v
+          s[2 * j + 1] += q.x * v.y - q.y * v.x;
+        }
+    }
+    wg_reduce(s, sh);
+    double cr[4], ci[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const double w = j < nk ? df.w[(size_t)(k0 + j) * df.ws] : 0.0;
+      cr[j] = w * sh.red[2 * j];
+      ci[j] = w * sh.red[2 * j + 1];
+    }
+    for (long e = tid; e < N; e += SS_THREADS) {  // un[e] is read next by this thread only
+      zc u = un[e];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < nk) {
+          const zc q = q0[(size_t)j * df.qs + e];
+          u.x += q.x * cr[j] - q.y * ci[j];
+          u.y += q.x * ci[j] + q.y * cr[j];
+        }
+      un[e] = u;
+    }
+  }
+}
+template <bool DEFL>
+__device__ __forceinline__ int bt_diag_body(const BtOp& op, zc* x, zc* U, long N, int kcap_in, double thresh, zc shift, const BtSh& sh,
+                                            const BrSh& rs, int* kprev_p, long long* stats, long long flops_per_apply, const BtDefl& df) {
   const int tid = threadIdx.x;
   const bool add_shift = shift.x != 0.0 || shift.y != 0.0;
   const int kcap = (int)min((long)kcap_in, N);
@@ -859,6 +911,7 @@ __device__ __noinline__ int bt_diag(const BtOp& op, zc* x, zc* U, long N, int kc
     zc* un = U + (size_t)(i + 1) * N;
     bt_apply(op, vi, 1.0, un);
     napply += 1;
+    if (DEFL) bt_defl_add(df, vi, un, N, sh);
     {  // (Op + shift) v_i, and alpha_i
       double s[1] = {0.0};
       for (long e = tid; e < N; e += SS_THREADS) {
@@ -1007,13 +1060,165 @@ __device__ __noinline__ int bt_diag(const BtOp& op, zc* x, zc* U, long N, int kc
   __syncthreads();
   return rc;
 }
+__device__ __noinline__ int bt_diag(const BtOp& op, zc* x, zc* U, long N, int kcap_in, double thresh, zc shift, const BtSh& sh,
+                                    const BrSh& rs, int* kprev_p, long long* stats, long long flops_per_apply) {
+  return bt_diag_body<false>(op, x, U, N, kcap_in, thresh, shift, sh, rs, kprev_p, stats, flops_per_apply, BtDefl{});
+}
 
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, 512 threads = 8 waves): 248 VGPRs, 106 SGPRs, no vector
 // register spills, 46 scalar registers spilled around the calls of the stage functions, 320 bytes of private memory per
 // lane (the argument blocks the stage functions take by reference: none of it inside a product loop), 23 120 bytes of
 // LDS; occupancy 2 waves per SIMD, i.e. one workgroup (replica) per compute unit.  The other kernels compile to the figures
 // they had (profiles/batch_relax_resources.txt, batch_relax_restart_resources.txt have the listings).
-__global__ __launch_bounds__(SS_THREADS) void k_batch_relax(BatchRelaxArgs g) {
+//
+// Excited states by deflation (DEFL, k_batch_relax_defl): with dg.count stored states phi_k (copies of all site tensors,
+// the snapshot's layout) and weights w_k per replica, every local solve runs on H_eff + shift + sum_k w_k |q_k><q_k|, q_k
+// being phi_k in the replica's current basis at the site: q_k = OL_k[p] . phi_k[p] . OR_k[p + 1]^T with the overlap
+// blocks OL_k[b][a][a'] = <replica's left basis state a | phi_k's a'> of bond b (and OR_k the same from the right).  One
+// block per slot and bond lives in the replica's part of dg.work: the left block while the centre is at or right of the
+// bond, the right block otherwise.  At the start of a launch the workgroup builds the blocks of the side the first
+// half-sweep looks at from the tensors as they stand (nothing persists between launches); after every gauge move the
+// block of the bond the centre crossed is rewritten from the new A (or B), beside the H block's bt_env.  The stop rule,
+// the restarts and the status words are those above; E_n, the lowest Ritz value at site 0, is then the energy PLUS
+// sum_k w_k |<phi_k|psi>|^2.
+// The overlap products of the deflation, each by the whole workgroup through wg_gemm; U / V: N elements of scratch.
+//   left:  T2 (dr x dr) = sum conj(Bra) T Ket, the step of wg_overlap
+__device__ __noinline__ void bdf_left(const zc* T, const zc* Ket, const zc* Bra, zc* U, zc* T2, int dl, int d, int dr, zc* tiles) {
+  assume_lds(tiles);
+  wg_walk_u(T, Ket, U, dl, d * dr, tiles);
+  wg_walk_t<true>(Bra, U, T2, dr, dl * d, tiles);
+}
+//   V[(a,s)][t] = sum_t' A[(a,s)][t'] R[t][t']
+__device__ __forceinline__ void wg_mul_rt(const zc* A, const zc* R, zc* V, int rows, int dr, zc* tiles) {
+  wg_gemm<true, true>(rows, dr, dr, tiles,
+      [&](int m, int k) { return A[(long)m * dr + k]; },
+      [&](int k, int n) { return R[(long)n * dr + k]; },
+      [&](int m, int n, zc z) { V[(long)m * dr + n] = z; });
+}
+//   right: T2[r][r'] (dl x dl) = sum_(s,t) conj(Bra[r][(s,t)]) V[r'][(s,t)], V = Ket . T^T; Bra in gauge B, (dl, d, dr) as it lies
+__device__ __noinline__ void bdf_right(const zc* T, const zc* Ket, const zc* Bra, zc* V, zc* T2, int dl, int d, int dr, zc* tiles) {
+  assume_lds(tiles);
+  wg_mul_rt(Ket, T, V, dl * d, dr, tiles);
+  const int ddr = d * dr;
+  wg_gemm<true, true>(dl, dl, ddr, tiles,
+      [&](int m, int k) { const zc z = Bra[(long)m * ddr + k]; return make_double2(z.x, -z.y); },
+      [&](int k, int n) { return V[(long)n * ddr + k]; },
+      [&](int m, int n, zc z) { T2[(long)m * dl + n] = z; });
+}
+//   q = OL . phi . OR^T: two products, as bt_keff arranges its own
+__device__ __noinline__ void bdf_project(const zc* OL, const zc* OR, const zc* phi, zc* tmp, zc* q, int dl, int d, int dr, zc* tiles) {
+  assume_lds(tiles);
+  wg_walk_u(OL, phi, tmp, dl, d * dr, tiles);
+  wg_mul_rt(tmp, OR, q, dl * d, dr, tiles);
+}
+// where the block of bond b starts in a slot's blocks (bond L shares the 1 of bond 0), and site p in a stored state
+__device__ __forceinline__ size_t bdf_boff(const BatchShape* shp, int L, int b) {
+  size_t o = 0;
+  if (b < L)
+    for (int j = 0; j < b; ++j) o += (size_t)shp[j].dl * shp[j].dl;
+  return o;
+}
+__device__ __forceinline__ size_t bdf_soff(const BatchShape* shp, int p) {
+  size_t o = 0;
+  for (int j = 0; j < p; ++j) o += (size_t)shp[j].dl * shp[j].d * shp[j].dr;
+  return o;
+}
+// The helpers below take the launch's arguments and work out the replica's own pointers themselves: every value the
+// kernel body keeps across their calls costs it registers.  Each counts its flops into the replica's stats.
+struct BdfCtx {
+  const BatchShape* shp;
+  int L, r;
+  zc* const* site;
+  zc* X;             // N elements of scratch: the X carve of the sweep, free between the applies
+  zc* dwork;         // the replica's blocks [count][blk_len], then q_k [count][max_site]
+  long long* stats;
+};
+__device__ __forceinline__ BdfCtx bdf_ctx(const BatchRelaxDeflArgs& gg) {
+  const int r = blockIdx.x, L = gg.r.L;
+  void* const* tab = gg.r.ptrs + (size_t)r * gg.r.ptr_stride;
+  return BdfCtx{gg.r.shp, L, r, reinterpret_cast<zc* const*>(tab), reinterpret_cast<zc*>(tab[6 * L + 2]) + gg.r.plan.o_x,
+                gg.d.work + (size_t)r * gg.d.plan.per, gg.r.stats + (size_t)r * 4};
+}
+// the blocks a launch starts from: right blocks of bonds L-1 .. 1 before a forward half-sweep (sites 1 .. L-1 in gauge
+// B), left blocks of bonds 1 .. L-1 before a backward one (sites 0 .. L-2 in gauge A)
+__device__ __noinline__ void bdf_build(const BatchRelaxDeflArgs& gg, bool fwd, zc* tiles) {
+  const BatchDeflArgs& dg = gg.d;
+  const BdfCtx c = bdf_ctx(gg);
+  const BatchShape* shp = c.shp;
+  const int L = c.L, r = c.r;
+  zc* const* site = c.site;
+  zc* V = c.X;
+  zc* dwork = c.dwork;
+  long long* stats = c.stats;
+  double fl = 0.0;
+  for (int k = 0; k < dg.count; ++k) {
+    const zc* phi = dg.slot[k] + (size_t)r * dg.snap_len;
+    zc* blk = dwork + (size_t)k * dg.plan.blk_len;
+    if (threadIdx.x == 0) blk[0] = make_double2(1.0, 0.0);
+    __syncthreads();
+    for (int step = 0; step + 1 < L; ++step) {
+      const int p = fwd ? L - 1 - step : step;
+      const BatchShape s = shp[p];
+      const zc* ket = phi + bdf_soff(shp, p);
+      if (fwd) bdf_right(blk + bdf_boff(shp, L, p + 1), ket, site[p], V, blk + bdf_boff(shp, L, p), s.dl, s.d, s.dr, tiles);
+      else bdf_left(blk + bdf_boff(shp, L, p), ket, site[p], V, blk + bdf_boff(shp, L, p + 1), s.dl, s.d, s.dr, tiles);
+      fl += 8.0 * (double)s.dl * s.d * s.dr * (s.dl + s.dr);
+    }
+  }
+  if (threadIdx.x == 0) stats[2] += (long long)fl;
+}
+// q_k of every slot at site p, into the replica's projected vectors
+__device__ __forceinline__ void bdf_site(const BatchRelaxDeflArgs& gg, int p, zc* tiles) {
+  const BatchDeflArgs& dg = gg.d;
+  const BdfCtx c = bdf_ctx(gg);
+  const BatchShape* shp = c.shp;
+  const int L = c.L, r = c.r;
+  zc* tmp = c.X;
+  zc* dwork = c.dwork;
+  long long* stats = c.stats;
+  const BatchShape s = shp[p];
+  const size_t bo = bdf_boff(shp, L, p), bn = bdf_boff(shp, L, p + 1), so = bdf_soff(shp, p);
+  for (int k = 0; k < dg.count; ++k) {
+    const zc* blk = dwork + (size_t)k * dg.plan.blk_len;
+    bdf_project(blk + bo, blk + bn, dg.slot[k] + (size_t)r * dg.snap_len + so, tmp, dwork + dg.plan.o_q + (size_t)k * dg.plan.max_site,
+                s.dl, s.d, s.dr, tiles);
+  }
+  if (threadIdx.x == 0) stats[2] += (long long)dg.count * (long long)(8.0 * (double)s.dl * s.d * s.dr * (s.dl + s.dr));
+}
+// the deflated solve at site p: q_k of every slot first (op.X is free until the first apply), then bt_diag's text with the
+// rank-one terms; 16 N flops per slot and apply come on top of the apply's own
+__device__ __noinline__ int bt_diag_defl(const BtOp& op, zc* x, zc* U, long N, int kcap_in, double thresh, zc shift, const BtSh& sh,
+                                         const BrSh& rs, int* kprev_p, long long* stats, long long flops_per_apply,
+                                         const BatchRelaxDeflArgs& gg, int p) {
+  const BatchDeflArgs& dg = gg.d;
+  const int r = blockIdx.x;
+  bdf_site(gg, p, op.tiles);
+  const BtDefl df{dg.count, dg.work + (size_t)r * dg.plan.per + dg.plan.o_q, dg.plan.max_site, dg.w + r, (size_t)gridDim.x};
+  return bt_diag_body<true>(op, x, U, N, kcap_in, thresh, shift, sh, rs, kprev_p, stats, flops_per_apply + 16LL * N * dg.count, df);
+}
+// the block of the bond the centre crossed, of every slot, from the new A (forward: OL_k[p + 1]) or B (backward: OR_k[p])
+__device__ __noinline__ void bdf_move(const BatchRelaxDeflArgs& gg, int p, bool fwd, zc* tiles) {
+  const BatchDeflArgs& dg = gg.d;
+  const BdfCtx c = bdf_ctx(gg);
+  const BatchShape* shp = c.shp;
+  const int L = c.L, r = c.r;
+  const zc* sp = c.site[p];
+  zc* V = c.X;
+  zc* dwork = c.dwork;
+  long long* stats = c.stats;
+  const BatchShape s = shp[p];
+  const size_t bo = bdf_boff(shp, L, p), bn = bdf_boff(shp, L, p + 1), so = bdf_soff(shp, p);
+  for (int k = 0; k < dg.count; ++k) {
+    zc* blk = dwork + (size_t)k * dg.plan.blk_len;
+    const zc* ket = dg.slot[k] + (size_t)r * dg.snap_len + so;
+    if (fwd) bdf_left(blk + bo, ket, sp, V, blk + bn, s.dl, s.d, s.dr, tiles);
+    else bdf_right(blk + bn, ket, sp, V, blk + bo, s.dl, s.d, s.dr, tiles);
+  }
+  if (threadIdx.x == 0) stats[2] += (long long)dg.count * (long long)(8.0 * (double)s.dl * s.d * s.dr * (s.dl + s.dr));
+}
+
+template <bool DEFL>
+__device__ __forceinline__ void batch_relax_body(const BatchRelaxArgs& g, const BatchRelaxDeflArgs* gg) {
   __shared__ __attribute__((aligned(16))) zc s_tiles[2 * BT_TK * BT_LD];
   __shared__ zc s_z[2 * BATCH_MAX_BOND];
   __shared__ double s_d[SS_WAVES * 8 + 8 + BATCH_MAX_BOND + 6 * BATCH_RELAX_MAX_KRYLOV + 2];
@@ -1061,6 +1266,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_relax(BatchRelaxArgs g) {
   int nstep = 0;
   double e_prev = 0.0;
   bool fwd = g.forward != 0;
+  if (DEFL) bdf_build(*gg, fwd, tiles);
   for (int h = 0; h < g.nhalf && rc == SS_OK; ++h, fwd = !fwd) {
     double theta = 0.0;
     for (int step = 0; step < L; ++step) {
@@ -1072,7 +1278,11 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_relax(BatchRelaxArgs g) {
         const long long fl = (long long)(8.0 * ((double)dl * dl * s.ml * d * dr + (double)dl * dr * s.ml * s.mr * d * d +
                                                 (double)dl * dr * dr * s.mr * d));
         const BtOp op{s, envL[p], w2l[p], envR[p + 1], 0, 0, X, Y, tiles};
-        rc = bt_diag(op, site[p], U, N, g.kcap, g.thresh, shift, sh, rs, kprev + p, stats, fl);
+        if (DEFL) {
+          rc = bt_diag_defl(op, site[p], U, N, g.kcap, g.thresh, shift, sh, rs, kprev + p, stats, fl, *gg, p);
+        } else {
+          rc = bt_diag(op, site[p], U, N, g.kcap, g.thresh, shift, sh, rs, kprev + p, stats, fl);
+        }
         theta = rs.out[0];
       }
       if (rc != SS_OK || step == L - 1) break;
@@ -1080,6 +1290,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_relax(BatchRelaxArgs g) {
         // 2. Psi2Asigma, 3. L[p + 1], 5. Psi(p + 1) = sigma . B(p + 1)
         bt_qr(site[p], site[p], dr, 1, sig, dr, 1, dl * d, dr, work, sh);
         bt_env(envL[p], site[p], site[p], (long)d * dr, dr, 1, w2el[p], dl, s.ml, d, dr, s.mr, X, Y, envL[p + 1], tiles);
+        if (DEFL) bdf_move(*gg, p, true, tiles);  // OL_k[p + 1] from the new A
         const BatchShape q = g.shp[p + 1];
         zc* nxt = site[p + 1];
         bt_matmul(sig, nxt, spare, nxt, dr, q.d * q.dr, dr, tiles);
@@ -1088,6 +1299,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_relax(BatchRelaxArgs g) {
         const int mq = d * dr;
         bt_qr(site[p], site[p], 1, mq, sig, 1, dl, mq, dl, work, sh);
         bt_env(envR[p + 1], site[p], site[p], 1, dr, (long)d * dr, w2er[p], dr, s.mr, d, dl, s.ml, X, Y, envR[p], tiles);
+        if (DEFL) bdf_move(*gg, p, false, tiles);  // OR_k[p] from the new B
         const BatchShape q = g.shp[p - 1];
         zc* prv = site[p - 1];
         bt_matmul(prv, sig, spare, prv, q.dl * q.d, dl, dl, tiles);
@@ -1107,6 +1319,31 @@ __global__ __launch_bounds__(SS_THREADS) void k_batch_relax(BatchRelaxArgs g) {
     }
   }
   if (rc != SS_OK && tid == 0) g.status[r] = rc;
+}
+__global__ __launch_bounds__(SS_THREADS) void k_batch_relax(BatchRelaxArgs g) { batch_relax_body<false>(g, nullptr); }
+// Resources of the deflated instance (profiles/batch_deflate_resources.txt): 256 VGPRs, 106 SGPRs, 23 120 bytes of LDS,
+// occupancy 2 waves per SIMD as above, 704 bytes of private memory per lane -- and 6 vector and 2 scalar registers spilled
+// in this body around the calls of the stage functions, none inside a loop over elements (those are all in functions of
+// their own: bdf_left / bdf_right / bdf_project 136 .. 148 VGPRs, bt_defl_add 102, bt_diag_defl 248, no private memory
+// beyond their argument blocks).
+__global__ __launch_bounds__(SS_THREADS) void k_batch_relax_defl(BatchRelaxDeflArgs g) { batch_relax_body<true>(g.r, &g); }
+
+// <phi_k | psi_r> for every slot k and replica r: workgroup k * B + r walks wg_overlap with the replica as ket and the
+// stored state as bra; T, its successor and U lie in the request's own buffer.  Replicas and slots are only read.
+__global__ __launch_bounds__(SS_THREADS) void k_batch_defl_overlaps(BatchDeflOvArgs g) {
+  __shared__ __attribute__((aligned(16))) zc tiles[2 * BT_TK * BT_LD];
+  const int B = g.nrep, k = blockIdx.x / B, r = blockIdx.x - k * B;
+  const zc* const* tab = reinterpret_cast<const zc* const*>(g.ptrs + (size_t)r * g.ptr_stride);
+  const zc* phi = g.slot[k] + (size_t)r * g.snap_len;
+  zc* T = g.buf + (size_t)blockIdx.x * g.buf_len;
+  const zc* res = wg_overlap(g.L, g.shp,
+      [&](int p, size_t) { return tab[p]; },
+      [&](int, size_t soff) { return phi + soff; }, T, T + g.o_t2, T + g.o_u, tiles);
+  if (threadIdx.x == 0) {
+    const zc z = res[0];
+    g.rec[2 * (size_t)blockIdx.x] = z.x;
+    g.rec[2 * (size_t)blockIdx.x + 1] = z.y;
+  }
 }
 
 // test hook: bt_trilow alone, one workgroup of one wave per case
@@ -3142,7 +3379,7 @@ void batch_sweep_launch(hipStream_t st, const BatchArgs& a, int nrep) {
   HIP_CHECK(hipGetLastError());
 }
 
-void batch_relax_launch(hipStream_t st, const BatchRelaxArgs& a, int nrep) {
+static void batch_relax_args_ok(const BatchRelaxArgs& a, int nrep) {
   if (nrep < 1 || a.L < 1 || a.nhalf < 1) throw ArgError("batch: nothing to launch");
   if (a.kcap < 2 || a.kcap > BATCH_RELAX_MAX_KRYLOV) throw ArgError("batch: max_diag_krylov must be in [2, 64]");
   if (a.max_restarts < 0 || a.max_restarts > BATCH_RELAX_MAX_RESTARTS) throw ArgError("batch: max_restarts must be in [0, 4096]");
@@ -3151,7 +3388,32 @@ void batch_relax_launch(hipStream_t st, const BatchRelaxArgs& a, int nrep) {
     throw ArgError("batch: the Krylov carve is too small for the improved relaxation");
   if ((a.energy != nullptr) != (a.steps != nullptr) || (a.energy != nullptr) != (a.history != nullptr) || (a.energy && a.hist_len < 1))
     throw ArgError("batch: the relaxation's outputs go together");
+}
+
+void batch_relax_launch(hipStream_t st, const BatchRelaxArgs& a, int nrep) {
+  batch_relax_args_ok(a, nrep);
   hipLaunchKernelGGL(k_batch_relax, dim3(nrep), dim3(SS_THREADS), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+}
+
+void batch_relax_defl_launch(hipStream_t st, const BatchRelaxArgs& a, const BatchDeflArgs& d, int nrep) {
+  batch_relax_args_ok(a, nrep);
+  if (d.count < 1 || d.count > BATCH_MAX_DEFLATE || !d.w || !d.work) throw ArgError("batch: the deflated relaxation needs its stored states");
+  for (int k = 0; k < d.count; ++k)
+    if (!d.slot[k]) throw ArgError("batch: a stored state of the deflation set is missing");
+  if (d.plan.o_q != (size_t)d.count * d.plan.blk_len || d.plan.per != (size_t)d.count * (d.plan.blk_len + d.plan.max_site) ||
+      d.plan.max_site < (size_t)a.plan.max_site)
+    throw ArgError("batch: the deflation's work buffer is not laid out for its stored states");
+  const BatchRelaxDeflArgs g{a, d};
+  hipLaunchKernelGGL(k_batch_relax_defl, dim3(nrep), dim3(SS_THREADS), 0, st, g);
+  HIP_CHECK(hipGetLastError());
+}
+
+void batch_defl_overlaps_launch(hipStream_t st, const BatchDeflOvArgs& a) {
+  if (a.count < 1 || a.count > BATCH_MAX_DEFLATE || a.nrep < 1 || a.L < 1 || !a.buf || !a.rec) throw ArgError("batch: no stored state to overlap with");
+  for (int k = 0; k < a.count; ++k)
+    if (!a.slot[k]) throw ArgError("batch: a stored state of the deflation set is missing");
+  hipLaunchKernelGGL(k_batch_defl_overlaps, dim3(a.count * a.nrep), dim3(SS_THREADS), 0, st, a);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -417,6 +417,24 @@ int mitdvp_batch_relax_restarts(mitdvp_batch* b, long long* total, int* most) {
   if (!b || !b->b) { g_err = "mitdvp_batch_relax_restarts: null handle"; return MITDVP_EINVAL; }
   return guard(nullptr, [&] { b->b->relax_restarts(total, most); });
 }
+int mitdvp_batch_deflate_push(mitdvp_batch* b, const double* weights) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_deflate_push: null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->deflate_push(weights); });
+}
+int mitdvp_batch_deflate_clear(mitdvp_batch* b) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_deflate_clear: null handle"; return MITDVP_EINVAL; }
+  b->b->deflate_clear();
+  return MITDVP_OK;
+}
+int mitdvp_batch_deflate_count(mitdvp_batch* b, int* count) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_deflate_count: null handle"; return MITDVP_EINVAL; }
+  if (!count) { g_err = "mitdvp_batch_deflate_count: count is NULL"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { *count = b->b->deflate_count(); });
+}
+int mitdvp_batch_deflate_overlaps(mitdvp_batch* b, double* reim) {
+  if (!b || !b->b) { g_err = "mitdvp_batch_deflate_overlaps: null handle"; return MITDVP_EINVAL; }
+  return guard(nullptr, [&] { b->b->deflate_overlaps(reim); });
+}
 int mitdvp_batch_trilow(int device, const double* alpha, const double* beta, const int* k, int ncases, double* theta, double* vec) {
   return guard(nullptr, [&] { mitdvp::batch_trilow(device, alpha, beta, k, ncases, theta, vec); });
 }

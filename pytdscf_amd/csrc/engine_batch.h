@@ -289,6 +289,27 @@ class Batch {
   // solves.  Either may be null.  One host wait.
   void relax_restarts(long long* total, int* most);
 
+  // ---- excited states by deflation against stored states (k_batch_relax_defl, k_batch_defl_overlaps) ----
+  // The batch owns up to BATCH_MAX_DEFLATE slots, each a copy of every replica's site tensors (the snapshot's layout,
+  // copied by k_batch_snapshot) and one weight per replica.  While the set is not empty, relax() and the relax == 2 paths
+  // of step / sweep / run solve every local problem on H_eff + shift + sum_k w_k |q_k><q_k|, q_k the stored state k in the
+  // replica's current site basis: the same launches, one workgroup per replica, and E_n is then the energy plus
+  // sum_k w_k |<phi_k|psi>|^2.  With an empty set the batch launches k_batch_relax as ever.  The states are stored as they
+  // are: the penalty is w |<phi|psi>|^2, so the caller pushes normalised states (relax() leaves them normalised).  The set
+  // is dropped where the snapshot is (the replicas' shapes changed); it is independent of the snapshot, of every request,
+  // of channels and of fields.
+  // deflate_push: ONE launch and one host wait; weights: B doubles.  Refused before the GPU is touched, with an ArgError
+  // that names the entry point and the limit and leaves everything as it was: replicas whose relax != 2, a replica whose
+  // centre is not at site 0 (or whose chain is not canonical around it), a full set, a null list, a weight that is not
+  // finite or not > 0 (the replica is named), a work buffer (batch_deflate_plan.h) above BATCH_DEFLATE_MAX_BYTES (both
+  // figures and the largest number of slots that fits are named).
+  void deflate_push(const double* weights);
+  void deflate_clear() { defl_count_ = 0; }
+  int deflate_count();  // validates first: a set that other shapes have dropped counts as empty
+  // reim [count][B][2]: <phi_k | psi_r>; ONE launch, one workgroup per (slot, replica), one host wait; with an empty set
+  // no launch.  The centre may be at site 0 or at site L-1.  Neither the replicas nor the slots are written.
+  void deflate_overlaps(double* reim);
+
   std::string status_message(int code) const;
   int size() const { return (int)eng_.size(); }
   int device() const { return device_; }
@@ -516,6 +537,13 @@ class Batch {
   int rx_restarts_ = 0;                     // set_relax_restarts()
   DevArr<long long> d_rx_rst_total_;        // [B] restarts taken; made and zeroed by the first launch_relax
   DevArr<int> d_rx_rst_most_;               // [B] the most of one local solve
+  // the deflation set: the filled slots [B][snap_len] each, their weights [BATCH_MAX_DEFLATE][B] (host copy and device
+  // image), the kernel's work buffer [B][plan.per] and the buffers of deflate_overlaps
+  int defl_count_ = 0;
+  DevArr<zc> d_defl_slot_[BATCH_MAX_DEFLATE];
+  std::vector<double> h_defl_w_;
+  DevArr<double> d_defl_w_, d_defl_ov_;
+  DevArr<zc> d_defl_work_, d_defl_ovbuf_;
   void launch_observe(int what, int nsites, long record, long rec_len);
   void launch_density(int nkeys, bool zero_head, long record, long rec_len, long dens_off);
   void finish(bool ends_forward, int half_sweeps, int* statuses, int other_launches = 0, int channel_passes = 0, int field_passes = 0);

@@ -158,6 +158,7 @@ void Batch::validate() {
     shp_ = s0;
     shapes_dirty_ = true;
     has_snap_ = false;  // a snapshot of other shapes names nothing any more
+    defl_count_ = 0;    // nor do the stored states of the deflation set
     spec_rec_.drop();   // nor do spectra records of other bond dimensions
     smp_rec_.drop();    // nor sampled configurations of other shapes
     exp_rec_.drop();    // nor expectation values walked over other bonds
@@ -326,7 +327,19 @@ void Batch::launch_relax(bool forward, int nhalf, double conv_tol, double* energ
   a.steps = steps;
   a.history = history;
   a.hist_len = hist_len;
-  batch_relax_launch(st_, a, (int)n);
+  if (defl_count_ > 0) {  // the deflated instance of the same kernel: still one launch
+    BatchDeflArgs d{};
+    d.count = defl_count_;
+    for (int k = 0; k < defl_count_; ++k) d.slot[k] = d_defl_slot_[k];
+    d.snap_len = snap_len();
+    d.w = d_defl_w_;
+    d.plan = batch_deflate_plan(shp_.data(), L_, defl_count_);
+    reserve_synced(d_defl_work_, n * d.plan.per);
+    d.work = d_defl_work_;
+    batch_relax_defl_launch(st_, a, d, (int)n);
+  } else {
+    batch_relax_launch(st_, a, (int)n);
+  }
   n_launch_ += 1;
 }
 
@@ -1784,6 +1797,74 @@ void Batch::relax_restarts(long long* total, int* most) {
   }
   if (total) std::memcpy(total, t.data(), n * sizeof(long long));
   if (most) std::memcpy(most, m.data(), n * sizeof(int));
+}
+
+// ---- excited states by deflation against stored states (k_batch_relax_defl, k_batch_defl_overlaps) ----
+void Batch::deflate_push(const double* weights) {
+  const std::string at = "mitdvp_batch_deflate_push: ";
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  const size_t n = eng_.size();
+  if (eng_[0]->cfg.relax != 2)
+    throw ArgError(at + "the replicas have relax = " + std::to_string(eng_[0]->cfg.relax) +
+                   ", stored states deflate the improved relaxation (relax must be 2)");
+  for (size_t i = 0; i < n; ++i) {
+    const Engine& e = *eng_[i];
+    if (e.center_ != 0)
+      throw ArgError(at + "replica " + std::to_string(i) + " has its centre at site " + std::to_string(e.center_) +
+                     "; a state is stored with the centre at site 0 (the state mitdvp_batch_relax leaves)");
+    for (int p = 0; p < L_; ++p)
+      if (e.gauge_[p] != (p == 0 ? MITDVP_GAUGE_PSI : MITDVP_GAUGE_B))
+        throw ArgError(at + "replica " + std::to_string(i) + ": the chain is not canonical around site 0");
+  }
+  std::string bad;
+  if (!batch_deflate_room(defl_count_, bad)) throw ArgError(at + bad);
+  if (!batch_deflate_weights_ok(weights, (int)n, bad)) throw ArgError(at + bad);
+  if (!batch_deflate_fits(shp_.data(), L_, defl_count_ + 1, n, bad)) throw ArgError(at + bad);
+  prepare(true, false);
+  const int k = defl_count_;
+  if (h_defl_w_.size() != n * BATCH_MAX_DEFLATE) h_defl_w_.assign(n * BATCH_MAX_DEFLATE, 0.0);
+  reserve_synced(d_defl_slot_[k], n * snap_len(), d_defl_w_, n * BATCH_MAX_DEFLATE);
+  std::memcpy(h_defl_w_.data() + (size_t)k * n, weights, n * sizeof(double));
+  HIP_CHECK(hipMemcpyAsync(d_defl_w_, h_defl_w_.data(), h_defl_w_.size() * sizeof(double), hipMemcpyHostToDevice, st_));
+  batch_snapshot_launch(st_, d_shp_, d_ptrs_, (int)ptrs_per_replica(), d_defl_slot_[k], snap_len(), L_, (int)n);
+  n_launch_ += 1;
+  finish_observe(1, nullptr);
+  defl_count_ = k + 1;
+}
+
+int Batch::deflate_count() {
+  validate();
+  return defl_count_;
+}
+
+void Batch::deflate_overlaps(double* reim) {
+  HIP_CHECK(hipSetDevice(device_));
+  validate();
+  if (defl_count_ == 0) return;
+  const size_t n = eng_.size(), rows = (size_t)defl_count_ * n;
+  prepare_observing();
+  reserve_synced(d_defl_ovbuf_, rows * cross_buf_len(), d_defl_ov_, 2 * rows);
+  BatchDeflOvArgs a{};
+  a.L = L_;
+  a.nrep = (int)n;
+  a.count = defl_count_;
+  a.shp = d_shp_;
+  a.ptrs = d_ptrs_;
+  a.ptr_stride = (int)ptrs_per_replica();
+  for (int k = 0; k < defl_count_; ++k) a.slot[k] = d_defl_slot_[k];
+  a.snap_len = snap_len();
+  a.buf = d_defl_ovbuf_;
+  a.o_t2 = (size_t)plan_.max_bond;
+  a.o_u = 2 * (size_t)plan_.max_bond;
+  a.buf_len = cross_buf_len();
+  a.rec = d_defl_ov_;
+  batch_defl_overlaps_launch(st_, a);
+  n_launch_ += 1;
+  std::vector<double> h(2 * rows);
+  HIP_CHECK(hipMemcpyAsync(h.data(), d_defl_ov_, h.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
+  finish_observe(1, nullptr);
+  if (reim) std::memcpy(reim, h.data(), h.size() * sizeof(double));
 }
 
 // the eigen-solve of the improved relaxation alone (k_batch_trilow), for tests

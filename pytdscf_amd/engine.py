@@ -1898,6 +1898,44 @@ class TDVPBatch:
                                                               steps.ctypes.data_as(C.POINTER(C.c_int)), _dp(history), st))
         return dict(self.relaxed)
 
+    # ---- excited states by deflation against stored states (mitdvp_batch_deflate_*) ----
+    def deflate_push(self, weights):
+        """Stores the present state of every replica in the next free slot of the batch's deflation set
+        (``mitdvp_batch_deflate_push``; at most 8 slots, ONE launch).  ``weights``: a scalar, or one weight per replica,
+        finite and ``> 0``.  The replicas must be ``relax="improved"`` ones with their centre at site 0, as ``relax``
+        leaves them, and normalised.  While the set is not empty ``relax`` (and ``propagate`` / ``sweep``) solve every
+        local problem on ``H_eff + sum_k w_k |q_k><q_k|`` with ``q_k`` the stored state ``k`` in the replica's site basis
+        (``k_batch_relax_defl``): from a fresh start the replicas then relax to the lowest state orthogonal to the stored
+        ones, provided every weight exceeds the gap to it.  ``relax``'s ``"energy"`` is then the energy plus
+        ``sum_k w_k |<phi_k|psi>|^2``; ``propagate(0, 0, observe={"energy": True})`` gives ``<psi|H|psi>``.  The library
+        validates and names what it refuses; a refused call changes nothing."""
+        n = len(self.engines)
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(weights, dtype=np.float64), (n,)) if np.ndim(weights) == 0
+                                 else np.asarray(weights, dtype=np.float64))
+        if w.shape != (n,):
+            raise ValueError(f"deflate_push: {w.shape} weights for {n} replicas (a scalar, or one weight per replica)")
+        _lib.check(self._lib.mitdvp_batch_deflate_push(self._handle(), _dp(w)))
+
+    def deflate_clear(self):
+        """Empties the deflation set (``mitdvp_batch_deflate_clear``): ``relax`` finds ground states again, bit for bit."""
+        _lib.check(self._lib.mitdvp_batch_deflate_clear(self._handle()))
+
+    def deflate_count(self) -> int:
+        """The number of stored states (``mitdvp_batch_deflate_count``)."""
+        c = C.c_int(0)
+        _lib.check(self._lib.mitdvp_batch_deflate_count(self._handle(), C.byref(c)))
+        return int(c.value)
+
+    def deflate_overlaps(self):
+        """``(count, B)`` complex: ``<phi_k|psi_r>`` of every stored state ``k`` with replica ``r`` as it is now, ONE launch
+        (``mitdvp_batch_deflate_overlaps``); nothing is written to the replicas or the slots."""
+        n = len(self.engines)
+        k = self.deflate_count()
+        out = np.zeros((k, n, 2), dtype=np.float64)
+        if k:
+            _lib.check(self._lib.mitdvp_batch_deflate_overlaps(self._handle(), _dp(out)))
+        return out[..., 0] + 1j * out[..., 1]
+
     def launches(self) -> int:
         """kernel launches counted so far on replica 0, where the batch's launches are counted once"""
         return int(self.engines[0].counters()["n_launch"])

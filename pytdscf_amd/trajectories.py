@@ -449,7 +449,7 @@ def correlation_function(model, starts, maxstep, stepsize, A=None, B=None, every
 
 
 def relax_trajectories(models, starts=None, maxstep=20, conv_tol=1.0e-10, thresh_sil=1.0e-09, device=0, max_diag_krylov=0,
-                       max_restarts=0):
+                       max_restarts=0, nstates=1, penalty=None, seed=0):
     """Ground states of an ensemble by improved relaxation in ONE batch and one launch (``TDVPBatch.relax``,
     ``k_batch_relax``): the reference's ``Simulator.relax(improved=True)`` for every realisation at once.
 
@@ -468,10 +468,40 @@ def relax_trajectories(models, starts=None, maxstep=20, conv_tol=1.0e-10, thresh
     [cores of replica 0, ...]}``; the states are normalised MPS cores with the centre at site 0, in the form
     ``correlation_function(starts=...)`` and ``propagate_trajectories`` accept.  The energies contain the Hamiltonian's
     scalar term.  With ``max_restarts > 0`` there is also ``"restarts"``: (B,) int64, the restarts every replica took.
-    A model the batch does not take raises with the library's message; nothing falls back."""
+    A model the batch does not take raises with the library's message; nothing falls back.
+
+    ``nstates > 1``: the lowest ``nstates`` eigenstates of every realisation by deflation (``TDVPBatch.deflate_push``,
+    ``k_batch_relax_defl``), at most 9.  State 0 relaxes as above; then, for every further state, the states found so far
+    are stored with the weight ``penalty``, every replica gets a fresh start, and the batch relaxes again on
+    ``H + penalty * sum_j |j><j|``.  ``penalty`` is required then: a scalar, or one value per model.  It must EXCEED the
+    largest gap wanted, ``E_(nstates-1) - E_0``: a weight that is too small makes a higher root fall back onto a lower
+    state (the ``"overlaps"`` show it).  ``starts`` then holds one entry per state, ``starts[k][replica]`` or ``None``
+    for the default of that state: state 0 starts as above and state ``k > 0`` from the engine's ``init_random`` seeded
+    from ``(seed, k, replica)`` -- never from the converged lower state, which is an exact eigenvector of the penalised operator
+    (eigenvalue ``E + penalty``) on which the Lanczos solve stops at once.  The return value then has the keys above for
+    the LAST state (``"energy"`` is its Ritz value, the energy plus the penalties, which vanish at convergence) and
+    ``"energies"`` ``(nstates, B)``: ``<psi|H|psi>`` from the batch's energy observable; ``"overlaps"`` ``(nstates,
+    nstates, B)``: ``<state j|state k>`` of the final states; ``"states"``: for each state the list of per-replica MPS
+    cores.  The deflation set is cleared before the call returns."""
     models = list(models) if isinstance(models, (list, tuple)) else [models]
     if not models:
         raise ValueError("relax_trajectories: no model")
+    nstates = int(nstates)
+    if nstates < 1 or nstates > 9:
+        raise ValueError(f"relax_trajectories: nstates = {nstates}, it must be in 1 .. 9 (the ground state and 8 stored states)")
+    if nstates > 1:
+        if penalty is None:
+            raise ValueError("relax_trajectories: nstates > 1 needs penalty, a weight above the largest gap wanted")
+        pen = np.broadcast_to(np.asarray(penalty, dtype=np.float64), (len(models),)).copy()
+        if not (np.all(np.isfinite(pen)) and np.all(pen > 0.0)):
+            raise ValueError("relax_trajectories: penalty must be finite and > 0")
+        state_starts = [None] * nstates if starts is None else [None if s is None else [list(c) for c in s] for s in starts]
+        if len(state_starts) != nstates:
+            raise ValueError(f"relax_trajectories: {len(state_starts)} entries of starts for {nstates} states (starts[k][replica])")
+        for k, sk in enumerate(state_starts):
+            if sk is not None and len(sk) != len(models):
+                raise ValueError(f"relax_trajectories: {len(sk)} starts of state {k} for {len(models)} models (one start per replica)")
+        starts = state_starts[0]
     m0 = models[0]
     dims = list(m0.dims)
     nsite = len(dims)
@@ -503,9 +533,37 @@ def relax_trajectories(models, starts=None, maxstep=20, conv_tol=1.0e-10, thresh
         if max_restarts:
             bt.set_relax_restarts(max_restarts)
         out = bt.relax(maxstep, conv_tol)
+        if nstates == 1:
+            if max_restarts:
+                out["restarts"] = bt.relax_restarts()["total"]
+            out["states"] = [e.get_mps() for e in bt.engines]
+            return out
+        states = [[e.get_mps() for e in bt.engines]]
+        energies = [bt.observe(norm=False, energy=True)["energy"].real]
+        overlaps = np.zeros((nstates, nstates, ns), dtype=np.complex128)
+        overlaps[0, 0] = [e.norm() ** 2 for e in bt.engines]
+        for k in range(1, nstates):
+            bt.deflate_push(pen)
+            sk = state_starts[k]
+            mk = None if sk is None else core_starts(sk, dims, D)
+            for r, (e, m) in enumerate(zip(bt.engines, models)):
+                if sk is None:
+                    e.init_random(dims, int(min(D, 2**31 - 1)), seed=((int(seed) * 1000003 + k) * 1000003 + r + 1) % 2**64)
+                else:
+                    e.set_mps(product_state_cores(sk[r], D, space=m.space) if mk is None else mk[r], canonicalize=True, scale=1.0)
+            out = bt.relax(maxstep, conv_tol)
+            states.append([e.get_mps() for e in bt.engines])
+            energies.append(bt.observe(norm=False, energy=True)["energy"].real)
+            ov = bt.deflate_overlaps()  # <state j | state k>, j < k
+            overlaps[:k, k] = ov
+            overlaps[k, :k] = ov.conj()
+            overlaps[k, k] = [e.norm() ** 2 for e in bt.engines]
         if max_restarts:
             out["restarts"] = bt.relax_restarts()["total"]
-        out["states"] = [e.get_mps() for e in bt.engines]
+        out["states"] = states
+        out["energies"] = np.array(energies)
+        out["overlaps"] = overlaps
+        bt.deflate_clear()
     finally:
         bt.close()
     return out
